@@ -10,12 +10,22 @@ render are inside it.
   one GPU (default): dragon.ply 2048x2048 frames (BASELINE configs[2]), two
                  frames in flight for frames up to 2048x2048 (--inflight:
                  frame k on stream k % 2 into its own output planes; both
-                 checked bit for bit after timing).  Before the timed
-                 region: W untimed steps (the first frame, with its list
+                 checked bit for bit after timing under --full).  Before the
+                 timed region: W untimed steps (the first frame, with its list
                  sizing, and W - 1 warm-up steps), nothing else unless
-                 --ramp-ms asks for it.  After it, --loaded-ms of untimed
-                 steps and K more timed steps give the rate at the GPU's
-                 loaded clocks (at_loaded_clocks, reported beside `value`).
+                 --ramp-ms asks for it.  A plain run ends there: it writes the
+                 last timed step's planes when --dump-outputs names a
+                 directory and prints the result line.
+  --full         everything else, after the timed region and never inside
+                 `value`: --loaded-ms of untimed steps and K more timed steps
+                 (the rate at the GPU's loaded clocks, at_loaded_clocks), the
+                 opt-in tile plan's leg, the moving-camera legs, the
+                 end-to-end latency windows, the CPU baseline, the bit-for-bit
+                 checks of the frames in flight and of the gathered frame, and
+                 over N > 1 GPUs the C ABI's own multi-GPU entry (capi_multi).
+                 The options that size or skip one of these (--loaded-ms,
+                 --orbit-legs, --no-latency, --no-cpu-baseline, ...) act
+                 under --full only.
   --gpus N > 1 (default --mode strips, 4096x4096: BASELINE configs[3]):
                  strong scaling -- one frame per step split into row strips
                  (--root-share balanced: from the frame's per-band render cost
@@ -24,12 +34,12 @@ render are inside it.
                  strip to rank 0 over RCCL (--transit hits: per 8x8 tile a hit
                  mask and the hit rays' L values; packed / dense as named),
                  which expands it into its frame's three planes; frame k's
-                 gather overlaps frame k+1's render.  The gathered frame is
-                 checked bit for bit against rank 0's own single-device render
-                 after timing.
+                 gather overlaps frame k+1's render.  Under --full the gathered
+                 frame is checked bit for bit against rank 0's own
+                 single-device render after timing.
   --mode frames  weak scaling: every rank renders whole frames, no exchange.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size W H]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--size W H]
                     [--kernel auto|binned|tiled|brute] [--mode frames|strips]
                     [--tile-mesh n] [--no-cpu-baseline] [--dist-backend nccl|gloo]
 
@@ -60,6 +70,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what is not the headline figure: at_loaded_clocks, "
+                         "the tile plan's leg, the orbit legs, the latency windows, the CPU baseline, the "
+                         "bit-for-bit checks of the timed frames and, over N > 1 GPUs, capi_multi")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the planes of the last timed step (rank 0: image, L-buffer, "
+                         "u8) as DIR/image.npy, DIR/lbuffer.npy, DIR/lbuffer_nonfinite.npy and DIR/u8.npy, float32 and "
+                         "finite (a miss's +inf L is 0 in lbuffer.npy and code 1 in lbuffer_nonfinite.npy); frames of "
+                         "more pixels than DUMP_BUDGET_BYTES holds are sampled at fixed, seeded pixel indices")
     ap.add_argument("--size", type=int, nargs=2, default=None, metavar=("W", "H"),
                     help="default 2048 2048; 4096 4096 for strips over N > 1 GPUs (BASELINE configs[3])")
     ap.add_argument("--kernel", choices=["auto", "binned", "tiled", "brute"], default="auto")
@@ -401,6 +420,43 @@ gc.callbacks.append(GC)
 
 DIST_TIMEOUT_S = 120            # every collective of a multi-rank run (a hung link fails the run)
 EXIT_GATHER_MISMATCH = 3        # the gathered frame differs from rank 0's own render
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay below 64 MB
+DUMP_NAMES = ("image", "lbuffer", "lbuffer_nonfinite", "u8")
+
+
+def dump_outputs(directory, planes) -> dict:
+    """--dump-outputs: the three device planes of a frame (image, L-buffer, u8)
+    as float32 .npy files under `directory`, every value finite.  The L-buffer
+    of a ray that hits nothing is +inf (include/xrt.h), so it travels as two
+    files: lbuffer.npy with every non-finite value written as 0, and
+    lbuffer_nonfinite.npy with a code per pixel -- 0 finite, 1 +inf, 2 -inf,
+    3 NaN -- from which the plane is restored exactly (NaN payloads apart).
+    A frame whose files would exceed DUMP_BUDGET_BYTES is sampled: the same
+    pixel indices of every plane, drawn once from a generator seeded with 0
+    (so two runs with the same arguments keep the same pixels), in ascending
+    order."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    n = planes[0].numel()
+    keep = DUMP_BUDGET_BYTES // (4 * len(DUMP_NAMES))
+    idx = None
+    if n > keep:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).integers(0, n, size=keep))).to(planes[0].device)
+    img, lb, u8 = (t if idx is None else t.index_select(0, idx) for t in planes)
+    finite = torch.isfinite(lb)
+    code = torch.where(finite, 0.0, torch.where(torch.isnan(lb), 3.0, torch.where(lb > 0, 1.0, 2.0)))
+    lb = torch.where(finite, lb, torch.zeros_like(lb))
+    for name, t in zip(DUMP_NAMES, (img, lb, code, u8)):
+        a = t.to(torch.float32).cpu().numpy()
+        if not np.isfinite(a).all():
+            raise SystemExit(f"bench.py: --dump-outputs: {name} holds a value that is not finite")
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {"dir": directory, "files": [nm + ".npy" for nm in DUMP_NAMES], "dtype": "float32",
+            "pixels": int(n if idx is None else keep),
+            "sample": None if idx is None else f"{keep} of {n} pixel indices, numpy default_rng(0).integers, sorted"}
 
 
 def planes_equal(a, b) -> bool:
@@ -1011,6 +1067,12 @@ def main():
     tile_plan_timed = ctx.tile_plan_counters()["frames"] - tp_before
     if tile_plan_timed:
         raise SystemExit(f"bench.py: {tile_plan_timed} timed frames used the tile plan")
+    # --dump-outputs: the last timed step's planes, kept on the device now (the
+    # legs of --full render into the same planes) and written before the result line
+    dump_planes = None
+    if args.dump_outputs and rank == 0:
+        dump_planes = [p_.clone() for p_ in planes_of[(frame_no[0] - 1) % inflight][:3]]
+        torch.cuda.synchronize(dev)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev if nccl else "cpu")
     if world > 1:
@@ -1023,7 +1085,7 @@ def main():
     # ramped under sustained load (DESIGN.md "Measurement").  The frame count
     # comes from the region's max-over-ranks step, so every rank agrees.
     loaded = None
-    if args.loaded_ms > 0 and args.steps > 0:
+    if args.full and args.loaded_ms > 0 and args.steps > 0:
         n_load = int(min(20000, max(0.0, args.loaded_ms / 1e3 / max(elapsed_max / args.steps, 1e-7))))
         t_r = time.perf_counter()
         run_steps(n_load)
@@ -1055,7 +1117,7 @@ def main():
     # Opt-in tile plan, never `value`: the same loop with it on (its frames skip
     # the cull of tiles an earlier frame of the same camera found dead).
     with_tile_plan = None
-    if root and not strips and not signed and not orbit_cams and world == 1 and args.steps > 0 and \
+    if args.full and root and not strips and not signed and not orbit_cams and world == 1 and args.steps > 0 and \
             args.kernel in ("auto", "binned") and not args.no_tile_plan_leg:
         ctx.set_tile_plan(True)
         run_steps(max(args.warmup, 4))
@@ -1079,7 +1141,7 @@ def main():
     # (frames in flight as in the main loop), every frame prepared for its
     # own camera.  The last frames are checked bit for bit afterwards.
     orbit = None
-    if root and not strips and not signed and not orbit_cams and world == 1 and args.steps > 0 and \
+    if args.full and root and not strips and not signed and not orbit_cams and world == 1 and args.steps > 0 and \
             args.orbit_legs:
         orbit = {"fixed_camera_ms_per_step": elapsed_max / args.steps * 1e3}
         lo_, hi_ = xrt.mesh_bbox(tris)
@@ -1176,7 +1238,7 @@ def main():
 
     # untimed: the gathered frame against rank 0's own render of the whole frame
     gather = None
-    if gathering and rank == 0:
+    if args.full and gathering and rank == 0:
         full = ctx.render_rows(cam)
         ok = planes_equal((img.cpu().numpy(), lb.cpu().numpy(), u8.cpu().numpy()), full)
         if hits and int(d_bad.item()) != 0:   # a mask disagreed with its sender's plan
@@ -1244,6 +1306,7 @@ def main():
             "value": value,
             "unit": "Mrays/s",
             "n_gpus": world,
+            "full": args.full,
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
@@ -1294,7 +1357,7 @@ def main():
             "dist_backend": args.dist_backend if world > 1 else None,
         }
 
-    if rank == 0 and world == 1 and not signed:
+    if args.full and rank == 0 and world == 1 and not signed:
         # the timed loop's own planes (its last frame), checked against the oracle's rows
         last_cam = orbit_cams[(frame_no[0] - 1) % len(orbit_cams)] if orbit_cams else cam
         img_l, lb_l, u8_l, _ = planes_of[(frame_no[0] - 1) % inflight]
@@ -1315,7 +1378,7 @@ def main():
             planes = (img_l.cpu().numpy(), lb_l.cpu().numpy(), u8_l.cpu().numpy())
             result["cpu_baseline"] = cpu_baseline(tris, last_cam, W, H, args.cpu_seconds, planes)
 
-    if root and not strips and not signed and inflight > 1:
+    if args.full and root and not strips and not signed and inflight > 1:
         # untimed: each in-flight buffer set's last frame against a synchronous
         # render of its camera (frames that overlapped must not change a bit)
         ok = True
@@ -1330,7 +1393,7 @@ def main():
             result["frames_in_flight_exact"] = True
 
     code = 0
-    if gathering:
+    if args.full and gathering:
         code = gather_verdict(dist, torch, rank, bool(gather and gather["bit_exact_vs_single_device_frame"]),
                               dev if nccl else "cpu")
     # The C ABI's own multi-GPU entry (the drop-in's renderLoopMultiGPU / xrt_main
@@ -1338,7 +1401,7 @@ def main():
     # every rank's device while the other ranks wait on the host.
     capi_devices = ([int(d) for d in args.capi_devices.split(",")] if args.capi_devices
                     else ([device_index] * world if args.same_device else list(range(world)))
-                    if gathering and args.capi_multi == "auto" else None)
+                    if args.full and gathering and args.capi_multi == "auto" else None)
     if capi_devices:
         torch.cuda.synchronize(dev)
         if rank == 0:
@@ -1349,6 +1412,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if dump_planes is not None:
+            result["dumped_outputs"] = dump_outputs(args.dump_outputs, dump_planes)
         print(json.dumps(result), flush=True)
     ctx.close()
     return code

@@ -404,6 +404,46 @@ def test_frames_in_flight_rule():
         bench.frames_in_flight(0, False, 2048, 2048)
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): the planes as finite float32 .npy
+    files -- an L that is not finite is 0 in lbuffer.npy and coded in
+    lbuffer_nonfinite.npy (1 +inf, 2 -inf, 3 NaN); whole when they fit the
+    budget; above it the same seeded pixel indices of every plane, identical
+    from call to call and within the budget."""
+    import torch
+
+    import bench
+    n = 1000
+    lb = torch.arange(n, dtype=torch.float32) * 0.5
+    lb[3::7] = float("inf")
+    lb[5] = float("-inf")
+    lb[6] = float("nan")
+    code = np.zeros(n, np.float32)
+    code[3::7], code[5], code[6] = 1, 2, 3
+    planes = (torch.arange(n, dtype=torch.float32), lb, (torch.arange(n) % 256).to(torch.uint8))
+    want = (planes[0].numpy(), np.where(code == 0, lb.numpy(), np.float32(0)), code,
+            planes[2].numpy().astype(np.float32))
+    assert bench.DUMP_NAMES == ("image", "lbuffer", "lbuffer_nonfinite", "u8")
+    info = bench.dump_outputs(str(tmp_path / "whole"), planes)
+    assert info["sample"] is None and info["pixels"] == n
+    for name, w in zip(bench.DUMP_NAMES, want):
+        a = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, w), name
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 16 * 100)          # 100 pixels of each file
+    first = bench.dump_outputs(str(tmp_path / "s1"), planes)
+    bench.dump_outputs(str(tmp_path / "s2"), planes)
+    assert first["pixels"] == 100 and first["sample"]
+    idx = np.load(tmp_path / "s1" / "image.npy").astype(np.int64)      # plane 0 holds its own indices
+    assert idx.shape == (100,) and np.all(np.diff(idx) >= 0) and idx.min() >= 0 and idx.max() < n
+    total = 0
+    for name, w in zip(bench.DUMP_NAMES, want):
+        a, b = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b)
+        assert np.array_equal(a, w[idx]), name
+        total += a.nbytes
+    assert total <= 16 * 100
+
+
 def test_bench_exits_nonzero_on_rank_exception():
     """bench.run(): an exception in main() leaves through os._exit(1) after its
     traceback (no hang in a collective or RCCL teardown)."""

@@ -1810,7 +1810,7 @@ def test_bench_strips_two_ranks_one_gpu(tmp_path, transit, ranks, share, size):
     (gloo, host-staged): the gathered frame is bit-equal to rank 0's
     single-device render.  The 8-rank cases are BASELINE configs[3]'s real split
     (4096^2, 8 strips, balanced; packed, and hits -- the default), and they also run the bench's
-    capi_multi leg: the C ABI's xrt_render_rows_multi_device over device 0
+    capi_multi leg (the gather check and that leg are bench.py --full's): the C ABI's xrt_render_rows_multi_device over device 0
     listed 8 times (one-rank RCCL), bit-equal as well."""
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
@@ -1818,7 +1818,7 @@ def test_bench_strips_two_ranks_one_gpu(tmp_path, transit, ranks, share, size):
     capi = ranks == 8
     cmd = ["python", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(ranks), "--dist-backend", "gloo", "--same-device", "--size", str(size), str(size),
+           "--gpus", str(ranks), "--full", "--dist-backend", "gloo", "--same-device", "--size", str(size), str(size),
            "--steps", "4", "--warmup", "1", "--transit", transit, "--kernel", "binned", "--root-share", share,
            "--loaded-ms", "0", "--capi-multi", "auto" if capi else "off"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=280, cwd=ROOT)
@@ -1852,6 +1852,41 @@ def test_bench_strips_two_ranks_one_gpu(tmp_path, transit, ranks, share, size):
         assert g["bytes_gathered_per_step"] < g["dense_bytes_per_step"]
     else:
         assert g["bytes_gathered_per_step"] == g["dense_bytes_per_step"]
+
+
+def test_bench_plain_run_dumps_last_timed_frame(tmp_path):
+    """A plain bench.py run (no --full) times its steps and nothing after them:
+    the result line keeps the headline keys, the legs of --full are absent, and
+    --dump-outputs writes the last timed frame's planes as float32 -- the
+    committed 256^2 frame of the reference's own classes, bit for bit."""
+    import json
+    import sys
+    out = tmp_path / "planes"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+           "--size", "256", "256", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=120, cwd=ROOT)
+    if r.returncode != 0:
+        print(r.stderr[-6000:])
+    assert r.returncode == 0
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["full"] is False and d["steps"] == 3 and d["unit"] == "Mrays/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(256 * 256 / (d["ms_per_step"] * 1e-3) / 1e6)
+    for key in ("at_loaded_clocks", "with_tile_plan", "orbit", "cpu_baseline", "frames_in_flight_exact", "gather_check"):
+        assert d[key] is None, key
+    assert "end_to_end_ms" not in d["latency"] and "child_process" not in d["latency"]
+    g = np.load(os.path.join(GOLDEN, "planes_dragon_256.npz"), allow_pickle=False)
+    assert np.array_equal(g["rows"], np.arange(256))
+    got = {name: np.load(out / f"{name}.npy") for name in ("image", "lbuffer", "lbuffer_nonfinite", "u8")}
+    for name, a in got.items():
+        assert a.dtype == np.float32 and a.shape == (256 * 256,) and np.isfinite(a).all(), name
+    # a miss's L is +inf: 0 in lbuffer.npy, code 1 in lbuffer_nonfinite.npy
+    code = got["lbuffer_nonfinite"]
+    assert set(np.unique(code)) == {0.0, 1.0} and np.all(got["lbuffer"][code == 1] == 0)
+    lb = np.where(code == 1, np.float32(np.inf), got["lbuffer"])
+    assert np.array_equal(bits(got["image"]), bits(g["image"].reshape(-1)))
+    assert np.array_equal(bits(lb), bits(g["lbuffer"].reshape(-1)))
+    assert np.array_equal(got["u8"], g["u8"].reshape(-1))
 
 
 def test_render_frames_batch_equals_single_calls(dragon):

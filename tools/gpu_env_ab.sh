@@ -16,7 +16,7 @@ for v in $VALUES; do
 for cfg in "1024|--size 1024 1024" "2048|--size 2048 2048" "4096|--size 4096 4096 --steps 100 --warmup 10" "1m|--size 8192 8192 --tile-mesh 7 --steps 30 --warmup 5"; do
   IFS='|' read -r name args <<< "$cfg"
   f=$OUT/${v}_${name}_$rep
-  env $KNOB=$v timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-latency $args > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+  env $KNOB=$v timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-latency $args > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$f.json')); lo=d['at_loaded_clocks']
 print('$KNOB=$v $name rep$rep step %.1f us loaded %.1f us span %.1f check %s' % (d['ms_per_step']*1e3, lo['ms_per_step']*1e3, d['roofline']['avg_kernel_ms']*1e3, d.get('frames_in_flight_exact')))"

@@ -19,7 +19,7 @@ for v in ${VARIANTS:-base}; do
     IFS='|' read -r name cfg steps <<< "$c"
     d=$OUT/${v}_${name}
     XRT_LIB=$L/libxrt_$v.so timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o run -- python3 bench.py --no-cpu-baseline --no-latency --no-timing-check --loaded-ms 0 $cfg $steps > $d.trace.json 2> $d.trace.err || { tail -5 $d.trace.err; exit 1; }
-    XRT_LIB=$L/libxrt_$v.so timeout -k 10 240 python3 bench.py --no-cpu-baseline --no-latency --no-timing-check $cfg $steps > $d.json 2> $d.err || { tail -5 $d.err; exit 1; }
+    XRT_LIB=$L/libxrt_$v.so timeout -k 10 240 python3 bench.py --full --no-cpu-baseline --no-latency --no-timing-check $cfg $steps > $d.json 2> $d.err || { tail -5 $d.err; exit 1; }
     python3 - "$d" "$v" "$name" <<'EOF'
 import csv, glob, json, sys
 d, v, name = sys.argv[1:4]

@@ -10,7 +10,7 @@ for rep in 1 2; do
   for cfg in "2048|--size 2048 2048" "1024|--size 1024 1024" "4096|--size 4096 4096" "1m|--size 8192 8192 --tile-mesh 7 --steps 60 --warmup 5"; do
     IFS='|' read -r name args <<< "$cfg"
     for tp in 1 0; do
-      XRT_TILE_PLAN=$tp timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-latency --no-timing-check $args > $OUT/${name}_tp${tp}_$rep.json 2> $OUT/${name}_tp${tp}_$rep.err || { tail -5 $OUT/${name}_tp${tp}_$rep.err; exit 1; }
+      XRT_TILE_PLAN=$tp timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-latency --no-timing-check $args > $OUT/${name}_tp${tp}_$rep.json 2> $OUT/${name}_tp${tp}_$rep.err || { tail -5 $OUT/${name}_tp${tp}_$rep.err; exit 1; }
       python3 -c "import json; d=json.load(open('$OUT/${name}_tp${tp}_$rep.json')); l=d['at_loaded_clocks']; print('$name tp$tp rep$rep step %.1f us loaded %.1f us span %.1f us' % (d['ms_per_step']*1e3, l['ms_per_step']*1e3, d['roofline']['avg_kernel_ms']*1e3))"
     done
   done

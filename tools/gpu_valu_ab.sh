@@ -17,7 +17,7 @@ for v in ${VARIANTS:-base}; do
     d=$OUT/${v}_$c
     XRT_LIB=$L/libxrt_$v.so timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $d -o run -- python3 bench.py --no-cpu-baseline --no-latency --no-timing-check --loaded-ms 0 ${CFG[$c]} --steps 6 --warmup 2 > /dev/null 2> $d.pmc.err || { tail -5 $d.pmc.err; exit 1; }
     python3 tools/pmc_summary.py $d > /dev/null || exit 1
-    XRT_LIB=$L/libxrt_$v.so timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-latency --no-timing-check ${CFG[$c]} --steps 50 --warmup 5 > $d.json 2> $d.err || { tail -5 $d.err; exit 1; }
+    XRT_LIB=$L/libxrt_$v.so timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-latency --no-timing-check ${CFG[$c]} --steps 50 --warmup 5 > $d.json 2> $d.err || { tail -5 $d.err; exit 1; }
     python3 - "$d" "$v" "$c" <<'PY'
 import json, sys
 d, v, c = sys.argv[1:4]
