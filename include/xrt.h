@@ -301,6 +301,39 @@ int xrt_hole_fill_device(xrt_context* ctx, uint32_t width, uint32_t height, cons
 int xrt_render_signed(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
                       uint8_t* image_u8, xrt_stats* stats);
 
+/* --- the materials model: every mesh with its own coefficient ------------- */
+
+/*
+ * A scene of num_meshes meshes (1..XRT_MAX_MESHES, any of them empty): their
+ * triangle soups one after another in `triangles`, mesh m holding
+ * mesh_triangles[m] of them.  xrt_upload_mesh is a one-mesh scene.  The
+ * attenuation and the signed model render mesh 0 only, as the reference does
+ * (src/main.cxx:687, main-pthreads-lbuffer.cxx:788).
+ */
+#define XRT_MAX_MESHES 16
+int xrt_upload_scene(xrt_context* ctx, const float* triangles, const uint64_t* mesh_triangles,
+                     uint32_t num_meshes);
+
+/*
+ * XRT_MODEL_MATERIALS: the fork's loop over the meshes (:770-810) with its
+ * mesh filter lifted, the model of the paper it follows.  Per ray, with the
+ * ray, the once-normalised direction and the unit normals of XRT_MODEL_SIGNED:
+ *   L = 80; for each mesh m in scene order, unless L is already -1:
+ *     distance = the f32 sum of sign(direction . normal) * t over the hits of
+ *     mesh m in triangle order; L = -1 when its signs do not cancel, else
+ *     L = (float)((double)L * exp(-(mu[m] * (distance * 0.1)))).
+ * With one mesh it is XRT_MODEL_SIGNED.  xrt_set_materials selects the model
+ * and sets one coefficient per mesh (finite, >= 0); a render whose scene has
+ * another number of meshes fails with XRT_ERR_ARGUMENT.  Renders write the
+ * L-buffer plane only, kernels BRUTE or BINNED, as for XRT_MODEL_SIGNED.
+ * xrt_render_materials is xrt_render_signed for this model: render and hole
+ * fill; stats.odd_rays counts the flagged rays, hits and hit_rays every mesh's.
+ */
+#define XRT_MODEL_MATERIALS 2
+int xrt_set_materials(xrt_context* ctx, const float* mu, uint32_t num_meshes);
+int xrt_render_materials(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
+                         uint8_t* image_u8, xrt_stats* stats);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*
@@ -347,6 +380,10 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
  * the hole-filled image (device 0 fills the assembled frame).
  */
 int xrt_multi_set_model(xrt_multi* m, int model, float mu);
+/* The scene and the materials model of every device (xrt_upload_scene, xrt_set_materials). */
+int xrt_multi_upload_scene(xrt_multi* m, const float* triangles, const uint64_t* mesh_triangles,
+                           uint32_t num_meshes);
+int xrt_multi_set_materials(xrt_multi* m, const float* mu, uint32_t num_meshes);
 
 /* Waits for the last frame's gathers; the devices' statistics, summed. */
 int xrt_multi_read_stats(xrt_multi* m, xrt_stats* stats);

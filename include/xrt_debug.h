@@ -65,6 +65,18 @@ void xrt_host_signed_lbuffer_batch(const float* distance, const int32_t* sign_su
                                    uint64_t n);
 
 /*
+ * The materials model's chained update for n rays of given per-mesh sums: ray
+ * i's mesh m has distance[i * num_meshes + m] and sign_sum[i * num_meshes + m]
+ * (sign_sum may be NULL for all zero); out[i] = L after the last mesh, from
+ * L = 80.  _host_: the device source compiled for the host; _probe_: the same
+ * on the device (beside XRT_PROBE_SIGNED_L).  Host buffers.
+ */
+void xrt_host_materials_lbuffer_batch(const float* distance, const int32_t* sign_sum, const float* mu,
+                                      uint32_t num_meshes, float* out, uint64_t n);
+int xrt_probe_materials(xrt_context* ctx, const float* distance, const int32_t* sign_sum, const float* mu,
+                        uint32_t num_meshes, float* out, uint64_t n);
+
+/*
  * Test hook: caps the per-ray register hit list at `capacity` (1..12) so the
  * exact overflow path runs.  0 restores the default (12).
  */

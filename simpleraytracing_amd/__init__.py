@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -28,7 +28,8 @@ __all__ = [
     "camera_for_mesh", "device_count", "XRT_KERNEL_AUTO", "XRT_KERNEL_BRUTE", "XRT_KERNEL_TILED",
     "XRT_KERNEL_BINNED", "XRT_MISS_TRANSIT", "load_meshes", "scene_bbox", "camera_for_scene",
     "XRT_MODEL_ATTENUATION", "XRT_MODEL_SIGNED", "XRT_GATHER_AUTO", "XRT_GATHER_COPY", "XRT_GATHER_RCCL",
-    "XRT_SPLIT_EQUAL", "XRT_SPLIT_BALANCED", "XRT_TRANSIT_HITS", "XRT_TRANSIT_PACKED",
+    "XRT_SPLIT_EQUAL", "XRT_SPLIT_BALANCED", "XRT_TRANSIT_HITS", "XRT_TRANSIT_PACKED", "XRT_MODEL_MATERIALS",
+    "XRT_MAX_MESHES",
 ]
 
 
@@ -44,6 +45,14 @@ def _fptr(a):
 
 def _u8ptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
+def _scene_arrays(meshes):
+    """A list of (T, 9) soups as xrt_upload_scene takes it: (soups one after another, counts)."""
+    meshes = [np.ascontiguousarray(m, dtype=np.float32).reshape(-1, 9) for m in meshes]
+    counts = np.array([len(m) for m in meshes], np.uint64)
+    tris = np.ascontiguousarray(np.concatenate(meshes) if meshes else np.zeros((0, 9), np.float32))
+    return tris, counts
 
 
 def device_count() -> int:
@@ -176,6 +185,41 @@ class Context:
     def set_model(self, model: int, mu: float = 0.1037):
         """XRT_MODEL_ATTENUATION (main.cxx) or XRT_MODEL_SIGNED (the L-buffer fork, mesh-0 mu)."""
         self._check(self._lib.xrt_set_model(self._ctx, int(model), float(np.float32(mu))), "xrt_set_model")
+
+    def upload_scene(self, meshes):
+        """A scene of several meshes ((T, 9) soups, any of them empty); upload_mesh is a one-mesh scene."""
+        tris, counts = _scene_arrays(meshes)
+        self._check(self._lib.xrt_upload_scene(self._ctx, _fptr(tris),
+                                               counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(counts)),
+                    "xrt_upload_scene")
+
+    def set_materials(self, mu):
+        """XRT_MODEL_MATERIALS with one attenuation coefficient per mesh of the scene."""
+        mu = np.ascontiguousarray(mu, dtype=np.float32).reshape(-1)
+        self._check(self._lib.xrt_set_materials(self._ctx, _fptr(mu), mu.size), "xrt_set_materials")
+
+    def render_materials(self, cam: Camera):
+        """The materials model end to end: (hole-filled image f32, lbuffer f32 with -1 flags, u8, Stats)."""
+        n = cam.width * cam.height
+        img = np.empty(n, np.float32)
+        lb = np.empty(n, np.float32)
+        u8 = np.empty(n, np.uint8)
+        st = Stats()
+        self._check(self._lib.xrt_render_materials(self._ctx, ctypes.byref(cam), _fptr(img), _fptr(lb), _u8ptr(u8),
+                                                   ctypes.byref(st)), "xrt_render_materials")
+        return img, lb, u8, st
+
+    def probe_materials(self, distance: np.ndarray, sign_sum, mu):
+        """The device's chained L of rays with given per-mesh sums ((n, M) arrays; sign_sum may be None)."""
+        d = np.ascontiguousarray(distance, dtype=np.float32)
+        mu = np.ascontiguousarray(mu, dtype=np.float32).reshape(-1)
+        d = d.reshape(-1, mu.size)
+        s = None if sign_sum is None else np.ascontiguousarray(sign_sum, dtype=np.int32).reshape(d.shape)
+        out = np.empty(len(d), np.float32)
+        self._check(self._lib.xrt_probe_materials(
+            self._ctx, _fptr(d), s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if s is not None else None,
+            _fptr(mu), mu.size, _fptr(out), len(d)), "xrt_probe_materials")
+        return out
 
     def render_signed(self, cam: Camera):
         """The L-buffer fork end to end: (image f32, lbuffer f32 with -1 flags, u8, Stats)."""
@@ -525,6 +569,20 @@ class MultiContext:
 
     def set_model(self, model: int, mu: float = 0.1037):
         self._check(self._lib.xrt_multi_set_model(self._m, int(model), float(np.float32(mu))), "xrt_multi_set_model")
+
+    def upload_scene(self, meshes):
+        tris, counts = _scene_arrays(meshes)
+        self._check(self._lib.xrt_multi_upload_scene(self._m, _fptr(tris),
+                                                     counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                                     len(counts)), "xrt_multi_upload_scene")
+
+    def set_materials(self, mu):
+        mu = np.ascontiguousarray(mu, dtype=np.float32).reshape(-1)
+        self._check(self._lib.xrt_multi_set_materials(self._m, _fptr(mu), mu.size), "xrt_multi_set_materials")
+
+    def render_materials(self, cam: Camera):
+        """The materials model's frame: (hole-filled image, lbuffer with -1 flags, u8, stats)."""
+        return self.render(cam)
 
     def set_split(self, mode: int, link_bytes_per_us: float = 0.0):
         """XRT_SPLIT_EQUAL (the reference's H/N rows) or XRT_SPLIT_BALANCED (the default;

@@ -35,6 +35,8 @@ XRT_PROBE_SIGNED_L = 5
 
 XRT_MODEL_ATTENUATION = 0
 XRT_MODEL_SIGNED = 1
+XRT_MODEL_MATERIALS = 2
+XRT_MAX_MESHES = 16
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -141,6 +143,11 @@ XRT_SYMBOLS = {
     "xrt_hole_fill": (ctypes.c_int, [_CtxP, _u32, _u32, _fp, _fp, _u8p]),
     "xrt_hole_fill_device": (ctypes.c_int, [_CtxP, _u32, _u32, _vp, _vp, _vp, _vp]),
     "xrt_render_signed": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _fp, _fp, _u8p, ctypes.POINTER(Stats)]),
+    "xrt_upload_scene": (ctypes.c_int, [_CtxP, _fp, _u64p, _u32]),
+    "xrt_set_materials": (ctypes.c_int, [_CtxP, _fp, _u32]),
+    "xrt_render_materials": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _fp, _fp, _u8p, ctypes.POINTER(Stats)]),
+    "xrt_host_materials_lbuffer_batch": (None, [_fp, _i32p, _fp, _u32, _fp, _u64]),
+    "xrt_probe_materials": (ctypes.c_int, [_CtxP, _fp, _i32p, _fp, _u32, _fp, _u64]),
     "xrt_host_mt_check": (None, [_fp, _fp, _fp, _fp, _u64, ctypes.POINTER(ctypes.c_uint8),
                                  ctypes.POINTER(ctypes.c_uint8), _fp]),
     "xrt_set_hit_capacity": (ctypes.c_int, [_CtxP, _u32]),
@@ -180,6 +187,8 @@ XRT_SYMBOLS = {
     "xrt_multi_upload_mesh": (ctypes.c_int, [_MultiP, _fp, _u64]),
     "xrt_multi_set_kernel": (ctypes.c_int, [_MultiP, ctypes.c_int]),
     "xrt_multi_set_model": (ctypes.c_int, [_MultiP, ctypes.c_int, _f]),
+    "xrt_multi_upload_scene": (ctypes.c_int, [_MultiP, _fp, _u64p, _u32]),
+    "xrt_multi_set_materials": (ctypes.c_int, [_MultiP, _fp, _u32]),
     "xrt_render_rows_multi": (ctypes.c_int, [_MultiP, ctypes.POINTER(Camera), _fp, _fp, _u8p,
                                              ctypes.POINTER(Stats)]),
     "xrt_render_rows_multi_device": (ctypes.c_int, [_MultiP, ctypes.POINTER(Camera), _vp, _vp, _vp, _vp]),

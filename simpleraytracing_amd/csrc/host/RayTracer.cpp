@@ -190,6 +190,16 @@ std::vector<float> mesh0_soup(const std::vector<TriangleMesh>& meshes)
     return meshes.empty() ? std::vector<float>() : meshes[0].flatten();
 }
 
+// Every mesh of the scene, one soup after another (xrt_upload_scene).
+void scene_soup(const std::vector<TriangleMesh>& meshes, std::vector<float>& soup, std::vector<uint64_t>& counts)
+{
+    for (const TriangleMesh& m : meshes) {
+        const std::vector<float> s = m.flatten();
+        soup.insert(soup.end(), s.begin(), s.end());
+        counts.push_back(s.size() / 9);
+    }
+}
+
 void report_odd(unsigned long long odd)
 {
     for (unsigned long long i = 0; i < odd; ++i) std::cout << "Only one intersect on this ray" << std::endl;
@@ -270,6 +280,30 @@ unsigned long long renderLoopLBuffer(Image& image, const std::vector<TriangleMes
     return stats.odd_rays;
 }
 
+unsigned long long renderLoopMaterials(Image& image, const std::vector<TriangleMesh>& meshes, RayTracerInfo& info,
+                                       const std::vector<float>& mu, std::vector<float>* lbuffer)
+{
+    if (mu.size() != meshes.size()) throw std::invalid_argument("renderLoopMaterials: one coefficient per mesh");
+    xrt_camera cam = camera_for(image, meshes, info);
+    std::vector<float> soup;
+    std::vector<uint64_t> counts;
+    scene_soup(meshes, soup, counts);
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    int k = kernel_choice();
+    check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
+    slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
+    check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
+    check(ctx, xrt_set_materials(ctx, mu.data(), (uint32_t)mu.size()), "xrt_set_materials");
+    if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
+    xrt_stats stats;
+    const int rc = xrt_render_materials(ctx, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
+    xrt_set_model(ctx, XRT_MODEL_ATTENUATION, 0.0f);
+    check(ctx, rc, "xrt_render_materials");
+    return stats.odd_rays;
+}
+
 namespace {
 
 // One multi-device context per device list for the process lifetime: the
@@ -344,6 +378,29 @@ unsigned long long renderLoopLBufferMultiGPU(Image& image, const std::vector<Tri
     mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
     mcheck(m, xrt_multi_upload_mesh(m, soup.data(), soup.size() / 9), "xrt_multi_upload_mesh");
     mcheck(m, xrt_multi_set_model(m, XRT_MODEL_SIGNED, 0.1037f), "xrt_multi_set_model");   // :800
+    if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
+    xrt_stats stats;
+    const int rc = xrt_render_rows_multi(m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
+    xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f);
+    mcheck(m, rc, "xrt_render_rows_multi");
+    return stats.odd_rays;
+}
+
+unsigned long long renderLoopMaterialsMultiGPU(Image& image, const std::vector<TriangleMesh>& meshes,
+                                               RayTracerInfo& info, const std::vector<float>& mu, int num_gpus,
+                                               std::vector<float>* lbuffer)
+{
+    if (mu.size() != meshes.size()) throw std::invalid_argument("renderLoopMaterialsMultiGPU: one coefficient per mesh");
+    xrt_camera cam = camera_for(image, meshes, info);
+    std::vector<float> soup;
+    std::vector<uint64_t> counts;
+    scene_soup(meshes, soup, counts);
+    std::lock_guard<std::mutex> g(multi_lock());
+    xrt_multi* m = multi_context(num_gpus);
+    const int k = kernel_choice();
+    mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
+    mcheck(m, xrt_multi_upload_scene(m, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_multi_upload_scene");
+    mcheck(m, xrt_multi_set_materials(m, mu.data(), (uint32_t)mu.size()), "xrt_multi_set_materials");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
     const int rc = xrt_render_rows_multi(m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);

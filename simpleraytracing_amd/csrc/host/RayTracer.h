@@ -85,6 +85,17 @@ unsigned long long renderLoopLBuffer(Image& output_image, const std::vector<Tria
 unsigned long long renderLoopLBufferMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,
                                              RayTracerInfo& info, int num_gpus, std::vector<float>* lbuffer = nullptr);
 
+// The materials model (XRT_MODEL_MATERIALS): the fork's loop over every mesh
+// of the scene, mesh m attenuating with mu[m] (one value per mesh), and the
+// hole fill into output_image.  `lbuffer` (optional) receives the L-buffer
+// (-1 flags).  Returns the number of flagged pixels.  MultiGPU: as row strips.
+unsigned long long renderLoopMaterials(Image& output_image, const std::vector<TriangleMesh>& meshes,
+                                       RayTracerInfo& info, const std::vector<float>& mu,
+                                       std::vector<float>* lbuffer = nullptr);
+unsigned long long renderLoopMaterialsMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,
+                                               RayTracerInfo& info, const std::vector<float>& mu, int num_gpus,
+                                               std::vector<float>* lbuffer = nullptr);
+
 // Row strips over `num_gpus` devices (rows_per = H / n, remainder to the first
 // strips), one host thread per device; returns the number of odd rays.
 unsigned long long renderLoopMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,

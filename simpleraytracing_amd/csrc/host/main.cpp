@@ -15,6 +15,8 @@
 //   -t, --threads N            accepted for main-pthreads*.cxx compatibility (ignored)
 //       --signed               the L-buffer fork (main-pthreads-lbuffer.cxx): signed
 //                              multi-material L-buffer + hole fill
+//       --materials MU0,MU1,.. the materials model: every mesh attenuates with its
+//                              own coefficient (one value per loaded mesh) + hole fill
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -52,6 +54,7 @@ void showUsage(const std::string& prog)
               << "\t-g,--gpus N\t\t\tRender row strips on N GPUs (default: 1)\n"
               << "\t-k,--kernel brute|tiled|binned\tRender kernel (default: automatic)\n"
               << "\t--signed\t\t\tSigned multi-material L-buffer and hole fill (main-pthreads-lbuffer.cxx)\n"
+              << "\t--materials MU0,MU1,...\t\tMaterials model: one attenuation coefficient per loaded mesh, and hole fill\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -69,6 +72,7 @@ struct Options {
     std::string lbuffer, u8;
     bool time = false;
     bool signed_model = false;
+    std::vector<float> materials;              // --materials: one coefficient per mesh
     bool rows = false;
     unsigned row_begin = 0, row_end = 0;
     unsigned batch = 0;
@@ -128,6 +132,14 @@ Options processCmd(int argc, char** argv)
             o.u8 = parse_str(argv[0], argc, argv, i);
         } else if (a == "--signed") {
             o.signed_model = true;
+        } else if (a == "--materials") {
+            const std::string list = parse_str(argv[0], argc, argv, i);
+            for (size_t pos = 0; pos <= list.size();) {
+                size_t next = list.find(',', pos);
+                if (next == std::string::npos) next = list.size();
+                o.materials.push_back(std::stof(list.substr(pos, next - pos)));
+                pos = next + 1;
+            }
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -154,8 +166,10 @@ Options processCmd(int argc, char** argv)
     if (o.inputs.empty()) o.inputs.push_back("./dragon.ply");
     if (o.rows && (o.row_begin >= o.row_end || o.row_end > o.height))
         throw std::out_of_range("--rows A:B must satisfy 0 <= A < B <= image height");
-    if ((o.rows || o.batch) && (o.signed_model || o.gpus > 1))
+    if ((o.rows || o.batch) && (o.signed_model || !o.materials.empty() || o.gpus > 1))
         throw std::runtime_error("--rows and --batch render the attenuation model on one GPU");
+    if (o.signed_model && !o.materials.empty())
+        throw std::runtime_error("--signed and --materials are two models: give one");
     return o;
 }
 
@@ -196,6 +210,13 @@ int main(int argc, char** argv)
             xrt_stats st;
             renderLoopRows(image, meshes, info, rb, re, nullptr, nullptr, &st);
             for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
+        } else if (!opt.materials.empty()) {
+            if (opt.materials.size() != meshes.size())
+                throw std::runtime_error("--materials takes one coefficient per mesh: " + std::to_string(meshes.size()) +
+                                         " meshes loaded, " + std::to_string(opt.materials.size()) + " coefficients");
+            std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
+            if (opt.gpus > 1) renderLoopMaterialsMultiGPU(image, meshes, info, opt.materials, opt.gpus, l);
+            else renderLoopMaterials(image, meshes, info, opt.materials, l);
         } else if (opt.signed_model && opt.gpus > 1) {
             renderLoopLBufferMultiGPU(image, meshes, info, opt.gpus, opt.lbuffer.empty() ? nullptr : &lb);
         } else if (opt.signed_model) {

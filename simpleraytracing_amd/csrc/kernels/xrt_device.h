@@ -74,12 +74,21 @@ struct RenderParams {
     uint32_t num_triangles;
     uint32_t hit_capacity;  // <= XRT_MAX_HITS
     uint32_t prep_tris;     // triangles per k_prep wave (prep_tris_for)
-    uint32_t model;         // kModelAttenuation (main.cxx) or kModelSigned (the L-buffer fork)
+    uint32_t model;         // kModelAttenuation (main.cxx), kModelSigned (the L-buffer fork) or kModelMaterials
 };
 
 // What a render computes per ray.
 constexpr uint32_t kModelAttenuation = 0;   // renderLoop, src/main.cxx:626-743
 constexpr uint32_t kModelSigned = 1;        // renderLoopCallBack, src/main-pthreads-lbuffer.cxx:733-813
+constexpr uint32_t kModelMaterials = 2;     // the fork's loop over every mesh, each with its own coefficient
+
+// The materials model's scene: mesh m holds the triangle ids [end of mesh
+// m - 1, end) of the scene soup and attenuates with mu (at most kMaxMeshes).
+constexpr uint32_t kMaxMeshes = 16;
+struct MeshMaterial {
+    uint32_t end;
+    float mu;
+};
 
 // Register hit list per ray.  Each slot costs every exact test one
 // v_med3_f32; a ray with more hits is recomputed exactly by its wave
@@ -695,6 +704,24 @@ __host__ __device__ __forceinline__ float signed_lbuffer(float distance, int sig
     if (sign_sum != 0) return -1.0f;
     if (distance != distance) return xrt_f32_from_bits(kX86SignedNaN);
     return (float)((double)80.000f * xrt_exp(-((double)mu * ((double)distance * 0.1))));
+}
+
+// The materials model's update of L by one mesh the ray hit (the fork's
+// :772 and :805-808 with the mesh filter lifted): a flagged ray stays -1, a
+// mesh whose signs do not cancel flags it, otherwise L is multiplied by
+// exp(-(mu * (distance * 0.1))) in f64 and rounded to f32.  Non-finite values
+// as x86 evaluates them: a NaN exponent (a NaN distance, or mu == 0 with an
+// infinite one) comes back from exp with its sign cleared by the negation and
+// replaces a number; a NaN L keeps its bits; inf * 0 is x86's default NaN.
+__host__ __device__ __forceinline__ float materials_update(float L, float distance, int sign_sum, float mu)
+{
+    if (L == -1.0f) return L;
+    if (sign_sum != 0) return -1.0f;
+    if (L != L) return L;
+    const double x = (double)mu * ((double)distance * 0.1);
+    if (x != x) return xrt_f32_from_bits(kX86SignedNaN);
+    const float f = (float)((double)L * xrt_exp(-x));
+    return f != f ? xrt_f32_from_bits(kX86DefaultNaN) : f;
 }
 
 // 8-bit image: Image::applyLUT's per-pixel formula (include/Image.inl:195-211)

@@ -108,6 +108,10 @@ struct Outputs {
     uint32_t packed;
     uint32_t hit_tiles;
     const uint32_t* hit_off;
+    // kModelMaterials: the scene's meshes (id range and coefficient each), read
+    // wave-uniformly through the constant address space
+    const __attribute__((address_space(4))) MeshMaterial* materials;
+    uint32_t num_meshes;
 };
 // (the hit layout has its own instantiation of the binned render, kHits: its
 // stores in the ordinary render cost 10-35% of the kernel's time)
@@ -689,12 +693,57 @@ __device__ __forceinline__ void finish_ray(const RenderParams& p, const Outputs&
 // by the whole wave: the hits in triangle order by repeated scans for the
 // next larger triangle id (ids are distinct), each term added in turn.  Ray
 // (both directions) and result are wave-uniform; rare path.
-template <typename Fetch>
-__device__ float wave_signed_overflow_distance(const TriRec* __restrict__ recs, uint32_t n_cand, Fetch fetch,
+//
+// Both walks hand each term, in triangle order, to an accumulator: the signed
+// model's sums them (SignedSum); the materials model's closes a mesh at each
+// id range boundary and chains L (MaterialsChain).
+struct SignedSum {
+    float distance = 0.0f;
+    __device__ __forceinline__ void add(uint32_t, float term) { distance += term; }
+    __device__ __forceinline__ float result() const { return distance; }
+};
+
+// The sign a term sign * t carries (t > 1e-7): 0 for a zero or NaN term.
+__device__ __forceinline__ int term_sign(float term) { return (int)(0.0f < term) - (int)(term < 0.0f); }
+
+// Wave-uniform throughout (ids and terms come from readlane / wave minima).
+struct MaterialsChain {
+    const __attribute__((address_space(4))) MeshMaterial* tab;
+    uint32_t num_meshes;
+    uint32_t m = 0;
+    float L = 80.0f;                               // fork :314
+    float distance = 0.0f;
+    int sign_sum = 0;
+    bool any = false;
+    __device__ __forceinline__ void close()
+    {
+        if (any) L = materials_update(L, distance, sign_sum, tab[m].mu);
+        distance = 0.0f;
+        sign_sum = 0;
+        any = false;
+    }
+    __device__ __forceinline__ void add(uint32_t id, float term)
+    {
+        while (m + 1u < num_meshes && id >= tab[m].end) {   // ids ascend: earlier meshes are complete
+            close();
+            ++m;
+        }
+        distance += term;
+        sign_sum += term_sign(term);
+        any = true;
+    }
+    __device__ __forceinline__ float result()
+    {
+        close();
+        return L;
+    }
+};
+
+template <typename Acc, typename Fetch>
+__device__ float wave_signed_overflow_distance(Acc acc, const TriRec* __restrict__ recs, uint32_t n_cand, Fetch fetch,
                                                float dx, float dy, float dz, float sx, float sy, float sz)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    float distance = 0.0f;
     uint32_t prev = 0;
     bool first = true;
     for (;;) {
@@ -716,18 +765,18 @@ __device__ float wave_signed_overflow_distance(const TriRec* __restrict__ recs, 
         float t = 0.0f;
         fixup_hit(recs, best, dx, dy, dz, t);
         const TriRec& r = recs[best];
-        distance += (float)hit_sign(sx, sy, sz, r.pad0, r.pad1, r.pad2) * t;
+        acc.add(best, (float)hit_sign(sx, sy, sz, r.pad0, r.pad1, r.pad2) * t);
         prev = best;
         first = false;
     }
-    return distance;
+    return acc.result();
 }
 
 // The same over the tile's survivors (collect_survivors): each lane tests at
 // most kSurvSlots records and keeps (triangle id, term); the wave takes the
 // terms by ascending id, one wave minimum per hit.
-template <typename Fetch>
-__device__ float wave_signed_survivor_distance(const TriRec* __restrict__ recs,
+template <typename Acc, typename Fetch>
+__device__ float wave_signed_survivor_distance(Acc acc, const TriRec* __restrict__ recs,
                                                const uint32_t (&surv)[kSurvSlots], uint32_t n_surv, Fetch fetch,
                                                float dx, float dy, float dz, float sx, float sy, float sz)
 {
@@ -752,7 +801,6 @@ __device__ float wave_signed_survivor_distance(const TriRec* __restrict__ recs,
         }
     }
     const uint32_t total = wave_reduce_u32<false>(cnt);
-    float distance = 0.0f;
     for (uint32_t q = 0; q < total; ++q) {
         uint32_t mine = id[0];
 #pragma unroll
@@ -767,9 +815,39 @@ __device__ float wave_signed_survivor_distance(const TriRec* __restrict__ recs,
                 id[i] = 0xFFFFFFFFu;
             }
         }
-        distance += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)owner));
+        acc.add(best, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)owner)));
     }
-    return distance;
+    return acc.result();
+}
+
+// The exact results of the wave's overflowed rays (lanes of om, not 0; whole
+// wave): each lane of om gets its ray's accumulator result in `mine`.
+template <typename Acc, typename Fetch, typename Cull>
+__device__ __forceinline__ void signed_overflow_fixup(unsigned long long om, Acc acc,
+                                                      const TriRec* __restrict__ recs, uint32_t n_cand,
+                                                      Fetch fetch, Cull cull, float dx, float dy, float dz,
+                                                      float sx, float sy, float sz, float& mine)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t surv[kSurvSlots] = {}, n_surv = 0;
+    const bool few = cull_enabled(cull) && collect_survivors(n_cand, cull, surv, n_surv);
+    auto each = [&](auto dist) {                      // one loop per path, as in finish_ray
+        do {
+            const uint32_t L = (uint32_t)__builtin_ctzll(om);
+            om &= om - 1ull;
+            auto at = [L](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)L)); };
+            const float d = dist(at(dx), at(dy), at(dz), at(sx), at(sy), at(sz));
+            if (lane == L) mine = d;
+        } while (om);
+    };
+    if (few)
+        each([&](float rx, float ry, float rz, float qx, float qy, float qz) {
+            return wave_signed_survivor_distance(acc, recs, surv, n_surv, fetch, rx, ry, rz, qx, qy, qz);
+        });
+    else
+        each([&](float rx, float ry, float rz, float qx, float qy, float qz) {
+            return wave_signed_overflow_distance(acc, recs, n_cand, fetch, rx, ry, rz, qx, qy, qz);
+        });
 }
 
 // finish_ray of the signed model: the fork's L-buffer value (-1 flags) into
@@ -782,36 +860,64 @@ __device__ __forceinline__ void finish_ray_signed(const RenderParams& p, const O
                                                   float dy, float dz, float sx, float sy, float sz,
                                                   uint32_t n_cand, Fetch fetch, Cull cull = Cull())
 {
-    const uint32_t lane = threadIdx.x & 63u;
     const bool overflow = hl.n > p.hit_capacity;
     const bool flagged = hl.sign_sum != 0;
     wave_stats(ws, active, hl.n, flagged, overflow);
     float distance = hl.distance();
-    unsigned long long om = __ballot(active && overflow && !flagged);
-    if (om) {                                         // wave-uniform, rare
-        uint32_t surv[kSurvSlots] = {}, n_surv = 0;
-        const bool few = cull_enabled(cull) && collect_survivors(n_cand, cull, surv, n_surv);
-        auto each = [&](auto dist) {                  // one loop per path, as in finish_ray
-            do {
-                const uint32_t L = (uint32_t)__builtin_ctzll(om);
-                om &= om - 1ull;
-                auto at = [L](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)L)); };
-                const float d = dist(at(dx), at(dy), at(dz), at(sx), at(sy), at(sz));
-                if (lane == L) distance = d;
-            } while (om);
-        };
-        if (few)
-            each([&](float rx, float ry, float rz, float qx, float qy, float qz) {
-                return wave_signed_survivor_distance(recs, surv, n_surv, fetch, rx, ry, rz, qx, qy, qz);
-            });
-        else
-            each([&](float rx, float ry, float rz, float qx, float qy, float qz) {
-                return wave_signed_overflow_distance(recs, n_cand, fetch, rx, ry, rz, qx, qy, qz);
-            });
-    }
+    const unsigned long long om = __ballot(active && overflow && !flagged);
+    if (om)                                           // wave-uniform, rare
+        signed_overflow_fixup(om, SignedSum(), recs, n_cand, fetch, cull, dx, dy, dz, sx, sy, sz, distance);
     if (!active || !out.lbuffer) return;
     float lval = 80.0f;                               // no term: 80 * exp(-0.0)
     if (__ballot(distance != 0.0f || flagged)) lval = signed_lbuffer(distance, hl.sign_sum, out.mu);
+    out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = lval;
+}
+
+// finish_ray of the materials model: the fork's loop over the meshes with its
+// mesh filter lifted, each mesh with its own coefficient (Outputs::materials).
+// The hit list is in triangle order and a mesh's ids are one range, so per
+// mesh each lane sums, in slot order from 0.0f, the terms of its slots in the
+// range, and their signs (a term sign * t carries its sign); a mesh no lane
+// hit is skipped (L * exp(-0.0) = L exactly), the lanes with hits flag or
+// update L in f64.  A ray with more hits than slots needs every mesh's exact
+// sums -- the global sign sum can cancel between meshes --: the fix-up walks
+// chain L for it, unless the global sum is non-zero (some mesh's is, too, and
+// the ray is flagged).  The odd counter counts flagged rays.
+template <typename Fetch, typename Cull = NoCull>
+__device__ __forceinline__ void finish_ray_materials(const RenderParams& p, const Outputs& out, bool active,
+                                                     uint32_t row, uint32_t col, const SignedHits& hl,
+                                                     WaveStats& ws, const TriRec* __restrict__ recs, float dx,
+                                                     float dy, float dz, float sx, float sy, float sz,
+                                                     uint32_t n_cand, Fetch fetch, Cull cull = Cull())
+{
+    const bool overflow = hl.n > p.hit_capacity;
+    const uint32_t M = out.num_meshes;
+    float lval = 80.0f;                               // fork :314
+    uint32_t begin = 0;
+    for (uint32_t m = 0; m < M; ++m) {                // wave-uniform
+        const uint32_t end = out.materials[m].end;
+        float distance = 0.0f;                        // :778
+        int sign_sum = 0;
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < kMaxHits; ++k) {
+            const bool in = hl.id[k] - begin < end - begin;   // (the empty slots' 0xFFFFFFFF is no triangle's id)
+            distance = in ? distance + hl.v[k] : distance;
+            sign_sum += in ? term_sign(hl.v[k]) : 0;
+            any |= in;
+        }
+        begin = end;
+        if (!__ballot(any)) continue;
+        if (any) lval = materials_update(lval, distance, sign_sum, out.materials[m].mu);
+    }
+    if (hl.sign_sum != 0) lval = -1.0f;               // (an overflowed ray's slots need not show it)
+    const unsigned long long om = __ballot(active && overflow && hl.sign_sum == 0);
+    if (om) {                                         // wave-uniform, rare
+        const MaterialsChain chain{out.materials, M};
+        signed_overflow_fixup(om, chain, recs, n_cand, fetch, cull, dx, dy, dz, sx, sy, sz, lval);
+    }
+    wave_stats(ws, active, hl.n, lval == -1.0f, overflow);
+    if (!active || !out.lbuffer) return;
     out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = lval;
 }
 
@@ -844,7 +950,9 @@ __device__ __forceinline__ void test_record(const TriRec* __restrict__ recs, uin
     if (__ballot(hit)) hl.push_if(hit, t, j, hit_sign(sx, sy, sz, d.y, d.z, d.w));
 }
 
-template <bool kSigned>
+// kModel: what the rays compute (RenderParams::model).  The signed and the
+// materials model share the hit collection (SignedHits) and differ in the finish.
+template <uint32_t kModel>
 __global__ __launch_bounds__(256) void k_render_brute(const TriRec* __restrict__ recs,
                                                       RenderParams p, Outputs out)
 {
@@ -854,6 +962,7 @@ __global__ __launch_bounds__(256) void k_render_brute(const TriRec* __restrict__
     const uint32_t col = (blockIdx.x * 2u + (wave & 1u)) * 8u + (lane & 7u);
     const uint32_t row = p.row_begin + (blockIdx.y * 2u + (wave >> 1)) * 8u + (lane >> 3);
     const bool active = col < p.width && row < p.row_end;
+    constexpr bool kSigned = kModel != kModelAttenuation;
 
     float dx, dy, dz, sx, sy, sz;
     make_tile_ray(p, out, row, col, dx, dy, dz, sx, sy, sz);
@@ -867,7 +976,9 @@ __global__ __launch_bounds__(256) void k_render_brute(const TriRec* __restrict__
     WaveStats ws = {};
     ws.tile_tests = T;
     auto fetch = [](uint32_t k) { return k; };
-    if constexpr (kSigned)
+    if constexpr (kModel == kModelMaterials)
+        finish_ray_materials(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, T, fetch);
+    else if constexpr (kSigned)
         finish_ray_signed(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, T, fetch);
     else
         finish_ray(p, out, active, (size_t)(row - p.row_begin) * p.width + col, hl, ws, recs, dx, dy, dz, T, fetch);
@@ -1730,7 +1841,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
         r.qvz = r.tvx * r.e1y - r.tvy * r.e1x;
         r.tnum = (r.e2x * r.qvx + r.e2y * r.qvy) + r.e2z * r.qvz;
         r.pad0 = r.pad1 = r.pad2 = 0.0f;
-        if (p.model == kModelSigned) {             // Triangle::computeNormal, Triangle.inl:170-178
+        if (p.model != kModelAttenuation) {        // Triangle::computeNormal, Triangle.inl:170-178
             const float nx = r.e1y * r.e2z - r.e1z * r.e2y;
             const float ny = r.e1z * r.e2x - r.e1x * r.e2z;
             const float nz = r.e1x * r.e2y - r.e1y * r.e2x;
@@ -2501,13 +2612,14 @@ __device__ __forceinline__ void merge_half(const RecStage& other, HitList& hl, u
     tests += wave_uniform(__float_as_uint(d.y));
 }
 
-template <bool kSigned, bool kHits>
+template <uint32_t kModel, bool kHits>
 __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restrict__ recs,
                                             const float4* __restrict__ culls, const RenderParams& p,
                                             const Outputs& out, const BinBuffers& bins, uint32_t n_glob,
                                             uint32_t slot, uint32_t tile, WaveStats& ws, uint32_t& cand,
                                             uint32_t split = kSplitNone, const RecStage* partner = nullptr)
 {
+    constexpr bool kSigned = kModel != kModelAttenuation;
     const uint32_t lane = threadIdx.x & 63u;
     // the slot's count (k_prep) and description (host): two scalar loads in flight together
     uint32_t n_local, box_mask, d_base, d_cap, d_xy, d_live;
@@ -2637,7 +2749,9 @@ __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restri
             return whole ? k : __float_as_uint((k < nl ? local[k] : glob[k - nl]).e0.w);
         };
         const EntryCull cull{local, glob, nl, tx0, ty0, !whole};
-        if constexpr (kSigned)
+        if constexpr (kModel == kModelMaterials)
+            finish_ray_materials(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, n_cand, fetch, cull);
+        else if constexpr (kSigned)
             finish_ray_signed(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, n_cand, fetch, cull);
         else
             finish_ray<kHits>(p, out, active, o, hl, ws, recs, dx, dy, dz, n_cand, fetch, cull);
@@ -2697,7 +2811,7 @@ __device__ __forceinline__ void fill_region_rows(const RenderParams& p, const Ou
 // launches a plan that this frame's k_prep confirmed (no pair binned past
 // tile_slots, an empty global list: BinBuffers::plan_miss); otherwise every
 // region renders as tiles.  The signed model always renders tiles.
-template <bool kSigned, bool kHits>
+template <uint32_t kModel, bool kHits>
 __device__ __forceinline__ void render_binned(RecStage* st, const TriRec* __restrict__ recs,
                                               const float4* __restrict__ culls, const RenderParams& p,
                                               const Outputs& out, const BinBuffers& bins,
@@ -2706,6 +2820,7 @@ __device__ __forceinline__ void render_binned(RecStage* st, const TriRec* __rest
     static_assert(kWavesPerRegion >= kTileWaves && kWavesPerRegion % kTileWaves == 0,
                   "a workgroup's waves render tiles of one region");
     constexpr uint32_t kBlocksPerRegion = kWavesPerRegion / kTileWaves;
+    constexpr bool kSigned = kModel != kModelAttenuation;
     const uint64_t t_start = block_start_stamp();
     // a device-planned frame (BinBuffers::dev_plan, a moving camera): its tile
     // regions' number from k_size_lists
@@ -2765,7 +2880,7 @@ __device__ __forceinline__ void render_binned(RecStage* st, const TriRec* __rest
         slot = g / kWavesPerRegion;                  // workgroup-uniform
         tile = g % kWavesPerRegion;
     }
-    render_tile<kSigned, kHits>(st[wave], recs, culls, p, out, bins, n_glob, slot, tile, ws, cand, split, partner);
+    render_tile<kModel, kHits>(st[wave], recs, culls, p, out, bins, n_glob, slot, tile, ws, cand, split, partner);
     // one record per tile (a split tile's by half 0); candidates are counted
     // once per region (by the wave holding tile 0)
     if (split != kSplitHalf1)
@@ -2773,13 +2888,13 @@ __device__ __forceinline__ void render_binned(RecStage* st, const TriRec* __rest
                          out.wave_times, t_start);
 }
 
-template <bool kSigned>
-__global__ __launch_bounds__(64 * kTileWaves) __attribute__((amdgpu_waves_per_eu(kSigned ? 5 : XRT_RENDER_WAVES, 8))) void k_render_binned(
+template <uint32_t kModel>
+__global__ __launch_bounds__(64 * kTileWaves) __attribute__((amdgpu_waves_per_eu(kModel != kModelAttenuation ? 5 : XRT_RENDER_WAVES, 8))) void k_render_binned(
     const TriRec* __restrict__ recs, const float4* __restrict__ culls, RenderParams p, Outputs out,
     BinBuffers bins, const BinState* __restrict__ bs)
 {
     __shared__ RecStage st[kTileWaves];            // one private stage per wave
-    render_binned<kSigned, false>(st, recs, culls, p, out, bins, bs);
+    render_binned<kModel, false>(st, recs, culls, p, out, bins, bs);
 }
 
 // The same render writing the hit layout (Outputs::packed == kLayoutHits).
@@ -2788,7 +2903,7 @@ __global__ __launch_bounds__(64 * kTileWaves) __attribute__((amdgpu_waves_per_eu
     BinBuffers bins, const BinState* __restrict__ bs)
 {
     __shared__ RecStage st[kTileWaves];
-    render_binned<false, true>(st, recs, culls, p, out, bins, bs);
+    render_binned<kModelAttenuation, true>(st, recs, culls, p, out, bins, bs);
 }
 
 // ---------------------------------------------------------------------------
@@ -3220,6 +3335,19 @@ __global__ void k_probe_math(int op, const float* __restrict__ in, float* __rest
     default: y = (float)lut_u8(x); break;
     }
     outp[i] = y;
+}
+
+// The materials model's chain for n rays of given per-mesh sums: ray i's mesh
+// m has distance[i * M + m] and sign_sum[i * M + m] (null: all zero).
+__global__ void k_probe_materials(const float* __restrict__ distance, const int* __restrict__ sign_sum,
+                                  const float* __restrict__ mu, uint32_t M, float* __restrict__ outp, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float L = 80.0f;
+    for (uint32_t m = 0; m < M; ++m)
+        L = materials_update(L, distance[i * M + m], sign_sum ? sign_sum[i * M + m] : 0, mu[m]);
+    outp[i] = L;
 }
 
 }  // namespace XRT_KERNEL_NS

@@ -513,6 +513,13 @@ struct xrt_context {
     uint32_t miss_code = 0;            // L-buffer bits of a miss (0: +inf; xrt_set_miss_code)
     uint32_t model = kModelAttenuation;   // xrt_set_model
     float mu = 0.1037f;                // kModelSigned: mesh 0's attenuation coefficient
+    // The scene (xrt_upload_scene; xrt_upload_mesh uploads one mesh): mesh m
+    // holds mesh_tris[m] of d_tris' num_tris triangles, one after another.
+    std::vector<uint64_t> mesh_tris;
+    // kModelMaterials (xrt_set_materials): one coefficient per mesh, and the
+    // device table of the scene's id ranges with them (upload_materials)
+    std::vector<float> materials_mu;
+    MeshMaterial* d_materials = nullptr;
     xrt_camera cull_cam = {};          // camera of the cached cull parameters
     CullParams cull = {};
     bool cull_valid = false;
@@ -719,6 +726,15 @@ inline void normalise3(float a[3])
     a[2] /= len;
 }
 
+// The triangles the current model renders: the first of d_tris.  The
+// attenuation and the signed model see mesh 0 only (src/main.cxx:687,
+// main-pthreads-lbuffer.cxx:788), the materials model every mesh.
+inline uint64_t render_tris(const xrt_context* ctx)
+{
+    if (ctx->model == kModelMaterials || ctx->mesh_tris.empty()) return ctx->num_tris;
+    return ctx->mesh_tris[0];
+}
+
 RenderParams make_params(const xrt_camera& c, uint32_t row_begin, uint32_t row_end, uint64_t T,
                          uint32_t capacity)
 {
@@ -890,7 +906,7 @@ int check_camera(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, ui
 int launch_prep(xrt_context* ctx, FrameSet& fs, const RenderParams& p, const CullParams& cp, bool culled,
                 const BinBuffers& bins, BinState* bin_ctl, hipStream_t stream, hipEvent_t done)
 {
-    const uint64_t T = ctx->num_tris;
+    const uint64_t T = render_tris(ctx);
     // p.prep_tris triangles per wave; every thread covers a pixel-offset entry / counter
     const uint64_t threads = std::max<uint64_t>((uint64_t)p.height + p.width, bins.clear ? bins.clear_regions : 0u);
     const uint64_t per_block = (uint64_t)kPrepWaves * p.prep_tris;
@@ -924,7 +940,7 @@ int bin_buffers(xrt_context* ctx, FrameSet& fs, uint32_t n_regions, uint64_t lis
                 BinState*& ctl, hipStream_t stream, bool& cleared, bool rerun = false)
 {
     cleared = false;
-    const uint64_t T = ctx->num_tris;
+    const uint64_t T = render_tris(ctx);
     static_assert(sizeof(BinState) <= kCounterStride * sizeof(uint32_t), "BinState fits its line");
     int rc;
     // per half: control block padded to a line, then one line-padded counter per region
@@ -1078,13 +1094,16 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     if (ctx->num_tris > 0xFFFFFFFFull) return fail(ctx, XRT_ERR_ARGUMENT, "too many triangles");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
 
-    const uint64_t T = ctx->num_tris;
+    const uint64_t T = render_tris(ctx);
     const uint32_t rows = row_end - row_begin;
     const uint32_t rx = (cam->width + kRegion - 1) / kRegion, ry = (rows + kRegion - 1) / kRegion;
     // AUTO: the per-region footprint sweep of TILED costs T x regions box
     // tests; past kAutoSweep of them binning once per frame is cheaper.
     const uint64_t sweep = T * (uint64_t)rx * ry;
-    const bool signed_model = ctx->model == kModelSigned;
+    // (the signed and the materials model: one hit collection, L-buffer only)
+    const bool signed_model = ctx->model != kModelAttenuation;
+    if (ctx->model == kModelMaterials && ctx->materials_mu.size() != ctx->mesh_tris.size())
+        return fail(ctx, XRT_ERR_ARGUMENT, "the scene's mesh count differs from xrt_set_materials'");
     int kernel = ctx->kernel != XRT_KERNEL_AUTO ? ctx->kernel
                  : signed_model || sweep > kAutoSweep ? XRT_KERNEL_BINNED
                                                       : XRT_KERNEL_TILED;
@@ -1150,6 +1169,8 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     const uint32_t miss_bits = ctx->miss_code ? ctx->miss_code : 0x7F800000u;   // +inf
     std::memcpy(&out.miss_l, &miss_bits, sizeof miss_bits);
     out.mu = ctx->mu;
+    out.materials = (const __attribute__((address_space(4))) MeshMaterial*)ctx->d_materials;
+    out.num_meshes = (uint32_t)ctx->materials_mu.size();
     out.packed = 0u;
     out.wave_times = nullptr;          // launch_frame
     out.hit_tiles = 0u;
@@ -1243,7 +1264,7 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
         else if ((rc = fixed_layout(ctx, rx, ry, fixed_cap, bins))) return rc;
         bins.tile_plan = compact && fill_ok && !reuse && !sizing && ctx->plan_valid && ctx->tile_plan_enabled &&
                          ctx->tile_plan_state == 1 ? 1u : 0u;
-        bins.box_masks = ctx->box_masks == 2 || (ctx->box_masks == 1 && ctx->num_tris < kPrepBigMesh) ? 1u : 0u;
+        bins.box_masks = ctx->box_masks == 2 || (ctx->box_masks == 1 && T < kPrepBigMesh) ? 1u : 0u;
         if (sizing) prof_mark(ctx, "fixed layout upload");
         // the fill plan's test hook (every region planned empty) is checked every frame
         arm_plan_check(fs, n_regions, bins, false, ctx->fill_plan == 2);
@@ -1355,7 +1376,7 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
             const uint32_t scatter_blocks = (uint32_t)std::min<uint64_t>((d.pool + 255u) / 256u, 2048u);
             hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, ss, (const uint4*)fs.pairs,
                                (const BinState*)bin_ctl, d.pool, (const SlotDesc*)fs.dyn_desc,
-                               (const float4*)fs.cull, (uint32_t)ctx->num_tris, bins.list, d.flag);
+                               (const float4*)fs.cull, (uint32_t)T, bins.list, d.flag);
             XRT_HIP(ctx, hipGetLastError());
             XRT_HIP(ctx, hipEventRecord(prep_done, ss));
             pf.dev_size.on = false;
@@ -1556,7 +1577,7 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
         const uint32_t scatter_blocks = (uint32_t)std::min<uint64_t>((d.pool + 255u) / 256u, 2048u);
         hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, stream, (const uint4*)fs.pairs,
                            (const BinState*)bin_ctl, d.pool, (const SlotDesc*)fs.dyn_desc, (const float4*)fs.cull,
-                           (uint32_t)ctx->num_tris, pf.bins.list, d.flag);
+                           p.num_triangles, pf.bins.list, d.flag);
         XRT_HIP(ctx, hipGetLastError());
     }
     dim3 grid = pf.grid;
@@ -1638,17 +1659,22 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
         ctx->tev_used += 2;
     }
     if (rows > 0) {
-        const bool sgn = p.model == kModelSigned;
+        const bool sgn = p.model != kModelAttenuation;
+        const bool mat = p.model == kModelMaterials;
         const auto t_launch = HostClock::now();
         if (kernel == XRT_KERNEL_BRUTE)
-            hipExtLaunchKernelGGL(sgn ? k_render_brute<true> : k_render_brute<false>, grid, dim3(256), 0, stream,
+            hipExtLaunchKernelGGL(mat   ? k_render_brute<kModelMaterials>
+                                  : sgn ? k_render_brute<kModelSigned>
+                                        : k_render_brute<kModelAttenuation>, grid, dim3(256), 0, stream,
                                   t0, t1, 0, fs.recs, p, out);
         else if (kernel == XRT_KERNEL_TILED || !binned)
             hipExtLaunchKernelGGL(k_render_tiled, dim3(rx, ry), dim3(256), 0, stream, t0, t1, 0,
                                   fs.recs, fs.cull, p, out);
         else
-            hipExtLaunchKernelGGL(sgn ? k_render_binned<true>
-                                      : out.packed == kLayoutHits ? k_render_binned_hits : k_render_binned<false>, grid, dim3(64 * kTileWaves),
+            hipExtLaunchKernelGGL(mat   ? k_render_binned<kModelMaterials>
+                                  : sgn ? k_render_binned<kModelSigned>
+                                  : out.packed == kLayoutHits ? k_render_binned_hits
+                                                              : k_render_binned<kModelAttenuation>, grid, dim3(64 * kTileWaves),
                                   0, stream, t0, t1, 0, fs.recs, fs.cull, p, out, bins, (const BinState*)bin_ctl);
         XRT_HIP(ctx, hipGetLastError());
         ctx->acc_ms[4] += std::chrono::duration<double, std::milli>(HostClock::now() - t_launch).count();
@@ -1695,7 +1721,7 @@ xrt_context::BinKey geometry_key(const xrt_context* ctx, const xrt_camera* cam, 
     key.cam = *cam;
     key.row_begin = row_begin;
     key.row_end = row_end;
-    key.T = ctx->num_tris;
+    key.T = render_tris(ctx);
     key.gen = ctx->mesh_gen;
     return key;
 }
@@ -2019,6 +2045,7 @@ void xrt_destroy(xrt_context* ctx)
     (void)hipFree(ctx->d_stats_done);
     (void)hipFree(ctx->d_stats_out);
     (void)hipFree(ctx->d_hit_off);
+    (void)hipFree(ctx->d_materials);
     (void)hipFree(ctx->d_prep_times);
     for (auto& c : ctx->tchunks) (void)hipFree(c.p);
     lap(1);
@@ -2043,6 +2070,56 @@ const char* xrt_last_error(const xrt_context* ctx)
     return ctx ? ctx->error.c_str() : g_create_error.c_str();
 }
 
+// The materials model's device table from the scene's mesh sizes and the
+// coefficients, when both are set for the same number of meshes (a render
+// checks that they are).  No frame is in flight (the callers synchronise).
+static int upload_materials(xrt_context* ctx)
+{
+    const size_t M = ctx->mesh_tris.size();
+    if (M == 0 || ctx->materials_mu.size() != M) return XRT_OK;
+    MeshMaterial tab[XRT_MAX_MESHES];
+    uint64_t end = 0;
+    for (size_t m = 0; m < M; ++m) {
+        end += ctx->mesh_tris[m];
+        tab[m].end = (uint32_t)end;
+        tab[m].mu = ctx->materials_mu[m];
+    }
+    if (!ctx->d_materials && hipMalloc(&ctx->d_materials, sizeof tab) != hipSuccess)
+        return fail(ctx, XRT_ERR_DEVICE, "materials table allocation failed");
+    XRT_HIP(ctx, hipMemcpy(ctx->d_materials, tab, M * sizeof(MeshMaterial), hipMemcpyHostToDevice));
+    return XRT_OK;
+}
+
+int xrt_upload_scene(xrt_context* ctx, const float* triangles, const uint64_t* mesh_triangles,
+                     uint32_t num_meshes)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (num_meshes < 1 || num_meshes > XRT_MAX_MESHES)
+        return fail(ctx, XRT_ERR_ARGUMENT, "a scene has 1 to XRT_MAX_MESHES meshes");
+    if (!mesh_triangles) return fail(ctx, XRT_ERR_ARGUMENT, "mesh_triangles is NULL");
+    uint64_t num_triangles = 0;
+    for (uint32_t m = 0; m < num_meshes; ++m) {
+        if (mesh_triangles[m] > 0xFFFFFFFFull) return fail(ctx, XRT_ERR_ARGUMENT, "too many triangles");
+        num_triangles += mesh_triangles[m];
+    }
+    if (num_triangles && !triangles) return fail(ctx, XRT_ERR_ARGUMENT, "triangles is NULL");
+    // (ids are 32 bits, and 0xFFFFFFFF marks an empty hit slot)
+    if (num_triangles >= 0xFFFFFFFFull) return fail(ctx, XRT_ERR_ARGUMENT, "too many triangles");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = sync_context(ctx);                   // frames in flight read the mesh (prep stream)
+    if (rc) return rc;
+    rc = ensure(ctx, ctx->d_tris, ctx->tris_cap, 9 * num_triangles);
+    if (rc) return rc;
+    if (num_triangles)
+        XRT_HIP(ctx, hipMemcpy(ctx->d_tris, triangles, 9 * num_triangles * sizeof(float),
+                               hipMemcpyHostToDevice));
+    ctx->num_tris = num_triangles;
+    ctx->mesh_tris.assign(mesh_triangles, mesh_triangles + num_meshes);
+    ++ctx->mesh_gen;
+    ++ctx->state_gen;
+    return upload_materials(ctx);
+}
+
 int xrt_upload_mesh(xrt_context* ctx, const float* triangles, uint64_t num_triangles)
 {
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
@@ -2057,9 +2134,10 @@ int xrt_upload_mesh(xrt_context* ctx, const float* triangles, uint64_t num_trian
         XRT_HIP(ctx, hipMemcpy(ctx->d_tris, triangles, 9 * num_triangles * sizeof(float),
                                hipMemcpyHostToDevice));
     ctx->num_tris = num_triangles;
+    ctx->mesh_tris.assign(1, num_triangles);      // a one-mesh scene
     ++ctx->mesh_gen;
     ++ctx->state_gen;
-    return XRT_OK;
+    return upload_materials(ctx);
 }
 
 int xrt_mesh_bbox(const float* tris, uint64_t n, float lower[3], float upper[3])
@@ -2159,6 +2237,24 @@ int xrt_set_model(xrt_context* ctx, int model, float mu)
     return XRT_OK;
 }
 
+int xrt_set_materials(xrt_context* ctx, const float* mu, uint32_t num_meshes)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (num_meshes < 1 || num_meshes > XRT_MAX_MESHES)
+        return fail(ctx, XRT_ERR_ARGUMENT, "1 to XRT_MAX_MESHES coefficients");
+    if (!mu) return fail(ctx, XRT_ERR_ARGUMENT, "mu is NULL");
+    for (uint32_t m = 0; m < num_meshes; ++m)
+        if (!std::isfinite(mu[m]) || mu[m] < 0.0f)
+            return fail(ctx, XRT_ERR_ARGUMENT, "a coefficient must be finite and >= 0");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = sync_context(ctx);                   // frames in flight read the table
+    if (rc) return rc;
+    ctx->model = kModelMaterials;
+    ctx->materials_mu.assign(mu, mu + num_meshes);
+    ++ctx->state_gen;                   // frames prepared ahead are stale
+    return upload_materials(ctx);
+}
+
 int xrt_hole_fill_device(xrt_context* ctx, uint32_t width, uint32_t height, const float* d_lbuffer,
                          float* d_image, uint8_t* d_u8, void* stream)
 {
@@ -2198,11 +2294,10 @@ int xrt_hole_fill(xrt_context* ctx, uint32_t width, uint32_t height, const float
     return d2h_copy(ctx, ctx->host_stream, copies);
 }
 
-int xrt_render_signed(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
-                      uint8_t* image_u8, xrt_stats* stats)
+// Render of the L-buffer plane and the fork's hole fill over it, into host buffers.
+static int render_and_fill(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
+                           uint8_t* image_u8, xrt_stats* stats)
 {
-    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
-    if (ctx->model != kModelSigned) return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_signed needs XRT_MODEL_SIGNED");
     int rc = check_camera(ctx, camera, 0, camera ? camera->height : 0);
     if (rc) return rc;
     XRT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2227,6 +2322,23 @@ int xrt_render_signed(xrt_context* ctx, const xrt_camera* camera, float* image, 
     if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
     xrt_stats local;
     return xrt_read_stats(ctx, stats ? stats : &local);
+}
+
+int xrt_render_signed(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
+                      uint8_t* image_u8, xrt_stats* stats)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (ctx->model != kModelSigned) return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_signed needs XRT_MODEL_SIGNED");
+    return render_and_fill(ctx, camera, image, lbuffer, image_u8, stats);
+}
+
+int xrt_render_materials(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
+                         uint8_t* image_u8, xrt_stats* stats)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (ctx->model != kModelMaterials)
+        return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_materials needs xrt_set_materials");
+    return render_and_fill(ctx, camera, image, lbuffer, image_u8, stats);
 }
 
 int xrt_set_miss_code(xrt_context* ctx, uint32_t bits)
@@ -2865,13 +2977,47 @@ int xrt_probe_math(xrt_context* ctx, int op, const float* in, float* outp, uint6
     return rc;
 }
 
+int xrt_probe_materials(xrt_context* ctx, const float* distance, const int32_t* sign_sum, const float* mu,
+                        uint32_t num_meshes, float* outp, uint64_t n)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (num_meshes < 1 || num_meshes > XRT_MAX_MESHES) return fail(ctx, XRT_ERR_ARGUMENT, "bad mesh count");
+    if (n == 0) return XRT_OK;
+    if (!distance || !mu || !outp) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t terms = (size_t)n * num_meshes;
+    float *dd = nullptr, *dmu = nullptr, *dout = nullptr;
+    int* ds = nullptr;
+    int rc = XRT_OK;
+    if (hipMalloc(&dd, terms * sizeof(float)) != hipSuccess || hipMalloc(&dmu, num_meshes * sizeof(float)) != hipSuccess ||
+        hipMalloc(&dout, n * sizeof(float)) != hipSuccess ||
+        (sign_sum && hipMalloc(&ds, terms * sizeof(int)) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "probe allocation failed");
+    } else if (hipMemcpy(dd, distance, terms * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(dmu, mu, num_meshes * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+               (sign_sum && hipMemcpy(ds, sign_sum, terms * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "probe upload failed");
+    } else {
+        hipLaunchKernelGGL(k_probe_materials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dd, ds, dmu,
+                           num_meshes, dout, (size_t)n);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpy(outp, dout, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(ctx, XRT_ERR_DEVICE, "probe kernel failed");
+    }
+    (void)hipFree(dd);
+    (void)hipFree(dmu);
+    (void)hipFree(dout);
+    (void)hipFree(ds);
+    return rc;
+}
+
 int xrt_probe_prep(xrt_context* ctx, const xrt_camera* camera, float* records, float* footprint)
 {
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
     int rc = check_camera(ctx, camera, 0, camera ? camera->height : 0);
     if (rc) return rc;
     XRT_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t T = ctx->num_tris;
+    const uint64_t T = render_tris(ctx);
     if (!T) return XRT_OK;
     if ((rc = sync_context(ctx))) return rc;      // no frame in flight uses the set
     FrameSet& fs = ctx->sets[ctx->next_set];
@@ -2929,6 +3075,17 @@ void xrt_host_signed_lbuffer_batch(const float* distance, const int32_t* sign_su
                                    uint64_t n)
 {
     for (uint64_t i = 0; i < n; ++i) outp[i] = signed_lbuffer(distance[i], sign_sum ? sign_sum[i] : 0, mu);
+}
+
+void xrt_host_materials_lbuffer_batch(const float* distance, const int32_t* sign_sum, const float* mu,
+                                      uint32_t num_meshes, float* outp, uint64_t n)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        float L = 80.0f;
+        for (uint32_t m = 0; m < num_meshes; ++m)
+            L = materials_update(L, distance[i * num_meshes + m], sign_sum ? sign_sum[i * num_meshes + m] : 0, mu[m]);
+        outp[i] = L;
+    }
 }
 
 }  // extern "C"

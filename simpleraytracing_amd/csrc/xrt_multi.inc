@@ -677,7 +677,7 @@ int plan_strips(xrt_multi* m, const xrt_camera* camera, std::vector<uint32_t>& b
     };
     const xrt_context* c0 = m->ctx[0];
     const uint32_t bands = (H + kRegion - 1) / kRegion;
-    if (n < 2 || m->split == XRT_SPLIT_EQUAL || c0->model == kModelSigned || bands < n) {
+    if (n < 2 || m->split == XRT_SPLIT_EQUAL || c0->model != kModelAttenuation || bands < n) {
         equal();
         return XRT_OK;
     }
@@ -923,6 +923,17 @@ int xrt_multi_upload_mesh(xrt_multi* m, const float* triangles, uint64_t num_tri
     return XRT_OK;
 }
 
+int xrt_multi_upload_scene(xrt_multi* m, const float* triangles, const uint64_t* mesh_triangles,
+                           uint32_t num_meshes)
+{
+    if (!m) return mfail(nullptr, XRT_ERR_ARGUMENT, "multi context is NULL");
+    for (size_t g = 0; g < m->ctx.size(); ++g) {   // replicated, as the mesh is
+        int rc = check_ctx(m, g, xrt_upload_scene(m->ctx[g], triangles, mesh_triangles, num_meshes));
+        if (rc) return rc;
+    }
+    return XRT_OK;
+}
+
 int xrt_multi_set_kernel(xrt_multi* m, int kernel)
 {
     if (!m) return XRT_ERR_ARGUMENT;
@@ -946,6 +957,18 @@ int xrt_multi_set_model(xrt_multi* m, int model, float mu)
     return XRT_OK;
 }
 
+int xrt_multi_set_materials(xrt_multi* m, const float* mu, uint32_t num_meshes)
+{
+    if (!m) return XRT_ERR_ARGUMENT;
+    for (size_t g = 0; g < m->ctx.size(); ++g) {
+        int rc = check_ctx(m, g, xrt_set_materials(m->ctx[g], mu, num_meshes));
+        if (rc) return rc;
+        rc = check_ctx(m, g, xrt_set_miss_code(m->ctx[g], 0u));   // as for the signed model: a miss is L = 80
+        if (rc) return rc;
+    }
+    return XRT_OK;
+}
+
 int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* d_image, float* d_lbuffer,
                                  uint8_t* d_u8, void* stream)
 {
@@ -960,7 +983,7 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
     std::vector<uint32_t> b, e;
     if ((rc = plan_strips(m, camera, b, e))) return rc;
     const bool planes = d_image || d_lbuffer || d_u8;
-    const bool sgn = m->ctx[0]->model == kModelSigned;
+    const bool sgn = m->ctx[0]->model != kModelAttenuation;   // signed or materials: L-buffer strips, hole fill
     // device 0's L-buffer receives the other strips (a scratch frame when the caller wants none)
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
     float* lroot = d_lbuffer;

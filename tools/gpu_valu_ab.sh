@@ -22,7 +22,7 @@ for v in ${VARIANTS:-base}; do
 import json, sys
 d, v, c = sys.argv[1:4]
 s = json.load(open(d + "/summary.json"))
-k = [k for k in s if "k_render_binned" in k and "true" not in k][0]
+k = [k for k in s if "k_render_binned" in k and ("<0u>" in k or "<false>" in k)][0]   # the attenuation instantiation (older builds: a bool)
 r = s[k]
 b = json.load(open(d + ".json"))
 lo = b.get("at_loaded_clocks") or {}
