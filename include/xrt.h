@@ -334,6 +334,36 @@ int xrt_set_materials(xrt_context* ctx, const float* mu, uint32_t num_meshes);
 int xrt_render_materials(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
                          uint8_t* image_u8, xrt_stats* stats);
 
+/* --- the spectrum model: a polychromatic beam over the same scene --------- */
+
+/*
+ * XRT_MODEL_SPECTRUM: num_bins energy bins (1..XRT_MAX_BINS), bin e with the
+ * weight weight[e] (finite, > 0) and mesh m attenuating in it with
+ * mu[m * num_bins + e] (finite, >= 0; mesh-major).  Per ray, with the per-mesh
+ * f32 sums and flags of XRT_MODEL_MATERIALS:
+ *   L = -1 when some mesh's signs do not cancel, else, in f64 and in this order,
+ *   E = 0; for each bin e: x = 0; for each mesh m: x = x + mu[m][e] * (distance[m] * 0.1);
+ *          E = E + weight[e] * exp(-x);      L = (float)E.
+ * With one bin, weight {80} and one mesh it is XRT_MODEL_SIGNED.  It is not
+ * XRT_MODEL_MATERIALS with one bin and several meshes: that model rounds L to
+ * f32 after every mesh, this one once.  xrt_set_spectrum selects the model and
+ * sets the table (XRT_ERR_ARGUMENT for a NULL pointer, a count outside its
+ * limits, a weight or coefficient outside its range); it waits for the frames
+ * in flight, and no frame prepared under the old table is served.  A render
+ * whose scene has another number of meshes fails with XRT_ERR_ARGUMENT.
+ * Renders write the L-buffer plane only, kernels BRUTE or BINNED (AUTO:
+ * BINNED).  xrt_set_model and xrt_set_materials leave the model.
+ * xrt_render_spectrum is xrt_render_materials for this model: render and hole
+ * fill.  The 8-bit plane keeps its fixed window 0..80: weights that sum above
+ * 80 clamp to 255 there.
+ */
+#define XRT_MODEL_SPECTRUM 3
+#define XRT_MAX_BINS 32
+int xrt_set_spectrum(xrt_context* ctx, const float* weight, const float* mu, uint32_t num_meshes,
+                     uint32_t num_bins);
+int xrt_render_spectrum(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
+                        uint8_t* image_u8, xrt_stats* stats);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*
@@ -384,6 +414,9 @@ int xrt_multi_set_model(xrt_multi* m, int model, float mu);
 int xrt_multi_upload_scene(xrt_multi* m, const float* triangles, const uint64_t* mesh_triangles,
                            uint32_t num_meshes);
 int xrt_multi_set_materials(xrt_multi* m, const float* mu, uint32_t num_meshes);
+/* The spectrum model of every device (xrt_set_spectrum): strips as for the materials model. */
+int xrt_multi_set_spectrum(xrt_multi* m, const float* weight, const float* mu, uint32_t num_meshes,
+                           uint32_t num_bins);
 
 /* Waits for the last frame's gathers; the devices' statistics, summed. */
 int xrt_multi_read_stats(xrt_multi* m, xrt_stats* stats);

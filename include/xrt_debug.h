@@ -77,6 +77,21 @@ int xrt_probe_materials(xrt_context* ctx, const float* distance, const int32_t* 
                         uint32_t num_meshes, float* out, uint64_t n);
 
 /*
+ * The spectrum model's L (xrt.h, XRT_MODEL_SPECTRUM) for n rays of given
+ * per-mesh sums, laid out as the materials pair's; weight[num_bins] and
+ * mu[num_meshes * num_bins], mesh-major, as xrt_set_spectrum takes them (not
+ * validated here).  _host_: the device source compiled for the host; _probe_:
+ * the same on the device.  xrt_host_spectrum_miss: the value of a ray without
+ * a hit, the weight chain the device table carries.  Host buffers.
+ */
+void xrt_host_spectrum_lbuffer_batch(const float* distance, const int32_t* sign_sum, const float* weight,
+                                     const float* mu, uint32_t num_meshes, uint32_t num_bins, float* out,
+                                     uint64_t n);
+float xrt_host_spectrum_miss(const float* weight, uint32_t num_bins);
+int xrt_probe_spectrum(xrt_context* ctx, const float* distance, const int32_t* sign_sum, const float* weight,
+                       const float* mu, uint32_t num_meshes, uint32_t num_bins, float* out, uint64_t n);
+
+/*
  * Test hook: caps the per-ray register hit list at `capacity` (1..12) so the
  * exact overflow path runs.  0 restores the default (12).
  */

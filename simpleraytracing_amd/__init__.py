@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -29,7 +29,7 @@ __all__ = [
     "XRT_KERNEL_BINNED", "XRT_MISS_TRANSIT", "load_meshes", "scene_bbox", "camera_for_scene",
     "XRT_MODEL_ATTENUATION", "XRT_MODEL_SIGNED", "XRT_GATHER_AUTO", "XRT_GATHER_COPY", "XRT_GATHER_RCCL",
     "XRT_SPLIT_EQUAL", "XRT_SPLIT_BALANCED", "XRT_TRANSIT_HITS", "XRT_TRANSIT_PACKED", "XRT_MODEL_MATERIALS",
-    "XRT_MAX_MESHES",
+    "XRT_MAX_MESHES", "XRT_MODEL_SPECTRUM", "XRT_MAX_BINS",
 ]
 
 
@@ -53,6 +53,15 @@ def _scene_arrays(meshes):
     counts = np.array([len(m) for m in meshes], np.uint64)
     tris = np.ascontiguousarray(np.concatenate(meshes) if meshes else np.zeros((0, 9), np.float32))
     return tris, counts
+
+
+def _spectrum_arrays(weights, mu):
+    """K weights and an (M, K) table as xrt_set_spectrum takes them: (weight[K], mu[M, K] mesh-major)."""
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    mu = np.ascontiguousarray(mu, dtype=np.float32)
+    if mu.ndim != 2 or mu.shape[1] != w.size:
+        raise ValueError(f"mu must have shape (meshes, {w.size}), got {mu.shape}")
+    return w, mu
 
 
 def device_count() -> int:
@@ -219,6 +228,33 @@ class Context:
         self._check(self._lib.xrt_probe_materials(
             self._ctx, _fptr(d), s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if s is not None else None,
             _fptr(mu), mu.size, _fptr(out), len(d)), "xrt_probe_materials")
+        return out
+
+    def set_spectrum(self, weights, mu):
+        """XRT_MODEL_SPECTRUM: K bin weights and mu of shape (M, K), mesh m's coefficient in bin e at mu[m, e]."""
+        w, mu = _spectrum_arrays(weights, mu)
+        self._check(self._lib.xrt_set_spectrum(self._ctx, _fptr(w), _fptr(mu), mu.shape[0], w.size), "xrt_set_spectrum")
+
+    def render_spectrum(self, cam: Camera):
+        """The spectrum model end to end: (hole-filled image f32, lbuffer f32 with -1 flags, u8, Stats)."""
+        n = cam.width * cam.height
+        img = np.empty(n, np.float32)
+        lb = np.empty(n, np.float32)
+        u8 = np.empty(n, np.uint8)
+        st = Stats()
+        self._check(self._lib.xrt_render_spectrum(self._ctx, ctypes.byref(cam), _fptr(img), _fptr(lb), _u8ptr(u8),
+                                                  ctypes.byref(st)), "xrt_render_spectrum")
+        return img, lb, u8, st
+
+    def probe_spectrum(self, distance: np.ndarray, sign_sum, weights, mu):
+        """The device's spectrum L of rays with given per-mesh sums ((n, M) arrays; sign_sum may be None)."""
+        w, mu = _spectrum_arrays(weights, mu)
+        d = np.ascontiguousarray(distance, dtype=np.float32).reshape(-1, mu.shape[0])
+        s = None if sign_sum is None else np.ascontiguousarray(sign_sum, dtype=np.int32).reshape(d.shape)
+        out = np.empty(len(d), np.float32)
+        self._check(self._lib.xrt_probe_spectrum(
+            self._ctx, _fptr(d), s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if s is not None else None,
+            _fptr(w), _fptr(mu), mu.shape[0], w.size, _fptr(out), len(d)), "xrt_probe_spectrum")
         return out
 
     def render_signed(self, cam: Camera):
@@ -582,6 +618,15 @@ class MultiContext:
 
     def render_materials(self, cam: Camera):
         """The materials model's frame: (hole-filled image, lbuffer with -1 flags, u8, stats)."""
+        return self.render(cam)
+
+    def set_spectrum(self, weights, mu):
+        w, mu = _spectrum_arrays(weights, mu)
+        self._check(self._lib.xrt_multi_set_spectrum(self._m, _fptr(w), _fptr(mu), mu.shape[0], w.size),
+                    "xrt_multi_set_spectrum")
+
+    def render_spectrum(self, cam: Camera):
+        """The spectrum model's frame: (hole-filled image, lbuffer with -1 flags, u8, stats)."""
         return self.render(cam)
 
     def set_split(self, mode: int, link_bytes_per_us: float = 0.0):

@@ -37,6 +37,8 @@ XRT_MODEL_ATTENUATION = 0
 XRT_MODEL_SIGNED = 1
 XRT_MODEL_MATERIALS = 2
 XRT_MAX_MESHES = 16
+XRT_MODEL_SPECTRUM = 3
+XRT_MAX_BINS = 32
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -148,6 +150,11 @@ XRT_SYMBOLS = {
     "xrt_render_materials": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _fp, _fp, _u8p, ctypes.POINTER(Stats)]),
     "xrt_host_materials_lbuffer_batch": (None, [_fp, _i32p, _fp, _u32, _fp, _u64]),
     "xrt_probe_materials": (ctypes.c_int, [_CtxP, _fp, _i32p, _fp, _u32, _fp, _u64]),
+    "xrt_set_spectrum": (ctypes.c_int, [_CtxP, _fp, _fp, _u32, _u32]),
+    "xrt_render_spectrum": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _fp, _fp, _u8p, ctypes.POINTER(Stats)]),
+    "xrt_host_spectrum_lbuffer_batch": (None, [_fp, _i32p, _fp, _fp, _u32, _u32, _fp, _u64]),
+    "xrt_host_spectrum_miss": (_f, [_fp, _u32]),
+    "xrt_probe_spectrum": (ctypes.c_int, [_CtxP, _fp, _i32p, _fp, _fp, _u32, _u32, _fp, _u64]),
     "xrt_host_mt_check": (None, [_fp, _fp, _fp, _fp, _u64, ctypes.POINTER(ctypes.c_uint8),
                                  ctypes.POINTER(ctypes.c_uint8), _fp]),
     "xrt_set_hit_capacity": (ctypes.c_int, [_CtxP, _u32]),
@@ -189,6 +196,7 @@ XRT_SYMBOLS = {
     "xrt_multi_set_model": (ctypes.c_int, [_MultiP, ctypes.c_int, _f]),
     "xrt_multi_upload_scene": (ctypes.c_int, [_MultiP, _fp, _u64p, _u32]),
     "xrt_multi_set_materials": (ctypes.c_int, [_MultiP, _fp, _u32]),
+    "xrt_multi_set_spectrum": (ctypes.c_int, [_MultiP, _fp, _fp, _u32, _u32]),
     "xrt_render_rows_multi": (ctypes.c_int, [_MultiP, ctypes.POINTER(Camera), _fp, _fp, _u8p,
                                              ctypes.POINTER(Stats)]),
     "xrt_render_rows_multi_device": (ctypes.c_int, [_MultiP, ctypes.POINTER(Camera), _vp, _vp, _vp, _vp]),

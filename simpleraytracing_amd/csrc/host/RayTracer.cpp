@@ -304,6 +304,33 @@ unsigned long long renderLoopMaterials(Image& image, const std::vector<TriangleM
     return stats.odd_rays;
 }
 
+unsigned long long renderLoopSpectrum(Image& image, const std::vector<TriangleMesh>& meshes, RayTracerInfo& info,
+                                      const std::vector<float>& weight, const std::vector<float>& mu,
+                                      std::vector<float>* lbuffer)
+{
+    if (weight.empty() || mu.size() != meshes.size() * weight.size())
+        throw std::invalid_argument("renderLoopSpectrum: one coefficient per mesh and bin");
+    xrt_camera cam = camera_for(image, meshes, info);
+    std::vector<float> soup;
+    std::vector<uint64_t> counts;
+    scene_soup(meshes, soup, counts);
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    int k = kernel_choice();
+    check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
+    slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
+    check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
+    check(ctx, xrt_set_spectrum(ctx, weight.data(), mu.data(), (uint32_t)meshes.size(), (uint32_t)weight.size()),
+          "xrt_set_spectrum");
+    if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
+    xrt_stats stats;
+    const int rc = xrt_render_spectrum(ctx, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
+    xrt_set_model(ctx, XRT_MODEL_ATTENUATION, 0.0f);
+    check(ctx, rc, "xrt_render_spectrum");
+    return stats.odd_rays;
+}
+
 namespace {
 
 // One multi-device context per device list for the process lifetime: the
@@ -401,6 +428,31 @@ unsigned long long renderLoopMaterialsMultiGPU(Image& image, const std::vector<T
     mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
     mcheck(m, xrt_multi_upload_scene(m, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_multi_upload_scene");
     mcheck(m, xrt_multi_set_materials(m, mu.data(), (uint32_t)mu.size()), "xrt_multi_set_materials");
+    if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
+    xrt_stats stats;
+    const int rc = xrt_render_rows_multi(m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
+    xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f);
+    mcheck(m, rc, "xrt_render_rows_multi");
+    return stats.odd_rays;
+}
+
+unsigned long long renderLoopSpectrumMultiGPU(Image& image, const std::vector<TriangleMesh>& meshes,
+                                              RayTracerInfo& info, const std::vector<float>& weight,
+                                              const std::vector<float>& mu, int num_gpus, std::vector<float>* lbuffer)
+{
+    if (weight.empty() || mu.size() != meshes.size() * weight.size())
+        throw std::invalid_argument("renderLoopSpectrumMultiGPU: one coefficient per mesh and bin");
+    xrt_camera cam = camera_for(image, meshes, info);
+    std::vector<float> soup;
+    std::vector<uint64_t> counts;
+    scene_soup(meshes, soup, counts);
+    std::lock_guard<std::mutex> g(multi_lock());
+    xrt_multi* m = multi_context(num_gpus);
+    const int k = kernel_choice();
+    mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
+    mcheck(m, xrt_multi_upload_scene(m, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_multi_upload_scene");
+    mcheck(m, xrt_multi_set_spectrum(m, weight.data(), mu.data(), (uint32_t)meshes.size(), (uint32_t)weight.size()),
+           "xrt_multi_set_spectrum");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
     const int rc = xrt_render_rows_multi(m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);

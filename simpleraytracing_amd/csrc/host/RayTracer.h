@@ -96,6 +96,18 @@ unsigned long long renderLoopMaterialsMultiGPU(Image& output_image, const std::v
                                                RayTracerInfo& info, const std::vector<float>& mu, int num_gpus,
                                                std::vector<float>* lbuffer = nullptr);
 
+// The spectrum model (XRT_MODEL_SPECTRUM): a polychromatic beam of
+// weight.size() energy bins over the same scene, mesh m attenuating in bin e
+// with mu[m * weight.size() + e], and the hole fill into output_image (whose
+// 8-bit window stays 0..80).  `lbuffer` and the return value as above.
+unsigned long long renderLoopSpectrum(Image& output_image, const std::vector<TriangleMesh>& meshes,
+                                      RayTracerInfo& info, const std::vector<float>& weight,
+                                      const std::vector<float>& mu, std::vector<float>* lbuffer = nullptr);
+unsigned long long renderLoopSpectrumMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,
+                                              RayTracerInfo& info, const std::vector<float>& weight,
+                                              const std::vector<float>& mu, int num_gpus,
+                                              std::vector<float>* lbuffer = nullptr);
+
 // Row strips over `num_gpus` devices (rows_per = H / n, remainder to the first
 // strips), one host thread per device; returns the number of odd rays.
 unsigned long long renderLoopMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,

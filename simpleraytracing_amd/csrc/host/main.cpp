@@ -17,6 +17,10 @@
 //                              multi-material L-buffer + hole fill
 //       --materials MU0,MU1,.. the materials model: every mesh attenuates with its
 //                              own coefficient (one value per loaded mesh) + hole fill
+//       --spectrum FILE        the spectrum model: a polychromatic beam.  FILE is
+//                              text, '#' starts a comment; the first data line holds
+//                              the K bin weights, each further line one mesh's K
+//                              coefficients, in load order + hole fill
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -30,7 +34,9 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -55,6 +61,7 @@ void showUsage(const std::string& prog)
               << "\t-k,--kernel brute|tiled|binned\tRender kernel (default: automatic)\n"
               << "\t--signed\t\t\tSigned multi-material L-buffer and hole fill (main-pthreads-lbuffer.cxx)\n"
               << "\t--materials MU0,MU1,...\t\tMaterials model: one attenuation coefficient per loaded mesh, and hole fill\n"
+              << "\t--spectrum FILE\t\t\tSpectrum model: FILE holds a line of K bin weights, then one line of K coefficients per loaded mesh\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -73,6 +80,8 @@ struct Options {
     bool time = false;
     bool signed_model = false;
     std::vector<float> materials;              // --materials: one coefficient per mesh
+    bool spectrum = false;                     // --spectrum: K weights, one row of K coefficients per mesh
+    std::vector<float> spectrum_weight, spectrum_mu;
     bool rows = false;
     unsigned row_begin = 0, row_end = 0;
     unsigned batch = 0;
@@ -94,6 +103,46 @@ std::string parse_str(const char* prog, int argc, char** argv, int& i)
         std::exit(EXIT_FAILURE);
     }
     return argv[i];
+}
+
+// --spectrum FILE: the first data line is the K weights, every further one a
+// mesh's K coefficients ('#' starts a comment, blank lines are skipped).
+void read_spectrum(const std::string& path, std::vector<float>& weight, std::vector<float>& mu)
+{
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("--spectrum: cannot read " + path);
+    std::string line;
+    for (unsigned n = 1; std::getline(in, line); ++n) {
+        line = line.substr(0, line.find('#'));
+        std::istringstream fields(line);
+        std::vector<float> row;
+        for (std::string f; fields >> f;) {
+            size_t used = 0;
+            float v = 0.0f;
+            try {
+                v = std::stof(f, &used);
+            } catch (const std::exception&) {
+                used = 0;
+            }
+            if (used != f.size())
+                throw std::runtime_error("--spectrum: " + path + ":" + std::to_string(n) + ": '" + f + "' is not a number");
+            row.push_back(v);
+        }
+        if (row.empty()) continue;
+        if (weight.empty()) {
+            if (row.size() > XRT_MAX_BINS)
+                throw std::runtime_error("--spectrum: " + path + ":" + std::to_string(n) + ": " + std::to_string(row.size()) +
+                                         " bins, at most " + std::to_string(XRT_MAX_BINS));
+            weight = row;
+        } else if (row.size() != weight.size()) {
+            throw std::runtime_error("--spectrum: " + path + ":" + std::to_string(n) + ": " + std::to_string(row.size()) +
+                                     " coefficients in a row, " + std::to_string(weight.size()) + " bins");
+        } else {
+            mu.insert(mu.end(), row.begin(), row.end());
+        }
+    }
+    if (weight.empty()) throw std::runtime_error("--spectrum: " + path + " holds no weights");
+    if (mu.empty()) throw std::runtime_error("--spectrum: " + path + " holds no mesh's coefficients");
 }
 
 Options processCmd(int argc, char** argv)
@@ -140,6 +189,9 @@ Options processCmd(int argc, char** argv)
                 o.materials.push_back(std::stof(list.substr(pos, next - pos)));
                 pos = next + 1;
             }
+        } else if (a == "--spectrum") {
+            o.spectrum = true;
+            read_spectrum(parse_str(argv[0], argc, argv, i), o.spectrum_weight, o.spectrum_mu);
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -166,10 +218,12 @@ Options processCmd(int argc, char** argv)
     if (o.inputs.empty()) o.inputs.push_back("./dragon.ply");
     if (o.rows && (o.row_begin >= o.row_end || o.row_end > o.height))
         throw std::out_of_range("--rows A:B must satisfy 0 <= A < B <= image height");
-    if ((o.rows || o.batch) && (o.signed_model || !o.materials.empty() || o.gpus > 1))
+    if ((o.rows || o.batch) && (o.signed_model || !o.materials.empty() || o.spectrum || o.gpus > 1))
         throw std::runtime_error("--rows and --batch render the attenuation model on one GPU");
     if (o.signed_model && !o.materials.empty())
         throw std::runtime_error("--signed and --materials are two models: give one");
+    if (o.spectrum && (o.signed_model || !o.materials.empty()))
+        throw std::runtime_error("--spectrum, --signed and --materials are three models: give one");
     return o;
 }
 
@@ -217,6 +271,15 @@ int main(int argc, char** argv)
             std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
             if (opt.gpus > 1) renderLoopMaterialsMultiGPU(image, meshes, info, opt.materials, opt.gpus, l);
             else renderLoopMaterials(image, meshes, info, opt.materials, l);
+        } else if (opt.spectrum) {
+            const size_t rows = opt.spectrum_mu.size() / opt.spectrum_weight.size();
+            if (rows != meshes.size())
+                throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
+                                         " meshes loaded, " + std::to_string(rows) + " rows");
+            std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
+            if (opt.gpus > 1)
+                renderLoopSpectrumMultiGPU(image, meshes, info, opt.spectrum_weight, opt.spectrum_mu, opt.gpus, l);
+            else renderLoopSpectrum(image, meshes, info, opt.spectrum_weight, opt.spectrum_mu, l);
         } else if (opt.signed_model && opt.gpus > 1) {
             renderLoopLBufferMultiGPU(image, meshes, info, opt.gpus, opt.lbuffer.empty() ? nullptr : &lb);
         } else if (opt.signed_model) {

@@ -74,7 +74,7 @@ struct RenderParams {
     uint32_t num_triangles;
     uint32_t hit_capacity;  // <= XRT_MAX_HITS
     uint32_t prep_tris;     // triangles per k_prep wave (prep_tris_for)
-    uint32_t model;         // kModelAttenuation (main.cxx), kModelSigned (the L-buffer fork) or kModelMaterials
+    uint32_t model;         // kModelAttenuation (main.cxx), kModelSigned (the L-buffer fork), kModelMaterials or kModelSpectrum
 };
 
 // What a render computes per ray.
@@ -88,6 +88,21 @@ constexpr uint32_t kMaxMeshes = 16;
 struct MeshMaterial {
     uint32_t end;
     float mu;
+};
+
+// The spectrum model: num_bins energy bins over the materials
+// model's scene, I = sum_e weight[e] * exp(-sum_m mu[m * num_bins + e] * d_m).
+// One device table: the meshes' id-range ends, the bins' weights, the f32 a
+// ray without a hit gets (the host's weight chain, spectrum_miss) and the
+// coefficients, mesh-major.
+constexpr uint32_t kModelSpectrum = 3;
+constexpr uint32_t kMaxBins = 32;
+struct SpectrumTable {
+    uint32_t end[kMaxMeshes];
+    float weight[kMaxBins];
+    float miss;
+    uint32_t num_bins;
+    float mu[kMaxMeshes * kMaxBins];   // [m * num_bins + e]
 };
 
 // Register hit list per ray.  Each slot costs every exact test one
@@ -722,6 +737,44 @@ __host__ __device__ __forceinline__ float materials_update(float L, float distan
     if (x != x) return xrt_f32_from_bits(kX86SignedNaN);
     const float f = (float)((double)L * xrt_exp(-x));
     return f != f ? xrt_f32_from_bits(kX86DefaultNaN) : f;
+}
+
+// The spectrum model's L of one ray from its per-mesh sums: -1
+// when some mesh's signs do not cancel, otherwise, in f64, left to right and
+// without contraction,
+//   E = 0; for each bin e: x = 0; for each mesh j: x = x + mu(j, e) * (dist(j) * 0.1);
+//          E = E + weight(e) * exp(-x)
+// rounded to f32.  The n meshes are whichever the caller lists, in scene order:
+// a mesh the ray did not hit has distance +0.0f and adds +0.0 to an x that is
+// never -0.0, so leaving it out is exact.  dist(j), sign(j), mu(j, e) and
+// weight(e) are callables: the host reads arrays, the render kernels the lane's
+// parked distances and the device table.  With weight > 0 and mu >= 0 every
+// NaN x86 can reach here (x86's default NaN as a distance, 0 * inf, inf - inf
+// in x) is negative in x, positive after the negation, and stays E: it is
+// stored as 0x7FC00000 explicitly, as materials_update stores its.
+template <typename Dist, typename Sign, typename Mu, typename Weight>
+__host__ __device__ __forceinline__ float spectrum_lbuffer(uint32_t n, uint32_t num_bins, Dist dist, Sign sign,
+                                                           Mu mu, Weight weight)
+{
+    bool flagged = false;
+    for (uint32_t j = 0; j < n; ++j) flagged |= sign(j) != 0;
+    if (flagged) return -1.0f;
+    double E = 0.0;
+    for (uint32_t e = 0; e < num_bins; ++e) {
+        double x = 0.0;
+        for (uint32_t j = 0; j < n; ++j) x = x + (double)mu(j, e) * ((double)dist(j) * 0.1);
+        E = E + (double)weight(e) * xrt_exp(-x);
+    }
+    const float f = (float)E;
+    return f != f ? xrt_f32_from_bits(kX86SignedNaN) : f;
+}
+
+// The same for a ray that hits nothing: every exp(-0.0) is 1.
+__host__ __device__ __forceinline__ float spectrum_miss(const float* weight, uint32_t num_bins)
+{
+    double E = 0.0;
+    for (uint32_t e = 0; e < num_bins; ++e) E = E + (double)weight[e] * 1.0;
+    return (float)E;
 }
 
 // 8-bit image: Image::applyLUT's per-pixel formula (include/Image.inl:195-211)

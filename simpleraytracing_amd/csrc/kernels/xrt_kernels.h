@@ -110,7 +110,12 @@ struct Outputs {
     const uint32_t* hit_off;
     // kModelMaterials: the scene's meshes (id range and coefficient each), read
     // wave-uniformly through the constant address space
-    const __attribute__((address_space(4))) MeshMaterial* materials;
+    // (kModelSpectrum: the same meshes' ranges, the bins' weights and the
+    // coefficients per mesh and bin -- one table, read the same way)
+    union {
+        const __attribute__((address_space(4))) MeshMaterial* materials;
+        const __attribute__((address_space(4))) SpectrumTable* spectrum;
+    };
     uint32_t num_meshes;
 };
 // (the hit layout has its own instantiation of the binned render, kHits: its
@@ -696,9 +701,12 @@ __device__ __forceinline__ void finish_ray(const RenderParams& p, const Outputs&
 //
 // Both walks hand each term, in triangle order, to an accumulator: the signed
 // model's sums them (SignedSum); the materials model's closes a mesh at each
-// id range boundary and chains L (MaterialsChain).
+// id range boundary and chains L (MaterialsChain); the spectrum model's keeps
+// every mesh's distance for the finish's pass over the bins (SpectrumChain).
+// for_ray(lane): the accumulator of the ray of that lane, before its walk.
 struct SignedSum {
     float distance = 0.0f;
+    __device__ __forceinline__ SignedSum for_ray(uint32_t) const { return *this; }
     __device__ __forceinline__ void add(uint32_t, float term) { distance += term; }
     __device__ __forceinline__ float result() const { return distance; }
 };
@@ -715,6 +723,7 @@ struct MaterialsChain {
     float distance = 0.0f;
     int sign_sum = 0;
     bool any = false;
+    __device__ __forceinline__ MaterialsChain for_ray(uint32_t) const { return *this; }
     __device__ __forceinline__ void close()
     {
         if (any) L = materials_update(L, distance, sign_sum, tab[m].mu);
@@ -736,6 +745,51 @@ struct MaterialsChain {
     {
         close();
         return L;
+    }
+};
+
+// The spectrum model's: a ray's parked distances are column `lane` of the
+// wave's park (park[j * 64 + lane] for the j-th parked mesh; with an overflowed
+// ray in the wave every mesh is parked, j = m, and the ray's column starts as
+// zeros, finish_ray_spectrum).  Closing a mesh stores its exact f32 sum there,
+// by the ray's own lane, and notes whether its signs cancel; the result is the
+// flag (-1) or 0, and finish_ray_spectrum integrates the column over the bins
+// with every other lane's.  Wave-uniform but for that one store.
+struct SpectrumChain {
+    const __attribute__((address_space(4))) SpectrumTable* tab;
+    uint32_t num_meshes;
+    float* park;
+    uint32_t ray_lane = 0;
+    uint32_t m = 0;
+    float distance = 0.0f;
+    int sign_sum = 0;
+    bool flagged = false;
+    __device__ __forceinline__ SpectrumChain for_ray(uint32_t lane) const
+    {
+        SpectrumChain c = *this;
+        c.ray_lane = lane;
+        return c;
+    }
+    __device__ __forceinline__ void close()
+    {
+        if ((threadIdx.x & 63u) == ray_lane) park[m * 64u + ray_lane] = distance;
+        flagged |= sign_sum != 0;
+        distance = 0.0f;
+        sign_sum = 0;
+    }
+    __device__ __forceinline__ void add(uint32_t id, float term)
+    {
+        while (m + 1u < num_meshes && id >= tab->end[m]) {   // ids ascend: earlier meshes are complete
+            close();
+            ++m;
+        }
+        distance += term;
+        sign_sum += term_sign(term);
+    }
+    __device__ __forceinline__ float result()
+    {
+        close();
+        return flagged ? -1.0f : 0.0f;
     }
 };
 
@@ -836,17 +890,17 @@ __device__ __forceinline__ void signed_overflow_fixup(unsigned long long om, Acc
             const uint32_t L = (uint32_t)__builtin_ctzll(om);
             om &= om - 1ull;
             auto at = [L](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)L)); };
-            const float d = dist(at(dx), at(dy), at(dz), at(sx), at(sy), at(sz));
+            const float d = dist(acc.for_ray(L), at(dx), at(dy), at(dz), at(sx), at(sy), at(sz));
             if (lane == L) mine = d;
         } while (om);
     };
     if (few)
-        each([&](float rx, float ry, float rz, float qx, float qy, float qz) {
-            return wave_signed_survivor_distance(acc, recs, surv, n_surv, fetch, rx, ry, rz, qx, qy, qz);
+        each([&](Acc a, float rx, float ry, float rz, float qx, float qy, float qz) {
+            return wave_signed_survivor_distance(a, recs, surv, n_surv, fetch, rx, ry, rz, qx, qy, qz);
         });
     else
-        each([&](float rx, float ry, float rz, float qx, float qy, float qz) {
-            return wave_signed_overflow_distance(acc, recs, n_cand, fetch, rx, ry, rz, qx, qy, qz);
+        each([&](Acc a, float rx, float ry, float rz, float qx, float qy, float qz) {
+            return wave_signed_overflow_distance(a, recs, n_cand, fetch, rx, ry, rz, qx, qy, qz);
         });
 }
 
@@ -921,6 +975,79 @@ __device__ __forceinline__ void finish_ray_materials(const RenderParams& p, cons
     out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = lval;
 }
 
+// finish_ray of the spectrum model: the materials model's
+// per-mesh sums, kept instead of chained, then integrated over the energy
+// bins by spectrum_lbuffer.  Two passes, so that no lane holds per-bin or
+// per-mesh f64 state beside the hit list:
+//   1. per mesh (wave-uniform loop, slot order from 0.0f, as
+//      finish_ray_materials) each lane sums its slots in the range; a mesh some
+//      lane hit is parked -- the lanes' distances in park[j * 64 + lane], its
+//      index in a 4-bit field of `meshes` --, a non-zero sign sum flags the lane;
+//   2. the hit list is dead: bins outer, parked meshes inner, one x and one E
+//      live; coefficients and weights by scalar loads from the table.
+// `park` is the wave's own kMaxMeshes * 64 floats of LDS, each lane reading
+// and writing its own column only: no barrier.  A wave no lane of which hit
+// stores the table's miss value.  A ray with more hits than slots gets exact
+// per-mesh sums from the fix-up walks (SpectrumChain) into its column; such a
+// wave parks every mesh.  Only a non-zero global sign sum skips the walk.
+template <typename Fetch, typename Cull = NoCull>
+__device__ __forceinline__ void finish_ray_spectrum(const RenderParams& p, const Outputs& out, bool active,
+                                                    uint32_t row, uint32_t col, const SignedHits& hl,
+                                                    WaveStats& ws, const TriRec* __restrict__ recs, float dx,
+                                                    float dy, float dz, float sx, float sy, float sz,
+                                                    uint32_t n_cand, Fetch fetch, float* park, Cull cull = Cull())
+{
+    static_assert(kMaxMeshes <= 16u, "a parked mesh's index is a 4-bit field");
+    const uint32_t lane = threadIdx.x & 63u;
+    const auto tab = out.spectrum;
+    const bool overflow = hl.n > p.hit_capacity;
+    const uint32_t M = out.num_meshes;
+    const unsigned long long om = __ballot(active && overflow && hl.sign_sum == 0);
+    bool flagged = false;
+    unsigned long long meshes = 0ull;                 // wave-uniform: the parked meshes' indices
+    uint32_t n_parked = 0;
+    uint32_t begin = 0;
+    for (uint32_t m = 0; m < M; ++m) {                // wave-uniform
+        const uint32_t end = tab->end[m];
+        float distance = 0.0f;
+        int sign_sum = 0;
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < kMaxHits; ++k) {
+            const bool in = hl.id[k] - begin < end - begin;   // (the empty slots' 0xFFFFFFFF is no triangle's id)
+            distance = in ? distance + hl.v[k] : distance;
+            sign_sum += in ? term_sign(hl.v[k]) : 0;
+            any |= in;
+        }
+        begin = end;
+        if (!om && !__ballot(any)) continue;
+        // (an overflowed ray's column starts as zeros: its walk stores the meshes it meets)
+        park[n_parked * 64u + lane] = (om >> lane) & 1ull ? 0.0f : distance;
+        flagged |= sign_sum != 0;
+        meshes |= (unsigned long long)m << (4u * n_parked);
+        ++n_parked;
+    }
+    if (om) {                                         // wave-uniform, rare
+        float fix = 0.0f;
+        const SpectrumChain chain{tab, M, park};
+        signed_overflow_fixup(om, chain, recs, n_cand, fetch, cull, dx, dy, dz, sx, sy, sz, fix);
+        if ((om >> lane) & 1ull) flagged = fix == -1.0f;
+    }
+    if (hl.sign_sum != 0) flagged = true;             // (an overflowed ray's slots need not show it)
+    float lval = tab->miss;
+    if (n_parked) {
+        const uint32_t K = tab->num_bins;
+        lval = spectrum_lbuffer(
+            n_parked, K, [&](uint32_t j) { return park[j * 64u + lane]; },
+            [&](uint32_t j) { return (int)(j == 0u && flagged); },   // (the lane's meshes' flags, already reduced)
+            [&](uint32_t j, uint32_t e) { return tab->mu[(uint32_t)((meshes >> (4u * j)) & 15ull) * K + e]; },
+            [&](uint32_t e) { return tab->weight[e]; });
+    }
+    wave_stats(ws, active, hl.n, flagged, overflow);
+    if (!active || !out.lbuffer) return;
+    out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = lval;
+}
+
 // Loads one triangle record with a wave-uniform index (scalar loads).
 __device__ __forceinline__ void test_record(const TriRec* __restrict__ recs, uint32_t j, float dx,
                                             float dy, float dz, HitList& hl)
@@ -976,7 +1103,10 @@ __global__ __launch_bounds__(256) void k_render_brute(const TriRec* __restrict__
     WaveStats ws = {};
     ws.tile_tests = T;
     auto fetch = [](uint32_t k) { return k; };
-    if constexpr (kModel == kModelMaterials)
+    if constexpr (kModel == kModelSpectrum) {
+        __shared__ float park[4][kMaxMeshes * 64u];   // one wave's parked distances each
+        finish_ray_spectrum(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, T, fetch, park[wave]);
+    } else if constexpr (kModel == kModelMaterials)
         finish_ray_materials(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, T, fetch);
     else if constexpr (kSigned)
         finish_ray_signed(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, T, fetch);
@@ -2749,15 +2879,22 @@ __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restri
             return whole ? k : __float_as_uint((k < nl ? local[k] : glob[k - nl]).e0.w);
         };
         const EntryCull cull{local, glob, nl, tx0, ty0, !whole};
-        if constexpr (kModel == kModelMaterials)
+        if constexpr (kModel == kModelSpectrum) {
+            // the wave's stage is dead (its last records are tested): it parks the distances
+            static_assert(sizeof(RecStage) >= kMaxMeshes * 64u * sizeof(float), "the stage holds a wave's parked distances");
+            finish_ray_spectrum(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, n_cand, fetch,
+                                reinterpret_cast<float*>(&st), cull);
+        } else if constexpr (kModel == kModelMaterials)
             finish_ray_materials(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, n_cand, fetch, cull);
         else if constexpr (kSigned)
             finish_ray_signed(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, n_cand, fetch, cull);
         else
             finish_ray<kHits>(p, out, active, o, hl, ws, recs, dx, dy, dz, n_cand, fetch, cull);
-    } else if (kSigned) {   // no survivor: L stays 80 (fork :314; :808 with distance 0)
+    } else if (kSigned) {   // no survivor: L stays 80 (fork :314; :808 with distance 0), or the spectrum's miss value
         ws.rays += (uint32_t)__popcll(__ballot(active));
-        if (active && out.lbuffer) out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = 80.0f;
+        float miss = 80.0f;
+        if constexpr (kModel == kModelSpectrum) miss = out.spectrum->miss;
+        if (active && out.lbuffer) out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = miss;
     } else {   // no survivor: every ray of the tile misses (main.cxx:700-718 with no hit)
         ws.rays += (uint32_t)__popcll(__ballot(active));
         if (hits) store_hit_tile(out, o, false, 0.0f);
@@ -3348,6 +3485,20 @@ __global__ void k_probe_materials(const float* __restrict__ distance, const int*
     for (uint32_t m = 0; m < M; ++m)
         L = materials_update(L, distance[i * M + m], sign_sum ? sign_sum[i * M + m] : 0, mu[m]);
     outp[i] = L;
+}
+
+// The spectrum model's L for n rays of given per-mesh sums, laid out as
+// k_probe_materials' (weight[K], mu[M * K] mesh-major).
+__global__ void k_probe_spectrum(const float* __restrict__ distance, const int* __restrict__ sign_sum,
+                                 const float* __restrict__ weight, const float* __restrict__ mu, uint32_t M,
+                                 uint32_t K, float* __restrict__ outp, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    outp[i] = spectrum_lbuffer(
+        M, K, [=](uint32_t m) { return distance[i * M + m]; },
+        [=](uint32_t m) { return sign_sum ? sign_sum[i * M + m] : 0; },
+        [=](uint32_t m, uint32_t e) { return mu[m * K + e]; }, [=](uint32_t e) { return weight[e]; });
 }
 
 }  // namespace XRT_KERNEL_NS

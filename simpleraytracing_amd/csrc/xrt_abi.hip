@@ -520,6 +520,12 @@ struct xrt_context {
     // device table of the scene's id ranges with them (upload_materials)
     std::vector<float> materials_mu;
     MeshMaterial* d_materials = nullptr;
+    // kModelSpectrum (xrt_set_spectrum): the bins' weights, the coefficients
+    // (mesh-major, spectrum_meshes x weights.size()) and their device table
+    // (upload_spectrum)
+    std::vector<float> spectrum_weight, spectrum_mu;
+    uint32_t spectrum_meshes = 0;
+    SpectrumTable* d_spectrum = nullptr;
     xrt_camera cull_cam = {};          // camera of the cached cull parameters
     CullParams cull = {};
     bool cull_valid = false;
@@ -731,7 +737,7 @@ inline void normalise3(float a[3])
 // main-pthreads-lbuffer.cxx:788), the materials model every mesh.
 inline uint64_t render_tris(const xrt_context* ctx)
 {
-    if (ctx->model == kModelMaterials || ctx->mesh_tris.empty()) return ctx->num_tris;
+    if (ctx->model == kModelMaterials || ctx->model == kModelSpectrum || ctx->mesh_tris.empty()) return ctx->num_tris;
     return ctx->mesh_tris[0];
 }
 
@@ -1104,6 +1110,8 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     const bool signed_model = ctx->model != kModelAttenuation;
     if (ctx->model == kModelMaterials && ctx->materials_mu.size() != ctx->mesh_tris.size())
         return fail(ctx, XRT_ERR_ARGUMENT, "the scene's mesh count differs from xrt_set_materials'");
+    if (ctx->model == kModelSpectrum && ctx->spectrum_meshes != ctx->mesh_tris.size())
+        return fail(ctx, XRT_ERR_ARGUMENT, "the scene's mesh count differs from xrt_set_spectrum's");
     int kernel = ctx->kernel != XRT_KERNEL_AUTO ? ctx->kernel
                  : signed_model || sweep > kAutoSweep ? XRT_KERNEL_BINNED
                                                       : XRT_KERNEL_TILED;
@@ -1169,8 +1177,13 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     const uint32_t miss_bits = ctx->miss_code ? ctx->miss_code : 0x7F800000u;   // +inf
     std::memcpy(&out.miss_l, &miss_bits, sizeof miss_bits);
     out.mu = ctx->mu;
-    out.materials = (const __attribute__((address_space(4))) MeshMaterial*)ctx->d_materials;
-    out.num_meshes = (uint32_t)ctx->materials_mu.size();
+    if (ctx->model == kModelSpectrum) {
+        out.spectrum = (const __attribute__((address_space(4))) SpectrumTable*)ctx->d_spectrum;
+        out.num_meshes = ctx->spectrum_meshes;
+    } else {
+        out.materials = (const __attribute__((address_space(4))) MeshMaterial*)ctx->d_materials;
+        out.num_meshes = (uint32_t)ctx->materials_mu.size();
+    }
     out.packed = 0u;
     out.wave_times = nullptr;          // launch_frame
     out.hit_tiles = 0u;
@@ -1661,9 +1674,11 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
     if (rows > 0) {
         const bool sgn = p.model != kModelAttenuation;
         const bool mat = p.model == kModelMaterials;
+        const bool spc = p.model == kModelSpectrum;
         const auto t_launch = HostClock::now();
         if (kernel == XRT_KERNEL_BRUTE)
-            hipExtLaunchKernelGGL(mat   ? k_render_brute<kModelMaterials>
+            hipExtLaunchKernelGGL(spc   ? k_render_brute<kModelSpectrum>
+                                  : mat ? k_render_brute<kModelMaterials>
                                   : sgn ? k_render_brute<kModelSigned>
                                         : k_render_brute<kModelAttenuation>, grid, dim3(256), 0, stream,
                                   t0, t1, 0, fs.recs, p, out);
@@ -1671,7 +1686,8 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
             hipExtLaunchKernelGGL(k_render_tiled, dim3(rx, ry), dim3(256), 0, stream, t0, t1, 0,
                                   fs.recs, fs.cull, p, out);
         else
-            hipExtLaunchKernelGGL(mat   ? k_render_binned<kModelMaterials>
+            hipExtLaunchKernelGGL(spc   ? k_render_binned<kModelSpectrum>
+                                  : mat ? k_render_binned<kModelMaterials>
                                   : sgn ? k_render_binned<kModelSigned>
                                   : out.packed == kLayoutHits ? k_render_binned_hits
                                                               : k_render_binned<kModelAttenuation>, grid, dim3(64 * kTileWaves),
@@ -2046,6 +2062,7 @@ void xrt_destroy(xrt_context* ctx)
     (void)hipFree(ctx->d_stats_out);
     (void)hipFree(ctx->d_hit_off);
     (void)hipFree(ctx->d_materials);
+    (void)hipFree(ctx->d_spectrum);
     (void)hipFree(ctx->d_prep_times);
     for (auto& c : ctx->tchunks) (void)hipFree(c.p);
     lap(1);
@@ -2090,6 +2107,35 @@ static int upload_materials(xrt_context* ctx)
     return XRT_OK;
 }
 
+// The spectrum model's device table, likewise: the id ranges, the weights,
+// the miss value (the weight chain, in the kernels' order) and the coefficients.
+static int upload_spectrum(xrt_context* ctx)
+{
+    const size_t M = ctx->mesh_tris.size(), K = ctx->spectrum_weight.size();
+    if (M == 0 || K == 0 || ctx->spectrum_meshes != M) return XRT_OK;
+    SpectrumTable tab = {};
+    uint64_t end = 0;
+    for (size_t m = 0; m < M; ++m) {
+        end += ctx->mesh_tris[m];
+        tab.end[m] = (uint32_t)end;
+    }
+    std::copy(ctx->spectrum_weight.begin(), ctx->spectrum_weight.end(), tab.weight);
+    std::copy(ctx->spectrum_mu.begin(), ctx->spectrum_mu.end(), tab.mu);
+    tab.num_bins = (uint32_t)K;
+    tab.miss = spectrum_miss(tab.weight, tab.num_bins);
+    if (!ctx->d_spectrum && hipMalloc(&ctx->d_spectrum, sizeof tab) != hipSuccess)
+        return fail(ctx, XRT_ERR_DEVICE, "spectrum table allocation failed");
+    XRT_HIP(ctx, hipMemcpy(ctx->d_spectrum, &tab, sizeof tab, hipMemcpyHostToDevice));
+    return XRT_OK;
+}
+
+// Both models' tables (a scene upload changes the id ranges of either).
+static int upload_tables(xrt_context* ctx)
+{
+    const int rc = upload_materials(ctx);
+    return rc ? rc : upload_spectrum(ctx);
+}
+
 int xrt_upload_scene(xrt_context* ctx, const float* triangles, const uint64_t* mesh_triangles,
                      uint32_t num_meshes)
 {
@@ -2117,7 +2163,7 @@ int xrt_upload_scene(xrt_context* ctx, const float* triangles, const uint64_t* m
     ctx->mesh_tris.assign(mesh_triangles, mesh_triangles + num_meshes);
     ++ctx->mesh_gen;
     ++ctx->state_gen;
-    return upload_materials(ctx);
+    return upload_tables(ctx);
 }
 
 int xrt_upload_mesh(xrt_context* ctx, const float* triangles, uint64_t num_triangles)
@@ -2137,7 +2183,7 @@ int xrt_upload_mesh(xrt_context* ctx, const float* triangles, uint64_t num_trian
     ctx->mesh_tris.assign(1, num_triangles);      // a one-mesh scene
     ++ctx->mesh_gen;
     ++ctx->state_gen;
-    return upload_materials(ctx);
+    return upload_tables(ctx);
 }
 
 int xrt_mesh_bbox(const float* tris, uint64_t n, float lower[3], float upper[3])
@@ -2255,6 +2301,39 @@ int xrt_set_materials(xrt_context* ctx, const float* mu, uint32_t num_meshes)
     return upload_materials(ctx);
 }
 
+// The argument checks of xrt_set_spectrum (no device needed); null when they pass.
+static const char* spectrum_arguments(const float* weight, const float* mu, uint32_t num_meshes,
+                                      uint32_t num_bins)
+{
+    if (num_meshes < 1 || num_meshes > XRT_MAX_MESHES) return "1 to XRT_MAX_MESHES meshes";
+    if (num_bins < 1 || num_bins > XRT_MAX_BINS) return "1 to XRT_MAX_BINS energy bins";
+    if (!weight) return "weight is NULL";
+    if (!mu) return "mu is NULL";
+    for (uint32_t e = 0; e < num_bins; ++e)
+        if (!std::isfinite(weight[e]) || !(weight[e] > 0.0f)) return "a weight must be finite and > 0";
+    for (uint32_t i = 0; i < num_meshes * num_bins; ++i)
+        if (!std::isfinite(mu[i]) || mu[i] < 0.0f) return "a coefficient must be finite and >= 0";
+    return nullptr;
+}
+
+int xrt_set_spectrum(xrt_context* ctx, const float* weight, const float* mu, uint32_t num_meshes,
+                     uint32_t num_bins)
+{
+    // (the table's checks first: they need no context, and without one their message is xrt_last_error(NULL)'s)
+    if (const char* why = spectrum_arguments(weight, mu, num_meshes, num_bins))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = sync_context(ctx);                   // frames in flight read the table
+    if (rc) return rc;
+    ctx->model = kModelSpectrum;
+    ctx->spectrum_weight.assign(weight, weight + num_bins);
+    ctx->spectrum_mu.assign(mu, mu + (size_t)num_meshes * num_bins);
+    ctx->spectrum_meshes = num_meshes;
+    ++ctx->state_gen;                   // frames prepared ahead are stale
+    return upload_spectrum(ctx);
+}
+
 int xrt_hole_fill_device(xrt_context* ctx, uint32_t width, uint32_t height, const float* d_lbuffer,
                          float* d_image, uint8_t* d_u8, void* stream)
 {
@@ -2338,6 +2417,15 @@ int xrt_render_materials(xrt_context* ctx, const xrt_camera* camera, float* imag
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
     if (ctx->model != kModelMaterials)
         return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_materials needs xrt_set_materials");
+    return render_and_fill(ctx, camera, image, lbuffer, image_u8, stats);
+}
+
+int xrt_render_spectrum(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
+                        uint8_t* image_u8, xrt_stats* stats)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (ctx->model != kModelSpectrum)
+        return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_spectrum needs xrt_set_spectrum");
     return render_and_fill(ctx, camera, image, lbuffer, image_u8, stats);
 }
 
@@ -3011,6 +3099,43 @@ int xrt_probe_materials(xrt_context* ctx, const float* distance, const int32_t* 
     return rc;
 }
 
+int xrt_probe_spectrum(xrt_context* ctx, const float* distance, const int32_t* sign_sum, const float* weight,
+                       const float* mu, uint32_t num_meshes, uint32_t num_bins, float* outp, uint64_t n)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (num_meshes < 1 || num_meshes > XRT_MAX_MESHES) return fail(ctx, XRT_ERR_ARGUMENT, "bad mesh count");
+    if (num_bins < 1 || num_bins > XRT_MAX_BINS) return fail(ctx, XRT_ERR_ARGUMENT, "bad bin count");
+    if (n == 0) return XRT_OK;
+    if (!distance || !weight || !mu || !outp) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t terms = (size_t)n * num_meshes, coeffs = (size_t)num_meshes * num_bins;
+    float *dd = nullptr, *dw = nullptr, *dmu = nullptr, *dout = nullptr;
+    int* ds = nullptr;
+    int rc = XRT_OK;
+    if (hipMalloc(&dd, terms * sizeof(float)) != hipSuccess || hipMalloc(&dw, num_bins * sizeof(float)) != hipSuccess ||
+        hipMalloc(&dmu, coeffs * sizeof(float)) != hipSuccess || hipMalloc(&dout, n * sizeof(float)) != hipSuccess ||
+        (sign_sum && hipMalloc(&ds, terms * sizeof(int)) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "probe allocation failed");
+    } else if (hipMemcpy(dd, distance, terms * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(dw, weight, num_bins * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(dmu, mu, coeffs * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+               (sign_sum && hipMemcpy(ds, sign_sum, terms * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "probe upload failed");
+    } else {
+        hipLaunchKernelGGL(k_probe_spectrum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dd, ds, dw, dmu,
+                           num_meshes, num_bins, dout, (size_t)n);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpy(outp, dout, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(ctx, XRT_ERR_DEVICE, "probe kernel failed");
+    }
+    (void)hipFree(dd);
+    (void)hipFree(dw);
+    (void)hipFree(dmu);
+    (void)hipFree(dout);
+    (void)hipFree(ds);
+    return rc;
+}
+
 int xrt_probe_prep(xrt_context* ctx, const xrt_camera* camera, float* records, float* footprint)
 {
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
@@ -3087,6 +3212,21 @@ void xrt_host_materials_lbuffer_batch(const float* distance, const int32_t* sign
         outp[i] = L;
     }
 }
+
+void xrt_host_spectrum_lbuffer_batch(const float* distance, const int32_t* sign_sum, const float* weight,
+                                     const float* mu, uint32_t num_meshes, uint32_t num_bins, float* outp,
+                                     uint64_t n)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* d = distance + i * num_meshes;
+        const int32_t* s = sign_sum ? sign_sum + i * num_meshes : nullptr;
+        outp[i] = spectrum_lbuffer(
+            num_meshes, num_bins, [=](uint32_t m) { return d[m]; }, [=](uint32_t m) { return s ? s[m] : 0; },
+            [=](uint32_t m, uint32_t e) { return mu[m * num_bins + e]; }, [=](uint32_t e) { return weight[e]; });
+    }
+}
+
+float xrt_host_spectrum_miss(const float* weight, uint32_t num_bins) { return spectrum_miss(weight, num_bins); }
 
 }  // extern "C"
 

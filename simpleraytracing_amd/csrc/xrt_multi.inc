@@ -969,6 +969,19 @@ int xrt_multi_set_materials(xrt_multi* m, const float* mu, uint32_t num_meshes)
     return XRT_OK;
 }
 
+int xrt_multi_set_spectrum(xrt_multi* m, const float* weight, const float* mu, uint32_t num_meshes,
+                           uint32_t num_bins)
+{
+    if (!m) return XRT_ERR_ARGUMENT;
+    for (size_t g = 0; g < m->ctx.size(); ++g) {
+        int rc = check_ctx(m, g, xrt_set_spectrum(m->ctx[g], weight, mu, num_meshes, num_bins));
+        if (rc) return rc;
+        rc = check_ctx(m, g, xrt_set_miss_code(m->ctx[g], 0u));   // a miss is the table's miss value: no transit code
+        if (rc) return rc;
+    }
+    return XRT_OK;
+}
+
 int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* d_image, float* d_lbuffer,
                                  uint8_t* d_u8, void* stream)
 {
@@ -983,7 +996,7 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
     std::vector<uint32_t> b, e;
     if ((rc = plan_strips(m, camera, b, e))) return rc;
     const bool planes = d_image || d_lbuffer || d_u8;
-    const bool sgn = m->ctx[0]->model != kModelAttenuation;   // signed or materials: L-buffer strips, hole fill
+    const bool sgn = m->ctx[0]->model != kModelAttenuation;   // signed, materials or spectrum: L-buffer strips, hole fill
     // device 0's L-buffer receives the other strips (a scratch frame when the caller wants none)
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
     float* lroot = d_lbuffer;
