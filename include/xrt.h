@@ -364,6 +364,51 @@ int xrt_set_spectrum(xrt_context* ctx, const float* weight, const float* mu, uin
 int xrt_render_spectrum(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
                         uint8_t* image_u8, xrt_stats* stats);
 
+/* --- the paths model: trace once, apply any spectrum afterwards ----------- */
+
+/*
+ * XRT_MODEL_PATHS: the render stores what the materials and spectrum models
+ * integrate -- per ray and mesh m of the uploaded scene, the f32 sum of
+ * sign * t over the mesh's hits in triangle order (0.0f for a mesh the ray did
+ * not hit), and a mask whose bit m is set when mesh m's signs do not cancel
+ * (the rays those models flag with -1).  `paths` is num_meshes row-major f32
+ * planes of (row_end - row_begin) * width pixels, one after another; `open`
+ * one uint16 plane of the strip, or NULL.  Every pixel of every plane is
+ * written.  A flagged ray's distances are exact too.  A NaN distance
+ * (inf - inf) is stored as a NaN whose sign and payload are not specified.
+ * xrt_set_paths selects the model; the mesh count is the uploaded scene's at
+ * render time (a later xrt_upload_scene needs no new call), and num_meshes is
+ * the caller's statement of its buffers' size: another value fails with
+ * XRT_ERR_ARGUMENT.  Kernels BRUTE or BINNED (AUTO: BINNED).  With this model
+ * selected only xrt_render_paths[_device] render -- the other entries' planes
+ * mean something else and fail with XRT_ERR_ARGUMENT, as these two do under
+ * another model.  xrt_set_model, xrt_set_materials and xrt_set_spectrum leave
+ * the model.  xrt_render_paths: host buffers, synchronous; _device: device
+ * buffers, asynchronous on `stream`, pipelined as xrt_render_rows_device.
+ * There is no xrt_multi_ form yet: the model is single-device.
+ *
+ * xrt_apply_spectrum[_device]: the spectrum model's L-buffer (above) of
+ * num_pixels rays from such planes (contiguous, plane stride num_pixels; open
+ * NULL: no ray flagged) under the table (weight, mu, num_bins) -- bit for bit
+ * what xrt_render_spectrum stores for the scene, camera and table the planes
+ * came from.  The table is checked as xrt_set_spectrum checks it, before the
+ * context is looked at.  Neither entry touches the context's model, and the
+ * device entry may be called again with another table at once: each launch
+ * carries its own copy.
+ */
+#define XRT_MODEL_PATHS 4
+int xrt_set_paths(xrt_context* ctx);
+int xrt_render_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                     uint32_t num_meshes, float* paths, uint16_t* open, xrt_stats* stats);
+int xrt_render_paths_device(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                            uint32_t num_meshes, float* d_paths, uint16_t* d_open, void* stream);
+int xrt_apply_spectrum(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* paths,
+                       const uint16_t* open, const float* weight, const float* mu, uint32_t num_bins,
+                       float* lbuffer);
+int xrt_apply_spectrum_device(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* d_paths,
+                              const uint16_t* d_open, const float* weight, const float* mu, uint32_t num_bins,
+                              float* d_lbuffer, void* stream);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

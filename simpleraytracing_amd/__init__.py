@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -29,7 +29,7 @@ __all__ = [
     "XRT_KERNEL_BINNED", "XRT_MISS_TRANSIT", "load_meshes", "scene_bbox", "camera_for_scene",
     "XRT_MODEL_ATTENUATION", "XRT_MODEL_SIGNED", "XRT_GATHER_AUTO", "XRT_GATHER_COPY", "XRT_GATHER_RCCL",
     "XRT_SPLIT_EQUAL", "XRT_SPLIT_BALANCED", "XRT_TRANSIT_HITS", "XRT_TRANSIT_PACKED", "XRT_MODEL_MATERIALS",
-    "XRT_MAX_MESHES", "XRT_MODEL_SPECTRUM", "XRT_MAX_BINS",
+    "XRT_MAX_MESHES", "XRT_MODEL_SPECTRUM", "XRT_MAX_BINS", "XRT_MODEL_PATHS",
 ]
 
 
@@ -158,6 +158,7 @@ class Context:
     def __init__(self, device: int = 0):
         self._lib = _abi.load()
         self._ctx = _abi._CtxP()
+        self._num_meshes = 0               # of the uploaded scene (render_paths' planes)
         rc = self._lib.xrt_create(device, ctypes.byref(self._ctx))
         if rc != _abi.XRT_OK:
             raise XrtError(rc, self._lib.xrt_last_error(None).decode())
@@ -187,6 +188,7 @@ class Context:
     def upload_mesh(self, tris: np.ndarray):
         tris = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
         self._check(self._lib.xrt_upload_mesh(self._ctx, _fptr(tris), len(tris)), "xrt_upload_mesh")
+        self._num_meshes = 1
 
     def set_kernel(self, kernel: int):
         self._check(self._lib.xrt_set_kernel(self._ctx, int(kernel)), "xrt_set_kernel")
@@ -201,6 +203,7 @@ class Context:
         self._check(self._lib.xrt_upload_scene(self._ctx, _fptr(tris),
                                                counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(counts)),
                     "xrt_upload_scene")
+        self._num_meshes = len(counts)
 
     def set_materials(self, mu):
         """XRT_MODEL_MATERIALS with one attenuation coefficient per mesh of the scene."""
@@ -256,6 +259,61 @@ class Context:
             self._ctx, _fptr(d), s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if s is not None else None,
             _fptr(w), _fptr(mu), mu.shape[0], w.size, _fptr(out), len(d)), "xrt_probe_spectrum")
         return out
+
+    def set_paths(self):
+        """XRT_MODEL_PATHS: renders store the per-mesh path lengths of the uploaded scene (render_paths)."""
+        self._check(self._lib.xrt_set_paths(self._ctx), "xrt_set_paths")
+
+    def render_paths(self, cam: Camera, row_begin: int = 0, row_end: int | None = None, num_meshes: int | None = None):
+        """The paths model's strip: (paths (M, rows, W) f32, open (rows, W) uint16 -- bit m set where mesh m's
+        signs do not cancel --, Stats).  M is the uploaded scene's mesh count (num_meshes overrides the
+        buffers' size as stated to the library, which checks it against the scene)."""
+        if row_end is None:
+            row_end = cam.height
+        m = self._num_meshes if num_meshes is None else int(num_meshes)
+        rows = max(row_end - row_begin, 0)
+        paths = np.empty((max(m, 1), rows, cam.width), np.float32)
+        opn = np.empty((rows, cam.width), np.uint16)
+        st = Stats()
+        self._check(self._lib.xrt_render_paths(self._ctx, ctypes.byref(cam), row_begin, row_end, m, _fptr(paths),
+                                               opn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), ctypes.byref(st)),
+                    "xrt_render_paths")
+        return paths, opn, st
+
+    def render_paths_device(self, cam: Camera, row_begin: int, row_end: int, num_meshes: int, d_paths: int,
+                            d_open: int = 0, stream: int = 0):
+        """Device-buffer paths render (raw device pointers: num_meshes f32 planes of the strip, one after
+        another, and its uint16 mask plane or 0); asynchronous on `stream`."""
+        rc = self._lib.xrt_render_paths_device(self._ctx, ctypes.byref(cam), row_begin, row_end, int(num_meshes),
+                                               d_paths or None, d_open or None, stream or None)
+        self._check(rc, "xrt_render_paths_device")
+
+    def apply_spectrum(self, paths, open, weights, mu):
+        """The spectrum model's lbuffer from render_paths' planes ((M, ...) f32 and the masks, or None) under
+        the table (weights[K], mu[M, K]): what render_spectrum stores, shaped like one plane."""
+        w, mu = _spectrum_arrays(weights, mu)
+        p = np.ascontiguousarray(paths, dtype=np.float32)
+        if p.ndim < 1 or p.shape[0] != mu.shape[0]:
+            raise ValueError(f"paths must hold {mu.shape[0]} planes, got shape {p.shape}")
+        o = None if open is None else np.ascontiguousarray(open, dtype=np.uint16)
+        if o is not None and o.shape != p.shape[1:]:
+            raise ValueError(f"open must have a plane's shape {p.shape[1:]}, got {o.shape}")
+        out = np.empty(p.shape[1:], np.float32)
+        self._check(self._lib.xrt_apply_spectrum(
+            self._ctx, out.size, mu.shape[0], _fptr(p),
+            o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)) if o is not None else None, _fptr(w), _fptr(mu), w.size,
+            _fptr(out)), "xrt_apply_spectrum")
+        return out
+
+    def apply_spectrum_device(self, num_pixels: int, d_paths: int, d_open: int, weights, mu, d_lbuffer: int,
+                              stream: int = 0):
+        """apply_spectrum over device buffers (raw pointers; the table is host data and travels with the
+        launch); asynchronous on `stream`."""
+        w, mu = _spectrum_arrays(weights, mu)
+        rc = self._lib.xrt_apply_spectrum_device(self._ctx, int(num_pixels), mu.shape[0], d_paths or None,
+                                                 d_open or None, _fptr(w), _fptr(mu), w.size, d_lbuffer or None,
+                                                 stream or None)
+        self._check(rc, "xrt_apply_spectrum_device")
 
     def render_signed(self, cam: Camera):
         """The L-buffer fork end to end: (image f32, lbuffer f32 with -1 flags, u8, Stats)."""

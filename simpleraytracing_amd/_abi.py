@@ -39,6 +39,7 @@ XRT_MODEL_MATERIALS = 2
 XRT_MAX_MESHES = 16
 XRT_MODEL_SPECTRUM = 3
 XRT_MAX_BINS = 32
+XRT_MODEL_PATHS = 4
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -58,6 +59,7 @@ XRT_IMAGE_JPEG = 3
 _f = ctypes.c_float
 _fp = ctypes.POINTER(ctypes.c_float)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
+_u16p = ctypes.POINTER(ctypes.c_uint16)
 _u32 = ctypes.c_uint32
 _u64 = ctypes.c_uint64
 _vp = ctypes.c_void_p
@@ -152,6 +154,12 @@ XRT_SYMBOLS = {
     "xrt_probe_materials": (ctypes.c_int, [_CtxP, _fp, _i32p, _fp, _u32, _fp, _u64]),
     "xrt_set_spectrum": (ctypes.c_int, [_CtxP, _fp, _fp, _u32, _u32]),
     "xrt_render_spectrum": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _fp, _fp, _u8p, ctypes.POINTER(Stats)]),
+    "xrt_set_paths": (ctypes.c_int, [_CtxP]),
+    "xrt_render_paths": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _u32, _u32, _u32, _fp, _u16p,
+                                        ctypes.POINTER(Stats)]),
+    "xrt_render_paths_device": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _u32, _u32, _u32, _vp, _vp, _vp]),
+    "xrt_apply_spectrum": (ctypes.c_int, [_CtxP, _u64, _u32, _fp, _u16p, _fp, _fp, _u32, _fp]),
+    "xrt_apply_spectrum_device": (ctypes.c_int, [_CtxP, _u64, _u32, _vp, _vp, _fp, _fp, _u32, _vp, _vp]),
     "xrt_host_spectrum_lbuffer_batch": (None, [_fp, _i32p, _fp, _fp, _u32, _u32, _fp, _u64]),
     "xrt_host_spectrum_miss": (_f, [_fp, _u32]),
     "xrt_probe_spectrum": (ctypes.c_int, [_CtxP, _fp, _i32p, _fp, _fp, _u32, _u32, _fp, _u64]),

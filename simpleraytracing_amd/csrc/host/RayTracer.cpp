@@ -331,6 +331,60 @@ unsigned long long renderLoopSpectrum(Image& image, const std::vector<TriangleMe
     return stats.odd_rays;
 }
 
+unsigned long long renderLoopPaths(std::vector<std::vector<float>>& paths, std::vector<unsigned short>& open,
+                                   const Image& frame, const std::vector<TriangleMesh>& meshes, RayTracerInfo& info)
+{
+    if (meshes.empty() || meshes.size() > XRT_MAX_MESHES)
+        throw std::invalid_argument("renderLoopPaths: 1 to XRT_MAX_MESHES meshes");
+    xrt_camera cam = camera_for(frame, meshes, info);
+    std::vector<float> soup;
+    std::vector<uint64_t> counts;
+    scene_soup(meshes, soup, counts);
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    int k = kernel_choice();
+    check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
+    slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
+    check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
+    check(ctx, xrt_set_paths(ctx), "xrt_set_paths");
+    const size_t n = (size_t)frame.getWidth() * frame.getHeight();
+    std::vector<float> planes(n * meshes.size());
+    open.resize(n);
+    xrt_stats stats;
+    const int rc = xrt_render_paths(ctx, &cam, 0, cam.height, (uint32_t)meshes.size(), planes.data(), open.data(), &stats);
+    xrt_set_model(ctx, XRT_MODEL_ATTENUATION, 0.0f);
+    check(ctx, rc, "xrt_render_paths");
+    paths.resize(meshes.size());
+    for (size_t m = 0; m < meshes.size(); ++m) paths[m].assign(planes.begin() + m * n, planes.begin() + (m + 1) * n);
+    return stats.odd_rays;
+}
+
+void applySpectrum(Image& image, const std::vector<std::vector<float>>& paths, const std::vector<unsigned short>& open,
+                   const std::vector<float>& weight, const std::vector<float>& mu, std::vector<float>* lbuffer)
+{
+    const size_t n = (size_t)image.getWidth() * image.getHeight();
+    if (weight.empty() || paths.empty() || mu.size() != paths.size() * weight.size())
+        throw std::invalid_argument("applySpectrum: one coefficient per mesh and bin");
+    if (open.size() != n) throw std::invalid_argument("applySpectrum: the mask is not of the image's size");
+    std::vector<float> planes;
+    planes.reserve(n * paths.size());
+    for (const std::vector<float>& plane : paths) {
+        if (plane.size() != n) throw std::invalid_argument("applySpectrum: a plane is not of the image's size");
+        planes.insert(planes.end(), plane.begin(), plane.end());
+    }
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    std::vector<float> local;
+    std::vector<float>& lb = lbuffer ? *lbuffer : local;
+    lb.resize(n);
+    check(ctx, xrt_apply_spectrum(ctx, n, (uint32_t)paths.size(), planes.data(), open.data(), weight.data(), mu.data(),
+                                  (uint32_t)weight.size(), lb.data()), "xrt_apply_spectrum");
+    check(ctx, xrt_hole_fill(ctx, image.getWidth(), image.getHeight(), lb.data(), image.getData(), nullptr),
+          "xrt_hole_fill");
+}
+
 namespace {
 
 // One multi-device context per device list for the process lifetime: the

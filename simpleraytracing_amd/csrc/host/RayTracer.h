@@ -108,6 +108,20 @@ unsigned long long renderLoopSpectrumMultiGPU(Image& output_image, const std::ve
                                               const std::vector<float>& mu, int num_gpus,
                                               std::vector<float>* lbuffer = nullptr);
 
+// The paths model (XRT_MODEL_PATHS): one trace of the scene into per-mesh
+// planes of signed path lengths (paths[m], row-major, of frame's size -- only
+// its size is read) and a mask plane (bit m: mesh m's signs do not cancel on
+// the ray); returns the number of rays with a non-zero mask.  applySpectrum
+// integrates such planes under a spectrum table (renderLoopSpectrum's weight
+// and mu) and runs the hole fill into output_image: what renderLoopSpectrum
+// writes for the same scene, view and table, without tracing again.  One
+// device (there is no multi-GPU form yet).
+unsigned long long renderLoopPaths(std::vector<std::vector<float>>& paths, std::vector<unsigned short>& open,
+                                   const Image& frame, const std::vector<TriangleMesh>& meshes, RayTracerInfo& info);
+void applySpectrum(Image& output_image, const std::vector<std::vector<float>>& paths,
+                   const std::vector<unsigned short>& open, const std::vector<float>& weight,
+                   const std::vector<float>& mu, std::vector<float>* lbuffer = nullptr);
+
 // Row strips over `num_gpus` devices (rows_per = H / n, remainder to the first
 // strips), one host thread per device; returns the number of odd rays.
 unsigned long long renderLoopMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,

@@ -21,6 +21,11 @@
 //                              text, '#' starts a comment; the first data line holds
 //                              the K bin weights, each further line one mesh's K
 //                              coefficients, in load order + hole fill
+//       --paths                the paths model: trace once and write every mesh's plane
+//                              of signed path lengths to NAME.m<m>.EXT and the mask
+//                              of open meshes to NAME.open.EXT (-f NAME.EXT); with
+//                              --spectrum FILE the table is then applied to the planes
+//                              and NAME.EXT is what --spectrum FILE alone writes
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -62,6 +67,7 @@ void showUsage(const std::string& prog)
               << "\t--signed\t\t\tSigned multi-material L-buffer and hole fill (main-pthreads-lbuffer.cxx)\n"
               << "\t--materials MU0,MU1,...\t\tMaterials model: one attenuation coefficient per loaded mesh, and hole fill\n"
               << "\t--spectrum FILE\t\t\tSpectrum model: FILE holds a line of K bin weights, then one line of K coefficients per loaded mesh\n"
+              << "\t--paths\t\t\t\tPaths model: write each mesh's path-length plane (NAME.m<m>.EXT) and the open mask (NAME.open.EXT); with --spectrum FILE, apply it to the planes\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -82,6 +88,7 @@ struct Options {
     std::vector<float> materials;              // --materials: one coefficient per mesh
     bool spectrum = false;                     // --spectrum: K weights, one row of K coefficients per mesh
     std::vector<float> spectrum_weight, spectrum_mu;
+    bool paths = false;                        // --paths: the per-mesh planes (and --spectrum applied to them)
     bool rows = false;
     unsigned row_begin = 0, row_end = 0;
     unsigned batch = 0;
@@ -192,6 +199,8 @@ Options processCmd(int argc, char** argv)
         } else if (a == "--spectrum") {
             o.spectrum = true;
             read_spectrum(parse_str(argv[0], argc, argv, i), o.spectrum_weight, o.spectrum_mu);
+        } else if (a == "--paths") {
+            o.paths = true;
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -220,6 +229,10 @@ Options processCmd(int argc, char** argv)
         throw std::out_of_range("--rows A:B must satisfy 0 <= A < B <= image height");
     if ((o.rows || o.batch) && (o.signed_model || !o.materials.empty() || o.spectrum || o.gpus > 1))
         throw std::runtime_error("--rows and --batch render the attenuation model on one GPU");
+    if (o.paths && (o.signed_model || !o.materials.empty()))
+        throw std::runtime_error("--paths, --signed and --materials are three models: give one");
+    if (o.paths && (o.rows || o.batch || o.gpus > 1))
+        throw std::runtime_error("--paths renders whole frames on one GPU");
     if (o.signed_model && !o.materials.empty())
         throw std::runtime_error("--signed and --materials are two models: give one");
     if (o.spectrum && (o.signed_model || !o.materials.empty()))
@@ -264,6 +277,27 @@ int main(int argc, char** argv)
             xrt_stats st;
             renderLoopRows(image, meshes, info, rb, re, nullptr, nullptr, &st);
             for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
+        } else if (opt.paths) {
+            if (opt.spectrum && opt.spectrum_mu.size() / opt.spectrum_weight.size() != meshes.size())
+                throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
+                                         " meshes loaded, " +
+                                         std::to_string(opt.spectrum_mu.size() / opt.spectrum_weight.size()) + " rows");
+            std::vector<std::vector<float>> planes;
+            std::vector<unsigned short> open;
+            renderLoopPaths(planes, open, image, meshes, info);
+            const size_t dot = opt.output.find_last_of("./");
+            const bool ext = dot != std::string::npos && opt.output[dot] == '.';
+            const std::string stem = ext ? opt.output.substr(0, dot) : opt.output;
+            const std::string suffix = ext ? opt.output.substr(dot) : "";
+            Image plane(opt.width, opt.height, 0.0f);
+            for (size_t m = 0; m < planes.size(); ++m) {
+                std::copy(planes[m].begin(), planes[m].end(), plane.getData());
+                plane.saveTextFile(stem + ".m" + std::to_string(m) + suffix);
+            }
+            std::copy(open.begin(), open.end(), plane.getData());
+            plane.saveTextFile(stem + ".open" + suffix);
+            if (opt.spectrum)                     // (without a table the planes are the output)
+                applySpectrum(image, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.lbuffer.empty() ? nullptr : &lb);
         } else if (!opt.materials.empty()) {
             if (opt.materials.size() != meshes.size())
                 throw std::runtime_error("--materials takes one coefficient per mesh: " + std::to_string(meshes.size()) +
@@ -313,6 +347,7 @@ int main(int argc, char** argv)
                       strip.getData());
             out = &strip;
         }
+        if (opt.paths && !opt.spectrum) return 0;
         out->saveTextFile(opt.output);
         if (!opt.u8.empty()) out->savePGMFile(opt.u8, 0.0f, 80.0f);
         if (!opt.lbuffer.empty()) {

@@ -74,7 +74,7 @@ struct RenderParams {
     uint32_t num_triangles;
     uint32_t hit_capacity;  // <= XRT_MAX_HITS
     uint32_t prep_tris;     // triangles per k_prep wave (prep_tris_for)
-    uint32_t model;         // kModelAttenuation (main.cxx), kModelSigned (the L-buffer fork), kModelMaterials or kModelSpectrum
+    uint32_t model;         // kModelAttenuation (main.cxx), kModelSigned (the L-buffer fork), kModelMaterials, kModelSpectrum or kModelPaths
 };
 
 // What a render computes per ray.
@@ -104,6 +104,13 @@ struct SpectrumTable {
     uint32_t num_bins;
     float mu[kMaxMeshes * kMaxBins];   // [m * num_bins + e]
 };
+
+// The paths model: the render stores the per-mesh sums themselves
+// -- one f32 plane of signed path lengths per mesh and a 16-bit plane whose
+// bit m says that mesh m's signs do not cancel on the ray -- for
+// k_apply_spectrum to integrate under any spectrum table afterwards.
+constexpr uint32_t kModelPaths = 4;
+static_assert(kMaxMeshes <= 16u, "a ray's open mask is 16 bits");
 
 // Register hit list per ray.  Each slot costs every exact test one
 // v_med3_f32; a ray with more hits is recomputed exactly by its wave

@@ -111,10 +111,15 @@ struct Outputs {
     // kModelMaterials: the scene's meshes (id range and coefficient each), read
     // wave-uniformly through the constant address space
     // (kModelSpectrum: the same meshes' ranges, the bins' weights and the
-    // coefficients per mesh and bin -- one table, read the same way)
+    // coefficients per mesh and bin -- one table, read the same way;
+    // kModelPaths: the meshes' id-range ends alone.  That model's planes travel
+    // in the typed pointers above: lbuffer is the base of num_meshes f32 planes
+    // of (row_end - row_begin) * width pixels each, image_u8 the uint16 mask
+    // plane or null, finish_ray_paths)
     union {
         const __attribute__((address_space(4))) MeshMaterial* materials;
         const __attribute__((address_space(4))) SpectrumTable* spectrum;
+        const __attribute__((address_space(4))) uint32_t* path_ends;
     };
     uint32_t num_meshes;
 };
@@ -702,7 +707,8 @@ __device__ __forceinline__ void finish_ray(const RenderParams& p, const Outputs&
 // Both walks hand each term, in triangle order, to an accumulator: the signed
 // model's sums them (SignedSum); the materials model's closes a mesh at each
 // id range boundary and chains L (MaterialsChain); the spectrum model's keeps
-// every mesh's distance for the finish's pass over the bins (SpectrumChain).
+// every mesh's distance for the finish's pass over the bins (SpectrumChain);
+// the paths model's keeps every mesh's distance and flag bit (PathsChain).
 // for_ray(lane): the accumulator of the ray of that lane, before its walk.
 struct SignedSum {
     float distance = 0.0f;
@@ -790,6 +796,48 @@ struct SpectrumChain {
     {
         close();
         return flagged ? -1.0f : 0.0f;
+    }
+};
+
+// The paths model's: SpectrumChain with every mesh parked (column `lane` of
+// the wave's park, park[m * 64 + lane], zeros before the walk) and the meshes'
+// flags kept apart: bit m of the mask is set when mesh m's signs do not cancel.
+// The result is the mask as a float (at most 65535: exact).
+struct PathsChain {
+    const __attribute__((address_space(4))) uint32_t* end;
+    uint32_t num_meshes;
+    float* park;
+    uint32_t ray_lane = 0;
+    uint32_t m = 0;
+    float distance = 0.0f;
+    int sign_sum = 0;
+    uint32_t mask = 0;
+    __device__ __forceinline__ PathsChain for_ray(uint32_t lane) const
+    {
+        PathsChain c = *this;
+        c.ray_lane = lane;
+        return c;
+    }
+    __device__ __forceinline__ void close()
+    {
+        if ((threadIdx.x & 63u) == ray_lane) park[m * 64u + ray_lane] = distance;
+        mask |= (uint32_t)(sign_sum != 0) << m;
+        distance = 0.0f;
+        sign_sum = 0;
+    }
+    __device__ __forceinline__ void add(uint32_t id, float term)
+    {
+        while (m + 1u < num_meshes && id >= end[m]) {   // ids ascend: earlier meshes are complete
+            close();
+            ++m;
+        }
+        distance += term;
+        sign_sum += term_sign(term);
+    }
+    __device__ __forceinline__ float result()
+    {
+        close();
+        return (float)mask;
     }
 };
 
@@ -1048,6 +1096,82 @@ __device__ __forceinline__ void finish_ray_spectrum(const RenderParams& p, const
     out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = lval;
 }
 
+// The paths model's stores of a tile none of whose rays can hit: zeros in
+// every plane and in the mask.
+__device__ __forceinline__ void store_paths_miss(const RenderParams& p, const Outputs& out, bool active,
+                                                 uint32_t row, uint32_t col)
+{
+    if (!active) return;
+    const size_t plane = (size_t)(p.row_end - p.row_begin) * p.width;
+    const size_t o = (size_t)(row - p.row_begin) * p.width + col;
+    for (uint32_t m = 0; m < out.num_meshes; ++m) out.lbuffer[m * plane + o] = 0.0f;
+    if (out.image_u8) reinterpret_cast<uint16_t*>(out.image_u8)[o] = 0u;
+}
+
+// finish_ray of the paths model: the per-mesh sums of
+// finish_ray_materials, stored instead of integrated -- mesh m's f32 distance
+// to plane m (Outputs::lbuffer + m * plane) from inside the wave-uniform mesh
+// loop, a mask of the meshes whose signs do not cancel to the uint16 plane
+// (Outputs::image_u8, may be null).  Every active lane writes every plane: a
+// mesh no lane hit gets its zeros without the mask's update.  A ray with more
+// hits than slots always takes the fix-up walk here, flagged or not -- its
+// distances are the output --: the wave's overflowed lanes clear their column
+// of `park` (the wave's kMaxMeshes * 64 floats of LDS) in the loop, the walks
+// (PathsChain) store the exact sums there, and those lanes' stores come from
+// the park afterwards.  The odd counter counts rays with a non-zero mask.
+template <typename Fetch, typename Cull = NoCull>
+__device__ __forceinline__ void finish_ray_paths(const RenderParams& p, const Outputs& out, bool active,
+                                                 uint32_t row, uint32_t col, const SignedHits& hl,
+                                                 WaveStats& ws, const TriRec* __restrict__ recs, float dx,
+                                                 float dy, float dz, float sx, float sy, float sz,
+                                                 uint32_t n_cand, Fetch fetch, float* park, Cull cull = Cull())
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const auto ends = out.path_ends;
+    const bool overflow = hl.n > p.hit_capacity;
+    const uint32_t M = out.num_meshes;
+    const unsigned long long om = __ballot(active && overflow);
+    const bool walked = (om >> lane) & 1ull;
+    const bool direct = active && !walked;            // the lane's slots hold its ray's every hit
+    const size_t plane = (size_t)(p.row_end - p.row_begin) * p.width;
+    float* __restrict__ dst = out.lbuffer + ((size_t)(row - p.row_begin) * p.width + col);
+    uint32_t mask = 0;
+    uint32_t begin = 0;
+    for (uint32_t m = 0; m < M; ++m) {                // wave-uniform
+        const uint32_t end = ends[m];
+        float distance = 0.0f;
+        int sign_sum = 0;
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < kMaxHits; ++k) {
+            const bool in = hl.id[k] - begin < end - begin;   // (the empty slots' 0xFFFFFFFF is no triangle's id)
+            distance = in ? distance + hl.v[k] : distance;
+            sign_sum += in ? term_sign(hl.v[k]) : 0;
+            any |= in;
+        }
+        begin = end;
+        if (om && walked) park[m * 64u + lane] = 0.0f;   // (its walk stores the meshes it meets)
+        if (!__ballot(any)) {
+            if (direct) dst[m * plane] = 0.0f;
+            continue;
+        }
+        if (direct) dst[m * plane] = distance;
+        mask |= (uint32_t)(sign_sum != 0) << m;
+    }
+    if (om) {                                         // wave-uniform, rare
+        float fix = 0.0f;
+        const PathsChain chain{ends, M, park};
+        signed_overflow_fixup(om, chain, recs, n_cand, fetch, cull, dx, dy, dz, sx, sy, sz, fix);
+        if (walked) {
+            mask = (uint32_t)fix;
+            for (uint32_t m = 0; m < M; ++m) dst[m * plane] = park[m * 64u + lane];
+        }
+    }
+    wave_stats(ws, active, hl.n, mask != 0u, overflow);
+    if (active && out.image_u8)
+        reinterpret_cast<uint16_t*>(out.image_u8)[(size_t)(row - p.row_begin) * p.width + col] = (uint16_t)mask;
+}
+
 // Loads one triangle record with a wave-uniform index (scalar loads).
 __device__ __forceinline__ void test_record(const TriRec* __restrict__ recs, uint32_t j, float dx,
                                             float dy, float dz, HitList& hl)
@@ -1106,6 +1230,9 @@ __global__ __launch_bounds__(256) void k_render_brute(const TriRec* __restrict__
     if constexpr (kModel == kModelSpectrum) {
         __shared__ float park[4][kMaxMeshes * 64u];   // one wave's parked distances each
         finish_ray_spectrum(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, T, fetch, park[wave]);
+    } else if constexpr (kModel == kModelPaths) {
+        __shared__ float park[4][kMaxMeshes * 64u];   // one wave's overflowed rays' distances each
+        finish_ray_paths(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, T, fetch, park[wave]);
     } else if constexpr (kModel == kModelMaterials)
         finish_ray_materials(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, T, fetch);
     else if constexpr (kSigned)
@@ -2884,6 +3011,11 @@ __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restri
             static_assert(sizeof(RecStage) >= kMaxMeshes * 64u * sizeof(float), "the stage holds a wave's parked distances");
             finish_ray_spectrum(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, n_cand, fetch,
                                 reinterpret_cast<float*>(&st), cull);
+        } else if constexpr (kModel == kModelPaths) {
+            // the dead stage, likewise: the park of the wave's overflowed rays
+            static_assert(sizeof(RecStage) >= kMaxMeshes * 64u * sizeof(float), "the stage holds a wave's parked distances");
+            finish_ray_paths(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, n_cand, fetch,
+                             reinterpret_cast<float*>(&st), cull);
         } else if constexpr (kModel == kModelMaterials)
             finish_ray_materials(p, out, active, row, col, hl, ws, recs, dx, dy, dz, sx, sy, sz, n_cand, fetch, cull);
         else if constexpr (kSigned)
@@ -2892,9 +3024,13 @@ __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restri
             finish_ray<kHits>(p, out, active, o, hl, ws, recs, dx, dy, dz, n_cand, fetch, cull);
     } else if (kSigned) {   // no survivor: L stays 80 (fork :314; :808 with distance 0), or the spectrum's miss value
         ws.rays += (uint32_t)__popcll(__ballot(active));
-        float miss = 80.0f;
-        if constexpr (kModel == kModelSpectrum) miss = out.spectrum->miss;
-        if (active && out.lbuffer) out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = miss;
+        if constexpr (kModel == kModelPaths) {        // (zeros in every plane and the mask)
+            store_paths_miss(p, out, active, row, col);
+        } else {
+            float miss = 80.0f;
+            if constexpr (kModel == kModelSpectrum) miss = out.spectrum->miss;
+            if (active && out.lbuffer) out.lbuffer[(size_t)(row - p.row_begin) * p.width + col] = miss;
+        }
     } else {   // no survivor: every ray of the tile misses (main.cxx:700-718 with no hit)
         ws.rays += (uint32_t)__popcll(__ballot(active));
         if (hits) store_hit_tile(out, o, false, 0.0f);
@@ -3499,6 +3635,79 @@ __global__ void k_probe_spectrum(const float* __restrict__ distance, const int* 
         M, K, [=](uint32_t m) { return distance[i * M + m]; },
         [=](uint32_t m) { return sign_sum ? sign_sum[i * M + m] : 0; },
         [=](uint32_t m, uint32_t e) { return mu[m * K + e]; }, [=](uint32_t e) { return weight[e]; });
+}
+
+// k_apply_spectrum's integration of a wave's n_live parked meshes (kN >=
+// n_live, a compile-time bound): spectrum_lbuffer over kN meshes, those past
+// n_live with distance +0.0f (exact: the term is +0.0 and x is never -0.0).
+// With kN a constant both of its loops unroll: the lane's distances sit in
+// registers with static indices, and a bin's kN coefficients and its weight
+// are scalar loads from the kernel's argument segment with nothing between
+// them and no f64 result among their addresses -- issued together, ahead of
+// the bin's chain.
+template <uint32_t kN>
+__device__ __forceinline__ float apply_bins(const SpectrumTable& tab, const float* park, uint32_t n_live,
+                                            unsigned long long meshes)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t K = tab.num_bins;
+    float d[kN];
+    uint32_t row[kN];                                 // wave-uniform: the j-th live mesh's row of mu
+#pragma unroll
+    for (uint32_t j = 0; j < kN; ++j) {
+        d[j] = j < n_live ? park[j * 64u + lane] : 0.0f;
+        row[j] = (uint32_t)((meshes >> (4u * j)) & 15ull) * K;   // (past n_live: mesh 0's, times +0.0)
+    }
+    return spectrum_lbuffer(
+        kN, K, [&](uint32_t j) { return d[j]; }, [](uint32_t) { return 0; },
+        [&](uint32_t j, uint32_t e) { return tab.mu[row[j] + e]; }, [&](uint32_t e) { return tab.weight[e]; });
+}
+
+// The spectrum model's L-buffer from the paths model's planes:
+// one thread per pixel; paths is M planes of n f32 each, open the uint16 masks
+// (null: none set).  L = -1 where the mask is set, else spectrum_lbuffer of
+// the pixel's distances under `tab` -- passed by value: a launch owns its
+// table, so the next call may bring another before this one has run.  Per
+// wave: a mesh whose distance bits are zero on every lane is left out (exact,
+// apply_bins), the others are parked in the wave's LDS in scene order; a wave
+// with no such mesh and no mask stores tab.miss without an exp.  7 waves per
+// SIMD (<= 72 VGPRs; 8 would spill the 16-mesh chain): a bin's time is the
+// latency of xrt_exp's table load, which only occupancy hides.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_apply_spectrum(const float* __restrict__ paths,
+                                                        const uint16_t* __restrict__ open, size_t n, uint32_t M,
+                                                        const SpectrumTable tab, float* __restrict__ outp)
+{
+    __shared__ float s_park[4][kMaxMeshes * 64u];
+    const uint32_t lane = threadIdx.x & 63u;
+    float* park = s_park[wave_in_block()];
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    const bool in = i < n;
+    const uint32_t flags = in && open ? open[i] : 0u;
+    unsigned long long meshes = 0ull;                 // wave-uniform: the parked meshes' indices
+    uint32_t n_live = 0;
+    for (uint32_t m = 0; m < M; ++m) {                // wave-uniform
+        const float d = in ? paths[m * n + i] : 0.0f;
+        if (!__ballot(__float_as_uint(d) != 0u)) continue;
+        park[n_live * 64u + lane] = d;
+        meshes |= (unsigned long long)m << (4u * n_live);
+        ++n_live;
+    }
+    float lval = tab.miss;
+    if (n_live == 0u) {
+        if (!__ballot(flags != 0u)) {                 // the wave's every pixel is a miss
+            if (in) outp[i] = lval;
+            return;
+        }
+    } else if (n_live <= 2u) {
+        lval = apply_bins<2>(tab, park, n_live, meshes);
+    } else if (n_live <= 4u) {
+        lval = apply_bins<4>(tab, park, n_live, meshes);
+    } else if (n_live <= 8u) {
+        lval = apply_bins<8>(tab, park, n_live, meshes);
+    } else {
+        lval = apply_bins<kMaxMeshes>(tab, park, n_live, meshes);
+    }
+    if (in) outp[i] = flags ? -1.0f : lval;
 }
 
 }  // namespace XRT_KERNEL_NS

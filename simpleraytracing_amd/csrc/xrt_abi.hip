@@ -526,6 +526,9 @@ struct xrt_context {
     std::vector<float> spectrum_weight, spectrum_mu;
     uint32_t spectrum_meshes = 0;
     SpectrumTable* d_spectrum = nullptr;
+    // kModelPaths (xrt_set_paths): the scene's id-range ends, kMaxMeshes words,
+    // kept with every scene upload (upload_path_ends)
+    uint32_t* d_path_ends = nullptr;
     xrt_camera cull_cam = {};          // camera of the cached cull parameters
     CullParams cull = {};
     bool cull_valid = false;
@@ -737,7 +740,9 @@ inline void normalise3(float a[3])
 // main-pthreads-lbuffer.cxx:788), the materials model every mesh.
 inline uint64_t render_tris(const xrt_context* ctx)
 {
-    if (ctx->model == kModelMaterials || ctx->model == kModelSpectrum || ctx->mesh_tris.empty()) return ctx->num_tris;
+    if (ctx->model == kModelMaterials || ctx->model == kModelSpectrum || ctx->model == kModelPaths ||
+        ctx->mesh_tris.empty())
+        return ctx->num_tris;
     return ctx->mesh_tris[0];
 }
 
@@ -1118,7 +1123,8 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     if (signed_model) {
         if (kernel == XRT_KERNEL_TILED)
             return fail(ctx, XRT_ERR_ARGUMENT, "the signed model renders with the BRUTE or BINNED kernel");
-        if (d_image || d_u8)
+        // (the paths model's planes travel in d_lbuffer and d_u8: Outputs, xrt_render_paths_device)
+        if (d_image || (d_u8 && ctx->model != kModelPaths))
             return fail(ctx, XRT_ERR_ARGUMENT,
                         "the signed model writes the L-buffer only (the image is xrt_hole_fill's)");
     }
@@ -1180,6 +1186,9 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     if (ctx->model == kModelSpectrum) {
         out.spectrum = (const __attribute__((address_space(4))) SpectrumTable*)ctx->d_spectrum;
         out.num_meshes = ctx->spectrum_meshes;
+    } else if (ctx->model == kModelPaths) {
+        out.path_ends = (const __attribute__((address_space(4))) uint32_t*)ctx->d_path_ends;
+        out.num_meshes = (uint32_t)ctx->mesh_tris.size();
     } else {
         out.materials = (const __attribute__((address_space(4))) MeshMaterial*)ctx->d_materials;
         out.num_meshes = (uint32_t)ctx->materials_mu.size();
@@ -1675,9 +1684,11 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
         const bool sgn = p.model != kModelAttenuation;
         const bool mat = p.model == kModelMaterials;
         const bool spc = p.model == kModelSpectrum;
+        const bool pth = p.model == kModelPaths;
         const auto t_launch = HostClock::now();
         if (kernel == XRT_KERNEL_BRUTE)
-            hipExtLaunchKernelGGL(spc   ? k_render_brute<kModelSpectrum>
+            hipExtLaunchKernelGGL(pth   ? k_render_brute<kModelPaths>
+                                  : spc ? k_render_brute<kModelSpectrum>
                                   : mat ? k_render_brute<kModelMaterials>
                                   : sgn ? k_render_brute<kModelSigned>
                                         : k_render_brute<kModelAttenuation>, grid, dim3(256), 0, stream,
@@ -1686,7 +1697,8 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
             hipExtLaunchKernelGGL(k_render_tiled, dim3(rx, ry), dim3(256), 0, stream, t0, t1, 0,
                                   fs.recs, fs.cull, p, out);
         else
-            hipExtLaunchKernelGGL(spc   ? k_render_binned<kModelSpectrum>
+            hipExtLaunchKernelGGL(pth   ? k_render_binned<kModelPaths>
+                                  : spc ? k_render_binned<kModelSpectrum>
                                   : mat ? k_render_binned<kModelMaterials>
                                   : sgn ? k_render_binned<kModelSigned>
                                   : out.packed == kLayoutHits ? k_render_binned_hits
@@ -1746,10 +1758,15 @@ xrt_context::BinKey geometry_key(const xrt_context* ctx, const xrt_camera* cam, 
 // render; `ahead` (the pipelined device-pointer entry) prepares the next
 // frames of a repeated geometry ahead of their calls (xrt_context::ahead).
 int enqueue_render(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, uint32_t row_end,
-                   float* d_image, float* d_lbuffer, uint8_t* d_u8, hipStream_t stream, bool ahead = false)
+                   float* d_image, float* d_lbuffer, uint8_t* d_u8, hipStream_t stream, bool ahead = false,
+                   bool paths = false)
 {
     int rc = check_camera(ctx, cam, row_begin, row_end);
     if (rc) return rc;
+    // the paths model's planes are not the other entries' (`paths`: xrt_render_paths_device's call)
+    if ((ctx->model == kModelPaths) != paths)
+        return fail(ctx, XRT_ERR_ARGUMENT, paths ? "xrt_render_paths needs xrt_set_paths"
+                                                 : "the paths model renders with xrt_render_paths");
     const xrt_context::BinKey key = geometry_key(ctx, cam, row_begin, row_end);
     const uint32_t outs = (d_image ? 1u : 0u) | (d_lbuffer ? 2u : 0u) | (d_u8 ? 4u : 0u);
     PendingFrame pf;
@@ -2063,6 +2080,7 @@ void xrt_destroy(xrt_context* ctx)
     (void)hipFree(ctx->d_hit_off);
     (void)hipFree(ctx->d_materials);
     (void)hipFree(ctx->d_spectrum);
+    (void)hipFree(ctx->d_path_ends);
     (void)hipFree(ctx->d_prep_times);
     for (auto& c : ctx->tchunks) (void)hipFree(c.p);
     lap(1);
@@ -2129,11 +2147,30 @@ static int upload_spectrum(xrt_context* ctx)
     return XRT_OK;
 }
 
-// Both models' tables (a scene upload changes the id ranges of either).
+// The paths model's: the id-range ends alone, whichever model is selected, so
+// that a scene uploaded after xrt_set_paths renders without another call.
+static int upload_path_ends(xrt_context* ctx)
+{
+    const size_t M = ctx->mesh_tris.size();
+    if (M == 0 || M > kMaxMeshes) return XRT_OK;
+    uint32_t ends[kMaxMeshes] = {};
+    uint64_t end = 0;
+    for (size_t m = 0; m < M; ++m) {
+        end += ctx->mesh_tris[m];
+        ends[m] = (uint32_t)end;
+    }
+    if (!ctx->d_path_ends && hipMalloc(&ctx->d_path_ends, sizeof ends) != hipSuccess)
+        return fail(ctx, XRT_ERR_DEVICE, "paths table allocation failed");
+    XRT_HIP(ctx, hipMemcpy(ctx->d_path_ends, ends, sizeof ends, hipMemcpyHostToDevice));
+    return XRT_OK;
+}
+
+// Every model's table (a scene upload changes the id ranges of each).
 static int upload_tables(xrt_context* ctx)
 {
-    const int rc = upload_materials(ctx);
-    return rc ? rc : upload_spectrum(ctx);
+    int rc = upload_materials(ctx);
+    if (!rc) rc = upload_spectrum(ctx);
+    return rc ? rc : upload_path_ends(ctx);
 }
 
 int xrt_upload_scene(xrt_context* ctx, const float* triangles, const uint64_t* mesh_triangles,
@@ -2332,6 +2369,126 @@ int xrt_set_spectrum(xrt_context* ctx, const float* weight, const float* mu, uin
     ctx->spectrum_meshes = num_meshes;
     ++ctx->state_gen;                   // frames prepared ahead are stale
     return upload_spectrum(ctx);
+}
+
+int xrt_set_paths(xrt_context* ctx)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    ctx->model = kModelPaths;
+    ++ctx->state_gen;                   // frames prepared ahead are stale
+    return XRT_OK;
+}
+
+int xrt_render_paths_device(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                            uint32_t num_meshes, float* d_paths, uint16_t* d_open, void* stream)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (ctx->model != kModelPaths) return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_paths needs xrt_set_paths");
+    if (num_meshes == 0 || num_meshes != ctx->mesh_tris.size())
+        return fail(ctx, XRT_ERR_ARGUMENT, "num_meshes differs from the scene's mesh count");
+    if (!d_paths) return fail(ctx, XRT_ERR_ARGUMENT, "paths is NULL");
+    return enqueue_render(ctx, camera, row_begin, row_end, nullptr, d_paths, reinterpret_cast<uint8_t*>(d_open),
+                          (hipStream_t)stream, true, true);
+}
+
+int xrt_render_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                     uint32_t num_meshes, float* paths, uint16_t* open, xrt_stats* stats)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    int rc = check_camera(ctx, camera, row_begin, row_end);
+    if (rc) return rc;
+    if (ctx->model != kModelPaths) return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_paths needs xrt_set_paths");
+    if (num_meshes == 0 || num_meshes != ctx->mesh_tris.size())
+        return fail(ctx, XRT_ERR_ARGUMENT, "num_meshes differs from the scene's mesh count");
+    if (!paths) return fail(ctx, XRT_ERR_ARGUMENT, "paths is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)(row_end - row_begin) * camera->width;
+    // the planes in the context's L-buffer staging, the masks in its 8-bit one (2 bytes a pixel)
+    const size_t need = n * std::max<size_t>(num_meshes, sizeof(uint16_t));
+    size_t cap_f = ctx->stage_cap, cap_l = ctx->stage_cap, cap_u = ctx->stage_cap;
+    if ((rc = ensure(ctx, ctx->d_image, cap_f, need))) return rc;
+    if ((rc = ensure(ctx, ctx->d_lbuffer, cap_l, need))) return rc;
+    if ((rc = ensure(ctx, ctx->d_u8, cap_u, need))) return rc;
+    ctx->stage_cap = std::min(cap_f, std::min(cap_l, cap_u));
+    uint16_t* d_open = open ? reinterpret_cast<uint16_t*>(ctx->d_u8) : nullptr;
+    // (not prepared ahead: a host-buffer call, as xrt_render_rows)
+    if ((rc = enqueue_render(ctx, camera, row_begin, row_end, nullptr, ctx->d_lbuffer,
+                             reinterpret_cast<uint8_t*>(d_open), ctx->host_stream, false, true)))
+        return rc;
+    std::vector<D2HCopy> copies;
+    if (n) {
+        copies.push_back({paths, ctx->d_lbuffer, n * num_meshes * sizeof(float)});
+        if (open) copies.push_back({open, d_open, n * sizeof(uint16_t)});
+    }
+    if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
+    xrt_stats local;
+    return xrt_read_stats(ctx, stats ? stats : &local);
+}
+
+// The launch of k_apply_spectrum (validated arguments, device pointers).
+static int launch_apply_spectrum(xrt_context* ctx, uint64_t n, uint32_t num_meshes, const float* d_paths,
+                                 const uint16_t* d_open, const float* weight, const float* mu, uint32_t num_bins,
+                                 float* d_lbuffer, hipStream_t stream)
+{
+    SpectrumTable tab = {};             // by value: the launch owns its copy (no context state, no wait)
+    std::copy(weight, weight + num_bins, tab.weight);
+    std::copy(mu, mu + (size_t)num_meshes * num_bins, tab.mu);
+    tab.num_bins = num_bins;
+    tab.miss = spectrum_miss(tab.weight, num_bins);
+    hipLaunchKernelGGL(k_apply_spectrum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_paths, d_open,
+                       (size_t)n, num_meshes, tab, d_lbuffer);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+// The checks both apply entries share, the table's first (no context needed).
+static int apply_arguments(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* paths,
+                           const float* weight, const float* mu, uint32_t num_bins, const float* lbuffer)
+{
+    if (const char* why = spectrum_arguments(weight, mu, num_meshes, num_bins))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (num_pixels > (1ull << 38)) return fail(ctx, XRT_ERR_ARGUMENT, "too many pixels");
+    if (num_pixels && (!paths || !lbuffer)) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
+    return XRT_OK;
+}
+
+int xrt_apply_spectrum_device(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* d_paths,
+                              const uint16_t* d_open, const float* weight, const float* mu, uint32_t num_bins,
+                              float* d_lbuffer, void* stream)
+{
+    int rc = apply_arguments(ctx, num_pixels, num_meshes, d_paths, weight, mu, num_bins, d_lbuffer);
+    if (rc || !num_pixels) return rc;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_apply_spectrum(ctx, num_pixels, num_meshes, d_paths, d_open, weight, mu, num_bins, d_lbuffer,
+                                 (hipStream_t)stream);
+}
+
+int xrt_apply_spectrum(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* paths,
+                       const uint16_t* open, const float* weight, const float* mu, uint32_t num_bins,
+                       float* lbuffer)
+{
+    int rc = apply_arguments(ctx, num_pixels, num_meshes, paths, weight, mu, num_bins, lbuffer);
+    if (rc || !num_pixels) return rc;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)num_pixels;
+    float *dp = nullptr, *dl = nullptr;
+    uint16_t* dopen = nullptr;
+    if (hipMalloc(&dp, n * num_meshes * sizeof(float)) != hipSuccess || hipMalloc(&dl, n * sizeof(float)) != hipSuccess ||
+        (open && hipMalloc(&dopen, n * sizeof(uint16_t)) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "apply allocation failed");
+    } else if (hipMemcpy(dp, paths, n * num_meshes * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+               (open && hipMemcpy(dopen, open, n * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "apply upload failed");
+    } else if (!(rc = launch_apply_spectrum(ctx, n, num_meshes, dp, dopen, weight, mu, num_bins, dl, ctx->host_stream))) {
+        if (hipMemcpyAsync(lbuffer, dl, n * sizeof(float), hipMemcpyDeviceToHost, ctx->host_stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->host_stream) != hipSuccess)
+            rc = fail(ctx, XRT_ERR_DEVICE, "apply kernel failed");
+    }
+    (void)hipFree(dp);
+    (void)hipFree(dl);
+    (void)hipFree(dopen);
+    return rc;
 }
 
 int xrt_hole_fill_device(xrt_context* ctx, uint32_t width, uint32_t height, const float* d_lbuffer,
