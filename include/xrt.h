@@ -409,6 +409,44 @@ int xrt_apply_spectrum_device(xrt_context* ctx, uint64_t num_pixels, uint32_t nu
                               const uint16_t* d_open, const float* weight, const float* mu, uint32_t num_bins,
                               float* d_lbuffer, void* stream);
 
+/*
+ * Mesh poses: the fork's transformMatrix hook
+ * (src/main-pthreads-lbuffer.cxx:561-564), per mesh and on the device -- a
+ * sample turning on a turntable beside a fixture that stays put, without an
+ * upload.  A pose is 12 f32, row-major 3x4: [r00 r01 r02 t0 | r10 r11 r12 t1 |
+ * r20 r21 r22 t2].  A vertex (x, y, z) of the mesh's REST soup (what was
+ * uploaded) becomes
+ *     p_i  = (r_i0 * x + r_i1 * y) + r_i2 * z
+ *     v'_i = p_i + t_i   if some t_j is not +-0, else p_i
+ * every product and sum a separately rounded f32 operation in that order:
+ * with t = 0 this is the fork's expression bit for bit.  A mesh whose 12
+ * values are bitwise the identity (1 and +0.0) is not computed: its rest
+ * vertices are used.  Poses always apply to the rest soup, never to an earlier
+ * pose.  Every model and kernel then renders the posed scene exactly as an
+ * upload of the same numbers would.
+ *
+ * xrt_set_pose sets the pose of mesh `mesh` of the uploaded scene (NULL: the
+ * identity); XRT_ERR_ARGUMENT when the mesh is not one of the scene or a value
+ * is not finite.  xrt_reset_poses returns every mesh to the identity, as
+ * xrt_upload_scene and xrt_upload_mesh do.  A change waits for the frames in
+ * flight; the posed soup is written on the device by the next render (only
+ * the meshes whose pose changed), and a frame whose only change is a pose is
+ * a new geometry over the same layout: where a moving camera reuses the region
+ * lists of the frame before (the attenuation model's BINNED frames), it does.
+ * While every pose is the identity nothing is allocated or launched.
+ */
+int xrt_set_pose(xrt_context* ctx, uint32_t mesh, const float pose[12]);
+int xrt_reset_poses(xrt_context* ctx);
+/*
+ * Host arithmetic (no device).  xrt_pose_rotation: the rotation by `degrees`
+ * about `axis` (normalised in f64) through `centre` -- R by Rodrigues' formula
+ * and t = centre - R centre in f64, each rounded once to f32;
+ * XRT_ERR_ARGUMENT for a zero or non-finite axis.  xrt_pose_triangles: the
+ * arithmetic above over a soup of n triangles (out may alias tris).
+ */
+int xrt_pose_rotation(const float axis[3], double degrees, const float centre[3], float pose[12]);
+int xrt_pose_triangles(const float* tris, uint64_t n, const float pose[12], float* out);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*
@@ -462,6 +500,9 @@ int xrt_multi_set_materials(xrt_multi* m, const float* mu, uint32_t num_meshes);
 /* The spectrum model of every device (xrt_set_spectrum): strips as for the materials model. */
 int xrt_multi_set_spectrum(xrt_multi* m, const float* weight, const float* mu, uint32_t num_meshes,
                            uint32_t num_bins);
+/* The mesh poses of every device (xrt_set_pose, xrt_reset_poses). */
+int xrt_multi_set_pose(xrt_multi* m, uint32_t mesh, const float pose[12]);
+int xrt_multi_reset_poses(xrt_multi* m);
 
 /* Waits for the last frame's gathers; the devices' statistics, summed. */
 int xrt_multi_read_stats(xrt_multi* m, xrt_stats* stats);

@@ -229,6 +229,24 @@ int xrt_debug_prep_times(xrt_context* ctx, int enable, uint32_t* dst, uint64_t c
 int xrt_debug_destroy_ms(double ms[4]);
 
 /*
+ * The soup the next render would read (xrt_set_pose): runs k_pose if one is
+ * due, waits for it and copies the scene's 9 floats per triangle into dst.
+ * *n_floats = the soup's size; dst NULL only asks for it, a capacity below it
+ * is XRT_ERR_ARGUMENT.
+ */
+int xrt_debug_posed_triangles(xrt_context* ctx, float* dst, uint64_t capacity_floats, uint64_t* n_floats);
+
+/*
+ * Diagnostics: the whole posed soup written `launches` times back to back
+ * (every mesh marked due each time), by device events on the prep stream:
+ * microseconds per writing.  Needs a pose; waits for the context's work.
+ */
+int xrt_debug_pose_span(xrt_context* ctx, uint32_t launches, double* us_per_write);
+
+/* Diagnostics: [0] k_pose launches so far, [1] the triangles they wrote. */
+int xrt_debug_pose_counters(xrt_context* ctx, uint64_t counters[2]);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -29,7 +29,7 @@ __all__ = [
     "XRT_KERNEL_BINNED", "XRT_MISS_TRANSIT", "load_meshes", "scene_bbox", "camera_for_scene",
     "XRT_MODEL_ATTENUATION", "XRT_MODEL_SIGNED", "XRT_GATHER_AUTO", "XRT_GATHER_COPY", "XRT_GATHER_RCCL",
     "XRT_SPLIT_EQUAL", "XRT_SPLIT_BALANCED", "XRT_TRANSIT_HITS", "XRT_TRANSIT_PACKED", "XRT_MODEL_MATERIALS",
-    "XRT_MAX_MESHES", "XRT_MODEL_SPECTRUM", "XRT_MAX_BINS", "XRT_MODEL_PATHS",
+    "XRT_MAX_MESHES", "XRT_MODEL_SPECTRUM", "XRT_MAX_BINS", "XRT_MODEL_PATHS", "pose_rotation", "pose_triangles",
 ]
 
 
@@ -152,6 +152,40 @@ def camera_for_mesh(tris: np.ndarray, width: int, height: int) -> Camera:
     return camera_from_bbox(lo, hi, width, height)
 
 
+def _pose_array(pose):
+    """A pose as xrt_set_pose takes it: 12 f32, row-major 3x4 [R | t] (None: the identity, a NULL pointer)."""
+    if pose is None:
+        return None
+    q = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1)
+    if q.size != 12:
+        raise ValueError(f"a pose has 12 values (3x4, row-major), got {q.size}")
+    return q
+
+
+def pose_rotation(axis, degrees: float, centre=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """The pose (12 f32) turning a mesh by `degrees` about `axis` through `centre` (xrt_pose_rotation)."""
+    a = np.ascontiguousarray(axis, dtype=np.float32).reshape(3)
+    c = np.ascontiguousarray(centre, dtype=np.float32).reshape(3)
+    out = np.empty(12, np.float32)
+    rc = _abi.load().xrt_pose_rotation(_fptr(a), float(degrees), _fptr(c), _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_pose_rotation: the axis must be finite and not zero")
+    return out
+
+
+def pose_triangles(tris: np.ndarray, pose) -> np.ndarray:
+    """A (T, 9) soup under a pose, in the device's arithmetic on the host (xrt_pose_triangles)."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
+    q = _pose_array(pose)
+    if q is None:
+        return t.copy()
+    out = np.empty_like(t)
+    rc = _abi.load().xrt_pose_triangles(_fptr(t), len(t), _fptr(q), _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_pose_triangles")
+    return out
+
+
 class Context:
     """One xrt_context (one device).  Not thread-safe."""
 
@@ -204,6 +238,37 @@ class Context:
                                                counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(counts)),
                     "xrt_upload_scene")
         self._num_meshes = len(counts)
+
+    def set_pose(self, mesh: int, pose=None):
+        """Mesh `mesh` of the scene under a pose (12 f32, row-major 3x4 [R | t]; None: the identity), on the device."""
+        q = _pose_array(pose)
+        self._check(self._lib.xrt_set_pose(self._ctx, int(mesh), _fptr(q) if q is not None else None), "xrt_set_pose")
+
+    def reset_poses(self):
+        """Every mesh back at rest."""
+        self._check(self._lib.xrt_reset_poses(self._ctx), "xrt_reset_poses")
+
+    def posed_triangles(self) -> np.ndarray:
+        """The (T, 9) soup the next render would read (xrt_debug_posed_triangles)."""
+        n = ctypes.c_uint64()
+        self._check(self._lib.xrt_debug_posed_triangles(self._ctx, None, 0, ctypes.byref(n)),
+                    "xrt_debug_posed_triangles")
+        out = np.empty(n.value, np.float32)
+        self._check(self._lib.xrt_debug_posed_triangles(self._ctx, _fptr(out), out.size, ctypes.byref(n)),
+                    "xrt_debug_posed_triangles")
+        return out.reshape(-1, 9)
+
+    def pose_span(self, launches: int = 200) -> float:
+        """Microseconds k_pose takes to write the whole posed soup, by device events over `launches` writings."""
+        us = ctypes.c_double()
+        self._check(self._lib.xrt_debug_pose_span(self._ctx, int(launches), ctypes.byref(us)), "xrt_debug_pose_span")
+        return us.value
+
+    def pose_counters(self) -> dict:
+        """k_pose launches so far and the triangles they wrote (xrt_debug_pose_counters)."""
+        c = (ctypes.c_uint64 * 2)()
+        self._check(self._lib.xrt_debug_pose_counters(self._ctx, c), "xrt_debug_pose_counters")
+        return {"launches": int(c[0]), "triangles": int(c[1])}
 
     def set_materials(self, mu):
         """XRT_MODEL_MATERIALS with one attenuation coefficient per mesh of the scene."""
@@ -669,6 +734,15 @@ class MultiContext:
         self._check(self._lib.xrt_multi_upload_scene(self._m, _fptr(tris),
                                                      counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
                                                      len(counts)), "xrt_multi_upload_scene")
+
+    def set_pose(self, mesh: int, pose=None):
+        """Context.set_pose on every device."""
+        q = _pose_array(pose)
+        self._check(self._lib.xrt_multi_set_pose(self._m, int(mesh), _fptr(q) if q is not None else None),
+                    "xrt_multi_set_pose")
+
+    def reset_poses(self):
+        self._check(self._lib.xrt_multi_reset_poses(self._m), "xrt_multi_reset_poses")
 
     def set_materials(self, mu):
         mu = np.ascontiguousarray(mu, dtype=np.float32).reshape(-1)

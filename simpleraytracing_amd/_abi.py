@@ -163,6 +163,15 @@ XRT_SYMBOLS = {
     "xrt_host_spectrum_lbuffer_batch": (None, [_fp, _i32p, _fp, _fp, _u32, _u32, _fp, _u64]),
     "xrt_host_spectrum_miss": (_f, [_fp, _u32]),
     "xrt_probe_spectrum": (ctypes.c_int, [_CtxP, _fp, _i32p, _fp, _fp, _u32, _u32, _fp, _u64]),
+    "xrt_set_pose": (ctypes.c_int, [_CtxP, _u32, _fp]),
+    "xrt_reset_poses": (ctypes.c_int, [_CtxP]),
+    "xrt_pose_rotation": (ctypes.c_int, [_fp, ctypes.c_double, _fp, _fp]),
+    "xrt_pose_triangles": (ctypes.c_int, [_fp, _u64, _fp, _fp]),
+    "xrt_debug_posed_triangles": (ctypes.c_int, [_CtxP, _fp, _u64, ctypes.POINTER(_u64)]),
+    "xrt_debug_pose_span": (ctypes.c_int, [_CtxP, _u32, _dp]),
+    "xrt_debug_pose_counters": (ctypes.c_int, [_CtxP, ctypes.POINTER(_u64)]),
+    "xrt_multi_set_pose": (ctypes.c_int, [_MultiP, _u32, _fp]),
+    "xrt_multi_reset_poses": (ctypes.c_int, [_MultiP]),
     "xrt_host_mt_check": (None, [_fp, _fp, _fp, _fp, _u64, ctypes.POINTER(ctypes.c_uint8),
                                  ctypes.POINTER(ctypes.c_uint8), _fp]),
     "xrt_set_hit_capacity": (ctypes.c_int, [_CtxP, _u32]),

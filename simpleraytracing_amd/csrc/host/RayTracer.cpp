@@ -2,6 +2,7 @@
 #include "RayTracer.h"
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -20,6 +21,7 @@ namespace {
 
 int g_kernel = -1;
 int g_device = -1;
+std::vector<std::array<float, 12>> g_poses;   // setMeshPoses (empty: every mesh at rest)
 
 int kernel_choice()
 {
@@ -42,6 +44,20 @@ void check(xrt_context* ctx, int rc, const char* what)
 {
     if (rc != XRT_OK)
         throw std::runtime_error(std::string(what) + ": " + xrt_last_error(ctx));
+}
+
+// setMeshPoses' poses onto the context's scene: the first `uploaded` of the
+// scene's `scene_meshes` meshes are on the device (the attenuation and signed
+// models upload mesh 0 only).  A pose the context already has costs nothing.
+void apply_poses(xrt_context* ctx, size_t scene_meshes, size_t uploaded)
+{
+    if (g_poses.empty()) {
+        check(ctx, xrt_reset_poses(ctx), "xrt_reset_poses");
+        return;
+    }
+    if (g_poses.size() != scene_meshes) throw std::invalid_argument("setMeshPoses: one pose per mesh of the scene");
+    for (size_t m = 0; m < uploaded && m < scene_meshes; ++m)
+        check(ctx, xrt_set_pose(ctx, (uint32_t)m, g_poses[m].data()), "xrt_set_pose");
 }
 
 }  // namespace
@@ -77,6 +93,7 @@ xrt_context* xrt_host_device_context(int device) { return device_slot(device).ct
 
 void setRenderKernel(int kernel) { g_kernel = kernel; }
 void setRenderDevice(int device) { g_device = device; }
+void setMeshPoses(const std::vector<std::array<float, 12>>& poses) { g_poses = poses; }
 
 // Assimp-free loadMeshes (main.cxx:455-508): each mesh of the file through
 // TriangleMesh::setGeometry(vertices, indices), in file order.
@@ -110,6 +127,28 @@ void getBBox(const std::vector<TriangleMesh>& meshes, Vec3& upper, Vec3& lower)
         for (unsigned k = 0; k < 3; ++k) {
             lower[k] = std::min(lower[k], m.getLowerBBoxCorner()[k]);
             upper[k] = std::max(upper[k], m.getUpperBBoxCorner()[k]);
+        }
+    }
+}
+
+// The box of the posed scene: every mesh's vertices under its pose (xrt_pose_triangles).
+void getPosedBBox(const std::vector<TriangleMesh>& meshes, const std::vector<std::array<float, 12>>& poses,
+                  Vec3& upper, Vec3& lower)
+{
+    if (!poses.empty() && poses.size() != meshes.size())
+        throw std::invalid_argument("getPosedBBox: one pose per mesh of the scene");
+    const float inf = std::numeric_limits<float>::infinity();
+    lower = Vec3(inf, inf, inf);
+    upper = Vec3(-inf, -inf, -inf);
+    for (size_t m = 0; m < meshes.size(); ++m) {
+        std::vector<float> soup = meshes[m].flatten();
+        if (!poses.empty() && xrt_pose_triangles(soup.data(), soup.size() / 9, poses[m].data(), soup.data()) != XRT_OK)
+            throw std::runtime_error("getPosedBBox: xrt_pose_triangles");
+        float lo[3], hi[3];
+        xrt_mesh_bbox(soup.data(), soup.size() / 9, lo, hi);
+        for (unsigned k = 0; k < 3; ++k) {
+            lower[k] = std::min(lower[k], lo[k]);
+            upper[k] = std::max(upper[k], hi[k]);
         }
     }
 }
@@ -166,7 +205,7 @@ xrt_camera camera_for(const Image& image, const std::vector<TriangleMesh>& meshe
     return cam;
 }
 
-void render_strip(int device, const xrt_camera& cam, const std::vector<float>& soup,
+void render_strip(int device, const xrt_camera& cam, const std::vector<float>& soup, size_t scene_meshes,
                   unsigned row_begin, unsigned row_end, float* image_strip, float* lbuffer_strip,
                   unsigned char* u8_strip, xrt_stats* stats)
 {
@@ -179,6 +218,7 @@ void render_strip(int device, const xrt_camera& cam, const std::vector<float>& s
         slot.mesh = soup;
         slot.uploaded = true;
     }
+    apply_poses(ctx, scene_meshes, 1);
     check(ctx, xrt_render_rows(ctx, &cam, row_begin, row_end, image_strip, lbuffer_strip, u8_strip, stats),
           "xrt_render_rows");
 }
@@ -215,7 +255,7 @@ void renderLoopRows(Image& image, const std::vector<TriangleMesh>& meshes, const
         throw std::out_of_range("renderLoopRows: row range outside the image");
     xrt_camera cam = camera_for(image, meshes, info);
     std::vector<float> soup = mesh0_soup(meshes);
-    render_strip(device_choice(), cam, soup, row_begin, row_end,
+    render_strip(device_choice(), cam, soup, meshes.size(), row_begin, row_end,
                  image.getData() + (size_t)row_begin * image.getWidth(), lbuffer_strip, u8_strip, stats);
 }
 
@@ -235,6 +275,7 @@ double renderLoopFrames(Image& image, const std::vector<TriangleMesh>& meshes, c
         slot.mesh = soup;
         slot.uploaded = true;
     }
+    apply_poses(ctx, meshes.size(), 1);
     double ms = 0.0;
     check(ctx, xrt_render_frames(ctx, &cam, row_begin, row_end, frames,
                                  image.getData() + (size_t)row_begin * image.getWidth(), nullptr, nullptr, stats, &ms),
@@ -271,6 +312,7 @@ unsigned long long renderLoopLBuffer(Image& image, const std::vector<TriangleMes
         slot.mesh = soup;
         slot.uploaded = true;
     }
+    apply_poses(ctx, meshes.size(), 1);
     check(ctx, xrt_set_model(ctx, XRT_MODEL_SIGNED, 0.1037f), "xrt_set_model");   // :800
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
@@ -295,6 +337,7 @@ unsigned long long renderLoopMaterials(Image& image, const std::vector<TriangleM
     check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
     slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
     check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
+    apply_poses(ctx, meshes.size(), meshes.size());
     check(ctx, xrt_set_materials(ctx, mu.data(), (uint32_t)mu.size()), "xrt_set_materials");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
@@ -321,6 +364,7 @@ unsigned long long renderLoopSpectrum(Image& image, const std::vector<TriangleMe
     check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
     slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
     check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
+    apply_poses(ctx, meshes.size(), meshes.size());
     check(ctx, xrt_set_spectrum(ctx, weight.data(), mu.data(), (uint32_t)meshes.size(), (uint32_t)weight.size()),
           "xrt_set_spectrum");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
@@ -347,6 +391,7 @@ unsigned long long renderLoopPaths(std::vector<std::vector<float>>& paths, std::
     check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
     slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
     check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
+    apply_poses(ctx, meshes.size(), meshes.size());
     check(ctx, xrt_set_paths(ctx), "xrt_set_paths");
     const size_t n = (size_t)frame.getWidth() * frame.getHeight();
     std::vector<float> planes(n * meshes.size());
@@ -428,6 +473,17 @@ void mcheck(xrt_multi* m, int rc, const char* what)
     if (rc != XRT_OK) throw std::runtime_error(std::string(what) + ": " + xrt_multi_last_error(m));
 }
 
+void apply_poses_multi(xrt_multi* m, size_t scene_meshes, size_t uploaded)
+{
+    if (g_poses.empty()) {
+        mcheck(m, xrt_multi_reset_poses(m), "xrt_multi_reset_poses");
+        return;
+    }
+    if (g_poses.size() != scene_meshes) throw std::invalid_argument("setMeshPoses: one pose per mesh of the scene");
+    for (size_t k = 0; k < uploaded && k < scene_meshes; ++k)
+        mcheck(m, xrt_multi_set_pose(m, (uint32_t)k, g_poses[k].data()), "xrt_multi_set_pose");
+}
+
 }  // namespace
 
 // Row strips over num_gpus devices gathered into device 0 with RCCL
@@ -442,6 +498,7 @@ unsigned long long renderLoopMultiGPU(Image& image, const std::vector<TriangleMe
     mcheck(m, xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f), "xrt_multi_set_model");
     mcheck(m, xrt_multi_set_kernel(m, kernel_choice()), "xrt_multi_set_kernel");
     mcheck(m, xrt_multi_upload_mesh(m, soup.data(), soup.size() / 9), "xrt_multi_upload_mesh");
+    apply_poses_multi(m, meshes.size(), 1);
     xrt_stats stats;
     mcheck(m, xrt_render_rows_multi(m, &cam, image.getData(), nullptr, nullptr, &stats), "xrt_render_rows_multi");
     report_odd(stats.odd_rays);
@@ -458,6 +515,7 @@ unsigned long long renderLoopLBufferMultiGPU(Image& image, const std::vector<Tri
     const int k = kernel_choice();
     mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
     mcheck(m, xrt_multi_upload_mesh(m, soup.data(), soup.size() / 9), "xrt_multi_upload_mesh");
+    apply_poses_multi(m, meshes.size(), 1);
     mcheck(m, xrt_multi_set_model(m, XRT_MODEL_SIGNED, 0.1037f), "xrt_multi_set_model");   // :800
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
@@ -481,6 +539,7 @@ unsigned long long renderLoopMaterialsMultiGPU(Image& image, const std::vector<T
     const int k = kernel_choice();
     mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
     mcheck(m, xrt_multi_upload_scene(m, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_multi_upload_scene");
+    apply_poses_multi(m, meshes.size(), meshes.size());
     mcheck(m, xrt_multi_set_materials(m, mu.data(), (uint32_t)mu.size()), "xrt_multi_set_materials");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
@@ -505,6 +564,7 @@ unsigned long long renderLoopSpectrumMultiGPU(Image& image, const std::vector<Tr
     const int k = kernel_choice();
     mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
     mcheck(m, xrt_multi_upload_scene(m, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_multi_upload_scene");
+    apply_poses_multi(m, meshes.size(), meshes.size());
     mcheck(m, xrt_multi_set_spectrum(m, weight.data(), mu.data(), (uint32_t)meshes.size(), (uint32_t)weight.size()),
            "xrt_multi_set_spectrum");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());

@@ -10,6 +10,7 @@
 // several GPUs).  Errors surface as exceptions, as in the reference.
 #pragma once
 
+#include <array>
 #include <string>
 #include <vector>
 
@@ -38,6 +39,12 @@ struct RayTracerInfo {
 // and $XRT_DEVICE.
 void setRenderKernel(int kernel);
 void setRenderDevice(int device);
+// Mesh poses (process-wide, as the options above): one row-major 3x4 [R | t]
+// per mesh of the scene -- the fork's transformMatrix, per mesh and applied on
+// the device (include/xrt.h, xrt_set_pose).  Empty (the default): every mesh at
+// rest.  Every renderLoop* honours it; a size other than the scene's mesh count
+// throws at render time.
+void setMeshPoses(const std::vector<std::array<float, 12>>& poses);
 
 // Every mesh of a file, replacing `meshes` (main.cxx:455-508): a PLY file is
 // one mesh, an OBJ file one mesh per object.  appendMeshes keeps the meshes
@@ -46,6 +53,10 @@ void loadMeshes(const std::string& file_name, std::vector<TriangleMesh>& meshes)
 void appendMeshes(const std::string& file_name, std::vector<TriangleMesh>& meshes);
 
 void getBBox(const std::vector<TriangleMesh>& meshes, Vec3& upper, Vec3& lower);
+// getBBox is the reference's, over the rest meshes; this one is over the
+// vertices under `poses` (one per mesh; empty: getBBox's vertices).
+void getPosedBBox(const std::vector<TriangleMesh>& meshes, const std::vector<std::array<float, 12>>& poses,
+                  Vec3& upper, Vec3& lower);
 
 RayTracerInfo initialiseRayTracing(std::vector<TriangleMesh>& meshes, const Vec3& upper,
                                    const Vec3& lower, unsigned int image_height,

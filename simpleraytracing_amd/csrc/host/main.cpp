@@ -26,6 +26,16 @@
 //                              of open meshes to NAME.open.EXT (-f NAME.EXT); with
 //                              --spectrum FILE the table is then applied to the planes
 //                              and NAME.EXT is what --spectrum FILE alone writes
+//       --pose M=v0,...,v11    mesh M (load order, from 0) under a pose: 12 values, a
+//                              row-major 3x4 [R | t] (the fork's transformMatrix and a
+//                              translation), applied on the device; repeatable, once
+//                              per mesh
+//       --turntable N[:x|y|z][:M,M,...]  N projections: projection k has the listed
+//                              meshes (every mesh when none is listed) turned k*360/N
+//                              degrees about the axis (default y, the fork's rotateMat)
+//                              through the rest scene's box centre, under the rest
+//                              scene's camera, and is written to NAME.pKKK.EXT (so are
+//                              --lbuffer's and --u8's files)
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -36,7 +46,9 @@
 //                              xrt_render_frames call) and write the last;
 //                              with --time, the device time per frame
 #include <algorithm>
+#include <array>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -68,6 +80,8 @@ void showUsage(const std::string& prog)
               << "\t--materials MU0,MU1,...\t\tMaterials model: one attenuation coefficient per loaded mesh, and hole fill\n"
               << "\t--spectrum FILE\t\t\tSpectrum model: FILE holds a line of K bin weights, then one line of K coefficients per loaded mesh\n"
               << "\t--paths\t\t\t\tPaths model: write each mesh's path-length plane (NAME.m<m>.EXT) and the open mask (NAME.open.EXT); with --spectrum FILE, apply it to the planes\n"
+              << "\t--pose M=v0,...,v11\t\tMesh M under a pose: 12 values, row-major 3x4 [R | t]; repeat for other meshes\n"
+              << "\t--turntable N[:x|y|z][:M,...]\tN projections, the listed meshes (default: all) turned k*360/N degrees about the axis (default y) through the scene's centre; writes NAME.pKKK.EXT\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -92,7 +106,86 @@ struct Options {
     bool rows = false;
     unsigned row_begin = 0, row_end = 0;
     unsigned batch = 0;
+    std::vector<std::pair<unsigned, std::array<float, 12>>> poses;   // --pose M=...: one per mesh at most
+    unsigned turntable = 0;                    // --turntable: projections (0: none)
+    int turn_axis = 1;                         // 0 x, 1 y, 2 z
+    std::vector<unsigned> turn_meshes;         // empty: every mesh
 };
+
+// A whole, non-negative decimal number.
+bool parse_index(const std::string& f, unsigned& out)
+{
+    if (f.empty() || f.size() > 9 || f.find_first_not_of("0123456789") != std::string::npos) return false;
+    out = (unsigned)std::stoul(f);
+    return true;
+}
+
+std::vector<std::string> split(const std::string& list, char sep)
+{
+    std::vector<std::string> out;
+    for (size_t pos = 0; pos <= list.size();) {
+        size_t next = list.find(sep, pos);
+        if (next == std::string::npos) next = list.size();
+        out.push_back(list.substr(pos, next - pos));
+        pos = next + 1;
+    }
+    return out;
+}
+
+// --pose M=v0,...,v11
+void parse_pose(const std::string& arg, Options& o)
+{
+    const size_t eq = arg.find('=');
+    unsigned mesh = 0;
+    if (eq == std::string::npos || !parse_index(arg.substr(0, eq), mesh))
+        throw std::runtime_error("--pose M=v0,...,v11: '" + arg.substr(0, eq) + "' is not a mesh number");
+    const std::vector<std::string> fields = split(arg.substr(eq + 1), ',');
+    if (fields.size() != 12)
+        throw std::runtime_error("--pose takes 12 values (a row-major 3x4 [R | t]), got " + std::to_string(fields.size()));
+    std::array<float, 12> q;
+    for (size_t k = 0; k < 12; ++k) {
+        size_t used = 0;
+        try {
+            q[k] = std::stof(fields[k], &used);
+        } catch (const std::exception&) {
+            used = 0;
+        }
+        if (fields[k].empty() || used != fields[k].size() || !std::isfinite(q[k]))
+            throw std::runtime_error("--pose: '" + fields[k] + "' is not a finite number");
+    }
+    for (const auto& have : o.poses)
+        if (have.first == mesh) throw std::runtime_error("--pose given twice for mesh " + std::to_string(mesh));
+    o.poses.push_back({mesh, q});
+}
+
+// --turntable N[:x|y|z][:M,M,...]
+void parse_turntable(const std::string& arg, Options& o)
+{
+    const std::vector<std::string> parts = split(arg, ':');
+    if (parts.size() > 3 || !parse_index(parts[0], o.turntable) || o.turntable == 0)
+        throw std::runtime_error("--turntable N[:x|y|z][:M,M,...]: N is a number of projections, at least 1");
+    size_t next = 1;
+    if (next < parts.size() && (parts[next] == "x" || parts[next] == "y" || parts[next] == "z"))
+        o.turn_axis = parts[next++][0] - 'x';
+    if (next < parts.size()) {
+        for (const std::string& f : split(parts[next++], ',')) {
+            unsigned mesh = 0;
+            if (!parse_index(f, mesh)) throw std::runtime_error("--turntable: '" + f + "' is not a mesh number");
+            o.turn_meshes.push_back(mesh);
+        }
+    }
+    if (next != parts.size()) throw std::runtime_error("--turntable N[:x|y|z][:M,M,...]: '" + arg + "'");
+}
+
+// NAME.EXT -> NAME.pKKK.EXT (three digits or more)
+std::string projection_name(const std::string& path, unsigned k)
+{
+    const size_t dot = path.find_last_of("./");
+    const bool ext = dot != std::string::npos && path[dot] == '.' && dot > 0 && path[dot - 1] != '/' && path[dot - 1] != '.';
+    char num[16];
+    std::snprintf(num, sizeof num, ".p%03u", k);
+    return ext ? path.substr(0, dot) + num + path.substr(dot) : path + num;
+}
 
 unsigned parse_uint(const char* prog, int argc, char** argv, int& i)
 {
@@ -201,6 +294,10 @@ Options processCmd(int argc, char** argv)
             read_spectrum(parse_str(argv[0], argc, argv, i), o.spectrum_weight, o.spectrum_mu);
         } else if (a == "--paths") {
             o.paths = true;
+        } else if (a == "--pose") {
+            parse_pose(parse_str(argv[0], argc, argv, i), o);
+        } else if (a == "--turntable") {
+            parse_turntable(parse_str(argv[0], argc, argv, i), o);
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -233,6 +330,8 @@ Options processCmd(int argc, char** argv)
         throw std::runtime_error("--paths, --signed and --materials are three models: give one");
     if (o.paths && (o.rows || o.batch || o.gpus > 1))
         throw std::runtime_error("--paths renders whole frames on one GPU");
+    if (o.turntable && (o.paths || o.batch || o.gpus > 1))
+        throw std::runtime_error("--turntable renders on one GPU, without --paths, --batch and -g");
     if (o.signed_model && !o.materials.empty())
         throw std::runtime_error("--signed and --materials are two models: give one");
     if (o.spectrum && (o.signed_model || !o.materials.empty()))
@@ -258,6 +357,15 @@ int main(int argc, char** argv)
                   << " seconds" << std::endl
                   << std::endl;
 
+        for (const auto& q : opt.poses)
+            if (q.first >= meshes.size())
+                throw std::runtime_error("--pose: mesh " + std::to_string(q.first) + " is not a mesh of the scene (" +
+                                         std::to_string(meshes.size()) + " meshes loaded)");
+        for (unsigned m : opt.turn_meshes)
+            if (m >= meshes.size())
+                throw std::runtime_error("--turntable: mesh " + std::to_string(m) + " is not a mesh of the scene (" +
+                                         std::to_string(meshes.size()) + " meshes loaded)");
+
         std::cout << "Getting scene bbox... " << std::endl;
         Vec3 lower, upper;
         getBBox(meshes, upper, lower);
@@ -265,101 +373,127 @@ int main(int argc, char** argv)
         Image image(opt.width, opt.height, lut);
         RayTracerInfo info = initialiseRayTracing(meshes, upper, lower, opt.height, opt.width, image, lut);
 
-        auto r0 = std::chrono::high_resolution_clock::now();
-        std::vector<float> lb;
-        const unsigned rb = opt.rows ? opt.row_begin : 0u, re = opt.rows ? opt.row_end : opt.height;
-        double ms_per_frame = 0.0;
-        if (opt.batch) {                          // N frames back to back, the last one kept
-            xrt_stats st;
-            ms_per_frame = renderLoopFrames(image, meshes, info, opt.batch, rb, re, &st);
-            for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
-        } else if (opt.rows && opt.lbuffer.empty()) {
-            xrt_stats st;
-            renderLoopRows(image, meshes, info, rb, re, nullptr, nullptr, &st);
-            for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
-        } else if (opt.paths) {
-            if (opt.spectrum && opt.spectrum_mu.size() / opt.spectrum_weight.size() != meshes.size())
-                throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
-                                         " meshes loaded, " +
-                                         std::to_string(opt.spectrum_mu.size() / opt.spectrum_weight.size()) + " rows");
-            std::vector<std::vector<float>> planes;
-            std::vector<unsigned short> open;
-            renderLoopPaths(planes, open, image, meshes, info);
-            const size_t dot = opt.output.find_last_of("./");
-            const bool ext = dot != std::string::npos && opt.output[dot] == '.';
-            const std::string stem = ext ? opt.output.substr(0, dot) : opt.output;
-            const std::string suffix = ext ? opt.output.substr(dot) : "";
-            Image plane(opt.width, opt.height, 0.0f);
-            for (size_t m = 0; m < planes.size(); ++m) {
-                std::copy(planes[m].begin(), planes[m].end(), plane.getData());
-                plane.saveTextFile(stem + ".m" + std::to_string(m) + suffix);
+        // the poses: --pose's, and over them each projection's turn of --turntable's meshes
+        const std::array<float, 12> rest = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
+        std::vector<std::array<float, 12>> poses;
+        if (!opt.poses.empty() || opt.turntable) poses.assign(meshes.size(), rest);
+        for (const auto& q : opt.poses) poses[q.first] = q.second;
+        const std::string name = opt.output, lbuffer_name = opt.lbuffer, u8_name = opt.u8;
+        for (unsigned projection = 0; projection < std::max(opt.turntable, 1u); ++projection) {
+            if (opt.turntable) {
+                // the rest scene's box centre, as initialiseRayTracing forms it (main.cxx:575-578)
+                float axis[3] = {0.0f, 0.0f, 0.0f}, centre[3];
+                axis[opt.turn_axis] = 1.0f;
+                for (unsigned k = 0; k < 3; ++k) centre[k] = lower[k] + (float)((double)(upper[k] - lower[k]) / 2.0);
+                std::array<float, 12> turn;
+                if (xrt_pose_rotation(axis, projection * 360.0 / opt.turntable, centre, turn.data()) != XRT_OK)
+                    throw std::runtime_error("--turntable: the scene's box is not finite");
+                for (size_t m = 0; m < meshes.size(); ++m)
+                    if (opt.turn_meshes.empty() ||
+                        std::find(opt.turn_meshes.begin(), opt.turn_meshes.end(), (unsigned)m) != opt.turn_meshes.end())
+                        poses[m] = turn;
+                opt.output = projection_name(name, projection);
+                if (!lbuffer_name.empty()) opt.lbuffer = projection_name(lbuffer_name, projection);
+                if (!u8_name.empty()) opt.u8 = projection_name(u8_name, projection);
             }
-            std::copy(open.begin(), open.end(), plane.getData());
-            plane.saveTextFile(stem + ".open" + suffix);
-            if (opt.spectrum)                     // (without a table the planes are the output)
-                applySpectrum(image, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.lbuffer.empty() ? nullptr : &lb);
-        } else if (!opt.materials.empty()) {
-            if (opt.materials.size() != meshes.size())
-                throw std::runtime_error("--materials takes one coefficient per mesh: " + std::to_string(meshes.size()) +
-                                         " meshes loaded, " + std::to_string(opt.materials.size()) + " coefficients");
-            std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
-            if (opt.gpus > 1) renderLoopMaterialsMultiGPU(image, meshes, info, opt.materials, opt.gpus, l);
-            else renderLoopMaterials(image, meshes, info, opt.materials, l);
-        } else if (opt.spectrum) {
-            const size_t rows = opt.spectrum_mu.size() / opt.spectrum_weight.size();
-            if (rows != meshes.size())
-                throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
-                                         " meshes loaded, " + std::to_string(rows) + " rows");
-            std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
-            if (opt.gpus > 1)
-                renderLoopSpectrumMultiGPU(image, meshes, info, opt.spectrum_weight, opt.spectrum_mu, opt.gpus, l);
-            else renderLoopSpectrum(image, meshes, info, opt.spectrum_weight, opt.spectrum_mu, l);
-        } else if (opt.signed_model && opt.gpus > 1) {
-            renderLoopLBufferMultiGPU(image, meshes, info, opt.gpus, opt.lbuffer.empty() ? nullptr : &lb);
-        } else if (opt.signed_model) {
-            renderLoopLBuffer(image, meshes, info, opt.lbuffer.empty() ? nullptr : &lb);
-        } else if (opt.gpus > 1) {
-            renderLoopMultiGPU(image, meshes, info, opt.gpus);
-        } else if (!opt.lbuffer.empty()) {       // the image and the L-buffer in one render
-            lb.resize((size_t)opt.width * (re - rb));
-            xrt_stats st;
-            renderLoopRows(image, meshes, info, rb, re, lb.data(), nullptr, &st);
-            for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
-        } else {
-            renderLoop(image, meshes, info);
-        }
-        auto r1 = std::chrono::high_resolution_clock::now();
-        if (opt.time) {
-            double s = std::chrono::duration<double>(r1 - r0).count();
-            const double rays = (double)opt.width * (re - rb);
-            std::cout << "Render took: " << s << " seconds (" << rays * (opt.batch ? opt.batch : 1) / s / 1e6
-                      << " Mrays/s, " << opt.gpus << " GPU(s))" << std::endl;
-            if (opt.batch)
-                std::cout << "Frames: " << opt.batch << ", device time per frame " << ms_per_frame << " ms ("
-                          << rays / (ms_per_frame * 1e3) << " Mrays/s)" << std::endl;
-        }
+            setMeshPoses(poses);
 
-        Image* out = &image;
-        Image strip;
-        if (opt.rows) {                           // the strip's rows only
-            strip = Image(opt.width, re - rb, 0.0f);
-            std::copy(image.getData() + (size_t)rb * opt.width, image.getData() + (size_t)re * opt.width,
-                      strip.getData());
-            out = &strip;
-        }
-        if (opt.paths && !opt.spectrum) return 0;
-        out->saveTextFile(opt.output);
-        if (!opt.u8.empty()) out->savePGMFile(opt.u8, 0.0f, 80.0f);
-        if (!opt.lbuffer.empty()) {
-            if (lb.empty()) {                   // multi-GPU, batch: the L-buffer of the same frame
+            auto r0 = std::chrono::high_resolution_clock::now();
+            std::vector<float> lb;
+            const unsigned rb = opt.rows ? opt.row_begin : 0u, re = opt.rows ? opt.row_end : opt.height;
+            double ms_per_frame = 0.0;
+            if (opt.batch) {                          // N frames back to back, the last one kept
+                xrt_stats st;
+                ms_per_frame = renderLoopFrames(image, meshes, info, opt.batch, rb, re, &st);
+                for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
+            } else if (opt.rows && opt.lbuffer.empty()) {
+                xrt_stats st;
+                renderLoopRows(image, meshes, info, rb, re, nullptr, nullptr, &st);
+                for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
+            } else if (opt.paths) {
+                if (opt.spectrum && opt.spectrum_mu.size() / opt.spectrum_weight.size() != meshes.size())
+                    throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
+                                             " meshes loaded, " +
+                                             std::to_string(opt.spectrum_mu.size() / opt.spectrum_weight.size()) + " rows");
+                std::vector<std::vector<float>> planes;
+                std::vector<unsigned short> open;
+                renderLoopPaths(planes, open, image, meshes, info);
+                const size_t dot = opt.output.find_last_of("./");
+                const bool ext = dot != std::string::npos && opt.output[dot] == '.';
+                const std::string stem = ext ? opt.output.substr(0, dot) : opt.output;
+                const std::string suffix = ext ? opt.output.substr(dot) : "";
+                Image plane(opt.width, opt.height, 0.0f);
+                for (size_t m = 0; m < planes.size(); ++m) {
+                    std::copy(planes[m].begin(), planes[m].end(), plane.getData());
+                    plane.saveTextFile(stem + ".m" + std::to_string(m) + suffix);
+                }
+                std::copy(open.begin(), open.end(), plane.getData());
+                plane.saveTextFile(stem + ".open" + suffix);
+                if (opt.spectrum)                     // (without a table the planes are the output)
+                    applySpectrum(image, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.lbuffer.empty() ? nullptr : &lb);
+            } else if (!opt.materials.empty()) {
+                if (opt.materials.size() != meshes.size())
+                    throw std::runtime_error("--materials takes one coefficient per mesh: " + std::to_string(meshes.size()) +
+                                             " meshes loaded, " + std::to_string(opt.materials.size()) + " coefficients");
+                std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
+                if (opt.gpus > 1) renderLoopMaterialsMultiGPU(image, meshes, info, opt.materials, opt.gpus, l);
+                else renderLoopMaterials(image, meshes, info, opt.materials, l);
+            } else if (opt.spectrum) {
+                const size_t rows = opt.spectrum_mu.size() / opt.spectrum_weight.size();
+                if (rows != meshes.size())
+                    throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
+                                             " meshes loaded, " + std::to_string(rows) + " rows");
+                std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
+                if (opt.gpus > 1)
+                    renderLoopSpectrumMultiGPU(image, meshes, info, opt.spectrum_weight, opt.spectrum_mu, opt.gpus, l);
+                else renderLoopSpectrum(image, meshes, info, opt.spectrum_weight, opt.spectrum_mu, l);
+            } else if (opt.signed_model && opt.gpus > 1) {
+                renderLoopLBufferMultiGPU(image, meshes, info, opt.gpus, opt.lbuffer.empty() ? nullptr : &lb);
+            } else if (opt.signed_model) {
+                renderLoopLBuffer(image, meshes, info, opt.lbuffer.empty() ? nullptr : &lb);
+            } else if (opt.gpus > 1) {
+                renderLoopMultiGPU(image, meshes, info, opt.gpus);
+            } else if (!opt.lbuffer.empty()) {       // the image and the L-buffer in one render
                 lb.resize((size_t)opt.width * (re - rb));
                 xrt_stats st;
                 renderLoopRows(image, meshes, info, rb, re, lb.data(), nullptr, &st);
+                for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
+            } else {
+                renderLoop(image, meshes, info);
             }
-            std::FILE* f = std::fopen(opt.lbuffer.c_str(), "wb");
-            if (!f) throw std::runtime_error("Cannot create the file " + opt.lbuffer);
-            std::fwrite(lb.data(), sizeof(float), lb.size(), f);
-            std::fclose(f);
+            auto r1 = std::chrono::high_resolution_clock::now();
+            if (opt.time) {
+                double s = std::chrono::duration<double>(r1 - r0).count();
+                const double rays = (double)opt.width * (re - rb);
+                std::cout << "Render took: " << s << " seconds (" << rays * (opt.batch ? opt.batch : 1) / s / 1e6
+                          << " Mrays/s, " << opt.gpus << " GPU(s))" << std::endl;
+                if (opt.batch)
+                    std::cout << "Frames: " << opt.batch << ", device time per frame " << ms_per_frame << " ms ("
+                              << rays / (ms_per_frame * 1e3) << " Mrays/s)" << std::endl;
+            }
+
+            Image* out = &image;
+            Image strip;
+            if (opt.rows) {                           // the strip's rows only
+                strip = Image(opt.width, re - rb, 0.0f);
+                std::copy(image.getData() + (size_t)rb * opt.width, image.getData() + (size_t)re * opt.width,
+                          strip.getData());
+                out = &strip;
+            }
+            if (opt.paths && !opt.spectrum) return 0;
+            out->saveTextFile(opt.output);
+            if (!opt.u8.empty()) out->savePGMFile(opt.u8, 0.0f, 80.0f);
+            if (!opt.lbuffer.empty()) {
+                if (lb.empty()) {                   // multi-GPU, batch: the L-buffer of the same frame
+                    lb.resize((size_t)opt.width * (re - rb));
+                    xrt_stats st;
+                    renderLoopRows(image, meshes, info, rb, re, lb.data(), nullptr, &st);
+                }
+                std::FILE* f = std::fopen(opt.lbuffer.c_str(), "wb");
+                if (!f) throw std::runtime_error("Cannot create the file " + opt.lbuffer);
+                std::fwrite(lb.data(), sizeof(float), lb.size(), f);
+                std::fclose(f);
+            }
         }
     } catch (const std::exception& e) {
         std::cerr << "ERROR: " << e.what() << std::endl;

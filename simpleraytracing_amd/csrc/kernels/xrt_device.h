@@ -112,6 +112,58 @@ struct SpectrumTable {
 constexpr uint32_t kModelPaths = 4;
 static_assert(kMaxMeshes <= 16u, "a ray's open mask is 16 bits");
 
+// Mesh poses: a pose is a row-major 3x4 [R | t]; k_pose writes
+// the posed soup from the rest soup (what was uploaded), mesh by mesh.  The
+// table travels by value in k_pose's kernel arguments: the poses, the meshes'
+// id-range ends (0xFFFFFFFF past the scene's last mesh) and a bit per mesh
+// whose pose is bitwise the identity (its vertices are copied, not computed).
+constexpr uint32_t kPoseFloats = 12;
+struct PoseTable {
+    float pose[kMaxMeshes][kPoseFloats];
+    uint32_t end[kMaxMeshes];
+    uint32_t identity;
+};
+
+// One vertex under one pose: the fork's transformMatrix product
+// (src/main-pthreads-lbuffer.cxx:561-564), three f32 products summed left to
+// right, p_i = (r_i0 * x + r_i1 * y) + r_i2 * z, every product and sum rounded
+// on its own (__fmul_rn / __fadd_rn on the device, no contraction on the
+// host).  The translation is added only when some t_j is not +-0: with t = 0
+// the result is the fork's expression bit for bit (p_i + 0.0f would turn a
+// -0.0f into +0.0f).  The identity is the caller's business (PoseTable).
+__host__ __device__ __forceinline__ float pose_mul(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmul_rn(a, b);
+#else
+    return a * b;
+#endif
+}
+
+__host__ __device__ __forceinline__ float pose_add(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fadd_rn(a, b);
+#else
+    return a + b;
+#endif
+}
+
+__host__ __device__ __forceinline__ void pose_vertex(const float* pose, float x, float y, float z, float& ox,
+                                                     float& oy, float& oz)
+{
+    float p[3];
+    for (int i = 0; i < 3; ++i) {
+        const float* r = pose + 4 * i;
+        p[i] = pose_add(pose_add(pose_mul(r[0], x), pose_mul(r[1], y)), pose_mul(r[2], z));
+    }
+    if (pose[3] != 0.0f || pose[7] != 0.0f || pose[11] != 0.0f)
+        for (int i = 0; i < 3; ++i) p[i] = pose_add(p[i], pose[4 * i + 3]);
+    ox = p[0];
+    oy = p[1];
+    oz = p[2];
+}
+
 // Register hit list per ray.  Each slot costs every exact test one
 // v_med3_f32; a ray with more hits is recomputed exactly by its wave
 // (finish_ray's fix-up, tens of microseconds for that wave).  dragon.ply rays

@@ -3710,4 +3710,56 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     if (in) outp[i] = flags ? -1.0f : lval;
 }
 
+// ---------------------------------------------------------------------------
+// k_pose: the posed soup from the rest soup, one thread per
+// vertex.  A lane reads and writes its vertex's 12 bytes, a wave 768
+// contiguous bytes: 72 bytes of traffic a triangle and three products and up
+// to three sums a coordinate -- memory-bound.  `rest` and `posed` point at
+// triangle tri_first of their soups (a launch covers whole triangles of a run
+// of meshes; the host keeps a launch under kPoseLaunchTris so that every
+// index here fits 32 bits with room to spare).  The meshes of a wave's first
+// and last triangle are wave-uniform scalars: the wave walks the meshes in
+// between, one as a rule, reading that mesh's pose from the kernel arguments
+// with scalar loads; only a wave that straddles a range end computes more
+// than one pose, each lane keeping its own mesh's.  A mesh at the identity is
+// copied.  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kPoseThreads = 256;
+constexpr uint32_t kPoseLaunchTris = 1u << 24;
+
+// The mesh of triangle `tri`: the number of range ends at or below it (an
+// empty mesh's end equals its predecessor's and is passed over with it).
+__device__ __forceinline__ uint32_t pose_mesh_of(const PoseTable& tab, uint32_t tri)
+{
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t k = 0; k + 1 < kMaxMeshes; ++k) m += tab.end[k] <= tri ? 1u : 0u;
+    return m;
+}
+
+__global__ __launch_bounds__(kPoseThreads) void k_pose(const float* __restrict__ rest, float* __restrict__ posed,
+                                                       uint32_t tri_first, uint32_t num_vertices, PoseTable tab)
+{
+    const uint32_t wave_first =
+        __builtin_amdgcn_readfirstlane(blockIdx.x * kPoseThreads + (threadIdx.x & ~63u));
+    if (wave_first >= num_vertices) return;
+    const uint32_t wave_last = min(wave_first + 63u, num_vertices - 1u);
+    const uint32_t v = blockIdx.x * kPoseThreads + threadIdx.x;
+    if (v >= num_vertices) return;
+    const uint32_t tri = tri_first + v / 3u;
+    const uint32_t m_first = __builtin_amdgcn_readfirstlane(pose_mesh_of(tab, tri_first + wave_first / 3u));
+    const uint32_t m_last = __builtin_amdgcn_readfirstlane(pose_mesh_of(tab, tri_first + wave_last / 3u));
+    const size_t at = 3u * (size_t)v;
+    const float x = rest[at], y = rest[at + 1], z = rest[at + 2];
+    float ox = x, oy = y, oz = z;
+    for (uint32_t m = m_first; m <= m_last; ++m) {
+        if ((tab.identity >> m) & 1u) continue;
+        const uint32_t begin = m ? tab.end[m - 1u] : 0u;
+        if (tri >= begin && tri < tab.end[m]) pose_vertex(tab.pose[m], x, y, z, ox, oy, oz);
+    }
+    posed[at] = ox;
+    posed[at + 1] = oy;
+    posed[at + 2] = oz;
+}
+
 }  // namespace XRT_KERNEL_NS

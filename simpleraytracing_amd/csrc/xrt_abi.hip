@@ -10,6 +10,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -323,7 +324,6 @@ struct xrt_context {
     float* d_tris = nullptr;       // raw triangle soup, 9 f32 per triangle
     uint64_t num_tris = 0;
     size_t tris_cap = 0;
-
     FrameSet sets[kFrameSets];
     int next_set = 0;
     FrameSet* last_set = nullptr;      // set of the last enqueued frame
@@ -456,13 +456,14 @@ struct xrt_context {
         xrt_camera cam;
         uint32_t row_begin, row_end;
         uint64_t T, gen;
+        uint64_t pose_gen;             // the meshes' poses (xrt_set_pose)
         // field by field (the struct has padding; the camera's floats by bits)
         bool same(const BinKey& o) const
         {
             return std::memcmp(&cam, &o.cam, sizeof cam) == 0 && row_begin == o.row_begin &&
-                   row_end == o.row_end && T == o.T && gen == o.gen;
+                   row_end == o.row_end && T == o.T && gen == o.gen && pose_gen == o.pose_gen;
         }
-        // the same region grid and mesh: only the camera's pose differs
+        // the same region grid and mesh: only the camera's or the meshes' pose differs
         bool same_layout(const BinKey& o) const
         {
             return cam.width == o.cam.width && cam.height == o.cam.height && row_begin == o.row_begin &&
@@ -540,6 +541,21 @@ struct xrt_context {
     uint64_t hp_calls = 0;
     uint64_t hp_sizings = 0, hp_reused = 0, hp_plan_miss = 0, hp_overflow = 0;   // frames by geometry path
     HostClock::time_point hp_last_end{};
+
+    // Mesh poses (xrt_set_pose): d_tris stays the rest soup.
+    // `poses` is empty while every mesh is at the identity: no posed soup, no
+    // kernel, every reader takes d_tris (render_soup).  Otherwise it holds one
+    // pose per mesh, readers take d_tris_posed, and `posed_written` the pose
+    // each mesh's range of it was last written with (empty: never written
+    // since the upload): the next render's k_pose rewrites the meshes that
+    // differ, on the prep stream ahead of its k_prep.
+    using Pose = std::array<float, kPoseFloats>;
+    float* d_tris_posed = nullptr;
+    size_t posed_cap = 0;
+    std::vector<Pose> poses;
+    std::vector<Pose> posed_written;
+    uint64_t pose_gen = 0;             // bumped by every pose change
+    uint64_t hp_pose_launches = 0, hp_pose_tris = 0;   // k_pose launches and the triangles they wrote
 };
 
 inline double seconds_since(HostClock::time_point t)
@@ -746,6 +762,75 @@ inline uint64_t render_tris(const xrt_context* ctx)
     return ctx->mesh_tris[0];
 }
 
+// The identity pose, bit for bit (+0.0 zeros).
+constexpr xrt_context::Pose kIdentityPose = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
+
+inline bool same_pose(const xrt_context::Pose& a, const xrt_context::Pose& b)
+{
+    return std::memcmp(a.data(), b.data(), sizeof(xrt_context::Pose)) == 0;
+}
+
+// Names the content of the soup the renders read: both counters only grow.
+inline uint64_t soup_gen(const xrt_context* ctx) { return ctx->mesh_gen + ctx->pose_gen; }
+
+// The soup a preparation reads (k_prep is the soup's only reader on the device:
+// the renders and their fix-up walks read k_prep's records): d_tris while
+// every pose is the identity, otherwise d_tris_posed -- after the k_pose
+// launches, enqueued here on the prep stream, that rewrite the id ranges of
+// the meshes whose pose differs from the one their range was last written
+// with.  A run of such meshes is one launch (kPoseLaunchTris triangles at
+// most).  Nothing on the device reads the posed soup while they are enqueued:
+// poses change only in xrt_set_pose / xrt_reset_poses and the uploads, which
+// wait for the context's work, and every reader is enqueued behind this on
+// the prep stream.  The host does not wait.
+int render_soup(xrt_context* ctx, const float*& soup)
+{
+    soup = ctx->d_tris;
+    if (ctx->poses.empty()) return XRT_OK;
+    const size_t M = ctx->mesh_tris.size();
+    if (!ctx->d_tris_posed || ctx->posed_cap < 9 * ctx->num_tris) ctx->posed_written.clear();
+    int rc = ensure(ctx, ctx->d_tris_posed, ctx->posed_cap, 9 * ctx->num_tris);
+    if (rc) return rc;
+    soup = ctx->d_tris_posed;
+    const bool all = ctx->posed_written.size() != M;
+    PoseTable tab;
+    std::memset(&tab, 0, sizeof tab);
+    uint64_t end = 0;
+    bool due = false;
+    for (size_t m = 0; m < kMaxMeshes; ++m) {
+        if (m < M) {
+            end += ctx->mesh_tris[m];
+            std::memcpy(tab.pose[m], ctx->poses[m].data(), sizeof tab.pose[m]);
+            if (same_pose(ctx->poses[m], kIdentityPose)) tab.identity |= 1u << m;
+            due = due || all || !same_pose(ctx->poses[m], ctx->posed_written[m]);
+        }
+        tab.end[m] = m < M ? (uint32_t)end : 0xFFFFFFFFu;
+    }
+    if (!due) return XRT_OK;
+    uint64_t first = 0;                            // of the run of meshes to write
+    for (size_t m = 0; m < M;) {
+        if (!all && same_pose(ctx->poses[m], ctx->posed_written[m])) {
+            first = tab.end[m++];
+            continue;
+        }
+        size_t last = m;
+        while (last + 1 < M && (all || !same_pose(ctx->poses[last + 1], ctx->posed_written[last + 1]))) ++last;
+        for (uint64_t t = first; t < tab.end[last]; t += kPoseLaunchTris) {
+            const uint64_t n = std::min<uint64_t>(kPoseLaunchTris, tab.end[last] - t);
+            hipLaunchKernelGGL(k_pose, dim3((unsigned)((3 * n + kPoseThreads - 1) / kPoseThreads)),
+                               dim3(kPoseThreads), 0, ctx->prep_stream, ctx->d_tris + 9 * t,
+                               ctx->d_tris_posed + 9 * t, (uint32_t)t, (uint32_t)(3 * n), tab);
+            XRT_HIP(ctx, hipGetLastError());
+            ++ctx->hp_pose_launches;
+            ctx->hp_pose_tris += n;
+        }
+        first = tab.end[last];
+        m = last + 1;
+    }
+    ctx->posed_written = ctx->poses;
+    return XRT_OK;
+}
+
 RenderParams make_params(const xrt_camera& c, uint32_t row_begin, uint32_t row_end, uint64_t T,
                          uint32_t capacity)
 {
@@ -930,10 +1015,12 @@ int launch_prep(xrt_context* ctx, FrameSet& fs, const RenderParams& p, const Cul
         ptimes = ctx->d_prep_times;
         ctx->prep_times_n = (size_t)blocks * kPrepWaves;
     }
+    const float* soup = nullptr;                   // (k_pose first when a pose changed: `stream` is the prep stream)
+    if (int rc = render_soup(ctx, soup)) return rc;
     const auto t_launch = HostClock::now();
     hipExtLaunchKernelGGL(k_prep, dim3((unsigned)blocks), dim3(kPrepThreads),
                           ctx->prep_lds, stream, nullptr, done, 0u,
-                          ctx->d_tris, (uint32_t)T, p, cp, fs.recs, culled ? fs.cull : nullptr, bins, bin_ctl,
+                          soup, (uint32_t)T, p, cp, fs.recs, culled ? fs.cull : nullptr, bins, bin_ctl,
                           fs.frame, fs.offsets, ptimes);
     XRT_HIP(ctx, hipGetLastError());
     if (bins.counts) ctx->prep_reads_layout = true;
@@ -1214,6 +1301,7 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     key.row_end = row_end;
     key.T = T;
     key.gen = ctx->mesh_gen;
+    key.pose_gen = ctx->pose_gen;
     // A new camera over the same region grid (a projection sweep) reuses the
     // lists sized for an earlier camera instead of the synchronous sizing
     // (DESIGN.md "Moving camera"), without a fill plan: k_prep flags a region
@@ -1751,6 +1839,7 @@ xrt_context::BinKey geometry_key(const xrt_context* ctx, const xrt_camera* cam, 
     key.row_end = row_end;
     key.T = render_tris(ctx);
     key.gen = ctx->mesh_gen;
+    key.pose_gen = ctx->pose_gen;
     return key;
 }
 
@@ -2049,6 +2138,7 @@ void xrt_destroy(xrt_context* ctx)
     lap(0);
     ctx->pool.reset();
     (void)hipFree(ctx->d_tris);
+    (void)hipFree(ctx->d_tris_posed);
     for (FrameSet& fs : ctx->sets) {
         (void)hipFree(fs.recs);
         (void)hipFree(fs.cull);
@@ -2200,6 +2290,8 @@ int xrt_upload_scene(xrt_context* ctx, const float* triangles, const uint64_t* m
     ctx->mesh_tris.assign(mesh_triangles, mesh_triangles + num_meshes);
     ++ctx->mesh_gen;
     ++ctx->state_gen;
+    ctx->poses.clear();                 // a new scene is at rest
+    ctx->posed_written.clear();
     return upload_tables(ctx);
 }
 
@@ -2220,6 +2312,8 @@ int xrt_upload_mesh(xrt_context* ctx, const float* triangles, uint64_t num_trian
     ctx->mesh_tris.assign(1, num_triangles);      // a one-mesh scene
     ++ctx->mesh_gen;
     ++ctx->state_gen;
+    ctx->poses.clear();                 // a new scene is at rest
+    ctx->posed_written.clear();
     return upload_tables(ctx);
 }
 
@@ -2376,6 +2470,103 @@ int xrt_set_paths(xrt_context* ctx)
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
     ctx->model = kModelPaths;
     ++ctx->state_gen;                   // frames prepared ahead are stale
+    return XRT_OK;
+}
+
+// Records a pose change: waits for the frames in flight (their k_prep reads the
+// soup the next k_pose rewrites) and drops the frames prepared ahead.  A pose
+// whose bits do not change is no change: no wait, no new generation.
+static int change_poses(xrt_context* ctx, std::vector<xrt_context::Pose> poses)
+{
+    bool rest = true;
+    for (const xrt_context::Pose& q : poses) rest = rest && same_pose(q, kIdentityPose);
+    if (rest) poses.clear();
+    if (poses.size() == ctx->poses.size() &&
+        std::equal(poses.begin(), poses.end(), ctx->poses.begin(), same_pose))
+        return XRT_OK;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = sync_context(ctx);
+    if (rc) return rc;
+    ctx->poses.swap(poses);
+    ++ctx->pose_gen;                    // BinKey::same: another geometry over the same layout
+    ++ctx->state_gen;                   // frames prepared ahead are stale
+    return XRT_OK;
+}
+
+int xrt_set_pose(xrt_context* ctx, uint32_t mesh, const float pose[12])
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (mesh >= ctx->mesh_tris.size())
+        return fail(ctx, XRT_ERR_ARGUMENT, "mesh " + std::to_string(mesh) + " is not a mesh of the scene (" +
+                                               std::to_string(ctx->mesh_tris.size()) + " meshes)");
+    xrt_context::Pose q = kIdentityPose;
+    if (pose) std::memcpy(q.data(), pose, sizeof q);
+    for (float v : q)
+        if (!std::isfinite(v)) return fail(ctx, XRT_ERR_ARGUMENT, "a pose value must be finite");
+    std::vector<xrt_context::Pose> poses = ctx->poses;
+    if (poses.empty()) poses.assign(ctx->mesh_tris.size(), kIdentityPose);
+    poses[mesh] = q;
+    return change_poses(ctx, std::move(poses));
+}
+
+int xrt_reset_poses(xrt_context* ctx)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    return change_poses(ctx, {});
+}
+
+#include "xrt_pose_host.inc"
+
+int xrt_debug_posed_triangles(xrt_context* ctx, float* dst, uint64_t capacity_floats, uint64_t* n_floats)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    const uint64_t n = 9 * ctx->num_tris;
+    if (n_floats) *n_floats = n;
+    if (!dst) return XRT_OK;
+    if (capacity_floats < n) return fail(ctx, XRT_ERR_ARGUMENT, "dst is smaller than the soup");
+    if (!n) return XRT_OK;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const float* soup = nullptr;
+    int rc = render_soup(ctx, soup);              // k_pose, if one is due
+    if (rc) return rc;
+    XRT_HIP(ctx, hipStreamSynchronize(ctx->prep_stream));
+    XRT_HIP(ctx, hipMemcpy(dst, soup, n * sizeof(float), hipMemcpyDeviceToHost));
+    return XRT_OK;
+}
+
+int xrt_debug_pose_span(xrt_context* ctx, uint32_t launches, double* us_per_write)
+{
+    if (!ctx || !us_per_write || !launches) return XRT_ERR_ARGUMENT;
+    if (ctx->poses.empty()) return fail(ctx, XRT_ERR_ARGUMENT, "no pose is set");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = sync_context(ctx);
+    if (rc) return rc;
+    const float* soup = nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    XRT_HIP(ctx, hipEventCreate(&t0));
+    XRT_HIP(ctx, hipEventCreate(&t1));
+    ctx->posed_written.clear();
+    rc = render_soup(ctx, soup);                  // (allocation and first touch outside the span)
+    if (!rc) rc = hipEventRecord(t0, ctx->prep_stream) == hipSuccess ? XRT_OK : XRT_ERR_DEVICE;
+    for (uint32_t k = 0; k < launches && !rc; ++k) {
+        ctx->posed_written.clear();               // every mesh due again
+        rc = render_soup(ctx, soup);
+    }
+    float ms = 0.0f;
+    if (!rc && (hipEventRecord(t1, ctx->prep_stream) != hipSuccess || hipEventSynchronize(t1) != hipSuccess ||
+                hipEventElapsedTime(&ms, t0, t1) != hipSuccess))
+        rc = fail(ctx, XRT_ERR_DEVICE, "pose span: events failed");
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    *us_per_write = (double)ms * 1e3 / launches;
+    return rc;
+}
+
+int xrt_debug_pose_counters(xrt_context* ctx, uint64_t counters[2])
+{
+    if (!ctx || !counters) return XRT_ERR_ARGUMENT;
+    counters[0] = ctx->hp_pose_launches;
+    counters[1] = ctx->hp_pose_tris;
     return XRT_OK;
 }
 
@@ -3309,8 +3500,12 @@ int xrt_probe_prep(xrt_context* ctx, const xrt_camera* camera, float* records, f
     p.model = ctx->model;
     CullParams cp = make_cull_params(*camera);
     BinBuffers nobins = {};
+    // (k_pose, when one is due, runs on the prep stream; this k_prep on the null stream)
+    const float* soup = nullptr;
+    if ((rc = render_soup(ctx, soup))) return rc;
+    XRT_HIP(ctx, hipStreamSynchronize(ctx->prep_stream));
     hipLaunchKernelGGL(k_prep, dim3((unsigned)((T + kPrepWaves * p.prep_tris - 1) / (kPrepWaves * p.prep_tris))),
-                       dim3(kPrepThreads), 0, 0, ctx->d_tris,
+                       dim3(kPrepThreads), 0, 0, soup,
                        (uint32_t)T, p, cp, fs.recs, fs.cull, nobins, nullptr, nullptr, nullptr, nullptr);
     XRT_HIP(ctx, hipGetLastError());
     if (records)

@@ -408,7 +408,7 @@ xrt_multi::HitKey hit_key(xrt_multi* m, uint32_t g, const xrt_camera* camera, ui
     k.cam = *camera;
     k.b = b;
     k.e = e;
-    k.gen = m->ctx[g]->mesh_gen;
+    k.gen = soup_gen(m->ctx[g]);
     k.kernel = m->ctx[g]->kernel;
     k.valid = true;
     return k;
@@ -614,7 +614,7 @@ int collect_model(xrt_multi* m, const xrt_camera* camera, const std::vector<uint
 {
     const uint32_t n = (uint32_t)m->devices.size();
     if (m->collected && std::memcmp(&m->pending_cam, camera, sizeof *camera) == 0 &&
-        m->pending_gen == m->ctx[0]->mesh_gen)
+        m->pending_gen == soup_gen(m->ctx[0]))
         return XRT_OK;                                 // this camera's strips were modelled already
     for (uint32_t g = 0; g < n; ++g)
         if (!pf[g].binned || pf[g].rows == 0 || !m->ctx[g]->last_set || !m->ctx[g]->last_set->binned) return XRT_OK;
@@ -661,7 +661,7 @@ int collect_model(xrt_multi* m, const xrt_camera* camera, const std::vector<uint
     m->model_pending = true;
     m->collected = true;
     m->pending_cam = *camera;
-    m->pending_gen = m->ctx[0]->mesh_gen;
+    m->pending_gen = soup_gen(m->ctx[0]);
     return XRT_OK;
 }
 
@@ -682,7 +682,7 @@ int plan_strips(xrt_multi* m, const xrt_camera* camera, std::vector<uint32_t>& b
         return XRT_OK;
     }
     xrt_multi::Plan& P = m->plan;
-    if (P.valid && std::memcmp(&P.cam, camera, sizeof *camera) == 0 && P.gen == c0->mesh_gen &&
+    if (P.valid && std::memcmp(&P.cam, camera, sizeof *camera) == 0 && P.gen == soup_gen(c0) &&
         P.kernel == c0->kernel && P.model == (int)c0->model && P.split == m->split && P.link_set == m->link_set) {
         b = P.b;
         e = P.e;
@@ -693,7 +693,7 @@ int plan_strips(xrt_multi* m, const xrt_camera* camera, std::vector<uint32_t>& b
     // context's first frame -- splits equally (not a plan: the next frame of
     // this camera plans from the first one's strips)
     harvest_model(m);
-    if (!m->model_valid || m->model_w != camera->width || m->model_h != H || m->model_gen != c0->mesh_gen ||
+    if (!m->model_valid || m->model_w != camera->width || m->model_h != H || m->model_gen != soup_gen(c0) ||
         m->model_cost.size() != bands) {
         equal();
         ++m->n_equal_no_model;
@@ -723,7 +723,7 @@ int plan_strips(xrt_multi* m, const xrt_camera* camera, std::vector<uint32_t>& b
     }
     P.valid = true;
     P.cam = *camera;
-    P.gen = c0->mesh_gen;
+    P.gen = soup_gen(c0);
     P.kernel = c0->kernel;
     P.model = (int)c0->model;
     P.split = m->split;
@@ -977,6 +977,26 @@ int xrt_multi_set_spectrum(xrt_multi* m, const float* weight, const float* mu, u
         int rc = check_ctx(m, g, xrt_set_spectrum(m->ctx[g], weight, mu, num_meshes, num_bins));
         if (rc) return rc;
         rc = check_ctx(m, g, xrt_set_miss_code(m->ctx[g], 0u));   // a miss is the table's miss value: no transit code
+        if (rc) return rc;
+    }
+    return XRT_OK;
+}
+
+int xrt_multi_set_pose(xrt_multi* m, uint32_t mesh, const float pose[12])
+{
+    if (!m) return mfail(nullptr, XRT_ERR_ARGUMENT, "multi context is NULL");
+    for (size_t g = 0; g < m->ctx.size(); ++g) {   // every device poses its own copy of the scene
+        int rc = check_ctx(m, g, xrt_set_pose(m->ctx[g], mesh, pose));
+        if (rc) return rc;
+    }
+    return XRT_OK;
+}
+
+int xrt_multi_reset_poses(xrt_multi* m)
+{
+    if (!m) return mfail(nullptr, XRT_ERR_ARGUMENT, "multi context is NULL");
+    for (size_t g = 0; g < m->ctx.size(); ++g) {
+        int rc = check_ctx(m, g, xrt_reset_poses(m->ctx[g]));
         if (rc) return rc;
     }
     return XRT_OK;
