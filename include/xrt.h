@@ -447,6 +447,55 @@ int xrt_reset_poses(xrt_context* ctx);
 int xrt_pose_rotation(const float axis[3], double degrees, const float centre[3], float pose[12]);
 int xrt_pose_triangles(const float* tris, uint64_t n, const float pose[12], float* out);
 
+/* --- the detector response: a separable line-spread function -------------- */
+
+/*
+ * What a real flat panel adds to the ideal detector's image (DESIGN.md section
+ * 10.5): every photon value spread over its neighbours by a separable
+ * line-spread function (LSF).  `image` is num_planes row-major f32 planes of
+ * width x height pixels, one after another (a scan's projections in one call);
+ * lsf_x[taps_x] and lsf_y[taps_y] are the taps, each count odd and in
+ * 1..XRT_MAX_LSF_TAPS, rx = (taps_x - 1) / 2, ry = (taps_y - 1) / 2.  With
+ * cx(i) = min(max(i, 0), width - 1) and cy likewise (the edge pixels are
+ * replicated), per plane
+ *   tmp[y][x] = (float)(sum over k = 0..taps_x-1, in this order, in f64, of
+ *                       (double)lsf_x[k] * (double)image[y][cx(x + k - rx)])
+ *   out[y][x] = (float)(sum over k = 0..taps_y-1, in this order, in f64, of
+ *                       (double)lsf_y[k] * (double)tmp[cy(y + k - ry)][x])
+ * each sum starting from its k = 0 product (not from +0.0: the one-tap LSF
+ * {1.0f} on both axes returns the image bit for bit, -0.0 included) and tmp
+ * rounded to f32.  The taps are applied as written -- a correlation: lsf_x[0]
+ * meets the pixel rx to the LEFT of the output, so an asymmetric LSF given as a
+ * convolution kernel is the caller's to flip -- and as given: nothing is
+ * normalised.  out_u8 is the 8-bit image of out in the fixed window 0..80.  A
+ * pixel whose window holds a non-finite value is NaN or +-inf as IEEE
+ * arithmetic gives it; a NaN's sign and payload are not specified.
+ *
+ * Either of out and out_u8 may be NULL, not both.  XRT_ERR_ARGUMENT for a NULL
+ * image or tap pointer, an even tap count or one outside 1..XRT_MAX_LSF_TAPS, a
+ * tap that is not finite, a width, height or num_planes of 0 (or more than
+ * 65535 planes or 64-row bands), and an output that overlaps the image: a
+ * pixel is computed from its neighbours' input, so in place is refused.  All of
+ * that is checked, the taps first, before the context is looked at.
+ * xrt_detector_response: host buffers, synchronous.  _device: device buffers,
+ * asynchronous on `stream`; the taps travel with the launch, so it may be
+ * called again with other taps at once.  Neither touches the context's model,
+ * scene or frames in flight.  There is no xrt_multi_ form.
+ *
+ * xrt_lsf_gaussian (host arithmetic, no device): g[k] = exp(-0.5 * ((k - r) /
+ * sigma_pixels)^2) in f64, s = the sum of g in index order, lsf[k] =
+ * (float)(g[k] / s); XRT_ERR_ARGUMENT unless sigma_pixels is finite and > 0 and
+ * taps odd and in range.
+ */
+#define XRT_MAX_LSF_TAPS 129
+int xrt_detector_response(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                          const float* image, const float* lsf_x, uint32_t taps_x, const float* lsf_y,
+                          uint32_t taps_y, float* out, uint8_t* out_u8);
+int xrt_detector_response_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                                 const float* d_image, const float* lsf_x, uint32_t taps_x, const float* lsf_y,
+                                 uint32_t taps_y, float* d_out, uint8_t* d_out_u8, void* stream);
+int xrt_lsf_gaussian(double sigma_pixels, uint32_t taps, float* lsf);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

@@ -247,6 +247,14 @@ int xrt_debug_pose_span(xrt_context* ctx, uint32_t launches, double* us_per_writ
 int xrt_debug_pose_counters(xrt_context* ctx, uint64_t counters[2]);
 
 /*
+ * Test hook (host code, no device): xrt_detector_response's arithmetic over
+ * whole planes, by the function k_lsf runs per tap (lsf_chunk, host-compiled).
+ * Arguments and checks as xrt_detector_response's, host buffers.
+ */
+int xrt_host_lsf(uint32_t width, uint32_t height, uint32_t num_planes, const float* image, const float* lsf_x,
+                 uint32_t taps_x, const float* lsf_y, uint32_t taps_y, float* out, uint8_t* out_u8);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

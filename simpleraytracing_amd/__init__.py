@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -30,6 +30,7 @@ __all__ = [
     "XRT_MODEL_ATTENUATION", "XRT_MODEL_SIGNED", "XRT_GATHER_AUTO", "XRT_GATHER_COPY", "XRT_GATHER_RCCL",
     "XRT_SPLIT_EQUAL", "XRT_SPLIT_BALANCED", "XRT_TRANSIT_HITS", "XRT_TRANSIT_PACKED", "XRT_MODEL_MATERIALS",
     "XRT_MAX_MESHES", "XRT_MODEL_SPECTRUM", "XRT_MAX_BINS", "XRT_MODEL_PATHS", "pose_rotation", "pose_triangles",
+    "XRT_MAX_LSF_TAPS", "lsf_gaussian", "host_lsf", "detector_response",
 ]
 
 
@@ -184,6 +185,50 @@ def pose_triangles(tris: np.ndarray, pose) -> np.ndarray:
     if rc != _abi.XRT_OK:
         raise XrtError(rc, "xrt_pose_triangles")
     return out
+
+
+def _lsf_arrays(lsf_x, lsf_y):
+    """The taps as xrt_detector_response takes them (lsf_y None: lsf_x on both axes)."""
+    hx = np.ascontiguousarray(lsf_x, dtype=np.float32).reshape(-1)
+    hy = hx if lsf_y is None else np.ascontiguousarray(lsf_y, dtype=np.float32).reshape(-1)
+    return hx, hy
+
+
+def _lsf_planes(image):
+    """An (H, W) image or a (P, H, W) stack as contiguous f32: (array, P, H, W)."""
+    a = np.ascontiguousarray(image, dtype=np.float32)
+    if a.ndim not in (2, 3):
+        raise ValueError(f"an image is (H, W) or (P, H, W), got shape {a.shape}")
+    p = 1 if a.ndim == 2 else a.shape[0]
+    return a, p, a.shape[-2], a.shape[-1]
+
+
+def lsf_gaussian(sigma: float, taps: int) -> np.ndarray:
+    """`taps` (odd) samples of a Gaussian line-spread function of `sigma` pixels, normalised (xrt_lsf_gaussian)."""
+    out = np.empty(max(int(taps), 1), np.float32)
+    rc = _abi.load().xrt_lsf_gaussian(float(sigma), int(taps), _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_lsf_gaussian: sigma must be finite and > 0, taps odd and in 1..XRT_MAX_LSF_TAPS")
+    return out
+
+
+def host_lsf(image, lsf_x, lsf_y=None, u8=True):
+    """The detector response in the device's arithmetic on the host (xrt_host_lsf, a test hook): (out, u8)."""
+    a, p, h, w = _lsf_planes(image)
+    hx, hy = _lsf_arrays(lsf_x, lsf_y)
+    out = np.empty_like(a)
+    u = np.empty(a.shape, np.uint8) if u8 else None
+    rc = _abi.load().xrt_host_lsf(w, h, p, _fptr(a), _fptr(hx), hx.size, _fptr(hy), hy.size, _fptr(out),
+                                  _u8ptr(u) if u is not None else None)
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_lsf")
+    return out, u
+
+
+def detector_response(image, lsf_x, lsf_y=None, device: int = 0) -> np.ndarray:
+    """The blurred f32 image(s) of Context.detector_response, on a context of its own on `device`."""
+    with Context(device) as ctx:
+        return ctx.detector_response(image, lsf_x, lsf_y, u8=False)[0]
 
 
 class Context:
@@ -379,6 +424,29 @@ class Context:
                                                  d_open or None, _fptr(w), _fptr(mu), w.size, d_lbuffer or None,
                                                  stream or None)
         self._check(rc, "xrt_apply_spectrum_device")
+
+    def detector_response(self, image, lsf_x, lsf_y=None, out=True, u8=True):
+        """The detector's line-spread function over an (H, W) image or a (P, H, W) stack of them (taps as
+        written -- a correlation --, edges replicated, lsf_y None: lsf_x on both axes): (out f32, u8), of the
+        image's shape; out=False or u8=False leaves that plane out (None)."""
+        a, p, h, w = _lsf_planes(image)
+        hx, hy = _lsf_arrays(lsf_x, lsf_y)
+        o = np.empty_like(a) if out else None
+        u = np.empty(a.shape, np.uint8) if u8 else None
+        self._check(self._lib.xrt_detector_response(
+            self._ctx, w, h, p, _fptr(a), _fptr(hx), hx.size, _fptr(hy), hy.size,
+            _fptr(o) if o is not None else None, _u8ptr(u) if u is not None else None), "xrt_detector_response")
+        return o, u
+
+    def detector_response_device(self, width: int, height: int, num_planes: int, d_image: int, lsf_x, lsf_y,
+                                 d_out: int, d_u8: int = 0, stream: int = 0):
+        """detector_response over device buffers (raw pointers; the taps are host data and travel with the
+        launch); asynchronous on `stream`."""
+        hx, hy = _lsf_arrays(lsf_x, lsf_y)
+        rc = self._lib.xrt_detector_response_device(self._ctx, int(width), int(height), int(num_planes),
+                                                    d_image or None, _fptr(hx), hx.size, _fptr(hy), hy.size,
+                                                    d_out or None, d_u8 or None, stream or None)
+        self._check(rc, "xrt_detector_response_device")
 
     def render_signed(self, cam: Camera):
         """The L-buffer fork end to end: (image f32, lbuffer f32 with -1 flags, u8, Stats)."""

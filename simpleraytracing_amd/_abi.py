@@ -40,6 +40,7 @@ XRT_MAX_MESHES = 16
 XRT_MODEL_SPECTRUM = 3
 XRT_MAX_BINS = 32
 XRT_MODEL_PATHS = 4
+XRT_MAX_LSF_TAPS = 129
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -170,6 +171,10 @@ XRT_SYMBOLS = {
     "xrt_debug_posed_triangles": (ctypes.c_int, [_CtxP, _fp, _u64, ctypes.POINTER(_u64)]),
     "xrt_debug_pose_span": (ctypes.c_int, [_CtxP, _u32, _dp]),
     "xrt_debug_pose_counters": (ctypes.c_int, [_CtxP, ctypes.POINTER(_u64)]),
+    "xrt_detector_response": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _fp, _u32, _fp, _u32, _fp, _u8p]),
+    "xrt_detector_response_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _fp, _u32, _fp, _u32, _vp, _vp, _vp]),
+    "xrt_lsf_gaussian": (ctypes.c_int, [ctypes.c_double, _u32, _fp]),
+    "xrt_host_lsf": (ctypes.c_int, [_u32, _u32, _u32, _fp, _fp, _u32, _fp, _u32, _fp, _u8p]),
     "xrt_multi_set_pose": (ctypes.c_int, [_MultiP, _u32, _fp]),
     "xrt_multi_reset_poses": (ctypes.c_int, [_MultiP]),
     "xrt_host_mt_check": (None, [_fp, _fp, _fp, _fp, _u64, ctypes.POINTER(ctypes.c_uint8),

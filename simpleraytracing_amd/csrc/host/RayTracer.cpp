@@ -430,6 +430,19 @@ void applySpectrum(Image& image, const std::vector<std::vector<float>>& paths, c
           "xrt_hole_fill");
 }
 
+void applyDetectorResponse(Image& image, const std::vector<float>& lsf_x, const std::vector<float>& lsf_y)
+{
+    const size_t n = (size_t)image.getWidth() * image.getHeight();
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    std::vector<float> out(n);
+    check(ctx, xrt_detector_response(ctx, image.getWidth(), image.getHeight(), 1, image.getData(), lsf_x.data(),
+                                     (uint32_t)lsf_x.size(), lsf_y.data(), (uint32_t)lsf_y.size(), out.data(), nullptr),
+          "xrt_detector_response");
+    std::copy(out.begin(), out.end(), image.getData());
+}
+
 namespace {
 
 // One multi-device context per device list for the process lifetime: the

@@ -133,6 +133,12 @@ void applySpectrum(Image& output_image, const std::vector<std::vector<float>>& p
                    const std::vector<unsigned short>& open, const std::vector<float>& weight,
                    const std::vector<float>& mu, std::vector<float>* lbuffer = nullptr);
 
+// The detector response (xrt_detector_response): the image under a separable
+// line-spread function, lsf_x along the rows and lsf_y down the columns (odd
+// counts, at most XRT_MAX_LSF_TAPS; applied as written -- a correlation --,
+// edges replicated, nothing normalised), in place in output_image.  One device.
+void applyDetectorResponse(Image& output_image, const std::vector<float>& lsf_x, const std::vector<float>& lsf_y);
+
 // Row strips over `num_gpus` devices (rows_per = H / n, remainder to the first
 // strips), one host thread per device; returns the number of odd rays.
 unsigned long long renderLoopMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,

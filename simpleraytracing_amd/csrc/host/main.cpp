@@ -36,6 +36,17 @@
 //                              through the rest scene's box centre, under the rest
 //                              scene's camera, and is written to NAME.pKKK.EXT (so are
 //                              --lbuffer's and --u8's files)
+//       --lsf FILE             the detector's line-spread function over the image that
+//                              NAME.EXT and --u8 receive (every model; every projection
+//                              of --turntable; with --paths, --spectrum's image).  FILE
+//                              is text as --spectrum's: the first data line holds the
+//                              taps along x, an optional second line those along y (one
+//                              line: both axes); an odd count, at most 129; applied as
+//                              written (a correlation), edges replicated, not normalised.
+//                              --lbuffer, NAME.m<m> and NAME.open stay as rendered
+//       --lsf-gaussian SIGMA[:TAPS]  the same with a normalised Gaussian of SIGMA pixels
+//                              on both axes, TAPS (odd) defaulting to 2*ceil(4*SIGMA)+1,
+//                              at most 129
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -82,6 +93,8 @@ void showUsage(const std::string& prog)
               << "\t--paths\t\t\t\tPaths model: write each mesh's path-length plane (NAME.m<m>.EXT) and the open mask (NAME.open.EXT); with --spectrum FILE, apply it to the planes\n"
               << "\t--pose M=v0,...,v11\t\tMesh M under a pose: 12 values, row-major 3x4 [R | t]; repeat for other meshes\n"
               << "\t--turntable N[:x|y|z][:M,...]\tN projections, the listed meshes (default: all) turned k*360/N degrees about the axis (default y) through the scene's centre; writes NAME.pKKK.EXT\n"
+              << "\t--lsf FILE\t\t\tDetector line-spread function over the written image: FILE holds a line of taps along x and, optionally, one along y (odd counts, at most 129)\n"
+              << "\t--lsf-gaussian SIGMA[:TAPS]\tThe same with a normalised Gaussian of SIGMA pixels (TAPS odd, default 2*ceil(4*SIGMA)+1, at most 129)\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -110,6 +123,8 @@ struct Options {
     unsigned turntable = 0;                    // --turntable: projections (0: none)
     int turn_axis = 1;                         // 0 x, 1 y, 2 z
     std::vector<unsigned> turn_meshes;         // empty: every mesh
+    bool lsf_file = false, lsf_gauss = false;  // --lsf, --lsf-gaussian
+    std::vector<float> lsf_x, lsf_y;           // the detector response's taps (empty: none)
 };
 
 // A whole, non-negative decimal number.
@@ -245,6 +260,72 @@ void read_spectrum(const std::string& path, std::vector<float>& weight, std::vec
     if (mu.empty()) throw std::runtime_error("--spectrum: " + path + " holds no mesh's coefficients");
 }
 
+// A tap count the library takes.
+void check_taps(const std::string& option, const std::string& where, size_t n)
+{
+    if (n % 2 == 0 || n > XRT_MAX_LSF_TAPS)
+        throw std::runtime_error(option + ": " + where + std::to_string(n) + " taps; the count must be odd and at most " +
+                                 std::to_string(XRT_MAX_LSF_TAPS));
+}
+
+// --lsf FILE: the first data line is the taps along x, an optional second one
+// those along y ('#' starts a comment, blank lines are skipped).
+void read_lsf(const std::string& path, std::vector<float>& lsf_x, std::vector<float>& lsf_y)
+{
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("--lsf: cannot read " + path);
+    std::string line;
+    unsigned rows = 0;
+    for (unsigned n = 1; std::getline(in, line); ++n) {
+        line = line.substr(0, line.find('#'));
+        std::istringstream fields(line);
+        std::vector<float> row;
+        for (std::string f; fields >> f;) {
+            size_t used = 0;
+            float v = 0.0f;
+            try {
+                v = std::stof(f, &used);
+            } catch (const std::exception&) {
+                used = 0;
+            }
+            if (used != f.size() || !std::isfinite(v))
+                throw std::runtime_error("--lsf: " + path + ":" + std::to_string(n) + ": '" + f + "' is not a finite number");
+            row.push_back(v);
+        }
+        if (row.empty()) continue;
+        if (++rows > 2)
+            throw std::runtime_error("--lsf: " + path + ":" + std::to_string(n) + ": a third line of taps (x, then y)");
+        check_taps("--lsf", path + ":" + std::to_string(n) + ": ", row.size());
+        (rows == 1 ? lsf_x : lsf_y) = row;
+    }
+    if (lsf_x.empty()) throw std::runtime_error("--lsf: " + path + " holds no taps");
+    if (lsf_y.empty()) lsf_y = lsf_x;
+}
+
+// --lsf-gaussian SIGMA[:TAPS]
+void parse_lsf_gaussian(const std::string& arg, std::vector<float>& lsf_x, std::vector<float>& lsf_y)
+{
+    const std::vector<std::string> parts = split(arg, ':');
+    double sigma = 0.0;
+    size_t used = 0;
+    try {
+        sigma = std::stod(parts[0], &used);
+    } catch (const std::exception&) {
+        used = 0;
+    }
+    if (parts.size() > 2 || parts[0].empty() || used != parts[0].size() || !std::isfinite(sigma) || !(sigma > 0.0))
+        throw std::runtime_error("--lsf-gaussian SIGMA[:TAPS]: SIGMA is a finite number of pixels above 0");
+    unsigned taps = (unsigned)std::min(2.0 * std::ceil(4.0 * sigma) + 1.0, (double)XRT_MAX_LSF_TAPS);
+    if (parts.size() == 2) {
+        if (!parse_index(parts[1], taps)) throw std::runtime_error("--lsf-gaussian SIGMA[:TAPS]: '" + parts[1] + "' is not a tap count");
+        check_taps("--lsf-gaussian", "", taps);
+    }
+    lsf_x.resize(taps);
+    if (xrt_lsf_gaussian(sigma, taps, lsf_x.data()) != XRT_OK)
+        throw std::runtime_error("--lsf-gaussian SIGMA[:TAPS]: '" + arg + "'");
+    lsf_y = lsf_x;
+}
+
 Options processCmd(int argc, char** argv)
 {
     Options o;
@@ -298,6 +379,12 @@ Options processCmd(int argc, char** argv)
             parse_pose(parse_str(argv[0], argc, argv, i), o);
         } else if (a == "--turntable") {
             parse_turntable(parse_str(argv[0], argc, argv, i), o);
+        } else if (a == "--lsf") {
+            o.lsf_file = true;
+            read_lsf(parse_str(argv[0], argc, argv, i), o.lsf_x, o.lsf_y);
+        } else if (a == "--lsf-gaussian") {
+            o.lsf_gauss = true;
+            parse_lsf_gaussian(parse_str(argv[0], argc, argv, i), o.lsf_x, o.lsf_y);
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -332,6 +419,13 @@ Options processCmd(int argc, char** argv)
         throw std::runtime_error("--paths renders whole frames on one GPU");
     if (o.turntable && (o.paths || o.batch || o.gpus > 1))
         throw std::runtime_error("--turntable renders on one GPU, without --paths, --batch and -g");
+    if (o.lsf_file && o.lsf_gauss) throw std::runtime_error("--lsf and --lsf-gaussian are two detector responses: give one");
+    if (!o.lsf_x.empty() && (o.gpus > 1 || o.rows))
+        throw std::runtime_error(std::string(o.lsf_file ? "--lsf" : "--lsf-gaussian") +
+                                 " needs whole frames on one GPU: not with -g N or --rows");
+    if (!o.lsf_x.empty() && o.paths && !o.spectrum)
+        throw std::runtime_error(std::string(o.lsf_file ? "--lsf" : "--lsf-gaussian") +
+                                 " with --paths needs --spectrum: the planes stay as rendered, there is no image to spread");
     if (o.signed_model && !o.materials.empty())
         throw std::runtime_error("--signed and --materials are two models: give one");
     if (o.spectrum && (o.signed_model || !o.materials.empty()))
@@ -471,6 +565,9 @@ int main(int argc, char** argv)
                     std::cout << "Frames: " << opt.batch << ", device time per frame " << ms_per_frame << " ms ("
                               << rays / (ms_per_frame * 1e3) << " Mrays/s)" << std::endl;
             }
+
+            // the detector's response, over the image only (the L-buffer and the planes stay as rendered)
+            if (!opt.lsf_x.empty()) applyDetectorResponse(image, opt.lsf_x, opt.lsf_y);
 
             Image* out = &image;
             Image strip;

@@ -849,4 +849,109 @@ __host__ __device__ __forceinline__ uint8_t lut_u8(float v)
     return v > vmax ? (uint8_t)255u : v >= vmin ? (uint8_t)r : (uint8_t)0u;
 }
 
+// ---------------------------------------------------------------------------
+// The detector response: a separable line-spread function over an
+// image plane, taps applied as written (a correlation), edges replicated, each
+// pass summed in f64 in tap order and rounded once to f32.  The taps travel by
+// value in k_lsf's kernel arguments, already widened to f64 (exact) -- scalar
+// loads put them where v_fma_f64 reads them, with no conversion per tap -- and
+// zero-padded to whole chunks of kLsfChunk, so that the next chunk's taps can
+// be fetched ahead unconditionally (a pad meets no value).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMaxLsfTaps = 129;
+constexpr uint32_t kLsfChunk = 8;       // outputs a thread carries along the axis of its pass
+constexpr uint32_t kLsfTapsPadded = (kMaxLsfTaps + kLsfChunk - 1) / kLsfChunk * kLsfChunk;
+struct LsfTable {
+    double hx[kLsfTapsPadded];
+    double hy[kLsfTapsPadded];
+    uint32_t nx, ny;
+};
+
+inline void lsf_table_set(LsfTable& tab, const float* lsf_x, uint32_t taps_x, const float* lsf_y, uint32_t taps_y)
+{
+    for (uint32_t k = 0; k < kLsfTapsPadded; ++k) {
+        tab.hx[k] = k < taps_x ? (double)lsf_x[k] : 0.0;
+        tab.hy[k] = k < taps_y ? (double)lsf_y[k] : 0.0;
+    }
+    tab.nx = taps_x;
+    tab.ny = taps_y;
+}
+
+// acc + h * v in f64.  The product of two f32 values is exact in f64 (48
+// significand bits, exponents in range), so the fused and the separate form
+// round identically: the device takes v_fma_f64, the host the plain expression.
+__host__ __device__ __forceinline__ double lsf_step(double h, double v, double acc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fma(h, v, acc);
+#else
+    return acc + h * v;
+#endif
+}
+
+// kLsfChunk neighbouring outputs of one pass: acc[r] = sum over k = 0..n-1, in
+// this order, of h[k] * (double)v(r + k), where h is a table's padded taps and
+// v(i) the i-th value of the line through the outputs, v(0) the first output's
+// leftmost (topmost) neighbour.  The values slide through a register window -- one new
+// value a tap, kLsfChunk sums -- whose rotation is static with the tap loop
+// unrolled by kLsfChunk.  The next chunk's values are fetched before the
+// current chunk's sums and the taps half a chunk ahead, so their latency hides
+// behind the FMAs.  That reads v ahead of need, up to index n + 2 kLsfChunk -
+// 2: what lies past n + kLsfChunk - 2 meets no tap, and only has to be
+// readable (k_lsf lays its LDS images out accordingly).  An
+// accumulator starts at -0.0, which gives the k = 0 product bit for bit once
+// that is added: x + -0.0 == x for every x, -0.0 and +0.0 included.
+template <class Value>
+__host__ __device__ __forceinline__ void lsf_chunk(const double* h, uint32_t n, Value v, double (&acc)[kLsfChunk])
+{
+    constexpr uint32_t kHalf = kLsfChunk / 2u;
+    double win[kLsfChunk], ha[kHalf], hb[kHalf];      // ha: a chunk's first taps, hb: its last
+    float raw[kLsfChunk];
+#pragma unroll
+    for (uint32_t r = 0; r < kLsfChunk; ++r) {
+        win[r] = (double)v(r);
+        acc[r] = -0.0;
+        raw[r] = v(kLsfChunk + r);
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kHalf; ++u) ha[u] = h[u];
+    uint32_t k = 0;
+    for (; k + kLsfChunk <= n; k += kLsfChunk) {
+        float raw_next[kLsfChunk];
+#pragma unroll
+        for (uint32_t u = 0; u < kLsfChunk; ++u) raw_next[u] = v(k + 2u * kLsfChunk + u);
+#pragma unroll
+        for (uint32_t u = 0; u < kHalf; ++u) hb[u] = h[k + kHalf + u];
+#pragma unroll
+        for (uint32_t u = 0; u < kHalf; ++u) {
+#pragma unroll
+            for (uint32_t r = 0; r < kLsfChunk; ++r) acc[r] = lsf_step(ha[u], win[(u + r) % kLsfChunk], acc[r]);
+            win[u] = (double)raw[u];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kHalf; ++u) ha[u] = h[k + kLsfChunk + u];   // (below kLsfTapsPadded: k + kLsfChunk <= n)
+#pragma unroll
+        for (uint32_t u = kHalf; u < kLsfChunk; ++u) {
+#pragma unroll
+            for (uint32_t r = 0; r < kLsfChunk; ++r) acc[r] = lsf_step(hb[u - kHalf], win[(u + r) % kLsfChunk], acc[r]);
+            win[u] = (double)raw[u];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kLsfChunk; ++u) raw[u] = raw_next[u];
+    }
+    if (k < n) {                                          // the last n % kLsfChunk taps
+#pragma unroll
+        for (uint32_t u = 0; u < kHalf; ++u) hb[u] = h[k + kHalf + u];
+#pragma unroll
+        for (uint32_t u = 0; u + 1 < kLsfChunk; ++u) {
+            if (k + u < n) {
+                const double hk = u < kHalf ? ha[u % kHalf] : hb[u % kHalf];
+#pragma unroll
+                for (uint32_t r = 0; r < kLsfChunk; ++r) acc[r] = lsf_step(hk, win[(u + r) % kLsfChunk], acc[r]);
+                win[u] = (double)raw[u];
+            }
+        }
+    }
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -3762,4 +3762,105 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose(const float* __restrict__
     posed[at + 2] = oz;
 }
 
+// ---------------------------------------------------------------------------
+// k_lsf: the detector response, both passes in one launch.  A
+// workgroup of four waves owns a kLsfTile x kLsfTile tile of output pixels of
+// plane blockIdx.z and keeps two images in its (dynamic) LDS:
+//   stage  64 input rows of the tile's columns and their 2 rx neighbours, the
+//          edge rule applied while loading (coalesced along x);
+//   tmp    the horizontal pass of the tile's rows and their 2 ry halo rows,
+//          rounded to f32 as the contract has it.
+// Horizontal pass, 64 rows at a time: lane = row, a wave takes runs of
+// kLsfChunk outputs along x (lsf_chunk: one LDS read and kLsfChunk f64 FMAs a
+// tap).  Vertical pass: lane = column, a wave takes runs of kLsfChunk rows.
+// Both pitches are odd, so the lanes of a row-per-lane access fall on
+// different banks; the column-per-lane accesses are consecutive.  lsf_chunk
+// reads up to kLsfChunk - 1 values ahead of the last one a tap meets: past a
+// stage row that is the next row, past the last one kLsfChunk floats of
+// padding, and past tmp, which lies first, the stage -- readable, never used.
+// The taps are scalar loads from the kernel's argument segment.  No scratch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kLsfTile = 64;
+constexpr uint32_t kLsfThreads = 256;
+
+__host__ __device__ constexpr uint32_t lsf_stage_pitch(uint32_t nx) { return kLsfTile + nx; }   // odd: nx is
+__host__ __device__ constexpr uint32_t lsf_tmp_rows(uint32_t ny) { return kLsfTile + ny - 1u; }
+constexpr uint32_t kLsfTmpPitch = kLsfTile + 1u;
+__host__ __device__ constexpr size_t lsf_lds_bytes(uint32_t nx, uint32_t ny)
+{
+    static_assert(kLsfTile * (kLsfTile + 1u) >= kLsfChunk * kLsfTmpPitch, "the look-ahead past tmp stays in the stage");
+    return ((size_t)lsf_tmp_rows(ny) * kLsfTmpPitch + (size_t)kLsfTile * lsf_stage_pitch(nx) + kLsfChunk) * sizeof(float);
+}
+
+__global__ __launch_bounds__(kLsfThreads) void k_lsf(const float* __restrict__ in, float* __restrict__ outp,
+                                                     uint8_t* __restrict__ out_u8, uint32_t W, uint32_t H,
+                                                     const LsfTable tab)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_lsf[];
+    const uint32_t nx = tab.nx, ny = tab.ny;
+    const uint32_t rx = (nx - 1u) / 2u, ry = (ny - 1u) / 2u;
+    const uint32_t SP = lsf_stage_pitch(nx);              // the tile's columns, 2 rx neighbours, one to make it odd
+    const uint32_t SW = SP - 1u;                          // columns staged
+    float* tmp = s_lsf;
+    float* stage = s_lsf + lsf_tmp_rows(ny) * kLsfTmpPitch;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t tx0 = blockIdx.x * kLsfTile, ty0 = blockIdx.y * kLsfTile;   // (below W and H)
+    const size_t row_z = (size_t)blockIdx.z * H;         // the plane's first row among all planes' rows
+    const uint32_t vwave = threadIdx.x >> 6;
+    const uint32_t rows_a = kLsfTile + 2u * ry;           // tmp rows the vertical pass meets
+
+    for (uint32_t row0 = 0; row0 < rows_a; row0 += kLsfTile) {
+        const uint32_t nrows = min(kLsfTile, rows_a - row0);
+        // (a wave's 16 rows of a column group are loaded before any is stored: one exposed latency, not
+        // 16; the rows' addresses are formed per lane -- as scalars, hoisted out of the column loop, the
+        // 16 of them do not fit the SGPR file)
+        for (uint32_t c = lane; c < SW; c += 64u) {
+            const int gx = min(max((int)tx0 - (int)rx + (int)c, 0), (int)W - 1);   // (W, H < 2^31: the host's check)
+            float v[kLsfTile / (kLsfThreads / 64u)];
+#pragma unroll
+            for (uint32_t j = 0; j < kLsfTile / (kLsfThreads / 64u); ++j) {
+                const uint32_t i = vwave + j * (kLsfThreads / 64u);
+                const int gy = min(max((int)ty0 - (int)ry + (int)(row0 + i), 0), (int)H - 1);
+                v[j] = i < nrows ? in[(row_z + (size_t)gy) * W + (size_t)gx] : 0.0f;
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < kLsfTile / (kLsfThreads / 64u); ++j) {
+                const uint32_t i = vwave + j * (kLsfThreads / 64u);
+                if (i < nrows) stage[i * SP + c] = v[j];
+            }
+        }
+        __syncthreads();
+        if (lane < nrows) {
+            for (uint32_t q = wave; q < kLsfTile / kLsfChunk; q += kLsfThreads / 64u) {
+                const float* s = stage + lane * SP + kLsfChunk * q;
+                double acc[kLsfChunk];
+                lsf_chunk(tab.hx, nx, [&](uint32_t i) { return s[i]; }, acc);
+                float* t = tmp + (row0 + lane) * kLsfTmpPitch + kLsfChunk * q;
+#pragma unroll
+                for (uint32_t r = 0; r < kLsfChunk; ++r) t[r] = (float)acc[r];
+            }
+        }
+        __syncthreads();
+    }
+
+    const uint32_t x = tx0 + lane;                        // (W < 2^31: no wrap)
+    for (uint32_t q = wave; q < kLsfTile / kLsfChunk; q += kLsfThreads / 64u) {
+        const uint32_t y0 = ty0 + kLsfChunk * q;          // (H is at most 65535 tiles: no wrap)
+        if (y0 >= H) break;                      // wave-uniform
+        const float* t = tmp + kLsfChunk * q * kLsfTmpPitch + lane;
+        double acc[kLsfChunk];
+        lsf_chunk(tab.hy, ny, [&](uint32_t i) { return t[i * kLsfTmpPitch]; }, acc);
+        if (x >= W) continue;
+#pragma unroll
+        for (uint32_t r = 0; r < kLsfChunk; ++r) {
+            if (y0 + r >= H) break;
+            const size_t o = (row_z + (size_t)(y0 + r)) * W + (size_t)x;
+            const float f = (float)acc[r];
+            if (outp) outp[o] = f;
+            if (out_u8) out_u8[o] = lut_u8(f);
+        }
+    }
+}
+
 }  // namespace XRT_KERNEL_NS

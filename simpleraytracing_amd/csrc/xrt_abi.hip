@@ -2721,6 +2721,70 @@ int xrt_hole_fill(xrt_context* ctx, uint32_t width, uint32_t height, const float
     return d2h_copy(ctx, ctx->host_stream, copies);
 }
 
+// --- the detector response -------------------------------------
+
+#include "xrt_lsf_host.inc"
+
+// The launch of k_lsf (validated arguments, device pointers).
+static int launch_lsf(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_image,
+                      const float* lsf_x, uint32_t taps_x, const float* lsf_y, uint32_t taps_y, float* d_out,
+                      uint8_t* d_out_u8, hipStream_t stream)
+{
+    LsfTable tab;                       // by value: the launch owns its copy (no context state, no wait)
+    lsf_table_set(tab, lsf_x, taps_x, lsf_y, taps_y);
+    const size_t lds = lsf_lds_bytes(taps_x, taps_y);
+    if (lds > 64u * 1024u)              // past the default limit of a launch's dynamic LDS
+        XRT_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsf),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 grid((width + kLsfTile - 1u) / kLsfTile, (height + kLsfTile - 1u) / kLsfTile, num_planes);
+    hipLaunchKernelGGL(k_lsf, grid, dim3(kLsfThreads), lds, stream, d_image, d_out, d_out_u8, width, height, tab);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_detector_response_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                                 const float* d_image, const float* lsf_x, uint32_t taps_x, const float* lsf_y,
+                                 uint32_t taps_y, float* d_out, uint8_t* d_out_u8, void* stream)
+{
+    if (const char* why = lsf_arguments(width, height, num_planes, d_image, lsf_x, taps_x, lsf_y, taps_y, d_out, d_out_u8))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_lsf(ctx, width, height, num_planes, d_image, lsf_x, taps_x, lsf_y, taps_y, d_out, d_out_u8,
+                      (hipStream_t)stream);
+}
+
+int xrt_detector_response(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                          const float* image, const float* lsf_x, uint32_t taps_x, const float* lsf_y,
+                          uint32_t taps_y, float* out, uint8_t* out_u8)
+{
+    if (const char* why = lsf_arguments(width, height, num_planes, image, lsf_x, taps_x, lsf_y, taps_y, out, out_u8))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)width * height * num_planes;
+    float *din = nullptr, *dout = nullptr;
+    uint8_t* du8 = nullptr;
+    int rc = XRT_OK;
+    if (hipMalloc(&din, n * sizeof(float)) != hipSuccess || (out && hipMalloc(&dout, n * sizeof(float)) != hipSuccess) ||
+        (out_u8 && hipMalloc(&du8, n) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "detector response allocation failed");
+    } else if (hipMemcpyAsync(din, image, n * sizeof(float), hipMemcpyHostToDevice, ctx->host_stream) != hipSuccess) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "detector response upload failed");
+    } else if (!(rc = launch_lsf(ctx, width, height, num_planes, din, lsf_x, taps_x, lsf_y, taps_y, dout, du8,
+                                 ctx->host_stream))) {
+        if ((out && hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, ctx->host_stream) != hipSuccess) ||
+            (out_u8 && hipMemcpyAsync(out_u8, du8, n, hipMemcpyDeviceToHost, ctx->host_stream) != hipSuccess) ||
+            hipStreamSynchronize(ctx->host_stream) != hipSuccess)
+            rc = fail(ctx, XRT_ERR_DEVICE, "detector response kernel failed");
+    }
+    (void)hipStreamSynchronize(ctx->host_stream);
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    (void)hipFree(du8);
+    return rc;
+}
+
 // Render of the L-buffer plane and the fork's hole fill over it, into host buffers.
 static int render_and_fill(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
                            uint8_t* image_u8, xrt_stats* stats)
