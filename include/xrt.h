@@ -496,6 +496,49 @@ int xrt_detector_response_device(xrt_context* ctx, uint32_t width, uint32_t heig
                                  uint32_t taps_y, float* d_out, uint8_t* d_out_u8, void* stream);
 int xrt_lsf_gaussian(double sigma_pixels, uint32_t taps, float* lsf);
 
+/* --- line-integral projections: flat field, -log, sinograms --------------- */
+
+/*
+ * What reconstruction consumes: intensities turned
+ * into line integrals p = -ln((I - dark) / (flat - dark)), on the device behind
+ * the render, the spectrum integrator, the hole fill and the detector
+ * response.  `image` is num_planes row-major f32 planes of width x height
+ * pixels, one after another (a scan's projections in one call); `flat` and
+ * `dark` are one width x height plane each, shared by every projection, or
+ * NULL.  Per pixel, every operation a separately rounded f32 operation:
+ *   num = dark ? image - dark : image
+ *   den = flat ? (dark ? flat - dark : flat) : (dark ? flat_value - dark : flat_value)
+ *   t   = num / den                           (IEEE division)
+ *   if (t_min > 0 && t < t_min) t = t_min     (a NaN stays a NaN)
+ *   out = 0.0f - logf(t)
+ * with logf glibc 2.35's, restated bit for bit on every input: t = 1 gives
+ * +0.0, t = 0 gives +inf, t = +inf gives -inf, t < 0 gives NaN; a NaN's sign
+ * and payload are not specified.  flat_value is read only where flat is NULL.
+ * `order` places the output rows:
+ *   XRT_ORDER_PROJECTIONS  out[p][y][x], as the image
+ *   XRT_ORDER_SINOGRAMS    out[y][p][x]: one num_planes x width sinogram per
+ *                          detector row
+ *
+ * XRT_ERR_ARGUMENT for a NULL image or out; a width, height or num_planes of 0
+ * (or a width above 2^31 - 4096, num_planes * height above 2^32 - 1, or a
+ * plane stack past the 2^31 - 1 workgroups of one launch); an order other than the two; a t_min that is NaN,
+ * infinite or negative; flat == NULL with a flat_value that is not finite or
+ * not > 0; an out that overlaps image, flat or dark -- with one exception: in
+ * XRT_ORDER_PROJECTIONS out == image exactly is allowed (in place: the pass is
+ * pointwise; a partial overlap is refused, and so is in place in sinogram
+ * order, which moves rows).  All of that is checked before the context is
+ * looked at.  xrt_log_projection: host buffers, synchronous.  _device: device
+ * buffers, asynchronous on `stream`.  Neither touches the context's model,
+ * scene or frames in flight.  There is no xrt_multi_ form.
+ */
+#define XRT_ORDER_PROJECTIONS 0
+#define XRT_ORDER_SINOGRAMS 1
+int xrt_log_projection(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* image,
+                       const float* flat, const float* dark, float flat_value, float t_min, int order, float* out);
+int xrt_log_projection_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                              const float* d_image, const float* d_flat, const float* d_dark, float flat_value,
+                              float t_min, int order, float* d_out, void* stream);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

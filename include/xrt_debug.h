@@ -32,8 +32,9 @@ typedef enum xrt_probe_op {
     XRT_PROBE_RCP = 2,      /* (float)(1.0 / (double)x), src/Ray.cxx:99           */
     XRT_PROBE_LUT_U8 = 3,   /* 8-bit LUT of a photon value (out[i] = (float)u8)  */
     XRT_PROBE_RCP_FAST = 4, /* the culled tests' 1/det (rcp + Newton where exact) */
-    XRT_PROBE_SIGNED_L = 5  /* (float)(80.0 * exp(-(0.1037f * (d * 0.1)))): the signed
+    XRT_PROBE_SIGNED_L = 5, /* (float)(80.0 * exp(-(0.1037f * (d * 0.1)))): the signed
                                model's L for distance d (glibc exp in f64)          */
+    XRT_PROBE_LOGF = 6      /* std::log(float) == glibc logf (a NaN by class)    */
 } xrt_probe_op;
 
 /* Evaluates one scalar device function elementwise.  Host buffers. */
@@ -253,6 +254,18 @@ int xrt_debug_pose_counters(xrt_context* ctx, uint64_t counters[2]);
  */
 int xrt_host_lsf(uint32_t width, uint32_t height, uint32_t num_planes, const float* image, const float* lsf_x,
                  uint32_t taps_x, const float* lsf_y, uint32_t taps_y, float* out, uint8_t* out_u8);
+
+/*
+ * Test hooks (host code, no device) of the line-integral projections:
+ * xrt_host_logf_batch is the device logf restatement compiled for the host
+ * (against libm and tests/logf_ref.py on a machine without a GPU);
+ * xrt_host_log_projection is xrt_log_projection's pixel function over whole
+ * buffers, arguments and checks as xrt_log_projection's, host buffers.
+ */
+void xrt_host_logf_batch(const float* in, float* out, uint64_t n);
+int xrt_host_log_projection(uint32_t width, uint32_t height, uint32_t num_planes, const float* image,
+                            const float* flat, const float* dark, float flat_value, float t_min, int order,
+                            float* out);
 
 /*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]

@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -31,6 +31,7 @@ __all__ = [
     "XRT_SPLIT_EQUAL", "XRT_SPLIT_BALANCED", "XRT_TRANSIT_HITS", "XRT_TRANSIT_PACKED", "XRT_MODEL_MATERIALS",
     "XRT_MAX_MESHES", "XRT_MODEL_SPECTRUM", "XRT_MAX_BINS", "XRT_MODEL_PATHS", "pose_rotation", "pose_triangles",
     "XRT_MAX_LSF_TAPS", "lsf_gaussian", "host_lsf", "detector_response",
+    "XRT_ORDER_PROJECTIONS", "XRT_ORDER_SINOGRAMS", "host_logf", "host_log_projection", "log_projection",
 ]
 
 
@@ -229,6 +230,51 @@ def detector_response(image, lsf_x, lsf_y=None, device: int = 0) -> np.ndarray:
     """The blurred f32 image(s) of Context.detector_response, on a context of its own on `device`."""
     with Context(device) as ctx:
         return ctx.detector_response(image, lsf_x, lsf_y, u8=False)[0]
+
+
+def _projection_arrays(image, flat, dark, flat_value, sinograms):
+    """xrt_log_projection's arguments from an (H, W) image or a (P, H, W) stack: the arrays, the sizes, the
+    scalar flat (0 where a flat plane is given and none was named), the order and the output's shape."""
+    a, p, h, w = _lsf_planes(image)
+    planes = []
+    for name, plane in (("flat", flat), ("dark", dark)):
+        if plane is not None:
+            plane = np.ascontiguousarray(plane, dtype=np.float32)
+            if plane.shape != (h, w):
+                raise ValueError(f"{name} is one (H, W) = ({h}, {w}) plane, got shape {plane.shape}")
+        planes.append(plane)
+    if flat_value is None:
+        if flat is None:
+            raise ValueError("log_projection needs a flat plane or a flat_value")
+        flat_value = 0.0
+    shape = ((h, p, w) if sinograms else a.shape) if a.ndim == 3 else ((h, 1, w) if sinograms else a.shape)
+    order = _abi.XRT_ORDER_SINOGRAMS if sinograms else _abi.XRT_ORDER_PROJECTIONS
+    return a, planes[0], planes[1], p, h, w, float(flat_value), order, shape
+
+
+def host_logf(x) -> np.ndarray:
+    """The device's logf restatement compiled for the host (xrt_host_logf_batch, a test hook)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    _abi.load().xrt_host_logf_batch(_fptr(x), _fptr(out), x.size)
+    return out
+
+
+def host_log_projection(image, flat=None, dark=None, flat_value=None, t_min=0.0, sinograms=False) -> np.ndarray:
+    """Context.log_projection in the device's arithmetic on the host (xrt_host_log_projection, a test hook)."""
+    a, f, d, p, h, w, fv, order, shape = _projection_arrays(image, flat, dark, flat_value, sinograms)
+    out = np.empty(shape, np.float32)
+    rc = _abi.load().xrt_host_log_projection(w, h, p, _fptr(a), _fptr(f) if f is not None else None,
+                                             _fptr(d) if d is not None else None, fv, float(t_min), order, _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_log_projection")
+    return out
+
+
+def log_projection(image, flat=None, dark=None, flat_value=None, t_min=0.0, sinograms=False, device: int = 0) -> np.ndarray:
+    """The line integrals of Context.log_projection, on a context of its own on `device`."""
+    with Context(device) as ctx:
+        return ctx.log_projection(image, flat, dark, flat_value, t_min, sinograms)
 
 
 class Context:
@@ -447,6 +493,29 @@ class Context:
                                                     d_image or None, _fptr(hx), hx.size, _fptr(hy), hy.size,
                                                     d_out or None, d_u8 or None, stream or None)
         self._check(rc, "xrt_detector_response_device")
+
+    def log_projection(self, image, flat=None, dark=None, flat_value=None, t_min=0.0, sinograms=False):
+        """Line integrals -ln((I - dark) / (flat - dark)) of an (H, W) image or a (P, H, W) stack of projections;
+        flat and dark are one (H, W) plane each or None (flat None: the scalar flat_value); a transmission below
+        t_min > 0 is raised to it.  Returns the image's shape, or (H, P, W) -- one sinogram per detector row --
+        with sinograms=True."""
+        a, f, d, p, h, w, fv, order, shape = _projection_arrays(image, flat, dark, flat_value, sinograms)
+        out = np.empty(shape, np.float32)
+        self._check(self._lib.xrt_log_projection(
+            self._ctx, w, h, p, _fptr(a), _fptr(f) if f is not None else None, _fptr(d) if d is not None else None,
+            fv, float(t_min), order, _fptr(out)), "xrt_log_projection")
+        return out
+
+    def log_projection_device(self, width: int, height: int, num_planes: int, d_image: int, d_out: int,
+                              d_flat: int = 0, d_dark: int = 0, flat_value: float = 0.0, t_min: float = 0.0,
+                              sinograms: bool = False, stream: int = 0):
+        """log_projection over device buffers (raw pointers; d_out == d_image is in place, projection order
+        only); asynchronous on `stream`."""
+        order = _abi.XRT_ORDER_SINOGRAMS if sinograms else _abi.XRT_ORDER_PROJECTIONS
+        rc = self._lib.xrt_log_projection_device(self._ctx, int(width), int(height), int(num_planes), d_image or None,
+                                                 d_flat or None, d_dark or None, float(flat_value), float(t_min), order,
+                                                 d_out or None, stream or None)
+        self._check(rc, "xrt_log_projection_device")
 
     def render_signed(self, cam: Camera):
         """The L-buffer fork end to end: (image f32, lbuffer f32 with -1 flags, u8, Stats)."""

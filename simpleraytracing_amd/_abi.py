@@ -32,6 +32,7 @@ XRT_PROBE_RCP = 2
 XRT_PROBE_LUT_U8 = 3
 XRT_PROBE_RCP_FAST = 4
 XRT_PROBE_SIGNED_L = 5
+XRT_PROBE_LOGF = 6
 
 XRT_MODEL_ATTENUATION = 0
 XRT_MODEL_SIGNED = 1
@@ -41,6 +42,8 @@ XRT_MODEL_SPECTRUM = 3
 XRT_MAX_BINS = 32
 XRT_MODEL_PATHS = 4
 XRT_MAX_LSF_TAPS = 129
+XRT_ORDER_PROJECTIONS = 0
+XRT_ORDER_SINOGRAMS = 1
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -175,6 +178,13 @@ XRT_SYMBOLS = {
     "xrt_detector_response_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _fp, _u32, _fp, _u32, _vp, _vp, _vp]),
     "xrt_lsf_gaussian": (ctypes.c_int, [ctypes.c_double, _u32, _fp]),
     "xrt_host_lsf": (ctypes.c_int, [_u32, _u32, _u32, _fp, _fp, _u32, _fp, _u32, _fp, _u8p]),
+    "xrt_log_projection": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _fp, _fp, ctypes.c_float, ctypes.c_float,
+                                          ctypes.c_int, _fp]),
+    "xrt_log_projection_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float,
+                                                 ctypes.c_int, _vp, _vp]),
+    "xrt_host_logf_batch": (None, [_fp, _fp, _u64]),
+    "xrt_host_log_projection": (ctypes.c_int, [_u32, _u32, _u32, _fp, _fp, _fp, ctypes.c_float, ctypes.c_float,
+                                               ctypes.c_int, _fp]),
     "xrt_multi_set_pose": (ctypes.c_int, [_MultiP, _u32, _fp]),
     "xrt_multi_reset_poses": (ctypes.c_int, [_MultiP]),
     "xrt_host_mt_check": (None, [_fp, _fp, _fp, _fp, _u64, ctypes.POINTER(ctypes.c_uint8),

@@ -443,6 +443,30 @@ void applyDetectorResponse(Image& image, const std::vector<float>& lsf_x, const 
     std::copy(out.begin(), out.end(), image.getData());
 }
 
+void applyLogProjection(Image& image, float flat_value, float t_min)
+{
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    check(ctx, xrt_log_projection(ctx, image.getWidth(), image.getHeight(), 1, image.getData(), nullptr, nullptr,
+                                  flat_value, t_min, XRT_ORDER_PROJECTIONS, image.getData()),
+          "xrt_log_projection");
+}
+
+void logProjectionSinograms(const std::vector<float>& stack, unsigned width, unsigned height, unsigned num_projections,
+                            float flat_value, float t_min, std::vector<float>& sinograms)
+{
+    if (stack.size() != (size_t)width * height * num_projections)
+        throw std::runtime_error("logProjectionSinograms: the stack does not hold num_projections images");
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    sinograms.resize(stack.size());
+    check(ctx, xrt_log_projection(ctx, width, height, num_projections, stack.data(), nullptr, nullptr, flat_value, t_min,
+                                  XRT_ORDER_SINOGRAMS, sinograms.data()),
+          "xrt_log_projection");
+}
+
 namespace {
 
 // One multi-device context per device list for the process lifetime: the

@@ -139,6 +139,17 @@ void applySpectrum(Image& output_image, const std::vector<std::vector<float>>& p
 // edges replicated, nothing normalised), in place in output_image.  One device.
 void applyDetectorResponse(Image& output_image, const std::vector<float>& lsf_x, const std::vector<float>& lsf_y);
 
+// Line integrals (xrt_log_projection): output_image becomes -ln(I / flat_value)
+// in place, flat_value finite and > 0 (the unattenuated intensity, 80 for the
+// models here); a transmission below t_min > 0 is raised to it.  One device.
+void applyLogProjection(Image& output_image, float flat_value, float t_min = 0.0f);
+
+// The same over a scan: `stack` holds num_projections width x height intensity
+// images one after another; `sinograms` receives the line integrals in
+// XRT_ORDER_SINOGRAMS, (height, num_projections, width).  One call, one device.
+void logProjectionSinograms(const std::vector<float>& stack, unsigned width, unsigned height, unsigned num_projections,
+                            float flat_value, float t_min, std::vector<float>& sinograms);
+
 // Row strips over `num_gpus` devices (rows_per = H / n, remainder to the first
 // strips), one host thread per device; returns the number of odd rays.
 unsigned long long renderLoopMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,

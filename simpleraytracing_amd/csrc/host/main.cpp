@@ -47,6 +47,15 @@
 //       --lsf-gaussian SIGMA[:TAPS]  the same with a normalised Gaussian of SIGMA pixels
 //                              on both axes, TAPS (odd) defaulting to 2*ceil(4*SIGMA)+1,
 //                              at most 129
+//       --log-projection I0    line integrals: the image that NAME.EXT receives becomes
+//                              -ln(I / I0), I0 finite and > 0 (80 is these models'
+//                              unattenuated intensity), after --lsf when both are
+//                              given (the detector blurs intensity); every model, every
+//                              projection of --turntable.  --u8, --lbuffer, NAME.m<m>
+//                              and NAME.open stay as rendered
+//       --sinogram FILE        with --turntable N and --log-projection: also write the N
+//                              projections' line integrals as one sinogram per detector
+//                              row, raw little-endian f32 in (height, N, width) order
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -95,6 +104,8 @@ void showUsage(const std::string& prog)
               << "\t--turntable N[:x|y|z][:M,...]\tN projections, the listed meshes (default: all) turned k*360/N degrees about the axis (default y) through the scene's centre; writes NAME.pKKK.EXT\n"
               << "\t--lsf FILE\t\t\tDetector line-spread function over the written image: FILE holds a line of taps along x and, optionally, one along y (odd counts, at most 129)\n"
               << "\t--lsf-gaussian SIGMA[:TAPS]\tThe same with a normalised Gaussian of SIGMA pixels (TAPS odd, default 2*ceil(4*SIGMA)+1, at most 129)\n"
+              << "\t--log-projection I0\t\tLine integrals: write -ln(I / I0) (I0 finite and > 0; after --lsf) instead of the intensity I; --u8 and --lbuffer stay as rendered\n"
+              << "\t--sinogram FILE\t\t\tWith --turntable N and --log-projection: also write the line integrals as raw float32 sinograms, (height, N, width)\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -125,6 +136,9 @@ struct Options {
     std::vector<unsigned> turn_meshes;         // empty: every mesh
     bool lsf_file = false, lsf_gauss = false;  // --lsf, --lsf-gaussian
     std::vector<float> lsf_x, lsf_y;           // the detector response's taps (empty: none)
+    bool log_projection = false;               // --log-projection I0
+    float flat_value = 0.0f;                   // I0
+    std::string sinogram;                      // --sinogram FILE
 };
 
 // A whole, non-negative decimal number.
@@ -385,6 +399,19 @@ Options processCmd(int argc, char** argv)
         } else if (a == "--lsf-gaussian") {
             o.lsf_gauss = true;
             parse_lsf_gaussian(parse_str(argv[0], argc, argv, i), o.lsf_x, o.lsf_y);
+        } else if (a == "--log-projection") {
+            const std::string f = parse_str(argv[0], argc, argv, i);
+            size_t used = 0;
+            try {
+                o.flat_value = std::stof(f, &used);
+            } catch (const std::exception&) {
+                used = 0;
+            }
+            if (f.empty() || used != f.size() || !std::isfinite(o.flat_value) || !(o.flat_value > 0.0f))
+                throw std::runtime_error("--log-projection I0: '" + f + "' is not a finite intensity above 0");
+            o.log_projection = true;
+        } else if (a == "--sinogram") {
+            o.sinogram = parse_str(argv[0], argc, argv, i);
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -426,6 +453,12 @@ Options processCmd(int argc, char** argv)
     if (!o.lsf_x.empty() && o.paths && !o.spectrum)
         throw std::runtime_error(std::string(o.lsf_file ? "--lsf" : "--lsf-gaussian") +
                                  " with --paths needs --spectrum: the planes stay as rendered, there is no image to spread");
+    if (!o.sinogram.empty() && (!o.turntable || !o.log_projection))
+        throw std::runtime_error("--sinogram needs --turntable N and --log-projection I0: it stacks a scan's line integrals");
+    if (o.log_projection && (o.gpus > 1 || o.rows))
+        throw std::runtime_error("--log-projection needs whole frames on one GPU: not with -g N or --rows");
+    if (o.log_projection && o.paths && !o.spectrum)
+        throw std::runtime_error("--log-projection with --paths needs --spectrum: the planes stay as rendered, there is no image");
     if (o.signed_model && !o.materials.empty())
         throw std::runtime_error("--signed and --materials are two models: give one");
     if (o.spectrum && (o.signed_model || !o.materials.empty()))
@@ -473,6 +506,7 @@ int main(int argc, char** argv)
         if (!opt.poses.empty() || opt.turntable) poses.assign(meshes.size(), rest);
         for (const auto& q : opt.poses) poses[q.first] = q.second;
         const std::string name = opt.output, lbuffer_name = opt.lbuffer, u8_name = opt.u8;
+        std::vector<float> scan;                      // --sinogram: the projections' intensity images
         for (unsigned projection = 0; projection < std::max(opt.turntable, 1u); ++projection) {
             if (opt.turntable) {
                 // the rest scene's box centre, as initialiseRayTracing forms it (main.cxx:575-578)
@@ -578,8 +612,17 @@ int main(int argc, char** argv)
                 out = &strip;
             }
             if (opt.paths && !opt.spectrum) return 0;
-            out->saveTextFile(opt.output);
-            if (!opt.u8.empty()) out->savePGMFile(opt.u8, 0.0f, 80.0f);
+            if (opt.log_projection) {                 // (whole frames: out is the image)
+                // the 8-bit image is the intensity's (the 0..80 window means nothing for line integrals)
+                if (!opt.u8.empty()) image.savePGMFile(opt.u8, 0.0f, 80.0f);
+                if (!opt.sinogram.empty()) scan.insert(scan.end(), image.getData(), image.getData() + (size_t)opt.width * opt.height);
+                Image integrals(image);
+                applyLogProjection(integrals, opt.flat_value);
+                integrals.saveTextFile(opt.output);
+            } else {
+                out->saveTextFile(opt.output);
+                if (!opt.u8.empty()) out->savePGMFile(opt.u8, 0.0f, 80.0f);
+            }
             if (!opt.lbuffer.empty()) {
                 if (lb.empty()) {                   // multi-GPU, batch: the L-buffer of the same frame
                     lb.resize((size_t)opt.width * (re - rb));
@@ -591,6 +634,14 @@ int main(int argc, char** argv)
                 std::fwrite(lb.data(), sizeof(float), lb.size(), f);
                 std::fclose(f);
             }
+        }
+        if (!opt.sinogram.empty()) {                  // the scan in one call, one sinogram per detector row
+            std::vector<float> sinograms;
+            logProjectionSinograms(scan, opt.width, opt.height, opt.turntable, opt.flat_value, 0.0f, sinograms);
+            std::FILE* f = std::fopen(opt.sinogram.c_str(), "wb");
+            if (!f) throw std::runtime_error("Cannot create the file " + opt.sinogram);
+            std::fwrite(sinograms.data(), sizeof(float), sinograms.size(), f);
+            std::fclose(f);
         }
     } catch (const std::exception& e) {
         std::cerr << "ERROR: " << e.what() << std::endl;

@@ -749,6 +749,83 @@ __host__ __device__ __forceinline__ float xrt_f32_from_bits(uint32_t u)
     return f;
 }
 
+// ---------------------------------------------------------------------------
+// glibc 2.35 logf (sysdeps/ieee754/flt-32/e_logf.c with e_logf_data.c,
+// LOGF_TABLE_BITS = 4, LOGF_POLY_ORDER = 4): x = 2^k * z with z in
+// [0x1.66p-1, 0x1.66p0), c the centre of z's sixteenth of that range,
+// log(x) = log1p(z/c - 1) + log(c) + k * Ln2 in f64, rounded once to f32.
+// Every f64 operation is rounded on its own (this file's fp contract(off)).
+// x86-64 glibc dispatches a build with fused steps on FMA hardware, yet no
+// input's f32 result differs: this form equals the system libm on all 2^32
+// inputs (tools/check_logf.c), so -- unlike xrt_expf -- a numpy
+// restatement, which cannot fuse, is exact (tests/logf_ref.py).  A returned NaN's sign and
+// payload are not part of the contract.  The table -- 16 pairs (1/c, log c),
+// 256 bytes -- is indexed per lane: cached global loads, as xrt_exp's.
+// ---------------------------------------------------------------------------
+struct LogfEntry {
+    double invc, logc;
+};
+
+__host__ __device__ __forceinline__ LogfEntry xrt_logf_tab(uint32_t i)
+{
+    constexpr LogfEntry tab[16] = {
+        {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2}, {0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2},
+        {0x1.49539f0f010b0p+0, -0x1.01eae7f513a67p-2}, {0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3},
+        {0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3}, {0x1.25e227b0b8ea0p+0, -0x1.1aa2bc79c8100p-3},
+        {0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4}, {0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4},
+        {0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5}, {0x1p+0, 0x0p+0},
+        {0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5},  {0x1.ca4b31f026aa0p-1, 0x1.c5e53aa362eb4p-4},
+        {0x1.b2036576afce6p-1, 0x1.526e57720db08p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.bc2860d224770p-3},
+        {0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2},  {0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2},
+    };
+    return tab[i & 15u];
+}
+
+// The inputs of the main path: positive, finite and normal.
+__host__ __device__ __forceinline__ bool xrt_logf_is_regular(uint32_t ix)
+{
+    return ix - 0x00800000u < 0x7f800000u - 0x00800000u;       // (u32 arithmetic)
+}
+
+// The main path, from the bits of a regular x (or of a subnormal scaled by
+// 2^23 with 23 taken off its exponent field again, which may wrap: every step
+// below is u32 arithmetic).  log(1) needs no case of its own: r = 0 gives
+// y = A2 * 0 + (0 + 0) = -0 + +0 = +0.0 in round-to-nearest, as the contract's
+// first line returns.
+__host__ __device__ __forceinline__ float xrt_logf_regular(uint32_t ix)
+{
+    constexpr double kLn2 = 0x1.62e42fefa39efp-1;
+    constexpr double kA0 = -0x1.00ea348b88334p-2;
+    constexpr double kA1 = 0x1.5575b0be00b6ap-2;
+    constexpr double kA2 = -0x1.ffffef20a4123p-2;
+    const uint32_t tmp = ix - 0x3f330000u;
+    const LogfEntry e = xrt_logf_tab(tmp >> 19);
+    const int32_t k = (int32_t)tmp >> 23;                       // arithmetic
+    const double z = (double)xrt_f32_from_bits(ix - (tmp & 0xff800000u));
+    const double r = z * e.invc - 1.0;
+    const double y0 = e.logc + (double)k * kLn2;
+    const double r2 = r * r;
+    double y = kA1 * r + kA2;
+    y = kA0 * r2 + y;
+    y = y * r2 + (y0 + r);
+    return (float)y;
+}
+
+// Every input.  The special cases are branches: a caller with several values
+// can test them together first (k_log_projection does, xrt_logf_is_regular).
+__host__ __device__ __forceinline__ float xrt_logf(float x)
+{
+    uint32_t ix;
+    __builtin_memcpy(&ix, &x, 4);
+    if (xrt_logf_is_regular(ix)) return xrt_logf_regular(ix);
+    if (ix * 2u == 0u) return -__builtin_inff();                // +-0
+    if (ix == 0x7f800000u) return x;                            // +inf
+    if ((ix & 0x80000000u) || ix * 2u >= 0xff000000u) return xrt_f32_from_bits(0x7fc00000u);   // x < 0, NaN
+    const float scaled = x * 0x1p23f;                           // subnormal: normalised (exact)
+    __builtin_memcpy(&ix, &scaled, 4);
+    return xrt_logf_regular(ix - (23u << 23));
+}
+
 // NaN path lengths.  The only NaN the reference's pair sum can produce is
 // inf - inf (two t = +inf "hits", which Ray.cxx records when 1/det overflows,
 // DESIGN.md "Tile cull" step 0); x86 SSE returns its default NaN for it
@@ -952,6 +1029,54 @@ __host__ __device__ __forceinline__ void lsf_chunk(const double* h, uint32_t n, 
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// Line-integral projections: one pixel of xrt_log_projection,
+// p = -ln((I - dark) / (flat - dark)), every step a separately rounded f32
+// operation.  `flat` is the flat plane's pixel, or flat_value where there is no
+// plane; `dark` is read only with has_dark.  A transmission below t_min > 0 is
+// raised to it (a NaN compares false and stays); t = 1 gives +0.0, t = 0
+// +inf, t < 0 NaN.
+// ---------------------------------------------------------------------------
+__host__ __device__ __forceinline__ float log_projection_transmission(float image, float flat, float dark, bool has_dark,
+                                                                      float t_min)
+{
+    const float num = has_dark ? image - dark : image;
+    const float den = has_dark ? flat - dark : flat;
+    const float t = num / den;
+    return t_min > 0.0f && t < t_min ? t_min : t;
+}
+
+__host__ __device__ __forceinline__ float log_projection_pixel(float image, float flat, float dark, bool has_dark,
+                                                               float t_min)
+{
+    return 0.0f - xrt_logf(log_projection_transmission(image, flat, dark, has_dark, t_min));
+}
+
+// The launch geometry of k_log_projection (kernels/xrt_kernels.h), formed on the host.
+constexpr uint32_t kProjThreads = 256;
+constexpr uint32_t kProjThreadsLog2 = 8;
+
+struct LogProjectionPlan {
+    uint32_t lanes_log2;                // a row's share of the workgroup: 2^lanes_log2 lanes, a quad each
+    uint32_t chunks;                    // workgroups along a row
+    uint64_t blocks;                    // the whole launch
+};
+
+// Quads that cover a row of W pixels under any misalignment 0..3: ceil((W + 3) / 4).
+__host__ __device__ constexpr uint32_t log_projection_quads(uint32_t W) { return (uint32_t)(((uint64_t)W + 6u) / 4u); }
+
+inline LogProjectionPlan log_projection_plan(uint32_t W, uint64_t rows)
+{
+    LogProjectionPlan plan;
+    const uint32_t quads = log_projection_quads(W);
+    plan.lanes_log2 = 0;
+    while (plan.lanes_log2 < kProjThreadsLog2 && (1u << plan.lanes_log2) < quads) ++plan.lanes_log2;
+    const uint32_t span = 1u << plan.lanes_log2, rows_per = kProjThreads >> plan.lanes_log2;
+    plan.chunks = (quads + span - 1u) / span;
+    plan.blocks = (rows + rows_per - 1u) / rows_per * plan.chunks;
+    return plan;
 }
 
 }  // namespace XRT_KERNEL_NS

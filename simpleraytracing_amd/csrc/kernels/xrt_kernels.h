@@ -3605,6 +3605,7 @@ __global__ void k_probe_math(int op, const float* __restrict__ in, float* __rest
     case 2: y = inv_det_of(x); break;
     case 4: y = rcp_newton_exact_for(x) ? rcp_newton(x) : inv_det_of(x); break;   // inv_det_fast per lane
     case 5: y = signed_lbuffer(x, 0, 0.1037f); break;   // the fork's 80 * exp(-(mu * (d * 0.1)))
+    case 6: y = xrt_logf(x); break;
     default: y = (float)lut_u8(x); break;
     }
     outp[i] = y;
@@ -3860,6 +3861,110 @@ __global__ __launch_bounds__(kLsfThreads) void k_lsf(const float* __restrict__ i
             if (outp) outp[o] = f;
             if (out_u8) out_u8[o] = lut_u8(f);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_log_projection: line-integral projections, pointwise.  The
+// planes are moved a row at a time -- W contiguous floats -- so both output
+// orders are coalesced: row (p, y) is read at (p H + y) W and written there
+// (XRT_ORDER_PROJECTIONS) or at (y P + p) W (XRT_ORDER_SINOGRAMS); flat and dark
+// are read at y W.  A lane owns one 16-byte quad of a row.  The quads are cut
+// at the multiples of 16 bytes of the row's *addresses*, not of its pixel
+// indices: with W odd, or in sinogram order, a row starts anywhere, so where
+// the row's starts in every plane it touches share one misalignment m (in
+// floats) quad j holds the pixels 4 j - m .. 4 j - m + 3, whole quads go as
+// dwordx4 and the two ragged ends pixel by pixel; where the starts disagree
+// the row goes pixel by pixel (m = 0).  A workgroup takes 2^lanes_log2 quads of
+// 256 >> lanes_log2 rows, chunk `blockIdx.x % chunks` of the row's quads
+// (log_projection_plan): narrow planes still fill their waves.  kWide is the
+// case lanes_log2 == 8, a workgroup within one row: the row, its offsets in
+// the four planes and their alignment are then scalar work, done once a wave
+// -- per lane they cost as much as the arithmetic of the lane's four pixels
+// (measured).  That arithmetic is an IEEE division and
+// xrt_logf's f64 chain a pixel; logf's special cases are tested once for the
+// lane's four transmissions: zeros, negatives, subnormals, infinities and NaNs
+// take the lane through xrt_logf's branches, everything else through the main
+// path alone.  In place (out == image, projection order) a lane reads its quad
+// before it writes it and no other lane touches it.  Offsets are 64-bit.
+// ---------------------------------------------------------------------------
+template <bool kHasDark>
+__device__ __forceinline__ void log_projection_values(const float (&v)[4], const float (&f)[4], const float (&d)[4],
+                                                      float t_min, float (&o)[4])
+{
+    uint32_t t[4];
+    bool regular = true;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        t[e] = __float_as_uint(log_projection_transmission(v[e], f[e], d[e], kHasDark, t_min));
+        regular &= xrt_logf_is_regular(t[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = 0.0f - xrt_logf_regular(t[e]);
+    if (!regular) {                                     // (the main path's value is discarded for a special input)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = 0.0f - xrt_logf(__uint_as_float(t[e]));
+    }
+}
+
+template <bool kWide>
+__global__ __launch_bounds__(kProjThreads) void k_log_projection(const float* image, const float* __restrict__ flat,
+                                                                 const float* __restrict__ dark, float* outp, uint32_t W,
+                                                                 uint32_t H, uint32_t P, float flat_value, float t_min,
+                                                                 uint32_t sinograms, uint32_t lanes_log2, uint32_t chunks)
+{
+    const uint32_t group = blockIdx.x / chunks, chunk = blockIdx.x - group * chunks;
+    const uint64_t row64 = kWide ? (uint64_t)group
+                                 : ((uint64_t)group << (kProjThreadsLog2 - lanes_log2)) + (threadIdx.x >> lanes_log2);
+    if (row64 >= (uint64_t)P * H) return;
+    const uint32_t row = (uint32_t)row64;                       // (P H < 2^32: the host's check)
+    const uint32_t p = row / H, y = row - p * H;
+    const float* src = image + (size_t)row * W;
+    float* dst = outp + (sinograms ? ((size_t)y * P + p) * W : (size_t)row * W);
+    const float* fl = flat ? flat + (size_t)y * W : nullptr;
+    const float* dk = dark ? dark + (size_t)y * W : nullptr;
+
+    // one misalignment for every plane of this row, or none
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src);
+    const bool vec = (a & 3u) == 0u && ((a ^ reinterpret_cast<uintptr_t>(dst)) & 15u) == 0u &&
+                     (!fl || ((a ^ reinterpret_cast<uintptr_t>(fl)) & 15u) == 0u) &&
+                     (!dk || ((a ^ reinterpret_cast<uintptr_t>(dk)) & 15u) == 0u);
+    const uint32_t m = vec ? (uint32_t)(a >> 2) & 3u : 0u;
+    const uint32_t j = kWide ? chunk * kProjThreads + threadIdx.x
+                             : (chunk << lanes_log2) + (threadIdx.x & ((1u << lanes_log2) - 1u));
+    // the quad's first pixel (below 0: the ragged head); 32-bit: W <= 2^31 - 4096 is the host's check
+    const int32_t w = (int32_t)W, x0 = (int32_t)(4u * j) - (int32_t)m;
+    if (x0 >= w) return;
+
+    float v[4], f[4], d[4], o[4];
+    if (vec && x0 >= 0 && x0 + 4 <= w) {                // a whole quad: every load in flight before the arithmetic
+        const float4 v4 = *reinterpret_cast<const float4*>(src + x0);
+        float4 f4 = make_float4(flat_value, flat_value, flat_value, flat_value), d4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (fl) f4 = *reinterpret_cast<const float4*>(fl + x0);
+        if (dk) d4 = *reinterpret_cast<const float4*>(dk + x0);
+        v[0] = v4.x, v[1] = v4.y, v[2] = v4.z, v[3] = v4.w;
+        f[0] = f4.x, f[1] = f4.y, f[2] = f4.z, f[3] = f4.w;
+        d[0] = d4.x, d[1] = d4.y, d[2] = d4.z, d[3] = d4.w;
+        if (dk) log_projection_values<true>(v, f, d, t_min, o);
+        else log_projection_values<false>(v, f, d, t_min, o);
+        *reinterpret_cast<float4*>(dst + x0) = make_float4(o[0], o[1], o[2], o[3]);
+        return;
+    }
+    // a ragged end, or a row whose planes' alignments disagree: pixel by pixel
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {                       // (a pixel outside the row: 1 / 1, a regular transmission)
+        const int32_t x = x0 + e;
+        const bool in = x >= 0 && x < w;
+        v[e] = in ? src[x] : 1.0f;
+        f[e] = in ? (fl ? fl[x] : flat_value) : 1.0f;
+        d[e] = in && dk ? dk[x] : 0.0f;
+    }
+    if (dk) log_projection_values<true>(v, f, d, t_min, o);
+    else log_projection_values<false>(v, f, d, t_min, o);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int32_t x = x0 + e;
+        if (x >= 0 && x < w) dst[x] = o[e];
     }
 }
 

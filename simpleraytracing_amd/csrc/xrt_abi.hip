@@ -2785,6 +2785,69 @@ int xrt_detector_response(xrt_context* ctx, uint32_t width, uint32_t height, uin
     return rc;
 }
 
+// --- line-integral projections ---------------------------------
+
+#include "xrt_projection_host.inc"
+
+// The launch of k_log_projection (validated arguments, device pointers).
+static int launch_log_projection(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                                 const float* d_image, const float* d_flat, const float* d_dark, float flat_value,
+                                 float t_min, int order, float* d_out, hipStream_t stream)
+{
+    const LogProjectionPlan plan = log_projection_plan(width, (uint64_t)num_planes * height);
+    // (a workgroup within one row -- planes from 510 pixels' width -- does the row's arithmetic as scalars)
+    const auto kernel = plan.lanes_log2 == kProjThreadsLog2 ? k_log_projection<true> : k_log_projection<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.blocks), dim3(kProjThreads), 0, stream, d_image, d_flat, d_dark, d_out,
+                       width, height, num_planes, flat_value, t_min, (uint32_t)(order == XRT_ORDER_SINOGRAMS),
+                       plan.lanes_log2, plan.chunks);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_log_projection_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                              const float* d_image, const float* d_flat, const float* d_dark, float flat_value,
+                              float t_min, int order, float* d_out, void* stream)
+{
+    if (const char* why = projection_arguments(width, height, num_planes, d_image, d_flat, d_dark, flat_value, t_min,
+                                               order, d_out))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_log_projection(ctx, width, height, num_planes, d_image, d_flat, d_dark, flat_value, t_min, order,
+                                 d_out, (hipStream_t)stream);
+}
+
+int xrt_log_projection(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* image,
+                       const float* flat, const float* dark, float flat_value, float t_min, int order, float* out)
+{
+    if (const char* why = projection_arguments(width, height, num_planes, image, flat, dark, flat_value, t_min, order, out))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t plane = (size_t)width * height * sizeof(float), all = plane * num_planes;
+    float *din = nullptr, *dflat = nullptr, *ddark = nullptr, *dout = nullptr;
+    int rc = XRT_OK;
+    if (hipMalloc(&din, all) != hipSuccess || hipMalloc(&dout, all) != hipSuccess ||
+        (flat && hipMalloc(&dflat, plane) != hipSuccess) || (dark && hipMalloc(&ddark, plane) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "log projection allocation failed");
+    } else if (hipMemcpyAsync(din, image, all, hipMemcpyHostToDevice, ctx->host_stream) != hipSuccess ||
+               (flat && hipMemcpyAsync(dflat, flat, plane, hipMemcpyHostToDevice, ctx->host_stream) != hipSuccess) ||
+               (dark && hipMemcpyAsync(ddark, dark, plane, hipMemcpyHostToDevice, ctx->host_stream) != hipSuccess)) {
+        rc = fail(ctx, XRT_ERR_DEVICE, "log projection upload failed");
+    } else if (!(rc = launch_log_projection(ctx, width, height, num_planes, din, dflat, ddark, flat_value, t_min, order,
+                                            dout, ctx->host_stream))) {
+        if (hipMemcpyAsync(out, dout, all, hipMemcpyDeviceToHost, ctx->host_stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->host_stream) != hipSuccess)
+            rc = fail(ctx, XRT_ERR_DEVICE, "log projection kernel failed");
+    }
+    (void)hipStreamSynchronize(ctx->host_stream);
+    (void)hipFree(din);
+    (void)hipFree(dflat);
+    (void)hipFree(ddark);
+    (void)hipFree(dout);
+    return rc;
+}
+
 // Render of the L-buffer plane and the fork's hole fill over it, into host buffers.
 static int render_and_fill(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
                            uint8_t* image_u8, xrt_stats* stats)
@@ -3454,7 +3517,7 @@ int xrt_probe_intersect(xrt_context* ctx, const float* rays, const float* tris, 
 int xrt_probe_math(xrt_context* ctx, int op, const float* in, float* outp, uint64_t n)
 {
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
-    if (op < XRT_PROBE_EXPF || op > XRT_PROBE_SIGNED_L) return fail(ctx, XRT_ERR_ARGUMENT, "bad op");
+    if (op < XRT_PROBE_EXPF || op > XRT_PROBE_LOGF) return fail(ctx, XRT_ERR_ARGUMENT, "bad op");
     if (n == 0) return XRT_OK;
     if (!in || !outp) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
