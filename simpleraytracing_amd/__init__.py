@@ -49,6 +49,14 @@ def _u8ptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
 
+def _u16ptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))
+
+
+def _i32ptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
 def _scene_arrays(meshes):
     """A list of (T, 9) soups as xrt_upload_scene takes it: (soups one after another, counts)."""
     meshes = [np.ascontiguousarray(m, dtype=np.float32).reshape(-1, 9) for m in meshes]
@@ -361,6 +369,16 @@ class Context:
         self._check(self._lib.xrt_debug_pose_counters(self._ctx, c), "xrt_debug_pose_counters")
         return {"launches": int(c[0]), "triangles": int(c[1])}
 
+    def _render_model(self, entry, name, cam):
+        """A whole-frame render and hole fill through `entry` (xrt_render_signed and its kin)."""
+        n = cam.width * cam.height
+        img = np.empty(n, np.float32)
+        lb = np.empty(n, np.float32)
+        u8 = np.empty(n, np.uint8)
+        st = Stats()
+        self._check(entry(self._ctx, ctypes.byref(cam), _fptr(img), _fptr(lb), _u8ptr(u8), ctypes.byref(st)), name)
+        return img, lb, u8, st
+
     def set_materials(self, mu):
         """XRT_MODEL_MATERIALS with one attenuation coefficient per mesh of the scene."""
         mu = np.ascontiguousarray(mu, dtype=np.float32).reshape(-1)
@@ -368,14 +386,7 @@ class Context:
 
     def render_materials(self, cam: Camera):
         """The materials model end to end: (hole-filled image f32, lbuffer f32 with -1 flags, u8, Stats)."""
-        n = cam.width * cam.height
-        img = np.empty(n, np.float32)
-        lb = np.empty(n, np.float32)
-        u8 = np.empty(n, np.uint8)
-        st = Stats()
-        self._check(self._lib.xrt_render_materials(self._ctx, ctypes.byref(cam), _fptr(img), _fptr(lb), _u8ptr(u8),
-                                                   ctypes.byref(st)), "xrt_render_materials")
-        return img, lb, u8, st
+        return self._render_model(self._lib.xrt_render_materials, "xrt_render_materials", cam)
 
     def probe_materials(self, distance: np.ndarray, sign_sum, mu):
         """The device's chained L of rays with given per-mesh sums ((n, M) arrays; sign_sum may be None)."""
@@ -385,7 +396,7 @@ class Context:
         s = None if sign_sum is None else np.ascontiguousarray(sign_sum, dtype=np.int32).reshape(d.shape)
         out = np.empty(len(d), np.float32)
         self._check(self._lib.xrt_probe_materials(
-            self._ctx, _fptr(d), s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if s is not None else None,
+            self._ctx, _fptr(d), _i32ptr(s) if s is not None else None,
             _fptr(mu), mu.size, _fptr(out), len(d)), "xrt_probe_materials")
         return out
 
@@ -396,14 +407,7 @@ class Context:
 
     def render_spectrum(self, cam: Camera):
         """The spectrum model end to end: (hole-filled image f32, lbuffer f32 with -1 flags, u8, Stats)."""
-        n = cam.width * cam.height
-        img = np.empty(n, np.float32)
-        lb = np.empty(n, np.float32)
-        u8 = np.empty(n, np.uint8)
-        st = Stats()
-        self._check(self._lib.xrt_render_spectrum(self._ctx, ctypes.byref(cam), _fptr(img), _fptr(lb), _u8ptr(u8),
-                                                  ctypes.byref(st)), "xrt_render_spectrum")
-        return img, lb, u8, st
+        return self._render_model(self._lib.xrt_render_spectrum, "xrt_render_spectrum", cam)
 
     def probe_spectrum(self, distance: np.ndarray, sign_sum, weights, mu):
         """The device's spectrum L of rays with given per-mesh sums ((n, M) arrays; sign_sum may be None)."""
@@ -412,7 +416,7 @@ class Context:
         s = None if sign_sum is None else np.ascontiguousarray(sign_sum, dtype=np.int32).reshape(d.shape)
         out = np.empty(len(d), np.float32)
         self._check(self._lib.xrt_probe_spectrum(
-            self._ctx, _fptr(d), s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if s is not None else None,
+            self._ctx, _fptr(d), _i32ptr(s) if s is not None else None,
             _fptr(w), _fptr(mu), mu.shape[0], w.size, _fptr(out), len(d)), "xrt_probe_spectrum")
         return out
 
@@ -432,7 +436,7 @@ class Context:
         opn = np.empty((rows, cam.width), np.uint16)
         st = Stats()
         self._check(self._lib.xrt_render_paths(self._ctx, ctypes.byref(cam), row_begin, row_end, m, _fptr(paths),
-                                               opn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), ctypes.byref(st)),
+                                               _u16ptr(opn), ctypes.byref(st)),
                     "xrt_render_paths")
         return paths, opn, st
 
@@ -456,9 +460,8 @@ class Context:
             raise ValueError(f"open must have a plane's shape {p.shape[1:]}, got {o.shape}")
         out = np.empty(p.shape[1:], np.float32)
         self._check(self._lib.xrt_apply_spectrum(
-            self._ctx, out.size, mu.shape[0], _fptr(p),
-            o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)) if o is not None else None, _fptr(w), _fptr(mu), w.size,
-            _fptr(out)), "xrt_apply_spectrum")
+            self._ctx, out.size, mu.shape[0], _fptr(p), _u16ptr(o) if o is not None else None, _fptr(w), _fptr(mu),
+            w.size, _fptr(out)), "xrt_apply_spectrum")
         return out
 
     def apply_spectrum_device(self, num_pixels: int, d_paths: int, d_open: int, weights, mu, d_lbuffer: int,
@@ -519,14 +522,7 @@ class Context:
 
     def render_signed(self, cam: Camera):
         """The L-buffer fork end to end: (image f32, lbuffer f32 with -1 flags, u8, Stats)."""
-        n = cam.width * cam.height
-        img = np.empty(n, np.float32)
-        lb = np.empty(n, np.float32)
-        u8 = np.empty(n, np.uint8)
-        st = Stats()
-        self._check(self._lib.xrt_render_signed(self._ctx, ctypes.byref(cam), _fptr(img), _fptr(lb), _u8ptr(u8),
-                                                ctypes.byref(st)), "xrt_render_signed")
-        return img, lb, u8, st
+        return self._render_model(self._lib.xrt_render_signed, "xrt_render_signed", cam)
 
     def hole_fill(self, lbuffer: np.ndarray, width: int, height: int):
         """The fork's hole fill of a whole-frame L-buffer: (image f32, u8)."""

@@ -205,24 +205,6 @@ xrt_camera camera_for(const Image& image, const std::vector<TriangleMesh>& meshe
     return cam;
 }
 
-void render_strip(int device, const xrt_camera& cam, const std::vector<float>& soup, size_t scene_meshes,
-                  unsigned row_begin, unsigned row_end, float* image_strip, float* lbuffer_strip,
-                  unsigned char* u8_strip, xrt_stats* stats)
-{
-    DeviceSlot& slot = device_slot(device);
-    std::lock_guard<std::mutex> g(slot.lock);
-    xrt_context* ctx = slot.ctx;
-    check(ctx, xrt_set_kernel(ctx, kernel_choice()), "xrt_set_kernel");
-    if (!slot.uploaded || slot.mesh != soup) {   // the mesh lives on the device between renders
-        check(ctx, xrt_upload_mesh(ctx, soup.data(), soup.size() / 9), "xrt_upload_mesh");
-        slot.mesh = soup;
-        slot.uploaded = true;
-    }
-    apply_poses(ctx, scene_meshes, 1);
-    check(ctx, xrt_render_rows(ctx, &cam, row_begin, row_end, image_strip, lbuffer_strip, u8_strip, stats),
-          "xrt_render_rows");
-}
-
 std::vector<float> mesh0_soup(const std::vector<TriangleMesh>& meshes)
 {
     // Only hits on meshes[0] count (main.cxx:687); other meshes cannot change
@@ -230,15 +212,67 @@ std::vector<float> mesh0_soup(const std::vector<TriangleMesh>& meshes)
     return meshes.empty() ? std::vector<float>() : meshes[0].flatten();
 }
 
-// Every mesh of the scene, one soup after another (xrt_upload_scene).
-void scene_soup(const std::vector<TriangleMesh>& meshes, std::vector<float>& soup, std::vector<uint64_t>& counts)
-{
-    for (const TriangleMesh& m : meshes) {
-        const std::vector<float> s = m.flatten();
-        soup.insert(soup.end(), s.begin(), s.end());
-        counts.push_back(s.size() / 9);
+// What a scene render sends to the device: mesh 0 alone (the attenuation and
+// signed models), or every mesh, one soup after another (xrt_upload_scene).
+struct SceneSoup {
+    std::vector<float> soup;
+    std::vector<uint64_t> counts;      // of every mesh's triangles (mesh 0 alone: unused)
+    const bool every_mesh;
+    const size_t scene_meshes, uploaded;   // apply_poses' pair
+    SceneSoup(const std::vector<TriangleMesh>& meshes, bool every_mesh)
+        : every_mesh(every_mesh), scene_meshes(meshes.size()), uploaded(every_mesh ? meshes.size() : 1)
+    {
+        if (!every_mesh) soup = mesh0_soup(meshes);
+        else
+            for (const TriangleMesh& m : meshes) {
+                const std::vector<float> s = m.flatten();
+                soup.insert(soup.end(), s.begin(), s.end());
+                counts.push_back(s.size() / 9);
+            }
     }
-}
+};
+
+constexpr bool kMesh0 = false, kEveryMesh = true;            // SceneSoup's every_mesh
+constexpr bool kAttenuation = false, kSignedModel = true;    // SceneRender's signed_model
+
+int signed_kernel(int k) { return k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k; }   // they have no TILED variant
+
+// The opening of every scene render on one device, held for its duration: the
+// device's context under its slot's lock, the kernel, the scene on the device
+// (mesh 0 through the slot's cache, or the whole scene) and setMeshPoses'
+// poses.  A render of a signed model (signed_model) then sets its model; the
+// destructor puts the context back to XRT_MODEL_ATTENUATION on every exit, a
+// throwing check included.
+class SceneRender {
+    const SceneSoup scene_;             // (built before the lock is taken)
+    DeviceSlot& slot_;
+    std::lock_guard<std::mutex> lock_;
+    const bool signed_model_;
+
+public:
+    xrt_context* const ctx;
+    SceneRender(const std::vector<TriangleMesh>& meshes, bool every_mesh, bool signed_model)
+        : scene_(meshes, every_mesh), slot_(device_slot(device_choice())), lock_(slot_.lock),
+          signed_model_(signed_model), ctx(slot_.ctx)
+    {
+        const int k = kernel_choice();
+        check(ctx, xrt_set_kernel(ctx, signed_model ? signed_kernel(k) : k), "xrt_set_kernel");
+        if (scene_.every_mesh) {
+            slot_.uploaded = false;                        // the slot's cache is of mesh-0 soups
+            check(ctx, xrt_upload_scene(ctx, scene_.soup.data(), scene_.counts.data(), (uint32_t)scene_.counts.size()),
+                  "xrt_upload_scene");
+        } else if (!slot_.uploaded || slot_.mesh != scene_.soup) {   // the mesh lives on the device between renders
+            check(ctx, xrt_upload_mesh(ctx, scene_.soup.data(), scene_.soup.size() / 9), "xrt_upload_mesh");
+            slot_.mesh = scene_.soup;
+            slot_.uploaded = true;
+        }
+        apply_poses(ctx, scene_.scene_meshes, scene_.uploaded);
+    }
+    ~SceneRender()
+    {
+        if (signed_model_) xrt_set_model(ctx, XRT_MODEL_ATTENUATION, 0.0f);
+    }
+};
 
 void report_odd(unsigned long long odd)
 {
@@ -254,9 +288,10 @@ void renderLoopRows(Image& image, const std::vector<TriangleMesh>& meshes, const
     if (row_begin > row_end || row_end > image.getHeight())
         throw std::out_of_range("renderLoopRows: row range outside the image");
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup = mesh0_soup(meshes);
-    render_strip(device_choice(), cam, soup, meshes.size(), row_begin, row_end,
-                 image.getData() + (size_t)row_begin * image.getWidth(), lbuffer_strip, u8_strip, stats);
+    SceneRender r(meshes, kMesh0, kAttenuation);
+    check(r.ctx, xrt_render_rows(r.ctx, &cam, row_begin, row_end, image.getData() + (size_t)row_begin * image.getWidth(),
+                                 lbuffer_strip, u8_strip, stats),
+          "xrt_render_rows");
 }
 
 double renderLoopFrames(Image& image, const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
@@ -265,20 +300,10 @@ double renderLoopFrames(Image& image, const std::vector<TriangleMesh>& meshes, c
     if (row_begin > row_end || row_end > image.getHeight())
         throw std::out_of_range("renderLoopFrames: row range outside the image");
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup = mesh0_soup(meshes);
-    DeviceSlot& slot = device_slot(device_choice());
-    std::lock_guard<std::mutex> g(slot.lock);
-    xrt_context* ctx = slot.ctx;
-    check(ctx, xrt_set_kernel(ctx, kernel_choice()), "xrt_set_kernel");
-    if (!slot.uploaded || slot.mesh != soup) {
-        check(ctx, xrt_upload_mesh(ctx, soup.data(), soup.size() / 9), "xrt_upload_mesh");
-        slot.mesh = soup;
-        slot.uploaded = true;
-    }
-    apply_poses(ctx, meshes.size(), 1);
+    SceneRender r(meshes, kMesh0, kAttenuation);
     double ms = 0.0;
-    check(ctx, xrt_render_frames(ctx, &cam, row_begin, row_end, frames,
-                                 image.getData() + (size_t)row_begin * image.getWidth(), nullptr, nullptr, stats, &ms),
+    check(r.ctx, xrt_render_frames(r.ctx, &cam, row_begin, row_end, frames,
+                                   image.getData() + (size_t)row_begin * image.getWidth(), nullptr, nullptr, stats, &ms),
           "xrt_render_frames");
     return ms;
 }
@@ -301,24 +326,12 @@ unsigned long long renderLoopLBuffer(Image& image, const std::vector<TriangleMes
                                      std::vector<float>* lbuffer)
 {
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup = mesh0_soup(meshes);
-    DeviceSlot& slot = device_slot(device_choice());
-    std::lock_guard<std::mutex> g(slot.lock);
-    xrt_context* ctx = slot.ctx;
-    int k = kernel_choice();
-    check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
-    if (!slot.uploaded || slot.mesh != soup) {
-        check(ctx, xrt_upload_mesh(ctx, soup.data(), soup.size() / 9), "xrt_upload_mesh");
-        slot.mesh = soup;
-        slot.uploaded = true;
-    }
-    apply_poses(ctx, meshes.size(), 1);
-    check(ctx, xrt_set_model(ctx, XRT_MODEL_SIGNED, 0.1037f), "xrt_set_model");   // :800
+    SceneRender r(meshes, kMesh0, kSignedModel);
+    check(r.ctx, xrt_set_model(r.ctx, XRT_MODEL_SIGNED, 0.1037f), "xrt_set_model");   // :800
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
-    const int rc = xrt_render_signed(ctx, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
-    xrt_set_model(ctx, XRT_MODEL_ATTENUATION, 0.0f);
-    check(ctx, rc, "xrt_render_signed");
+    check(r.ctx, xrt_render_signed(r.ctx, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats),
+          "xrt_render_signed");
     return stats.odd_rays;
 }
 
@@ -327,23 +340,12 @@ unsigned long long renderLoopMaterials(Image& image, const std::vector<TriangleM
 {
     if (mu.size() != meshes.size()) throw std::invalid_argument("renderLoopMaterials: one coefficient per mesh");
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup;
-    std::vector<uint64_t> counts;
-    scene_soup(meshes, soup, counts);
-    DeviceSlot& slot = device_slot(device_choice());
-    std::lock_guard<std::mutex> g(slot.lock);
-    xrt_context* ctx = slot.ctx;
-    int k = kernel_choice();
-    check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
-    slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
-    check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
-    apply_poses(ctx, meshes.size(), meshes.size());
-    check(ctx, xrt_set_materials(ctx, mu.data(), (uint32_t)mu.size()), "xrt_set_materials");
+    SceneRender r(meshes, kEveryMesh, kSignedModel);
+    check(r.ctx, xrt_set_materials(r.ctx, mu.data(), (uint32_t)mu.size()), "xrt_set_materials");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
-    const int rc = xrt_render_materials(ctx, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
-    xrt_set_model(ctx, XRT_MODEL_ATTENUATION, 0.0f);
-    check(ctx, rc, "xrt_render_materials");
+    check(r.ctx, xrt_render_materials(r.ctx, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats),
+          "xrt_render_materials");
     return stats.odd_rays;
 }
 
@@ -354,24 +356,13 @@ unsigned long long renderLoopSpectrum(Image& image, const std::vector<TriangleMe
     if (weight.empty() || mu.size() != meshes.size() * weight.size())
         throw std::invalid_argument("renderLoopSpectrum: one coefficient per mesh and bin");
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup;
-    std::vector<uint64_t> counts;
-    scene_soup(meshes, soup, counts);
-    DeviceSlot& slot = device_slot(device_choice());
-    std::lock_guard<std::mutex> g(slot.lock);
-    xrt_context* ctx = slot.ctx;
-    int k = kernel_choice();
-    check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
-    slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
-    check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
-    apply_poses(ctx, meshes.size(), meshes.size());
-    check(ctx, xrt_set_spectrum(ctx, weight.data(), mu.data(), (uint32_t)meshes.size(), (uint32_t)weight.size()),
+    SceneRender r(meshes, kEveryMesh, kSignedModel);
+    check(r.ctx, xrt_set_spectrum(r.ctx, weight.data(), mu.data(), (uint32_t)meshes.size(), (uint32_t)weight.size()),
           "xrt_set_spectrum");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
-    const int rc = xrt_render_spectrum(ctx, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
-    xrt_set_model(ctx, XRT_MODEL_ATTENUATION, 0.0f);
-    check(ctx, rc, "xrt_render_spectrum");
+    check(r.ctx, xrt_render_spectrum(r.ctx, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats),
+          "xrt_render_spectrum");
     return stats.odd_rays;
 }
 
@@ -381,25 +372,14 @@ unsigned long long renderLoopPaths(std::vector<std::vector<float>>& paths, std::
     if (meshes.empty() || meshes.size() > XRT_MAX_MESHES)
         throw std::invalid_argument("renderLoopPaths: 1 to XRT_MAX_MESHES meshes");
     xrt_camera cam = camera_for(frame, meshes, info);
-    std::vector<float> soup;
-    std::vector<uint64_t> counts;
-    scene_soup(meshes, soup, counts);
-    DeviceSlot& slot = device_slot(device_choice());
-    std::lock_guard<std::mutex> g(slot.lock);
-    xrt_context* ctx = slot.ctx;
-    int k = kernel_choice();
-    check(ctx, xrt_set_kernel(ctx, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_set_kernel");
-    slot.uploaded = false;                        // the slot's cache is of mesh-0 soups
-    check(ctx, xrt_upload_scene(ctx, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_upload_scene");
-    apply_poses(ctx, meshes.size(), meshes.size());
-    check(ctx, xrt_set_paths(ctx), "xrt_set_paths");
+    SceneRender r(meshes, kEveryMesh, kSignedModel);
+    check(r.ctx, xrt_set_paths(r.ctx), "xrt_set_paths");
     const size_t n = (size_t)frame.getWidth() * frame.getHeight();
     std::vector<float> planes(n * meshes.size());
     open.resize(n);
     xrt_stats stats;
-    const int rc = xrt_render_paths(ctx, &cam, 0, cam.height, (uint32_t)meshes.size(), planes.data(), open.data(), &stats);
-    xrt_set_model(ctx, XRT_MODEL_ATTENUATION, 0.0f);
-    check(ctx, rc, "xrt_render_paths");
+    check(r.ctx, xrt_render_paths(r.ctx, &cam, 0, cam.height, (uint32_t)meshes.size(), planes.data(), open.data(), &stats),
+          "xrt_render_paths");
     paths.resize(meshes.size());
     for (size_t m = 0; m < meshes.size(); ++m) paths[m].assign(planes.begin() + m * n, planes.begin() + (m + 1) * n);
     return stats.odd_rays;
@@ -521,6 +501,34 @@ void apply_poses_multi(xrt_multi* m, size_t scene_meshes, size_t uploaded)
         mcheck(m, xrt_multi_set_pose(m, (uint32_t)k, g_poses[k].data()), "xrt_multi_set_pose");
 }
 
+// SceneRender over the multi-device context of `num_gpus` devices, under
+// multi_lock().  A render of the attenuation model sets that model first.
+class MultiSceneRender {
+    const SceneSoup scene_;
+    std::lock_guard<std::mutex> lock_;
+    const bool signed_model_;
+
+public:
+    xrt_multi* const m;
+    MultiSceneRender(int num_gpus, const std::vector<TriangleMesh>& meshes, bool every_mesh, bool signed_model)
+        : scene_(meshes, every_mesh), lock_(multi_lock()), signed_model_(signed_model), m(multi_context(num_gpus))
+    {
+        const int k = kernel_choice();
+        if (!signed_model) mcheck(m, xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f), "xrt_multi_set_model");
+        mcheck(m, xrt_multi_set_kernel(m, signed_model ? signed_kernel(k) : k), "xrt_multi_set_kernel");
+        if (scene_.every_mesh)
+            mcheck(m, xrt_multi_upload_scene(m, scene_.soup.data(), scene_.counts.data(), (uint32_t)scene_.counts.size()),
+                   "xrt_multi_upload_scene");
+        else
+            mcheck(m, xrt_multi_upload_mesh(m, scene_.soup.data(), scene_.soup.size() / 9), "xrt_multi_upload_mesh");
+        apply_poses_multi(m, scene_.scene_meshes, scene_.uploaded);
+    }
+    ~MultiSceneRender()
+    {
+        if (signed_model_) xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f);
+    }
+};
+
 }  // namespace
 
 // Row strips over num_gpus devices gathered into device 0 with RCCL
@@ -529,15 +537,9 @@ unsigned long long renderLoopMultiGPU(Image& image, const std::vector<TriangleMe
                                       RayTracerInfo& info, int num_gpus)
 {
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup = mesh0_soup(meshes);
-    std::lock_guard<std::mutex> g(multi_lock());
-    xrt_multi* m = multi_context(num_gpus);
-    mcheck(m, xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f), "xrt_multi_set_model");
-    mcheck(m, xrt_multi_set_kernel(m, kernel_choice()), "xrt_multi_set_kernel");
-    mcheck(m, xrt_multi_upload_mesh(m, soup.data(), soup.size() / 9), "xrt_multi_upload_mesh");
-    apply_poses_multi(m, meshes.size(), 1);
+    MultiSceneRender r(num_gpus, meshes, kMesh0, kAttenuation);
     xrt_stats stats;
-    mcheck(m, xrt_render_rows_multi(m, &cam, image.getData(), nullptr, nullptr, &stats), "xrt_render_rows_multi");
+    mcheck(r.m, xrt_render_rows_multi(r.m, &cam, image.getData(), nullptr, nullptr, &stats), "xrt_render_rows_multi");
     report_odd(stats.odd_rays);
     return stats.odd_rays;
 }
@@ -546,19 +548,12 @@ unsigned long long renderLoopLBufferMultiGPU(Image& image, const std::vector<Tri
                                              RayTracerInfo& info, int num_gpus, std::vector<float>* lbuffer)
 {
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup = mesh0_soup(meshes);
-    std::lock_guard<std::mutex> g(multi_lock());
-    xrt_multi* m = multi_context(num_gpus);
-    const int k = kernel_choice();
-    mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
-    mcheck(m, xrt_multi_upload_mesh(m, soup.data(), soup.size() / 9), "xrt_multi_upload_mesh");
-    apply_poses_multi(m, meshes.size(), 1);
-    mcheck(m, xrt_multi_set_model(m, XRT_MODEL_SIGNED, 0.1037f), "xrt_multi_set_model");   // :800
+    MultiSceneRender r(num_gpus, meshes, kMesh0, kSignedModel);
+    mcheck(r.m, xrt_multi_set_model(r.m, XRT_MODEL_SIGNED, 0.1037f), "xrt_multi_set_model");   // :800
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
-    const int rc = xrt_render_rows_multi(m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
-    xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f);
-    mcheck(m, rc, "xrt_render_rows_multi");
+    mcheck(r.m, xrt_render_rows_multi(r.m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats),
+           "xrt_render_rows_multi");
     return stats.odd_rays;
 }
 
@@ -568,21 +563,12 @@ unsigned long long renderLoopMaterialsMultiGPU(Image& image, const std::vector<T
 {
     if (mu.size() != meshes.size()) throw std::invalid_argument("renderLoopMaterialsMultiGPU: one coefficient per mesh");
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup;
-    std::vector<uint64_t> counts;
-    scene_soup(meshes, soup, counts);
-    std::lock_guard<std::mutex> g(multi_lock());
-    xrt_multi* m = multi_context(num_gpus);
-    const int k = kernel_choice();
-    mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
-    mcheck(m, xrt_multi_upload_scene(m, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_multi_upload_scene");
-    apply_poses_multi(m, meshes.size(), meshes.size());
-    mcheck(m, xrt_multi_set_materials(m, mu.data(), (uint32_t)mu.size()), "xrt_multi_set_materials");
+    MultiSceneRender r(num_gpus, meshes, kEveryMesh, kSignedModel);
+    mcheck(r.m, xrt_multi_set_materials(r.m, mu.data(), (uint32_t)mu.size()), "xrt_multi_set_materials");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
-    const int rc = xrt_render_rows_multi(m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
-    xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f);
-    mcheck(m, rc, "xrt_render_rows_multi");
+    mcheck(r.m, xrt_render_rows_multi(r.m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats),
+           "xrt_render_rows_multi");
     return stats.odd_rays;
 }
 
@@ -593,22 +579,13 @@ unsigned long long renderLoopSpectrumMultiGPU(Image& image, const std::vector<Tr
     if (weight.empty() || mu.size() != meshes.size() * weight.size())
         throw std::invalid_argument("renderLoopSpectrumMultiGPU: one coefficient per mesh and bin");
     xrt_camera cam = camera_for(image, meshes, info);
-    std::vector<float> soup;
-    std::vector<uint64_t> counts;
-    scene_soup(meshes, soup, counts);
-    std::lock_guard<std::mutex> g(multi_lock());
-    xrt_multi* m = multi_context(num_gpus);
-    const int k = kernel_choice();
-    mcheck(m, xrt_multi_set_kernel(m, k == XRT_KERNEL_TILED ? XRT_KERNEL_BINNED : k), "xrt_multi_set_kernel");
-    mcheck(m, xrt_multi_upload_scene(m, soup.data(), counts.data(), (uint32_t)counts.size()), "xrt_multi_upload_scene");
-    apply_poses_multi(m, meshes.size(), meshes.size());
-    mcheck(m, xrt_multi_set_spectrum(m, weight.data(), mu.data(), (uint32_t)meshes.size(), (uint32_t)weight.size()),
+    MultiSceneRender r(num_gpus, meshes, kEveryMesh, kSignedModel);
+    mcheck(r.m, xrt_multi_set_spectrum(r.m, weight.data(), mu.data(), (uint32_t)meshes.size(), (uint32_t)weight.size()),
            "xrt_multi_set_spectrum");
     if (lbuffer) lbuffer->resize((size_t)image.getWidth() * image.getHeight());
     xrt_stats stats;
-    const int rc = xrt_render_rows_multi(m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats);
-    xrt_multi_set_model(m, XRT_MODEL_ATTENUATION, 0.0f);
-    mcheck(m, rc, "xrt_render_rows_multi");
+    mcheck(r.m, xrt_render_rows_multi(r.m, &cam, image.getData(), lbuffer ? lbuffer->data() : nullptr, nullptr, &stats),
+           "xrt_render_rows_multi");
     return stats.odd_rays;
 }
 

@@ -1977,6 +1977,106 @@ int d2h_copy(xrt_context* ctx, hipStream_t stream, const std::vector<D2HCopy>& c
     return XRT_OK;
 }
 
+// How a host buffer meets the device, one of two ways (DESIGN.md "Host entry
+// points"): the renders and the hole fill go through the context's staging
+// planes (stage_planes, plane_copies, d2h_copy); the operators and the probes
+// through buffers of their own call (DeviceScratch).
+
+// The context's staging planes (d_image, d_lbuffer, d_u8), each of at least
+// `need` elements: a plane that is too small is replaced by one of `need`,
+// and stage_cap is what all three hold.
+int stage_planes(xrt_context* ctx, size_t need)
+{
+    int rc;
+    size_t cap_f = ctx->stage_cap, cap_l = ctx->stage_cap, cap_u = ctx->stage_cap;
+    if ((rc = ensure(ctx, ctx->d_image, cap_f, need))) return rc;
+    if ((rc = ensure(ctx, ctx->d_lbuffer, cap_l, need))) return rc;
+    if ((rc = ensure(ctx, ctx->d_u8, cap_u, need))) return rc;
+    ctx->stage_cap = std::min(cap_f, std::min(cap_l, cap_u));
+    return XRT_OK;
+}
+
+// The copy-back list of a call's `n` pixels: the planes the caller asked for
+// (a NULL host pointer: not asked for), each from its device plane.
+std::vector<D2HCopy> plane_copies(size_t n, float* image, const float* d_image, float* lbuffer, const float* d_lbuffer,
+                                  uint8_t* image_u8, const uint8_t* d_u8)
+{
+    std::vector<D2HCopy> copies;
+    if (n) {
+        if (image) copies.push_back({image, d_image, n * sizeof(float)});
+        if (lbuffer) copies.push_back({lbuffer, d_lbuffer, n * sizeof(float)});
+        if (image_u8) copies.push_back({image_u8, d_u8, n});
+    }
+    return copies;
+}
+
+// The device buffers of one call of a host-buffer operator or probe, all on
+// `stream`: allocate (upload), launch, download, finish.  The first failure
+// sticks (rc(), the context's error "<name> allocation / upload / kernel
+// failed") and turns every later step into a no-op; the destructor waits for
+// the stream and frees the buffers on every path.
+class DeviceScratch {
+public:
+    DeviceScratch(xrt_context* ctx, hipStream_t stream, const char* name) : ctx_(ctx), stream_(stream), name_(name) {}
+    DeviceScratch(const DeviceScratch&) = delete;
+    DeviceScratch& operator=(const DeviceScratch&) = delete;
+    ~DeviceScratch()
+    {
+        (void)hipStreamSynchronize(stream_);
+        for (void* p : buffers_) (void)hipFree(p);
+    }
+    int rc() const { return rc_; }
+    // `n` elements; nullptr when there are none or the buffer is not wanted
+    template <typename T>
+    T* alloc(size_t n, bool wanted = true)
+    {
+        void* p = nullptr;
+        if (rc_ || !wanted || !n) return nullptr;
+        if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return failed("allocation");
+        buffers_.push_back(p);
+        return static_cast<T*>(p);
+    }
+    // a buffer holding the `n` elements at `host` (NULL: no buffer)
+    template <typename T>
+    T* upload(const T* host, size_t n)
+    {
+        T* p = alloc<T>(n, host != nullptr);
+        if (p && hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, stream_) != hipSuccess)
+            return failed("upload");
+        return p;
+    }
+    // after a bare hipLaunchKernelGGL
+    void launched()
+    {
+        if (!rc_ && hipGetLastError() != hipSuccess) failed("kernel");
+    }
+    // behind the launch (`host` NULL: not asked for)
+    template <typename T>
+    void download(T* host, const T* device, size_t n)
+    {
+        if (!rc_ && host && hipMemcpyAsync(host, device, n * sizeof(T), hipMemcpyDeviceToHost, stream_) != hipSuccess)
+            failed("kernel");
+    }
+    // the downloads are in the caller's buffers
+    int finish()
+    {
+        if (!rc_ && hipStreamSynchronize(stream_) != hipSuccess) failed("kernel");
+        return rc_;
+    }
+
+private:
+    std::nullptr_t failed(const char* step)
+    {
+        rc_ = fail(ctx_, XRT_ERR_DEVICE, std::string(name_) + " " + step + " failed");
+        return nullptr;
+    }
+    xrt_context* ctx_;
+    hipStream_t stream_;
+    const char* name_;
+    int rc_ = XRT_OK;
+    std::vector<void*> buffers_;
+};
+
 }  // namespace
 
 extern "C" {
@@ -2570,14 +2670,21 @@ int xrt_debug_pose_counters(xrt_context* ctx, uint64_t counters[2])
     return XRT_OK;
 }
 
+// The checks both paths renders share.
+static int paths_arguments(xrt_context* ctx, uint32_t num_meshes, const float* paths)
+{
+    if (ctx->model != kModelPaths) return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_paths needs xrt_set_paths");
+    if (num_meshes == 0 || num_meshes != ctx->mesh_tris.size())
+        return fail(ctx, XRT_ERR_ARGUMENT, "num_meshes differs from the scene's mesh count");
+    if (!paths) return fail(ctx, XRT_ERR_ARGUMENT, "paths is NULL");
+    return XRT_OK;
+}
+
 int xrt_render_paths_device(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
                             uint32_t num_meshes, float* d_paths, uint16_t* d_open, void* stream)
 {
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
-    if (ctx->model != kModelPaths) return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_paths needs xrt_set_paths");
-    if (num_meshes == 0 || num_meshes != ctx->mesh_tris.size())
-        return fail(ctx, XRT_ERR_ARGUMENT, "num_meshes differs from the scene's mesh count");
-    if (!d_paths) return fail(ctx, XRT_ERR_ARGUMENT, "paths is NULL");
+    if (int rc = paths_arguments(ctx, num_meshes, d_paths)) return rc;
     return enqueue_render(ctx, camera, row_begin, row_end, nullptr, d_paths, reinterpret_cast<uint8_t*>(d_open),
                           (hipStream_t)stream, true, true);
 }
@@ -2588,19 +2695,11 @@ int xrt_render_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_be
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
     int rc = check_camera(ctx, camera, row_begin, row_end);
     if (rc) return rc;
-    if (ctx->model != kModelPaths) return fail(ctx, XRT_ERR_ARGUMENT, "xrt_render_paths needs xrt_set_paths");
-    if (num_meshes == 0 || num_meshes != ctx->mesh_tris.size())
-        return fail(ctx, XRT_ERR_ARGUMENT, "num_meshes differs from the scene's mesh count");
-    if (!paths) return fail(ctx, XRT_ERR_ARGUMENT, "paths is NULL");
+    if ((rc = paths_arguments(ctx, num_meshes, paths))) return rc;
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)(row_end - row_begin) * camera->width;
     // the planes in the context's L-buffer staging, the masks in its 8-bit one (2 bytes a pixel)
-    const size_t need = n * std::max<size_t>(num_meshes, sizeof(uint16_t));
-    size_t cap_f = ctx->stage_cap, cap_l = ctx->stage_cap, cap_u = ctx->stage_cap;
-    if ((rc = ensure(ctx, ctx->d_image, cap_f, need))) return rc;
-    if ((rc = ensure(ctx, ctx->d_lbuffer, cap_l, need))) return rc;
-    if ((rc = ensure(ctx, ctx->d_u8, cap_u, need))) return rc;
-    ctx->stage_cap = std::min(cap_f, std::min(cap_l, cap_u));
+    if ((rc = stage_planes(ctx, n * std::max<size_t>(num_meshes, sizeof(uint16_t))))) return rc;
     uint16_t* d_open = open ? reinterpret_cast<uint16_t*>(ctx->d_u8) : nullptr;
     // (not prepared ahead: a host-buffer call, as xrt_render_rows)
     if ((rc = enqueue_render(ctx, camera, row_begin, row_end, nullptr, ctx->d_lbuffer,
@@ -2663,23 +2762,14 @@ int xrt_apply_spectrum(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshe
     if (rc || !num_pixels) return rc;
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)num_pixels;
-    float *dp = nullptr, *dl = nullptr;
-    uint16_t* dopen = nullptr;
-    if (hipMalloc(&dp, n * num_meshes * sizeof(float)) != hipSuccess || hipMalloc(&dl, n * sizeof(float)) != hipSuccess ||
-        (open && hipMalloc(&dopen, n * sizeof(uint16_t)) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "apply allocation failed");
-    } else if (hipMemcpy(dp, paths, n * num_meshes * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               (open && hipMemcpy(dopen, open, n * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "apply upload failed");
-    } else if (!(rc = launch_apply_spectrum(ctx, n, num_meshes, dp, dopen, weight, mu, num_bins, dl, ctx->host_stream))) {
-        if (hipMemcpyAsync(lbuffer, dl, n * sizeof(float), hipMemcpyDeviceToHost, ctx->host_stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->host_stream) != hipSuccess)
-            rc = fail(ctx, XRT_ERR_DEVICE, "apply kernel failed");
-    }
-    (void)hipFree(dp);
-    (void)hipFree(dl);
-    (void)hipFree(dopen);
-    return rc;
+    DeviceScratch s(ctx, ctx->host_stream, "apply");
+    const float* dp = s.upload(paths, n * num_meshes);
+    const uint16_t* dopen = s.upload(open, n);
+    float* dl = s.alloc<float>(n);
+    if (s.rc()) return s.rc();
+    if ((rc = launch_apply_spectrum(ctx, n, num_meshes, dp, dopen, weight, mu, num_bins, dl, ctx->host_stream))) return rc;
+    s.download(lbuffer, dl, n);
+    return s.finish();
 }
 
 int xrt_hole_fill_device(xrt_context* ctx, uint32_t width, uint32_t height, const float* d_lbuffer,
@@ -2706,19 +2796,12 @@ int xrt_hole_fill(xrt_context* ctx, uint32_t width, uint32_t height, const float
     if (!lbuffer) return fail(ctx, XRT_ERR_ARGUMENT, "L-buffer is NULL");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
-    size_t cap_f = ctx->stage_cap, cap_l = ctx->stage_cap, cap_u = ctx->stage_cap;
-    if ((rc = ensure(ctx, ctx->d_image, cap_f, n))) return rc;
-    if ((rc = ensure(ctx, ctx->d_lbuffer, cap_l, n))) return rc;
-    if ((rc = ensure(ctx, ctx->d_u8, cap_u, n))) return rc;
-    ctx->stage_cap = std::min(cap_f, std::min(cap_l, cap_u));
+    if ((rc = stage_planes(ctx, n))) return rc;
     XRT_HIP(ctx, hipMemcpyAsync(ctx->d_lbuffer, lbuffer, n * sizeof(float), hipMemcpyHostToDevice, ctx->host_stream));
     if ((rc = xrt_hole_fill_device(ctx, width, height, ctx->d_lbuffer, image ? ctx->d_image : nullptr,
                                    image_u8 ? ctx->d_u8 : nullptr, ctx->host_stream)))
         return rc;
-    std::vector<D2HCopy> copies;
-    if (image) copies.push_back({image, ctx->d_image, n * sizeof(float)});
-    if (image_u8) copies.push_back({image_u8, ctx->d_u8, n});
-    return d2h_copy(ctx, ctx->host_stream, copies);
+    return d2h_copy(ctx, ctx->host_stream, plane_copies(n, image, ctx->d_image, nullptr, nullptr, image_u8, ctx->d_u8));
 }
 
 // --- the detector response -------------------------------------
@@ -2763,26 +2846,16 @@ int xrt_detector_response(xrt_context* ctx, uint32_t width, uint32_t height, uin
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)width * height * num_planes;
-    float *din = nullptr, *dout = nullptr;
-    uint8_t* du8 = nullptr;
-    int rc = XRT_OK;
-    if (hipMalloc(&din, n * sizeof(float)) != hipSuccess || (out && hipMalloc(&dout, n * sizeof(float)) != hipSuccess) ||
-        (out_u8 && hipMalloc(&du8, n) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "detector response allocation failed");
-    } else if (hipMemcpyAsync(din, image, n * sizeof(float), hipMemcpyHostToDevice, ctx->host_stream) != hipSuccess) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "detector response upload failed");
-    } else if (!(rc = launch_lsf(ctx, width, height, num_planes, din, lsf_x, taps_x, lsf_y, taps_y, dout, du8,
-                                 ctx->host_stream))) {
-        if ((out && hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, ctx->host_stream) != hipSuccess) ||
-            (out_u8 && hipMemcpyAsync(out_u8, du8, n, hipMemcpyDeviceToHost, ctx->host_stream) != hipSuccess) ||
-            hipStreamSynchronize(ctx->host_stream) != hipSuccess)
-            rc = fail(ctx, XRT_ERR_DEVICE, "detector response kernel failed");
-    }
-    (void)hipStreamSynchronize(ctx->host_stream);
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    (void)hipFree(du8);
-    return rc;
+    DeviceScratch s(ctx, ctx->host_stream, "detector response");
+    const float* din = s.upload(image, n);
+    float* dout = s.alloc<float>(n, out != nullptr);
+    uint8_t* du8 = s.alloc<uint8_t>(n, out_u8 != nullptr);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_lsf(ctx, width, height, num_planes, din, lsf_x, taps_x, lsf_y, taps_y, dout, du8, ctx->host_stream))
+        return rc;
+    s.download(out, dout, n);
+    s.download(out_u8, du8, n);
+    return s.finish();
 }
 
 // --- line-integral projections ---------------------------------
@@ -2824,28 +2897,18 @@ int xrt_log_projection(xrt_context* ctx, uint32_t width, uint32_t height, uint32
         return fail(ctx, XRT_ERR_ARGUMENT, why);
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t plane = (size_t)width * height * sizeof(float), all = plane * num_planes;
-    float *din = nullptr, *dflat = nullptr, *ddark = nullptr, *dout = nullptr;
-    int rc = XRT_OK;
-    if (hipMalloc(&din, all) != hipSuccess || hipMalloc(&dout, all) != hipSuccess ||
-        (flat && hipMalloc(&dflat, plane) != hipSuccess) || (dark && hipMalloc(&ddark, plane) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "log projection allocation failed");
-    } else if (hipMemcpyAsync(din, image, all, hipMemcpyHostToDevice, ctx->host_stream) != hipSuccess ||
-               (flat && hipMemcpyAsync(dflat, flat, plane, hipMemcpyHostToDevice, ctx->host_stream) != hipSuccess) ||
-               (dark && hipMemcpyAsync(ddark, dark, plane, hipMemcpyHostToDevice, ctx->host_stream) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "log projection upload failed");
-    } else if (!(rc = launch_log_projection(ctx, width, height, num_planes, din, dflat, ddark, flat_value, t_min, order,
-                                            dout, ctx->host_stream))) {
-        if (hipMemcpyAsync(out, dout, all, hipMemcpyDeviceToHost, ctx->host_stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->host_stream) != hipSuccess)
-            rc = fail(ctx, XRT_ERR_DEVICE, "log projection kernel failed");
-    }
-    (void)hipStreamSynchronize(ctx->host_stream);
-    (void)hipFree(din);
-    (void)hipFree(dflat);
-    (void)hipFree(ddark);
-    (void)hipFree(dout);
-    return rc;
+    const size_t plane = (size_t)width * height, all = plane * num_planes;
+    DeviceScratch s(ctx, ctx->host_stream, "log projection");
+    const float* din = s.upload(image, all);
+    const float* dflat = s.upload(flat, plane);
+    const float* ddark = s.upload(dark, plane);
+    float* dout = s.alloc<float>(all);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_log_projection(ctx, width, height, num_planes, din, dflat, ddark, flat_value, t_min, order, dout,
+                                       ctx->host_stream))
+        return rc;
+    s.download(out, dout, all);
+    return s.finish();
 }
 
 // Render of the L-buffer plane and the fork's hole fill over it, into host buffers.
@@ -2856,23 +2919,15 @@ static int render_and_fill(xrt_context* ctx, const xrt_camera* camera, float* im
     if (rc) return rc;
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)camera->width * camera->height;
-    size_t cap_f = ctx->stage_cap, cap_l = ctx->stage_cap, cap_u = ctx->stage_cap;
-    if ((rc = ensure(ctx, ctx->d_image, cap_f, n))) return rc;
-    if ((rc = ensure(ctx, ctx->d_lbuffer, cap_l, n))) return rc;
-    if ((rc = ensure(ctx, ctx->d_u8, cap_u, n))) return rc;
-    ctx->stage_cap = std::min(cap_f, std::min(cap_l, cap_u));
+    if ((rc = stage_planes(ctx, n))) return rc;
     if ((rc = enqueue_render(ctx, camera, 0, camera->height, nullptr, ctx->d_lbuffer, nullptr, ctx->host_stream)))
         return rc;
     if ((rc = xrt_hole_fill_device(ctx, camera->width, camera->height, ctx->d_lbuffer,
                                    image ? ctx->d_image : nullptr, image_u8 ? ctx->d_u8 : nullptr,
                                    ctx->host_stream)))
         return rc;
-    std::vector<D2HCopy> copies;
-    if (n) {
-        if (image) copies.push_back({image, ctx->d_image, n * sizeof(float)});
-        if (lbuffer) copies.push_back({lbuffer, ctx->d_lbuffer, n * sizeof(float)});
-        if (image_u8) copies.push_back({image_u8, ctx->d_u8, n});
-    }
+    const std::vector<D2HCopy> copies =
+        plane_copies(n, image, ctx->d_image, lbuffer, ctx->d_lbuffer, image_u8, ctx->d_u8);
     if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
     xrt_stats local;
     return xrt_read_stats(ctx, stats ? stats : &local);
@@ -3257,11 +3312,7 @@ int xrt_render_frames(xrt_context* ctx, const xrt_camera* camera, uint32_t row_b
     if (!n_frames) return fail(ctx, XRT_ERR_ARGUMENT, "n_frames must be >= 1");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)(row_end - row_begin) * camera->width;
-    size_t cap_f = ctx->stage_cap, cap_l = ctx->stage_cap, cap_u = ctx->stage_cap;
-    if ((rc = ensure(ctx, ctx->d_image, cap_f, n))) return rc;
-    if ((rc = ensure(ctx, ctx->d_lbuffer, cap_l, n))) return rc;
-    if ((rc = ensure(ctx, ctx->d_u8, cap_u, n))) return rc;
-    ctx->stage_cap = std::min(cap_f, std::min(cap_l, cap_u));
+    if ((rc = stage_planes(ctx, n))) return rc;
     float* di = image ? ctx->d_image : nullptr;
     float* dl = lbuffer ? ctx->d_lbuffer : nullptr;
     uint8_t* du = image_u8 ? ctx->d_u8 : nullptr;
@@ -3271,12 +3322,8 @@ int xrt_render_frames(xrt_context* ctx, const xrt_camera* camera, uint32_t row_b
     XRT_HIP(ctx, hipStreamSynchronize(ctx->host_stream));
     if (ms_per_frame)
         *ms_per_frame = std::chrono::duration<double, std::milli>(HostClock::now() - t0).count() / n_frames;
-    std::vector<D2HCopy> copies;
-    if (n) {
-        if (image) copies.push_back({image, ctx->d_image, n * sizeof(float)});
-        if (lbuffer) copies.push_back({lbuffer, ctx->d_lbuffer, n * sizeof(float)});
-        if (image_u8) copies.push_back({image_u8, ctx->d_u8, n});
-    }
+    const std::vector<D2HCopy> copies =
+        plane_copies(n, image, ctx->d_image, lbuffer, ctx->d_lbuffer, image_u8, ctx->d_u8);
     if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
     xrt_stats local;
     return xrt_read_stats(ctx, stats ? stats : &local);
@@ -3448,11 +3495,7 @@ int xrt_render_rows(xrt_context* ctx, const xrt_camera* camera, uint32_t row_beg
     double acc0[kAccFields];
     std::copy(ctx->acc_ms, ctx->acc_ms + kAccFields, acc0);
     const size_t n = (size_t)(row_end - row_begin) * camera->width;
-    size_t cap_f = ctx->stage_cap, cap_l = ctx->stage_cap, cap_u = ctx->stage_cap;
-    if ((rc = ensure(ctx, ctx->d_image, cap_f, n))) return rc;
-    if ((rc = ensure(ctx, ctx->d_lbuffer, cap_l, n))) return rc;
-    if ((rc = ensure(ctx, ctx->d_u8, cap_u, n))) return rc;
-    ctx->stage_cap = std::min(cap_f, std::min(cap_l, cap_u));
+    if ((rc = stage_planes(ctx, n))) return rc;
     lap(0, t);
     // the context's own non-blocking stream (not the null stream)
     rc = enqueue_render(ctx, camera, row_begin, row_end, image ? ctx->d_image : nullptr,
@@ -3462,12 +3505,8 @@ int xrt_render_rows(xrt_context* ctx, const xrt_camera* camera, uint32_t row_beg
     lap(1, t);
     XRT_HIP(ctx, hipEventSynchronize(ctx->host_render_done));
     lap(2, t);
-    std::vector<D2HCopy> copies;
-    if (n) {
-        if (image) copies.push_back({image, ctx->d_image, n * sizeof(float)});
-        if (lbuffer) copies.push_back({lbuffer, ctx->d_lbuffer, n * sizeof(float)});
-        if (image_u8) copies.push_back({image_u8, ctx->d_u8, n});
-    }
+    const std::vector<D2HCopy> copies =
+        plane_copies(n, image, ctx->d_image, lbuffer, ctx->d_lbuffer, image_u8, ctx->d_u8);
     if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
     lap(3, t);
     double bytes = 0.0;
@@ -3489,29 +3528,17 @@ int xrt_probe_intersect(xrt_context* ctx, const float* rays, const float* tris, 
     if (n == 0) return XRT_OK;
     if (!rays || !tris || !hit || !t) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
-    float *dr = nullptr, *dt = nullptr, *dout = nullptr;
-    uint8_t* dh = nullptr;
-    int rc = XRT_OK;
-    if (hipMalloc(&dr, n * 6 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&dt, n * 9 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&dout, n * sizeof(float)) != hipSuccess || hipMalloc(&dh, n) != hipSuccess) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "probe allocation failed");
-    } else if (hipMemcpy(dr, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(dt, tris, n * 9 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "probe upload failed");
-    } else {
-        hipLaunchKernelGGL(k_probe_intersect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dr,
-                           dt, n, dh, dout);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpy(hit, dh, n, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(t, dout, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(ctx, XRT_ERR_DEVICE, "probe kernel failed");
-    }
-    (void)hipFree(dr);
-    (void)hipFree(dt);
-    (void)hipFree(dout);
-    (void)hipFree(dh);
-    return rc;
+    DeviceScratch s(ctx, nullptr, "probe");
+    const float* dr = s.upload(rays, n * 6);
+    const float* dt = s.upload(tris, n * 9);
+    float* dout = s.alloc<float>(n);
+    uint8_t* dh = s.alloc<uint8_t>(n);
+    if (s.rc()) return s.rc();
+    hipLaunchKernelGGL(k_probe_intersect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dr, dt, n, dh, dout);
+    s.launched();
+    s.download(hit, dh, n);
+    s.download(t, dout, n);
+    return s.finish();
 }
 
 int xrt_probe_math(xrt_context* ctx, int op, const float* in, float* outp, uint64_t n)
@@ -3521,23 +3548,14 @@ int xrt_probe_math(xrt_context* ctx, int op, const float* in, float* outp, uint6
     if (n == 0) return XRT_OK;
     if (!in || !outp) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
-    float *di = nullptr, *dout = nullptr;
-    int rc = XRT_OK;
-    if (hipMalloc(&di, n * sizeof(float)) != hipSuccess ||
-        hipMalloc(&dout, n * sizeof(float)) != hipSuccess) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "probe allocation failed");
-    } else if (hipMemcpy(di, in, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "probe upload failed");
-    } else {
-        hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, di,
-                           dout, n);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpy(outp, dout, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(ctx, XRT_ERR_DEVICE, "probe kernel failed");
-    }
-    (void)hipFree(di);
-    (void)hipFree(dout);
-    return rc;
+    DeviceScratch s(ctx, nullptr, "probe");
+    const float* di = s.upload(in, n);
+    float* dout = s.alloc<float>(n);
+    if (s.rc()) return s.rc();
+    hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, di, dout, n);
+    s.launched();
+    s.download(outp, dout, n);
+    return s.finish();
 }
 
 int xrt_probe_materials(xrt_context* ctx, const float* distance, const int32_t* sign_sum, const float* mu,
@@ -3549,29 +3567,17 @@ int xrt_probe_materials(xrt_context* ctx, const float* distance, const int32_t* 
     if (!distance || !mu || !outp) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t terms = (size_t)n * num_meshes;
-    float *dd = nullptr, *dmu = nullptr, *dout = nullptr;
-    int* ds = nullptr;
-    int rc = XRT_OK;
-    if (hipMalloc(&dd, terms * sizeof(float)) != hipSuccess || hipMalloc(&dmu, num_meshes * sizeof(float)) != hipSuccess ||
-        hipMalloc(&dout, n * sizeof(float)) != hipSuccess ||
-        (sign_sum && hipMalloc(&ds, terms * sizeof(int)) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "probe allocation failed");
-    } else if (hipMemcpy(dd, distance, terms * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(dmu, mu, num_meshes * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               (sign_sum && hipMemcpy(ds, sign_sum, terms * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "probe upload failed");
-    } else {
-        hipLaunchKernelGGL(k_probe_materials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dd, ds, dmu,
-                           num_meshes, dout, (size_t)n);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpy(outp, dout, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(ctx, XRT_ERR_DEVICE, "probe kernel failed");
-    }
-    (void)hipFree(dd);
-    (void)hipFree(dmu);
-    (void)hipFree(dout);
-    (void)hipFree(ds);
-    return rc;
+    DeviceScratch s(ctx, nullptr, "probe");
+    const float* dd = s.upload(distance, terms);
+    const float* dmu = s.upload(mu, num_meshes);
+    const int* ds = s.upload(sign_sum, terms);
+    float* dout = s.alloc<float>(n);
+    if (s.rc()) return s.rc();
+    hipLaunchKernelGGL(k_probe_materials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dd, ds, dmu, num_meshes,
+                       dout, (size_t)n);
+    s.launched();
+    s.download(outp, dout, n);
+    return s.finish();
 }
 
 int xrt_probe_spectrum(xrt_context* ctx, const float* distance, const int32_t* sign_sum, const float* weight,
@@ -3584,31 +3590,18 @@ int xrt_probe_spectrum(xrt_context* ctx, const float* distance, const int32_t* s
     if (!distance || !weight || !mu || !outp) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t terms = (size_t)n * num_meshes, coeffs = (size_t)num_meshes * num_bins;
-    float *dd = nullptr, *dw = nullptr, *dmu = nullptr, *dout = nullptr;
-    int* ds = nullptr;
-    int rc = XRT_OK;
-    if (hipMalloc(&dd, terms * sizeof(float)) != hipSuccess || hipMalloc(&dw, num_bins * sizeof(float)) != hipSuccess ||
-        hipMalloc(&dmu, coeffs * sizeof(float)) != hipSuccess || hipMalloc(&dout, n * sizeof(float)) != hipSuccess ||
-        (sign_sum && hipMalloc(&ds, terms * sizeof(int)) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "probe allocation failed");
-    } else if (hipMemcpy(dd, distance, terms * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(dw, weight, num_bins * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(dmu, mu, coeffs * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               (sign_sum && hipMemcpy(ds, sign_sum, terms * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)) {
-        rc = fail(ctx, XRT_ERR_DEVICE, "probe upload failed");
-    } else {
-        hipLaunchKernelGGL(k_probe_spectrum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dd, ds, dw, dmu,
-                           num_meshes, num_bins, dout, (size_t)n);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpy(outp, dout, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(ctx, XRT_ERR_DEVICE, "probe kernel failed");
-    }
-    (void)hipFree(dd);
-    (void)hipFree(dw);
-    (void)hipFree(dmu);
-    (void)hipFree(dout);
-    (void)hipFree(ds);
-    return rc;
+    DeviceScratch s(ctx, nullptr, "probe");
+    const float* dd = s.upload(distance, terms);
+    const float* dw = s.upload(weight, num_bins);
+    const float* dmu = s.upload(mu, coeffs);
+    const int* ds = s.upload(sign_sum, terms);
+    float* dout = s.alloc<float>(n);
+    if (s.rc()) return s.rc();
+    hipLaunchKernelGGL(k_probe_spectrum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dd, ds, dw, dmu, num_meshes,
+                       num_bins, dout, (size_t)n);
+    s.launched();
+    s.download(outp, dout, n);
+    return s.finish();
 }
 
 int xrt_probe_prep(xrt_context* ctx, const xrt_camera* camera, float* records, float* footprint)

@@ -1347,10 +1347,8 @@ int xrt_render_rows_multi(xrt_multi* m, const xrt_camera* camera, float* image, 
                                       image_u8 ? m->d_u8 : nullptr, m->own0);
     if (rc) return rc;
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
-    std::vector<D2HCopy> copies;                       // device 0's pinned ring and copy threads
-    if (image) copies.push_back({image, m->d_image, px * sizeof(float)});
-    if (lbuffer) copies.push_back({lbuffer, m->d_lbuffer, px * sizeof(float)});
-    if (image_u8) copies.push_back({image_u8, m->d_u8, px});
+    // (through device 0's pinned ring and copy threads)
+    const std::vector<D2HCopy> copies = plane_copies(px, image, m->d_image, lbuffer, m->d_lbuffer, image_u8, m->d_u8);
     if ((rc = check_ctx(m, 0, d2h_copy(m->ctx[0], m->own0, copies)))) return rc;
     XRT_MHIP(m, hipStreamSynchronize(m->own0));
     if (hit_mismatch(m)) return report_hit_mismatch(m);          // this frame's gather
