@@ -539,6 +539,77 @@ int xrt_log_projection_device(xrt_context* ctx, uint32_t width, uint32_t height,
                               const float* d_image, const float* d_flat, const float* d_dark, float flat_value,
                               float t_min, int order, float* d_out, void* stream);
 
+/* --- photon noise: a counter-based Poisson sampler ------------------------ */
+
+/*
+ * The quantum noise of a detector that counts photons (DESIGN.md section
+ * 10.7), on the device behind the detector response and ahead of the line
+ * integrals.  `image` is num_planes row-major f32 planes of width x height
+ * pixels, one after another, taken as one flat buffer: pixel i in [0, n),
+ * n = width * height * num_planes, has the global index g = first_index + i.
+ * `gain` is the photons per unit of image value.  The noise is a pure function
+ * of (seed, g, the pixel's mean): the same under any launch shape, for a strip
+ * or one projection of a scan given its first_index, and on host and device.
+ *
+ * The random word.  w is word g & 3 of Philox4x32-10 (multipliers 0xD2511F53
+ * and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85) at the counter
+ * (lo32(g >> 2), hi32(g >> 2), 0, 0) under the key (lo32(seed), hi32(seed)).
+ *   u = ((double)w + 0.5) * 2^-32             (exact in f64, never 0 or 1)
+ * The mean.
+ *   lam_f = image[i] * gain                   (one f32 rounding)
+ *   lam   = (double)lam_f
+ * A NaN or lam < 0 gives NaN (sign and payload not specified), +inf gives
+ * +inf, -0.0 counts as 0.
+ * lam < 64: inversion by sequential search, with xrt_exp glibc 2.35's exp
+ * restated bit for bit:
+ *   p = xrt_exp(-lam); s = p; N = 0
+ *   while (u > s && N < 255) { N += 1; p = (p * lam) / (double)N; s = s + p; }
+ * (at lam just under 64 the search ends within 108 steps for every word: the
+ * cap never binds).
+ * Otherwise: a normal deviate -- the normal CDF inverted by Wichura's AS241,
+ * PPND7 -- with the second-order Cornish-Fisher term:
+ *   q = u - 0.5
+ *   if (|q| <= 0.425) {
+ *     r = 0.180625 - q*q
+ *     z = q*(((A3*r + A2)*r + A1)*r + A0) / (((B3*r + B2)*r + B1)*r + 1)
+ *   } else {
+ *     t = q < 0 ? u : 1 - u
+ *     r = sqrt(-(double)logf((float)t)) - 1.6      (logf as xrt_log_projection's)
+ *     z = +-(((C3*r + C2)*r + C1)*r + C0) / ((D2*r + D1)*r + 1), negative for q < 0
+ *   }
+ *   x = lam + sqrt(lam)*z + (z*z - 1)/6
+ *   N = max(floor(x + 0.5), 0)
+ * with the f64 literals
+ *   A0 3.3871327179   A1 50.434271938   A2 159.29113202   A3 59.109374720
+ *                     B1 17.895169469   B2 78.757757664   B3 67.187563600
+ *   C0 1.4234372777   C1 2.7568153900   C2 1.3067284816   C3 0.17023821103
+ *                     D1 0.73700164250  D2 0.12021132975
+ * AS241's third branch (sqrt(-ln t) > 5) is unreachable and left out: the
+ * smallest t is 2^-33, and sqrt(-ln 2^-33) < 4.79.  Every f64 and f32
+ * operation above is rounded on its own -- no step of a polynomial, of x or of
+ * z*z - 1 is fused --, sqrt and / are IEEE-correct, and q*(...) / (...) is the
+ * product divided.
+ * The output.  XRT_NOISE_COUNTS: (float)N.  XRT_NOISE_INTENSITY: (float)N /
+ * gain, an IEEE f32 division.
+ *
+ * XRT_ERR_ARGUMENT for a NULL image or out; a width, height or num_planes of
+ * 0; more pixels than one launch's 2^31 - 1 workgroups, 1024 pixels each, hold;
+ * first_index + n overflowing 64 bits; a gain that is not finite or not > 0;
+ * a mode other than the two; an out that overlaps the image -- except
+ * out == image exactly, which is allowed (in place: the pass is pointwise).
+ * All of that is checked before the context is looked at.  xrt_photon_noise:
+ * host buffers, synchronous.  _device: device buffers, asynchronous on
+ * `stream`.  Neither touches the context's model, scene or frames in flight.
+ * There is no xrt_multi_ form: first_index is what lets a strip or a single
+ * projection of a scan draw the noise it would have drawn in the whole.
+ */
+#define XRT_NOISE_INTENSITY 0
+#define XRT_NOISE_COUNTS 1
+int xrt_photon_noise(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* image,
+                     float gain, uint64_t seed, uint64_t first_index, int mode, float* out);
+int xrt_photon_noise_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_image,
+                            float gain, uint64_t seed, uint64_t first_index, int mode, float* d_out, void* stream);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

@@ -268,6 +268,22 @@ int xrt_host_log_projection(uint32_t width, uint32_t height, uint32_t num_planes
                             float* out);
 
 /*
+ * Test hooks of the photon noise.  Host code, no device: xrt_host_philox4x32
+ * is the generator on one counter and key (the published known answers);
+ * xrt_host_poisson_batch is the device's sampler compiled for the host, out[i]
+ * = the count N (f64; NaN and +inf as the contract has them) of the mean
+ * lam[i] under the word words[i]; xrt_host_photon_noise is xrt_photon_noise's
+ * pixel function over whole buffers, arguments and checks as
+ * xrt_photon_noise's, host buffers.  xrt_debug_poisson_batch is
+ * xrt_host_poisson_batch on the device, by a small kernel of its own.
+ */
+void xrt_host_philox4x32(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+void xrt_host_poisson_batch(const double* lam, const uint32_t* words, uint64_t n, double* out);
+int xrt_host_photon_noise(uint32_t width, uint32_t height, uint32_t num_planes, const float* image, float gain,
+                          uint64_t seed, uint64_t first_index, int mode, float* out);
+int xrt_debug_poisson_batch(xrt_context* ctx, const double* lam, const uint32_t* words, uint64_t n, double* out);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -32,6 +32,7 @@ __all__ = [
     "XRT_MAX_MESHES", "XRT_MODEL_SPECTRUM", "XRT_MAX_BINS", "XRT_MODEL_PATHS", "pose_rotation", "pose_triangles",
     "XRT_MAX_LSF_TAPS", "lsf_gaussian", "host_lsf", "detector_response",
     "XRT_ORDER_PROJECTIONS", "XRT_ORDER_SINOGRAMS", "host_logf", "host_log_projection", "log_projection",
+    "XRT_NOISE_INTENSITY", "XRT_NOISE_COUNTS", "host_philox4x32", "host_poisson", "host_photon_noise", "photon_noise",
 ]
 
 
@@ -285,6 +286,59 @@ def log_projection(image, flat=None, dark=None, flat_value=None, t_min=0.0, sino
         return ctx.log_projection(image, flat, dark, flat_value, t_min, sinograms)
 
 
+def _u32ptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+
+
+def _dptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _noise_mode(counts):
+    return _abi.XRT_NOISE_COUNTS if counts else _abi.XRT_NOISE_INTENSITY
+
+
+def _poisson_arrays(lam, words):
+    """Means and words as the sampler's hooks take them: f64 and u32 of one shape."""
+    lam, words = np.broadcast_arrays(np.asarray(lam, np.float64), np.asarray(words, np.uint32))
+    return np.ascontiguousarray(lam), np.ascontiguousarray(words)
+
+
+def host_philox4x32(counter, key) -> np.ndarray:
+    """Philox4x32-10's four words for a counter of four u32 and a key of two (xrt_host_philox4x32, a test hook)."""
+    c = np.ascontiguousarray(counter, dtype=np.uint32).reshape(4)
+    k = np.ascontiguousarray(key, dtype=np.uint32).reshape(2)
+    out = np.empty(4, np.uint32)
+    _abi.load().xrt_host_philox4x32(_u32ptr(c), _u32ptr(k), _u32ptr(out))
+    return out
+
+
+def host_poisson(lam, words) -> np.ndarray:
+    """The device's Poisson sampler compiled for the host: the counts (f64) of the means `lam` under the random
+    words `words` (xrt_host_poisson_batch, a test hook)."""
+    lam, words = _poisson_arrays(lam, words)
+    out = np.empty(lam.shape, np.float64)
+    _abi.load().xrt_host_poisson_batch(_dptr(lam), _u32ptr(words), lam.size, _dptr(out))
+    return out
+
+
+def host_photon_noise(image, gain, seed, counts=False, first_index=0) -> np.ndarray:
+    """Context.photon_noise in the device's arithmetic on the host (xrt_host_photon_noise, a test hook)."""
+    a, p, h, w = _lsf_planes(image)
+    out = np.empty_like(a)
+    rc = _abi.load().xrt_host_photon_noise(w, h, p, _fptr(a), float(gain), int(seed), int(first_index),
+                                           _noise_mode(counts), _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_photon_noise")
+    return out
+
+
+def photon_noise(image, gain, seed, counts=False, first_index=0, device: int = 0) -> np.ndarray:
+    """The noisy image(s) of Context.photon_noise, on a context of its own on `device`."""
+    with Context(device) as ctx:
+        return ctx.photon_noise(image, gain, seed, counts, first_index)
+
+
 class Context:
     """One xrt_context (one device).  Not thread-safe."""
 
@@ -519,6 +573,33 @@ class Context:
                                                  d_flat or None, d_dark or None, float(flat_value), float(t_min), order,
                                                  d_out or None, stream or None)
         self._check(rc, "xrt_log_projection_device")
+
+    def photon_noise(self, image, gain, seed, counts=False, first_index=0):
+        """Photon noise over an (H, W) image or a (P, H, W) stack: each pixel a Poisson count of mean
+        image * gain, drawn from (seed, first_index + the pixel's flat index) alone, returned as counts or --
+        counts=False -- divided by gain again.  The image's shape."""
+        a, p, h, w = _lsf_planes(image)
+        out = np.empty_like(a)
+        self._check(self._lib.xrt_photon_noise(self._ctx, w, h, p, _fptr(a), float(gain), int(seed), int(first_index),
+                                               _noise_mode(counts), _fptr(out)), "xrt_photon_noise")
+        return out
+
+    def photon_noise_device(self, width: int, height: int, num_planes: int, d_image: int, d_out: int, gain: float,
+                            seed: int, counts: bool = False, first_index: int = 0, stream: int = 0):
+        """photon_noise over device buffers (raw pointers; d_out == d_image is in place); asynchronous on
+        `stream`."""
+        rc = self._lib.xrt_photon_noise_device(self._ctx, int(width), int(height), int(num_planes), d_image or None,
+                                               float(gain), int(seed), int(first_index), _noise_mode(counts),
+                                               d_out or None, stream or None)
+        self._check(rc, "xrt_photon_noise_device")
+
+    def debug_poisson(self, lam, words) -> np.ndarray:
+        """host_poisson on the device (xrt_debug_poisson_batch, a probe)."""
+        lam, words = _poisson_arrays(lam, words)
+        out = np.empty(lam.shape, np.float64)
+        self._check(self._lib.xrt_debug_poisson_batch(self._ctx, _dptr(lam), _u32ptr(words), lam.size, _dptr(out)),
+                    "xrt_debug_poisson_batch")
+        return out
 
     def render_signed(self, cam: Camera):
         """The L-buffer fork end to end: (image f32, lbuffer f32 with -1 flags, u8, Stats)."""

@@ -44,6 +44,8 @@ XRT_MODEL_PATHS = 4
 XRT_MAX_LSF_TAPS = 129
 XRT_ORDER_PROJECTIONS = 0
 XRT_ORDER_SINOGRAMS = 1
+XRT_NOISE_INTENSITY = 0
+XRT_NOISE_COUNTS = 1
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -70,6 +72,7 @@ _vp = ctypes.c_void_p
 _dp = ctypes.POINTER(ctypes.c_double)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
 
 
 class Camera(ctypes.Structure):
@@ -185,6 +188,13 @@ XRT_SYMBOLS = {
     "xrt_host_logf_batch": (None, [_fp, _fp, _u64]),
     "xrt_host_log_projection": (ctypes.c_int, [_u32, _u32, _u32, _fp, _fp, _fp, ctypes.c_float, ctypes.c_float,
                                                ctypes.c_int, _fp]),
+    "xrt_photon_noise": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),
+    "xrt_photon_noise_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, ctypes.c_float, _u64, _u64, ctypes.c_int, _vp,
+                                               _vp]),
+    "xrt_host_philox4x32": (None, [_u32p, _u32p, _u32p]),
+    "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
+    "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),
+    "xrt_debug_poisson_batch": (ctypes.c_int, [_CtxP, _dp, _u32p, _u64, _dp]),
     "xrt_multi_set_pose": (ctypes.c_int, [_MultiP, _u32, _fp]),
     "xrt_multi_reset_poses": (ctypes.c_int, [_MultiP]),
     "xrt_host_mt_check": (None, [_fp, _fp, _fp, _fp, _u64, ctypes.POINTER(ctypes.c_uint8),

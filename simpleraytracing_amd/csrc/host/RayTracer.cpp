@@ -433,6 +433,16 @@ void applyLogProjection(Image& image, float flat_value, float t_min)
           "xrt_log_projection");
 }
 
+void applyPhotonNoise(Image& image, float gain, unsigned long long seed, unsigned long long first_index)
+{
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    check(ctx, xrt_photon_noise(ctx, image.getWidth(), image.getHeight(), 1, image.getData(), gain, seed, first_index,
+                                XRT_NOISE_INTENSITY, image.getData()),
+          "xrt_photon_noise");
+}
+
 void logProjectionSinograms(const std::vector<float>& stack, unsigned width, unsigned height, unsigned num_projections,
                             float flat_value, float t_min, std::vector<float>& sinograms)
 {

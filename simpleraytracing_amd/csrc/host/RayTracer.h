@@ -144,6 +144,13 @@ void applyDetectorResponse(Image& output_image, const std::vector<float>& lsf_x,
 // models here); a transmission below t_min > 0 is raised to it.  One device.
 void applyLogProjection(Image& output_image, float flat_value, float t_min = 0.0f);
 
+// Photon noise (xrt_photon_noise, XRT_NOISE_INTENSITY): every pixel of
+// output_image becomes a Poisson count of mean pixel * gain, divided by gain
+// again, in place; gain finite and > 0.  The noise is a function of seed and
+// first_index + the pixel's index alone: projection p of a scan of W x H
+// images passes first_index = p * W * H.  One device.
+void applyPhotonNoise(Image& output_image, float gain, unsigned long long seed, unsigned long long first_index = 0);
+
 // The same over a scan: `stack` holds num_projections width x height intensity
 // images one after another; `sinograms` receives the line integrals in
 // XRT_ORDER_SINOGRAMS, (height, num_projections, width).  One call, one device.

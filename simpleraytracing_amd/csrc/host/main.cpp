@@ -56,6 +56,15 @@
 //       --sinogram FILE        with --turntable N and --log-projection: also write the N
 //                              projections' line integrals as one sinogram per detector
 //                              row, raw little-endian f32 in (height, N, width) order
+//       --noise GAIN[:SEED]    photon noise: every pixel of the image that NAME.EXT
+//                              receives becomes a Poisson count of mean I * GAIN (GAIN
+//                              photons per unit of image value, finite and > 0), divided
+//                              by GAIN again; after --lsf and before --log-projection
+//                              (and --sinogram).  SEED (unsigned, 64 bits) defaults to
+//                              0; projection p of --turntable draws the noise of pixels
+//                              p*W*H onwards, as one call over the stacked scan would.
+//                              Refused where --lsf is.  --u8, --lbuffer, NAME.m<m> and
+//                              NAME.open stay as rendered
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -106,6 +115,7 @@ void showUsage(const std::string& prog)
               << "\t--lsf-gaussian SIGMA[:TAPS]\tThe same with a normalised Gaussian of SIGMA pixels (TAPS odd, default 2*ceil(4*SIGMA)+1, at most 129)\n"
               << "\t--log-projection I0\t\tLine integrals: write -ln(I / I0) (I0 finite and > 0; after --lsf) instead of the intensity I; --u8 and --lbuffer stay as rendered\n"
               << "\t--sinogram FILE\t\t\tWith --turntable N and --log-projection: also write the line integrals as raw float32 sinograms, (height, N, width)\n"
+              << "\t--noise GAIN[:SEED]\t\tPhoton noise on the written image: each pixel a Poisson count of mean I * GAIN, divided by GAIN (after --lsf, before --log-projection; SEED defaults to 0); --u8 and --lbuffer stay as rendered\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -139,6 +149,9 @@ struct Options {
     bool log_projection = false;               // --log-projection I0
     float flat_value = 0.0f;                   // I0
     std::string sinogram;                      // --sinogram FILE
+    bool noise = false;                        // --noise GAIN[:SEED]
+    float noise_gain = 0.0f;
+    unsigned long long noise_seed = 0;
 };
 
 // A whole, non-negative decimal number.
@@ -340,6 +353,33 @@ void parse_lsf_gaussian(const std::string& arg, std::vector<float>& lsf_x, std::
     lsf_y = lsf_x;
 }
 
+// --noise GAIN[:SEED]
+void parse_noise(const std::string& arg, Options& o)
+{
+    const std::vector<std::string> parts = split(arg, ':');
+    size_t used = 0;
+    try {
+        o.noise_gain = std::stof(parts[0], &used);
+    } catch (const std::exception&) {
+        used = 0;
+    }
+    if (parts.size() > 2 || parts[0].empty() || used != parts[0].size() || !std::isfinite(o.noise_gain) || !(o.noise_gain > 0.0f))
+        throw std::runtime_error("--noise GAIN[:SEED]: GAIN is a finite number of photons per unit of image value, above 0");
+    o.noise_seed = 0;
+    if (parts.size() == 2) {
+        const std::string& s = parts[1];
+        used = 0;
+        try {
+            if (!s.empty() && std::isdigit((unsigned char)s[0])) o.noise_seed = std::stoull(s, &used, 10);
+        } catch (const std::exception&) {
+            used = 0;
+        }
+        if (s.empty() || used != s.size())
+            throw std::runtime_error("--noise GAIN[:SEED]: '" + s + "' is not a seed (an unsigned 64-bit integer, decimal)");
+    }
+    o.noise = true;
+}
+
 Options processCmd(int argc, char** argv)
 {
     Options o;
@@ -412,6 +452,8 @@ Options processCmd(int argc, char** argv)
             o.log_projection = true;
         } else if (a == "--sinogram") {
             o.sinogram = parse_str(argv[0], argc, argv, i);
+        } else if (a == "--noise") {
+            parse_noise(parse_str(argv[0], argc, argv, i), o);
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -459,6 +501,10 @@ Options processCmd(int argc, char** argv)
         throw std::runtime_error("--log-projection needs whole frames on one GPU: not with -g N or --rows");
     if (o.log_projection && o.paths && !o.spectrum)
         throw std::runtime_error("--log-projection with --paths needs --spectrum: the planes stay as rendered, there is no image");
+    if (o.noise && (o.gpus > 1 || o.rows))
+        throw std::runtime_error("--noise needs whole frames on one GPU: not with -g N or --rows");
+    if (o.noise && o.paths && !o.spectrum)
+        throw std::runtime_error("--noise with --paths needs --spectrum: the planes stay as rendered, there is no image");
     if (o.signed_model && !o.materials.empty())
         throw std::runtime_error("--signed and --materials are two models: give one");
     if (o.spectrum && (o.signed_model || !o.materials.empty()))
@@ -612,13 +658,16 @@ int main(int argc, char** argv)
                 out = &strip;
             }
             if (opt.paths && !opt.spectrum) return 0;
-            if (opt.log_projection) {                 // (whole frames: out is the image)
-                // the 8-bit image is the intensity's (the 0..80 window means nothing for line integrals)
+            if (opt.log_projection || opt.noise) {    // (whole frames: out is the image)
+                // the 8-bit image is the rendered intensity's (the 0..80 window means nothing for line integrals)
                 if (!opt.u8.empty()) image.savePGMFile(opt.u8, 0.0f, 80.0f);
-                if (!opt.sinogram.empty()) scan.insert(scan.end(), image.getData(), image.getData() + (size_t)opt.width * opt.height);
-                Image integrals(image);
-                applyLogProjection(integrals, opt.flat_value);
-                integrals.saveTextFile(opt.output);
+                Image written(image);
+                if (opt.noise)                        // a scan's projection draws what it would draw in the stack
+                    applyPhotonNoise(written, opt.noise_gain, opt.noise_seed,
+                                     (unsigned long long)projection * opt.width * opt.height);
+                if (!opt.sinogram.empty()) scan.insert(scan.end(), written.getData(), written.getData() + (size_t)opt.width * opt.height);
+                if (opt.log_projection) applyLogProjection(written, opt.flat_value);
+                written.saveTextFile(opt.output);
             } else {
                 out->saveTextFile(opt.output);
                 if (!opt.u8.empty()) out->savePGMFile(opt.u8, 0.0f, 80.0f);

@@ -826,6 +826,118 @@ __host__ __device__ __forceinline__ float xrt_logf(float x)
     return xrt_logf_regular(ix - (23u << 23));
 }
 
+// ---------------------------------------------------------------------------
+// Photon noise (the contract is include/xrt.h's): a counter-based
+// generator and a Poisson sampler whose every step is a rounded f64 or f32
+// operation, sqrt and / IEEE-correct, nothing fused (this file's fp
+// contract(off)) -- so that a numpy restatement is the exact reference
+// (tests/noise_ref.py) and host and device agree bit for bit.
+// ---------------------------------------------------------------------------
+
+// Philox4x32-10 (Salmon et al., Random123): ten rounds over the counter
+// c[0..3] under the key (k0, k1), the key bumped between rounds.
+__host__ __device__ __forceinline__ void xrt_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                                           uint32_t k0, uint32_t k1, uint32_t (&w)[4])
+{
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
+}
+
+// The four words of the pixels with global indices 4 j .. 4 j + 3 under `seed`.
+__host__ __device__ __forceinline__ void xrt_noise_words(uint64_t j, uint64_t seed, uint32_t (&w)[4])
+{
+    xrt_philox4x32_10((uint32_t)j, (uint32_t)(j >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+}
+
+// u = (w + 0.5) 2^-32: exact in f64, never 0 or 1.
+__host__ __device__ __forceinline__ double xrt_uniform_from_word(uint32_t w) { return ((double)w + 0.5) * 0x1p-32; }
+
+// The standard normal deviate at u(w): Wichura's AS241, PPND7.  Its third
+// branch (sqrt(-ln t) > 5) is unreachable -- the smallest t is 2^-33 and
+// sqrt(-ln 2^-33) < 4.79 -- and is left out; t lies in [2^-33, 0.075], so
+// xrt_logf's main path is the whole of it.
+__host__ __device__ __forceinline__ double xrt_normal_from_word(uint32_t w)
+{
+    const double u = xrt_uniform_from_word(w);
+    const double q = u - 0.5;
+    if (__builtin_fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        const double num = ((59.109374720 * r + 159.29113202) * r + 50.434271938) * r + 3.3871327179;
+        const double den = ((67.187563600 * r + 78.757757664) * r + 17.895169469) * r + 1.0;
+        return (q * num) / den;
+    }
+    const double t = q < 0.0 ? u : 1.0 - u;
+    const float tf = (float)t;
+    uint32_t it;
+    __builtin_memcpy(&it, &tf, 4);
+    const double r = ::sqrt(-(double)xrt_logf_regular(it)) - 1.6;
+    const double num = ((0.17023821103 * r + 1.3067284816) * r + 2.7568153900) * r + 1.4234372777;
+    const double den = (0.12021132975 * r + 0.73700164250) * r + 1.0;
+    const double z = num / den;
+    return q < 0.0 ? -z : z;
+}
+
+constexpr double kNoiseSmallMean = 64.0;
+constexpr uint32_t kNoiseSearchCap = 255;
+
+// lam < 64 (and not below 0): inversion by sequential search from exp(-lam).
+__host__ __device__ __forceinline__ double xrt_poisson_search(double lam, double u)
+{
+    double p = xrt_exp(-lam), s = p;
+    uint32_t N = 0;
+    while (u > s && N < kNoiseSearchCap) {
+        N += 1;
+        p = (p * lam) / (double)N;
+        s = s + p;
+    }
+    return (double)N;
+}
+
+// lam >= 64 and finite: the normal deviate with the second-order
+// Cornish-Fisher term, rounded to the nearest count.
+__host__ __device__ __forceinline__ double xrt_poisson_normal(double lam, uint32_t w)
+{
+    const double z = xrt_normal_from_word(w);
+    const double x = lam + ::sqrt(lam) * z + (z * z - 1.0) / 6.0;
+    const double v = __builtin_floor(x + 0.5);
+    return v > 0.0 ? v : 0.0;
+}
+
+// The count N of one pixel, as f64: NaN for a NaN or negative mean (-0.0 is
+// not negative), +inf for +inf.
+__host__ __device__ __forceinline__ double xrt_poisson_from_word(double lam, uint32_t w)
+{
+    if (!(lam >= 0.0)) return __builtin_nan("");
+    if (lam < kNoiseSmallMean) return xrt_poisson_search(lam, xrt_uniform_from_word(w));
+    if (lam == __builtin_inf()) return lam;
+    return xrt_poisson_normal(lam, w);
+}
+
+// One pixel's output from its count: XRT_NOISE_COUNTS or XRT_NOISE_INTENSITY.
+__host__ __device__ __forceinline__ float xrt_noise_output(double N, float gain, bool counts)
+{
+    const float c = (float)N;
+    return counts ? c : c / gain;
+}
+
+// The lanes of k_photon_noise: the Philox counters that n pixels from
+// first_index on touch (n >= 1, first_index + n <= 2^64 - 1: the host's check).
+__host__ __device__ constexpr uint64_t photon_noise_lanes(uint64_t first_index, uint64_t n)
+{
+    return ((first_index + (n - 1u)) >> 2) - (first_index >> 2) + 1u;
+}
+constexpr uint32_t kNoiseThreads = 256;
+
 // NaN path lengths.  The only NaN the reference's pair sum can produce is
 // inf - inf (two t = +inf "hits", which Ray.cxx records when 1/det overflows,
 // DESIGN.md "Tile cull" step 0); x86 SSE returns its default NaN for it

@@ -3968,4 +3968,103 @@ __global__ __launch_bounds__(kProjThreads) void k_log_projection(const float* im
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_photon_noise: photon noise, pointwise over a flat buffer of
+// n pixels, pixel i of global index g = first_index + i.  A lane owns one
+// Philox counter j = (first_index >> 2) + its number, so one Philox evaluation
+// serves the four pixels 4 j - first_index + 0..3, those of them that lie in
+// [0, n).  A whole group whose addresses in image and outp are both 16-byte
+// aligned moves as dwordx4; a ragged end, or a group of a misaligned buffer,
+// pixel by pixel -- every load before the arithmetic.  A pixel outside the
+// buffer takes the mean +inf, which costs nothing.  The lane's means of 64 and
+// above go through the normal branch one after another; those below 64 -- a
+// lane enters only if it has one -- through ONE search loop that steps all of
+// them together: step k divides by the same (double)k for each, a pixel drops
+// out where the contract's loop ends, and the loop runs as long as the slowest
+// pixel of the wave, not the sum over four.  In place (outp == image) a lane
+// reads its group before it writes it and no other lane touches it.  Indices
+// are 64-bit.  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kNoiseThreads) void k_photon_noise(const float* image, float* outp, uint64_t n, float gain,
+                                                                uint64_t seed, uint64_t first_index, uint32_t counts)
+{
+    const uint64_t lane = (uint64_t)blockIdx.x * kNoiseThreads + threadIdx.x;
+    // the group's first pixel, 4 j - first_index (below 0: the ragged head); n is far below 2^62 (the host's check)
+    const int64_t i0 = (int64_t)(4u * lane) - (int64_t)(first_index & 3u);
+    const int64_t end = (int64_t)n;
+    if (i0 >= end) return;
+    const uint64_t j = (first_index >> 2) + lane;
+
+    const uintptr_t at = (uintptr_t)i0 * sizeof(float);                 // (modulo 2^64: only its low bits are read)
+    const bool whole = i0 >= 0 && i0 + 4 <= end &&
+                       (((reinterpret_cast<uintptr_t>(image) + at) | (reinterpret_cast<uintptr_t>(outp) + at)) & 15u) == 0u;
+    float v[4];
+    if (whole) {
+        const float4 v4 = *reinterpret_cast<const float4*>(image + i0);
+        v[0] = v4.x, v[1] = v4.y, v[2] = v4.z, v[3] = v4.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (i0 + e >= 0 && i0 + e < end) ? image[i0 + e] : __builtin_inff();
+    }
+
+    uint32_t w[4];
+    xrt_noise_words(j, seed, w);
+    double lam[4], N[4];
+    bool small[4], any_small = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float lam_f = v[e] * gain;
+        lam[e] = (double)lam_f;
+        small[e] = lam[e] >= 0.0 && lam[e] < kNoiseSmallMean;
+        any_small |= small[e];
+        N[e] = lam[e] >= 0.0 ? lam[e] : __builtin_nan("");          // +inf stays; a finite mean's is set below
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (lam[e] >= kNoiseSmallMean && lam[e] != __builtin_inf()) N[e] = xrt_poisson_normal(lam[e], w[e]);
+    if (any_small) {
+        double u[4], p[4], s[4];
+        bool live[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            u[e] = xrt_uniform_from_word(w[e]);
+            p[e] = s[e] = xrt_exp(small[e] ? -lam[e] : 0.0);
+            live[e] = small[e] && u[e] > s[e];
+            if (small[e]) N[e] = 0.0;
+        }
+        for (uint32_t k = 1; (live[0] | live[1] | live[2] | live[3]) && k <= kNoiseSearchCap; ++k) {
+            const double kd = (double)k;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (!live[e]) continue;
+                p[e] = (p[e] * lam[e]) / kd;
+                s[e] = s[e] + p[e];
+                N[e] = kd;
+                live[e] = u[e] > s[e];
+            }
+        }
+    }
+
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = xrt_noise_output(N[e], gain, counts != 0u);
+    if (whole) {
+        *reinterpret_cast<float4*>(outp + i0) = make_float4(o[0], o[1], o[2], o[3]);
+        return;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (i0 + e >= 0 && i0 + e < end) outp[i0 + e] = o[e];
+}
+
+// The device probe of the sampler (xrt_debug_poisson_batch): xrt_poisson_from_word
+// over caller-chosen means and words, one thread a pair.
+__global__ void k_probe_poisson(const double* __restrict__ lam, const uint32_t* __restrict__ words, uint64_t n,
+                                double* __restrict__ outp)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    outp[i] = xrt_poisson_from_word(lam[i], words[i]);
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -2911,6 +2911,67 @@ int xrt_log_projection(xrt_context* ctx, uint32_t width, uint32_t height, uint32
     return s.finish();
 }
 
+// --- photon noise ----------------------------------------------
+
+#include "xrt_noise_host.inc"
+
+// The launch of k_photon_noise (validated arguments, device pointers).
+static int launch_photon_noise(xrt_context* ctx, uint64_t n, const float* d_image, float gain, uint64_t seed,
+                               uint64_t first_index, int mode, float* d_out, hipStream_t stream)
+{
+    const uint64_t blocks = (photon_noise_lanes(first_index, n) + kNoiseThreads - 1u) / kNoiseThreads;
+    hipLaunchKernelGGL(k_photon_noise, dim3((unsigned)blocks), dim3(kNoiseThreads), 0, stream, d_image, d_out, n, gain, seed,
+                       first_index, (uint32_t)(mode == XRT_NOISE_COUNTS));
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_photon_noise_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_image,
+                            float gain, uint64_t seed, uint64_t first_index, int mode, float* d_out, void* stream)
+{
+    uint64_t n = 0;
+    if (const char* why = noise_arguments(width, height, num_planes, d_image, gain, first_index, mode, d_out, &n))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_photon_noise(ctx, n, d_image, gain, seed, first_index, mode, d_out, (hipStream_t)stream);
+}
+
+int xrt_photon_noise(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* image,
+                     float gain, uint64_t seed, uint64_t first_index, int mode, float* out)
+{
+    uint64_t n = 0;
+    if (const char* why = noise_arguments(width, height, num_planes, image, gain, first_index, mode, out, &n))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceScratch s(ctx, ctx->host_stream, "photon noise");
+    float* d = s.upload(image, (size_t)n);              // in place on the device: the pass is pointwise
+    if (s.rc()) return s.rc();
+    if (int rc = launch_photon_noise(ctx, n, d, gain, seed, first_index, mode, d, ctx->host_stream)) return rc;
+    s.download(out, d, (size_t)n);
+    return s.finish();
+}
+
+// The sampler on the device over caller-chosen means and words (a test hook).
+int xrt_debug_poisson_batch(xrt_context* ctx, const double* lam, const uint32_t* words, uint64_t n, double* outp)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (n == 0) return XRT_OK;
+    if (!lam || !words || !outp) return fail(ctx, XRT_ERR_ARGUMENT, "NULL buffer");
+    if (n > 0x7FFFFFFFull * 256u) return fail(ctx, XRT_ERR_ARGUMENT, "too many values");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceScratch s(ctx, nullptr, "probe");
+    const double* dl = s.upload(lam, n);
+    const uint32_t* dw = s.upload(words, n);
+    double* dout = s.alloc<double>(n);
+    if (s.rc()) return s.rc();
+    hipLaunchKernelGGL(k_probe_poisson, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dl, dw, n, dout);
+    s.launched();
+    s.download(outp, dout, n);
+    return s.finish();
+}
+
 // Render of the L-buffer plane and the fork's hole fill over it, into host buffers.
 static int render_and_fill(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
                            uint8_t* image_u8, xrt_stats* stats)
