@@ -610,6 +610,83 @@ int xrt_photon_noise(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t
 int xrt_photon_noise_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_image,
                             float gain, uint64_t seed, uint64_t first_index, int mode, float* d_out, void* stream);
 
+/* --- area sampling: a finite focal spot and pixel-area integration -------- */
+
+/*
+ * The weighted mean of intensity over the source's area and over each pixel's
+ * area, on the device: the reduction that turns the
+ * renders of num_sources sub-sources at (height bin_y) x (width bin_x) pixels
+ * into one height x width image.  `image` is num_planes * num_sources row-major
+ * f32 planes of (height bin_y) x (width bin_x), one after another; plane
+ * p S + s (S = num_sources) is projection p seen from sub-source s.  `out` and
+ * `out_u8` are num_planes planes of height x width; either may be NULL, not
+ * both.  `weight` is num_sources f32 in HOST memory in both forms.  Per output
+ * pixel (p, y, x):
+ *   acc = -0.0                                                        (f64)
+ *   for s in 0..S-1, dy in 0..bin_y-1, dx in 0..bin_x-1, in this order:
+ *     acc = acc + (double)weight[s] * (double)image[p S + s][y bin_y + dy][x bin_x + dx]
+ *   wsum = (double)(bin_x bin_y) * (sum over s of (double)weight[s], f64, in index order)
+ *   out    = (float)(acc / wsum)                          (an IEEE f64 division)
+ *   out_u8 = round(255 * out / 80) clamped, NaN -> 0     (as xrt_detector_response's)
+ * The product of two f32 values is exact in f64, so a fused multiply-add and
+ * the separate operations round identically.  The accumulator starts at -0.0:
+ * bin 1 x 1 with one source of weight 1 returns the input's bits, -0.0 and
+ * denormals included.  With every weight 1.0 a constant plane returns its value
+ * exactly.  Non-finite values propagate as IEEE has it; a NaN's sign and
+ * payload are unspecified.
+ *
+ * XRT_ERR_ARGUMENT, with xrt_last_error naming the argument, for a NULL image
+ * or weight; out and out_u8 both NULL; a width, height or num_planes of 0;
+ * bin_x or bin_y outside 1..XRT_MAX_BIN; num_sources outside
+ * 1..XRT_MAX_SOURCES; a weight that is NaN, infinite or negative, or a weight
+ * sum of 0; width bin_x or height bin_y above 2^31 - 1; num_planes * height
+ * above 2^32 - 1 or more than one launch's 2^31 - 1 workgroups (256 lanes of at
+ * most four outputs each); an output that overlaps the image anywhere (nothing
+ * is computed in place: the output is smaller and rows move).  All of that is checked
+ * before the context is looked at.  xrt_area_integrate: host buffers,
+ * synchronous.  _device: device buffers, asynchronous on `stream`; the weights
+ * travel with the launch, so the next call may bring others at once.  Neither
+ * touches the context's model, scene or frames in flight.  There is no
+ * xrt_multi_ form: apply it to the gathered frame.
+ */
+#define XRT_MAX_SOURCES 64
+#define XRT_MAX_BIN 8
+int xrt_area_integrate(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t bin_x, uint32_t bin_y,
+                       uint32_t num_sources, uint32_t num_planes, const float* weight, const float* image, float* out,
+                       uint8_t* out_u8);
+int xrt_area_integrate_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t bin_x, uint32_t bin_y,
+                              uint32_t num_sources, uint32_t num_planes, const float* weight, const float* d_image,
+                              float* d_out, uint8_t* d_out_u8, void* stream);
+
+/*
+ * The cameras that area sampling renders.  Host arithmetic, no device; every
+ * operation below is a separately rounded f32 operation unless written as f64.
+ *
+ * xrt_camera_supersample: the camera whose pixels tile `cam`'s, bin x bin to
+ * each: width * bin, height * bin, pixel_spacing / (float)bin (one IEEE f32
+ * division), everything else copied (out may be cam).  Its pixel centres,
+ * spacing/bin * (0.5 + c' - W bin / 2), tile cam's pixels exactly.  For bin a
+ * power of two the spacing equals what renderLoop's prologue computes for the
+ * larger image, 2 * max(range / (W bin)); for other factors it may differ from
+ * that by an ulp.  XRT_ERR_ARGUMENT for a NULL pointer, bin outside
+ * 1..XRT_MAX_BIN or a product above 2^31 - 1.
+ *
+ * xrt_focal_spot: a uniform rectangular focal spot of size_u x size_v (the
+ * scene's length unit, along `right` and `up`), sampled at the centres of an
+ * nu x nv grid.  Sub-source s = j nu + i, i < nu, j < nv, is cam with
+ *   a = (float)((double)size_u * (((double)i + 0.5) / (double)nu - 0.5))
+ *   b = (float)((double)size_v * (((double)j + 0.5) / (double)nv - 0.5))
+ *   origin'[k] = (origin[k] + right[k] * a) + up[k] * b
+ * and weight[s] = 1.0f; detector, up, right, spacing and size are unchanged (the
+ * detector does not move).  A size of 0 with a count of 1 is the point source
+ * on that axis.  Other profiles are the caller's own offsets and weights.
+ * XRT_ERR_ARGUMENT for a NULL pointer, a size that is negative or not finite, a
+ * count of 0 or nu * nv above XRT_MAX_SOURCES.
+ */
+int xrt_camera_supersample(const xrt_camera* cam, uint32_t bin, xrt_camera* out);
+int xrt_focal_spot(const xrt_camera* cam, float size_u, float size_v, uint32_t nu, uint32_t nv, xrt_camera* cams,
+                   float* weight);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

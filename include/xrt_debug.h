@@ -284,6 +284,14 @@ int xrt_host_photon_noise(uint32_t width, uint32_t height, uint32_t num_planes, 
 int xrt_debug_poisson_batch(xrt_context* ctx, const double* lam, const uint32_t* words, uint64_t n, double* out);
 
 /*
+ * Test hook of the area sampling.  Host code, no device: xrt_area_integrate's
+ * pixel function -- the one k_area_integrate calls -- over whole buffers,
+ * arguments and checks as xrt_area_integrate's, host buffers.
+ */
+int xrt_host_area_integrate(uint32_t width, uint32_t height, uint32_t bin_x, uint32_t bin_y, uint32_t num_sources,
+                            uint32_t num_planes, const float* weight, const float* image, float* out, uint8_t* out_u8);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_MAX_SOURCES, XRT_MAX_BIN, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -33,6 +33,7 @@ __all__ = [
     "XRT_MAX_LSF_TAPS", "lsf_gaussian", "host_lsf", "detector_response",
     "XRT_ORDER_PROJECTIONS", "XRT_ORDER_SINOGRAMS", "host_logf", "host_log_projection", "log_projection",
     "XRT_NOISE_INTENSITY", "XRT_NOISE_COUNTS", "host_philox4x32", "host_poisson", "host_photon_noise", "photon_noise",
+    "XRT_MAX_SOURCES", "XRT_MAX_BIN", "supersampled_camera", "focal_spot", "host_area_integrate", "area_integrate",
 ]
 
 
@@ -339,6 +340,77 @@ def photon_noise(image, gain, seed, counts=False, first_index=0, device: int = 0
         return ctx.photon_noise(image, gain, seed, counts, first_index)
 
 
+def supersampled_camera(cam: Camera, bin: int) -> Camera:
+    """The camera whose pixels tile `cam`'s, bin x bin to each (xrt_camera_supersample)."""
+    out = Camera()
+    rc = _abi.load().xrt_camera_supersample(ctypes.byref(cam), int(bin), ctypes.byref(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_camera_supersample: bin must be in 1..XRT_MAX_BIN and the size stay below 2^31")
+    return out
+
+
+def focal_spot(cam: Camera, size_u: float, size_v: float, nu: int, nv: int):
+    """A uniform rectangular focal spot of size_u x size_v along `right` and `up`, sampled at the centres of an
+    nu x nv grid (xrt_focal_spot): (the nu * nv sub-source cameras, their weights)."""
+    n = max(int(nu) * int(nv), 1)
+    cams = (Camera * n)()
+    weights = np.empty(n, np.float32)
+    rc = _abi.load().xrt_focal_spot(ctypes.byref(cam), float(size_u), float(size_v), int(nu), int(nv), cams, _fptr(weights))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_focal_spot: sizes must be finite and >= 0, counts > 0 and nu * nv <= XRT_MAX_SOURCES")
+    out = []
+    for c in cams:                                          # copies that do not live in the ctypes array
+        one = Camera()
+        ctypes.memmove(ctypes.byref(one), ctypes.byref(c), ctypes.sizeof(Camera))
+        out.append(one)
+    return out, weights
+
+
+def _area_bins(bin):
+    """`bin` as (bin_y, bin_x): an int for both, or the pair."""
+    if isinstance(bin, (tuple, list)):
+        by, bx = bin
+        return int(by), int(bx)
+    return int(bin), int(bin)
+
+
+def _area_arrays(image, bin, weights):
+    """xrt_area_integrate's arguments from an (Hb, Wb), (S, Hb, Wb) or (P, S, Hb, Wb) image: the array, the weights,
+    P, S, H, W, bin_y, bin_x and the output's shape."""
+    a = np.ascontiguousarray(image, dtype=np.float32)
+    if a.ndim not in (2, 3, 4):
+        raise ValueError(f"an image is (Hb, Wb), (S, Hb, Wb) or (P, S, Hb, Wb), got shape {a.shape}")
+    by, bx = _area_bins(bin)
+    p = a.shape[0] if a.ndim == 4 else 1
+    s = a.shape[-3] if a.ndim >= 3 else 1
+    hb, wb = a.shape[-2], a.shape[-1]
+    if by < 1 or bx < 1 or hb % by or wb % bx:
+        raise ValueError(f"the planes' size ({hb}, {wb}) is no multiple of the bin ({by}, {bx})")
+    w = np.ones(s, np.float32) if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if w.size != s:
+        raise ValueError(f"{s} sub-sources need {s} weights, got {w.size}")
+    h, wd = hb // by, wb // bx
+    return a, w, p, s, h, wd, by, bx, ((p, h, wd) if a.ndim == 4 else (h, wd))
+
+
+def host_area_integrate(image, bin=1, weights=None, u8=False):
+    """Context.area_integrate in the device's arithmetic on the host (xrt_host_area_integrate, a test hook)."""
+    a, w, p, s, h, wd, by, bx, shape = _area_arrays(image, bin, weights)
+    out = np.empty(shape, np.float32)
+    u = np.empty(shape, np.uint8) if u8 else None
+    rc = _abi.load().xrt_host_area_integrate(wd, h, bx, by, s, p, _fptr(w), _fptr(a), _fptr(out),
+                                             _u8ptr(u) if u is not None else None)
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_area_integrate")
+    return (out, u) if u8 else out
+
+
+def area_integrate(image, bin=1, weights=None, u8=False, device: int = 0):
+    """The integrated image(s) of Context.area_integrate, on a context of its own on `device`."""
+    with Context(device) as ctx:
+        return ctx.area_integrate(image, bin, weights, u8)
+
+
 class Context:
     """One xrt_context (one device).  Not thread-safe."""
 
@@ -600,6 +672,52 @@ class Context:
         self._check(self._lib.xrt_debug_poisson_batch(self._ctx, _dptr(lam), _u32ptr(words), lam.size, _dptr(out)),
                     "xrt_debug_poisson_batch")
         return out
+
+    def area_integrate(self, image, bin=1, weights=None, u8=False):
+        """Area sampling: the weighted mean over S sub-sources and over each pixel's bin_y x bin_x block of finer
+        samples, in f64, rounded once.  `image` is (Hb, Wb), (S, Hb, Wb) or (P, S, Hb, Wb); `bin` an int or
+        (bin_y, bin_x); `weights` S values, ones by default.  The (H, W) or (P, H, W) image -- with u8=True
+        (image, u8)."""
+        a, w, p, s, h, wd, by, bx, shape = _area_arrays(image, bin, weights)
+        out = np.empty(shape, np.float32)
+        u = np.empty(shape, np.uint8) if u8 else None
+        self._check(self._lib.xrt_area_integrate(self._ctx, wd, h, bx, by, s, p, _fptr(w), _fptr(a), _fptr(out),
+                                                 _u8ptr(u) if u is not None else None), "xrt_area_integrate")
+        return (out, u) if u8 else out
+
+    def area_integrate_device(self, width: int, height: int, num_planes: int, d_image: int, d_out: int, d_out_u8: int = 0,
+                              bin=1, weights=None, num_sources: int | None = None, stream: int = 0):
+        """area_integrate over device buffers (raw pointers; width and height are the OUTPUT's; the weights are host
+        values that travel with the launch); asynchronous on `stream`."""
+        by, bx = _area_bins(bin)
+        if weights is None:
+            weights = np.ones(1 if num_sources is None else int(num_sources), np.float32)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        s = w.size if num_sources is None else int(num_sources)
+        if w.size != s:
+            raise ValueError(f"{s} sub-sources need {s} weights, got {w.size}")
+        rc = self._lib.xrt_area_integrate_device(self._ctx, int(width), int(height), bx, by, s, int(num_planes), _fptr(w),
+                                                 d_image or None, d_out or None, d_out_u8 or None, stream or None)
+        self._check(rc, "xrt_area_integrate_device")
+
+    def render_area(self, cam: Camera, bin: int = 1, spot=None):
+        """The attenuation model's image of `cam` under area sampling: every pixel the mean of bin x bin samples of
+        its area, seen from each sub-source of the focal spot `spot` = (size_u, size_v, nu, nv) (None: the point
+        source).  The sub-cameras' renders stay in one device buffer and are integrated there.  (H, W) f32."""
+        import torch
+        cams, weights = focal_spot(cam, *spot) if spot is not None else ([cam], np.ones(1, np.float32))
+        fine = [supersampled_camera(c, bin) for c in cams]
+        hb, wb = fine[0].height, fine[0].width
+        dev = torch.device("cuda", self.device)
+        samples = torch.empty((len(fine), hb, wb), dtype=torch.float32, device=dev)
+        out = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        for k, c in enumerate(fine):
+            self.render_rows_device(c, 0, hb, samples[k].data_ptr(), 0, 0)
+        self.area_integrate_device(cam.width, cam.height, 1, samples.data_ptr(), out.data_ptr(), 0, int(bin), weights)
+        self.read_stats()                                   # (synchronises the renders' stream)
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy()
 
     def render_signed(self, cam: Camera):
         """The L-buffer fork end to end: (image f32, lbuffer f32 with -1 flags, u8, Stats)."""

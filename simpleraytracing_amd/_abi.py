@@ -46,6 +46,8 @@ XRT_ORDER_PROJECTIONS = 0
 XRT_ORDER_SINOGRAMS = 1
 XRT_NOISE_INTENSITY = 0
 XRT_NOISE_COUNTS = 1
+XRT_MAX_SOURCES = 64
+XRT_MAX_BIN = 8
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -195,6 +197,14 @@ XRT_SYMBOLS = {
     "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
     "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),
     "xrt_debug_poisson_batch": (ctypes.c_int, [_CtxP, _dp, _u32p, _u64, _dp]),
+    "xrt_area_integrate": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _u32, _u32, _u32, _fp, _fp, _fp,
+                                          ctypes.POINTER(ctypes.c_uint8)]),
+    "xrt_area_integrate_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _u32, _u32, _u32, _fp, _vp, _vp, _vp, _vp]),
+    "xrt_host_area_integrate": (ctypes.c_int, [_u32, _u32, _u32, _u32, _u32, _u32, _fp, _fp, _fp,
+                                               ctypes.POINTER(ctypes.c_uint8)]),
+    "xrt_camera_supersample": (ctypes.c_int, [ctypes.POINTER(Camera), _u32, ctypes.POINTER(Camera)]),
+    "xrt_focal_spot": (ctypes.c_int, [ctypes.POINTER(Camera), ctypes.c_float, ctypes.c_float, _u32, _u32,
+                                      ctypes.POINTER(Camera), _fp]),
     "xrt_multi_set_pose": (ctypes.c_int, [_MultiP, _u32, _fp]),
     "xrt_multi_reset_poses": (ctypes.c_int, [_MultiP]),
     "xrt_host_mt_check": (None, [_fp, _fp, _fp, _fp, _u64, ctypes.POINTER(ctypes.c_uint8),

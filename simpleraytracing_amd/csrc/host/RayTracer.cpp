@@ -443,6 +443,45 @@ void applyPhotonNoise(Image& image, float gain, unsigned long long seed, unsigne
           "xrt_photon_noise");
 }
 
+std::vector<RayTracerInfo> focalSpotSources(const RayTracerInfo& info, float size_u, float size_v, unsigned nu, unsigned nv)
+{
+    xrt_camera cam = {};
+    for (unsigned k = 0; k < 3; ++k) {
+        cam.origin[k] = info.origin[k];
+        cam.detector[k] = info.detector_position[k];
+        cam.up[k] = info.up[k];
+        cam.right[k] = info.right[k];
+    }
+    std::vector<xrt_camera> cams((size_t)nu * nv <= XRT_MAX_SOURCES ? (size_t)nu * nv : 0);
+    std::vector<float> weight(cams.size());
+    if (cams.empty() || xrt_focal_spot(&cam, size_u, size_v, nu, nv, cams.data(), weight.data()) != XRT_OK)
+        throw std::runtime_error("focalSpotSources: the sizes must be finite and >= 0, the counts > 0 and nu * nv at most " +
+                                 std::to_string(XRT_MAX_SOURCES));
+    std::vector<RayTracerInfo> out(cams.size(), info);
+    for (size_t s = 0; s < cams.size(); ++s) out[s].origin = Vec3(cams[s].origin[0], cams[s].origin[1], cams[s].origin[2]);
+    return out;
+}
+
+void applyAreaIntegration(Image& image, const std::vector<Image>& samples, unsigned bin_x, unsigned bin_y,
+                          const std::vector<float>& weights)
+{
+    if (samples.empty() || samples.size() != weights.size())
+        throw std::runtime_error("applyAreaIntegration: one weight per sample image, at least one");
+    const size_t W = image.getWidth(), H = image.getHeight(), fine = W * bin_x * H * bin_y;
+    std::vector<float> stack(fine * samples.size());
+    for (size_t s = 0; s < samples.size(); ++s) {
+        if (samples[s].getWidth() != W * bin_x || samples[s].getHeight() != H * bin_y)
+            throw std::runtime_error("applyAreaIntegration: a sample image is not (width * bin_x) x (height * bin_y)");
+        std::copy(samples[s].getData(), samples[s].getData() + fine, stack.begin() + s * fine);
+    }
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    check(ctx, xrt_area_integrate(ctx, image.getWidth(), image.getHeight(), bin_x, bin_y, (uint32_t)samples.size(), 1,
+                                  weights.data(), stack.data(), image.getData(), nullptr),
+          "xrt_area_integrate");
+}
+
 void logProjectionSinograms(const std::vector<float>& stack, unsigned width, unsigned height, unsigned num_projections,
                             float flat_value, float t_min, std::vector<float>& sinograms)
 {

@@ -157,6 +157,20 @@ void applyPhotonNoise(Image& output_image, float gain, unsigned long long seed, 
 void logProjectionSinograms(const std::vector<float>& stack, unsigned width, unsigned height, unsigned num_projections,
                             float flat_value, float t_min, std::vector<float>& sinograms);
 
+// Area sampling (xrt_area_integrate).  focalSpotSources: the
+// sub-sources of a uniform rectangular focal spot of size_u x size_v (the
+// scene's length unit, along info.right and info.up), at the centres of an
+// nu x nv grid, nu * nv at most XRT_MAX_SOURCES: `info` with origin moved
+// (xrt_focal_spot's arithmetic; the detector does not move), source j * nu + i
+// at grid cell (i, j).  applyAreaIntegration: output_image (W x H, its size is
+// read) becomes the weighted mean over the samples -- any renderLoop* of an
+// Image of (W * bin_x) x (H * bin_y), one per source -- and over each pixel's
+// bin_y x bin_x block of them.  Throws on sizes that do not fit.  One device.
+std::vector<RayTracerInfo> focalSpotSources(const RayTracerInfo& info, float size_u, float size_v, unsigned nu,
+                                            unsigned nv);
+void applyAreaIntegration(Image& output_image, const std::vector<Image>& samples, unsigned bin_x, unsigned bin_y,
+                          const std::vector<float>& weights);
+
 // Row strips over `num_gpus` devices (rows_per = H / n, remainder to the first
 // strips), one host thread per device; returns the number of odd rays.
 unsigned long long renderLoopMultiGPU(Image& output_image, const std::vector<TriangleMesh>& meshes,

@@ -65,6 +65,28 @@
 //                              p*W*H onwards, as one call over the stacked scan would.
 //                              Refused where --lsf is.  --u8, --lbuffer, NAME.m<m> and
 //                              NAME.open stay as rendered
+//       --supersample B        pixel-area integration: every projection is rendered at
+//                              W*B x H*B pixels (B in 1..8; -s W H stays the size of
+//                              what is written) and each written pixel is the mean of
+//                              the B x B samples that tile its area, summed in f64 on
+//                              the device.  B a power of two samples at the centres
+//                              spacing/B apart exactly; for another B the finer frame's
+//                              spacing is renderLoop's own for W*B x H*B, which may
+//                              differ from spacing/B by an ulp
+//       --focal-spot UxV[:NUxNV]  a finite focal spot: a uniform rectangle of U (along the
+//                              detector's "right") by V (along "up") scene units, finite
+//                              and >= 0, sampled at the centres of an NU x NV grid
+//                              (default 3x3, NU*NV <= 64); every projection is rendered
+//                              from each sub-source -- the detector does not move -- and
+//                              the renders are averaged with --supersample's samples.
+//                              With either option every model (default, --signed,
+//                              --materials, --spectrum; the model's hole fill on each
+//                              sample) and every --turntable projection, with --pose;
+//                              NAME.EXT and --u8 receive the integrated image, and --lsf,
+//                              --noise (first_index p*W*H of the written size),
+//                              --log-projection and --sinogram follow in their order.
+//                              Refused with -g N, --rows, --batch, --paths and --lbuffer
+//                              (an integrated frame has no single L-buffer)
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -116,6 +138,8 @@ void showUsage(const std::string& prog)
               << "\t--log-projection I0\t\tLine integrals: write -ln(I / I0) (I0 finite and > 0; after --lsf) instead of the intensity I; --u8 and --lbuffer stay as rendered\n"
               << "\t--sinogram FILE\t\t\tWith --turntable N and --log-projection: also write the line integrals as raw float32 sinograms, (height, N, width)\n"
               << "\t--noise GAIN[:SEED]\t\tPhoton noise on the written image: each pixel a Poisson count of mean I * GAIN, divided by GAIN (after --lsf, before --log-projection; SEED defaults to 0); --u8 and --lbuffer stay as rendered\n"
+              << "\t--supersample B\t\t\tPixel-area integration: render W*B x H*B samples (B in 1..8) and write each pixel's mean over its B x B samples; -s stays the written size\n"
+              << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -152,6 +176,10 @@ struct Options {
     bool noise = false;                        // --noise GAIN[:SEED]
     float noise_gain = 0.0f;
     unsigned long long noise_seed = 0;
+    unsigned supersample = 0;                  // --supersample B (0: not given)
+    bool focal_spot = false;                   // --focal-spot UxV[:NUxNV]
+    float spot_u = 0.0f, spot_v = 0.0f;
+    unsigned spot_nu = 3, spot_nv = 3;
 };
 
 // A whole, non-negative decimal number.
@@ -380,6 +408,36 @@ void parse_noise(const std::string& arg, Options& o)
     o.noise = true;
 }
 
+// --focal-spot UxV[:NUxNV]
+void parse_focal_spot(const std::string& arg, Options& o)
+{
+    const std::vector<std::string> parts = split(arg, ':');
+    const std::vector<std::string> size = split(parts[0], 'x');
+    float v[2] = {0.0f, 0.0f};
+    bool ok = parts.size() <= 2 && size.size() == 2;
+    for (size_t k = 0; ok && k < 2; ++k) {
+        size_t used = 0;
+        try {
+            v[k] = std::stof(size[k], &used);
+        } catch (const std::exception&) {
+            used = 0;
+        }
+        ok = !size[k].empty() && used == size[k].size() && std::isfinite(v[k]) && v[k] >= 0.0f;
+    }
+    if (!ok)
+        throw std::runtime_error("--focal-spot UxV[:NUxNV]: U and V are the spot's sizes in scene units, finite and >= 0");
+    o.spot_u = v[0], o.spot_v = v[1];
+    o.spot_nu = o.spot_nv = 3;
+    if (parts.size() == 2) {
+        const std::vector<std::string> grid = split(parts[1], 'x');
+        if (grid.size() != 2 || !parse_index(grid[0], o.spot_nu) || !parse_index(grid[1], o.spot_nv) || !o.spot_nu ||
+            !o.spot_nv || (unsigned long long)o.spot_nu * o.spot_nv > XRT_MAX_SOURCES)
+            throw std::runtime_error("--focal-spot UxV[:NUxNV]: '" + parts[1] + "' is not a grid of 1 to " +
+                                     std::to_string(XRT_MAX_SOURCES) + " sub-sources");
+    }
+    o.focal_spot = true;
+}
+
 Options processCmd(int argc, char** argv)
 {
     Options o;
@@ -454,6 +512,12 @@ Options processCmd(int argc, char** argv)
             o.sinogram = parse_str(argv[0], argc, argv, i);
         } else if (a == "--noise") {
             parse_noise(parse_str(argv[0], argc, argv, i), o);
+        } else if (a == "--supersample") {
+            const std::string b = parse_str(argv[0], argc, argv, i);
+            if (!parse_index(b, o.supersample) || o.supersample < 1 || o.supersample > XRT_MAX_BIN)
+                throw std::runtime_error("--supersample B: '" + b + "' is not a factor in 1.." + std::to_string(XRT_MAX_BIN));
+        } else if (a == "--focal-spot") {
+            parse_focal_spot(parse_str(argv[0], argc, argv, i), o);
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -505,6 +569,16 @@ Options processCmd(int argc, char** argv)
         throw std::runtime_error("--noise needs whole frames on one GPU: not with -g N or --rows");
     if (o.noise && o.paths && !o.spectrum)
         throw std::runtime_error("--noise with --paths needs --spectrum: the planes stay as rendered, there is no image");
+    if (o.supersample || o.focal_spot) {
+        const std::string which = o.supersample ? "--supersample" : "--focal-spot";
+        if (o.gpus > 1 || o.rows || o.batch || o.paths)
+            throw std::runtime_error(which + " integrates whole frames on one GPU: not with -g N, --rows, --batch or --paths");
+        if (!o.lbuffer.empty())
+            throw std::runtime_error(which + " with --lbuffer: an integrated frame has no single L-buffer");
+        if ((unsigned long long)o.width * std::max(o.supersample, 1u) > 0x7FFFFFFFull ||
+            (unsigned long long)o.height * std::max(o.supersample, 1u) > 0x7FFFFFFFull)
+            throw std::runtime_error(which + ": the supersampled frame is above 2^31 - 1 pixels a side");
+    }
     if (o.signed_model && !o.materials.empty())
         throw std::runtime_error("--signed and --materials are two models: give one");
     if (o.spectrum && (o.signed_model || !o.materials.empty()))
@@ -576,6 +650,41 @@ int main(int argc, char** argv)
             std::vector<float> lb;
             const unsigned rb = opt.rows ? opt.row_begin : 0u, re = opt.rows ? opt.row_end : opt.height;
             double ms_per_frame = 0.0;
+            const bool area = opt.supersample || opt.focal_spot;
+            const unsigned bin = std::max(opt.supersample, 1u);
+            // the model's whole-frame render of `img` (its size) as seen from `inf`
+            const auto render_model = [&](Image& img, RayTracerInfo& inf) {
+                if (!opt.materials.empty()) {
+                    if (opt.materials.size() != meshes.size())
+                        throw std::runtime_error("--materials takes one coefficient per mesh: " + std::to_string(meshes.size()) +
+                                                 " meshes loaded, " + std::to_string(opt.materials.size()) + " coefficients");
+                    std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
+                    if (opt.gpus > 1) renderLoopMaterialsMultiGPU(img, meshes, inf, opt.materials, opt.gpus, l);
+                    else renderLoopMaterials(img, meshes, inf, opt.materials, l);
+                } else if (opt.spectrum) {
+                    const size_t rows = opt.spectrum_mu.size() / opt.spectrum_weight.size();
+                    if (rows != meshes.size())
+                        throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
+                                                 " meshes loaded, " + std::to_string(rows) + " rows");
+                    std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
+                    if (opt.gpus > 1)
+                        renderLoopSpectrumMultiGPU(img, meshes, inf, opt.spectrum_weight, opt.spectrum_mu, opt.gpus, l);
+                    else renderLoopSpectrum(img, meshes, inf, opt.spectrum_weight, opt.spectrum_mu, l);
+                } else if (opt.signed_model && opt.gpus > 1) {
+                    renderLoopLBufferMultiGPU(img, meshes, inf, opt.gpus, opt.lbuffer.empty() ? nullptr : &lb);
+                } else if (opt.signed_model) {
+                    renderLoopLBuffer(img, meshes, inf, opt.lbuffer.empty() ? nullptr : &lb);
+                } else if (opt.gpus > 1) {
+                    renderLoopMultiGPU(img, meshes, inf, opt.gpus);
+                } else if (!opt.lbuffer.empty()) {       // the image and the L-buffer in one render
+                    lb.resize((size_t)img.getWidth() * (re - rb));
+                    xrt_stats st;
+                    renderLoopRows(img, meshes, inf, rb, re, lb.data(), nullptr, &st);
+                    for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
+                } else {
+                    renderLoop(img, meshes, inf);
+                }
+            };
             if (opt.batch) {                          // N frames back to back, the last one kept
                 xrt_stats st;
                 ms_per_frame = renderLoopFrames(image, meshes, info, opt.batch, rb, re, &st);
@@ -605,35 +714,17 @@ int main(int argc, char** argv)
                 plane.saveTextFile(stem + ".open" + suffix);
                 if (opt.spectrum)                     // (without a table the planes are the output)
                     applySpectrum(image, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.lbuffer.empty() ? nullptr : &lb);
-            } else if (!opt.materials.empty()) {
-                if (opt.materials.size() != meshes.size())
-                    throw std::runtime_error("--materials takes one coefficient per mesh: " + std::to_string(meshes.size()) +
-                                             " meshes loaded, " + std::to_string(opt.materials.size()) + " coefficients");
-                std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
-                if (opt.gpus > 1) renderLoopMaterialsMultiGPU(image, meshes, info, opt.materials, opt.gpus, l);
-                else renderLoopMaterials(image, meshes, info, opt.materials, l);
-            } else if (opt.spectrum) {
-                const size_t rows = opt.spectrum_mu.size() / opt.spectrum_weight.size();
-                if (rows != meshes.size())
-                    throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
-                                             " meshes loaded, " + std::to_string(rows) + " rows");
-                std::vector<float>* l = opt.lbuffer.empty() ? nullptr : &lb;
-                if (opt.gpus > 1)
-                    renderLoopSpectrumMultiGPU(image, meshes, info, opt.spectrum_weight, opt.spectrum_mu, opt.gpus, l);
-                else renderLoopSpectrum(image, meshes, info, opt.spectrum_weight, opt.spectrum_mu, l);
-            } else if (opt.signed_model && opt.gpus > 1) {
-                renderLoopLBufferMultiGPU(image, meshes, info, opt.gpus, opt.lbuffer.empty() ? nullptr : &lb);
-            } else if (opt.signed_model) {
-                renderLoopLBuffer(image, meshes, info, opt.lbuffer.empty() ? nullptr : &lb);
-            } else if (opt.gpus > 1) {
-                renderLoopMultiGPU(image, meshes, info, opt.gpus);
-            } else if (!opt.lbuffer.empty()) {       // the image and the L-buffer in one render
-                lb.resize((size_t)opt.width * (re - rb));
-                xrt_stats st;
-                renderLoopRows(image, meshes, info, rb, re, lb.data(), nullptr, &st);
-                for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
+            } else if (area) {                        // every sub-source at the finer size, then one integration
+                std::vector<RayTracerInfo> sources(1, info);
+                if (opt.focal_spot) sources = focalSpotSources(info, opt.spot_u, opt.spot_v, opt.spot_nu, opt.spot_nv);
+                std::vector<Image> samples;
+                for (RayTracerInfo& source : sources) {
+                    samples.emplace_back(opt.width * bin, opt.height * bin, lut);
+                    render_model(samples.back(), source);
+                }
+                applyAreaIntegration(image, samples, bin, bin, std::vector<float>(samples.size(), 1.0f));
             } else {
-                renderLoop(image, meshes, info);
+                render_model(image, info);
             }
             auto r1 = std::chrono::high_resolution_clock::now();
             if (opt.time) {

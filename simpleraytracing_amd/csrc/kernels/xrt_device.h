@@ -1191,4 +1191,82 @@ inline LogProjectionPlan log_projection_plan(uint32_t W, uint64_t rows)
     return plan;
 }
 
+// ---------------------------------------------------------------------------
+// Area sampling: one output pixel of xrt_area_integrate, the
+// weighted mean over S sub-sources and a bin_y x bin_x block of the finer
+// plane, summed in f64 in the order (s, dy, dx) from -0.0 and divided once.
+// weight[s] * value is exact in f64 (two f32 factors), so lsf_step's fused and
+// separate forms round identically here too.  The weights travel by value in
+// k_area_integrate's kernel arguments, already widened to f64, with the
+// divisor wsum = bin_x bin_y sum(weight), formed on the host.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMaxAreaSources = 64;
+constexpr uint32_t kMaxAreaBin = 8;
+struct AreaWeights {
+    double w[kMaxAreaSources];
+    double wsum;
+};
+
+inline void area_weights_set(AreaWeights& tab, const float* weight, uint32_t num_sources, uint32_t bin_x, uint32_t bin_y)
+{
+    double sum = 0.0;
+    for (uint32_t s = 0; s < kMaxAreaSources; ++s) {
+        tab.w[s] = s < num_sources ? (double)weight[s] : 0.0;
+        if (s < num_sources) sum = sum + tab.w[s];
+    }
+    tab.wsum = (double)(bin_x * bin_y) * sum;
+}
+
+__host__ __device__ __forceinline__ float area_finish(double acc, double wsum) { return (float)(acc / wsum); }
+
+// `v(s, dy, dx)` is the sample of sub-source s at the block's row dy and column dx.
+template <typename Value>
+__host__ __device__ __forceinline__ float area_pixel(const AreaWeights& tab, uint32_t num_sources, uint32_t bin_x,
+                                                     uint32_t bin_y, Value v)
+{
+    double acc = -0.0;
+    for (uint32_t s = 0; s < num_sources; ++s) {
+        const double w = tab.w[s];
+        for (uint32_t dy = 0; dy < bin_y; ++dy)
+            for (uint32_t dx = 0; dx < bin_x; ++dx) acc = lsf_step(w, (double)v(s, dy, dx), acc);
+    }
+    return area_finish(acc, tab.wsum);
+}
+
+// The launch geometry of k_area_integrate (kernels/xrt_kernels.h), formed on
+// the host as log_projection_plan's: a row's share of the workgroup is the
+// power of two of lanes that covers its units, so narrow planes fill their
+// waves.  A unit is what one lane owns of an output row: with bin_x 1, 2 or 4
+// the outputs whose inputs are one 16-byte quad of an input row (4, 2, 1), with
+// bin_x 8 one output (two quads), otherwise -- `vector` 0 -- one output moved
+// pixel by pixel.  `uniform`: every input row of one output row starts at the
+// same address modulo 16 bytes (a row pitch and, past one source, a plane pitch
+// of whole quads, or a single row), which is what lets the quads be cut at the
+// addresses' multiples of 16 bytes.
+constexpr uint32_t kAreaThreads = 256;
+constexpr uint32_t kAreaThreadsLog2 = 8;
+
+struct AreaPlan {
+    uint32_t vector;                    // bin_x where the vector kernel serves (1, 2, 4, 8), else 0
+    uint32_t lanes_log2;
+    uint32_t chunks;
+    uint64_t blocks;
+};
+
+inline AreaPlan area_plan(uint32_t W, uint64_t rows, uint32_t bin_x, uint32_t bin_y, uint32_t num_sources, uint32_t H)
+{
+    AreaPlan plan;
+    const uint64_t Wb = (uint64_t)W * bin_x, plane = Wb * ((uint64_t)H * bin_y);
+    const bool uniform = ((Wb & 3u) == 0u || bin_y == 1u) && ((plane & 3u) == 0u || num_sources == 1u);
+    plan.vector = uniform && (bin_x == 1u || bin_x == 2u || bin_x == 4u || bin_x == 8u) ? bin_x : 0u;
+    // units that cover a row under any misalignment the kernel vectorises: ceil((Wb + 3) / 4) quads, Wb / 8 pairs
+    const uint64_t units = plan.vector == 0u ? W : plan.vector == 8u ? W : (Wb + 6u) / 4u;
+    plan.lanes_log2 = 0;
+    while (plan.lanes_log2 < kAreaThreadsLog2 && (1u << plan.lanes_log2) < units) ++plan.lanes_log2;
+    const uint32_t span = 1u << plan.lanes_log2, rows_per = kAreaThreads >> plan.lanes_log2;
+    plan.chunks = (uint32_t)((units + span - 1u) / span);
+    plan.blocks = (rows + rows_per - 1u) / rows_per * plan.chunks;
+    return plan;
+}
+
 }  // namespace XRT_KERNEL_NS

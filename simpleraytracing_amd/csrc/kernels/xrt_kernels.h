@@ -4067,4 +4067,146 @@ __global__ void k_probe_poisson(const double* __restrict__ lam, const uint32_t* 
     outp[i] = xrt_poisson_from_word(lam[i], words[i]);
 }
 
+// ---------------------------------------------------------------------------
+// k_area_integrate: area sampling.  Output row (p, y) reads the
+// rows y bin_y .. y bin_y + bin_y - 1 of the planes p S .. p S + S - 1, each
+// Wb = W bin_x floats; a lane sums its own outputs in the contract's order (s,
+// dy, dx), so there is no reduction across lanes.  kBinX = 1, 2, 4, 8: a lane
+// owns a unit of an output row -- the 4, 2, 1 outputs whose inputs are one
+// 16-byte quad of each input row, or one output of two quads -- and the quads
+// are cut at the multiples of 16 bytes of the rows' *addresses*
+// (k_log_projection's scheme; area_plan launches this form only where all input
+// rows of an output row share their address modulo 16): with the row's
+// misalignment m, in floats, a multiple of kBinX, unit j holds the input pixels
+// U j - m .. U j - m + U - 1; whole units go as dwordx4 and the ragged ends,
+// or a row whose m cuts an output, pixel by pixel (m = 0).  The rows (s, dy) are
+// one sequence of S bin_y rows, fetched kAreaRows at a time: a batch's loads are
+// issued before the batch ahead of it is summed.  kBinX = 0: one output a lane,
+// pixel by pixel, for every other bin_x or pitch.  Rows and workgroups are
+// planned as k_log_projection's (area_plan); kWide is a workgroup within one
+// row, whose row arithmetic is scalar.  Plane and row offsets are 64-bit,
+// coordinates 32-bit.  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kAreaRows = 4;
+
+template <uint32_t kBinX, bool kWide>
+__global__ __launch_bounds__(kAreaThreads) void k_area_integrate(const float* __restrict__ image, float* outp,
+                                                                 uint8_t* out_u8, uint32_t W, uint32_t H, uint32_t P,
+                                                                 uint32_t bin_x_arg, uint32_t bin_y, uint32_t S,
+                                                                 uint32_t lanes_log2, uint32_t chunks, AreaWeights tab)
+{
+    constexpr uint32_t U = kBinX == 8u ? 8u : 4u;               // input floats of a unit's row
+    constexpr uint32_t NO = kBinX ? U / kBinX : 1u;             // outputs of a unit
+    constexpr uint32_t NV = U / 4u;                             // quads of a unit's row
+    const uint32_t bin_x = kBinX ? kBinX : bin_x_arg;
+    const uint32_t group = blockIdx.x / chunks, chunk = blockIdx.x - group * chunks;
+    const uint64_t row64 = kWide ? (uint64_t)group
+                                 : ((uint64_t)group << (kAreaThreadsLog2 - lanes_log2)) + (threadIdx.x >> lanes_log2);
+    if (row64 >= (uint64_t)P * H) return;
+    const uint32_t row = (uint32_t)row64;                       // (P H < 2^32: the host's check)
+    const uint32_t p = row / H, y = row - p * H;
+    const size_t Wb = (size_t)W * bin_x, plane = Wb * ((size_t)H * bin_y);
+    const float* src = image + ((size_t)p * S) * plane + ((size_t)y * bin_y) * Wb;
+    const size_t o_row = (size_t)row * W;
+    const uint32_t j = kWide ? chunk * kAreaThreads + threadIdx.x
+                             : (chunk << lanes_log2) + (threadIdx.x & ((1u << lanes_log2) - 1u));
+
+    const auto put = [&](uint32_t x, float f) {
+        if (outp) outp[o_row + x] = f;
+        if (out_u8) out_u8[o_row + x] = lut_u8(f);
+    };
+    const auto pixel = [&](uint32_t x) {                        // output x of the row, pixel by pixel
+        const float* at = src + (size_t)x * bin_x;
+        return area_pixel(tab, S, bin_x, bin_y,
+                          [&](uint32_t s, uint32_t dy, uint32_t dx) { return at[s * plane + dy * Wb + dx]; });
+    };
+
+    if constexpr (kBinX == 0u) {
+        if (j < W) put(j, pixel(j));
+    } else {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(src);
+        const uint32_t mis = (uint32_t)(a >> 2) & 3u;
+        const bool vec = (a & 3u) == 0u && mis % (kBinX < 4u ? kBinX : 4u) == 0u;
+        const uint32_t m = vec ? mis : 0u;
+        // the unit's first input pixel and first output (below 0: the ragged head); 32-bit: Wb < 2^31 is the host's check
+        const int32_t wb = (int32_t)Wb, xin0 = (int32_t)(U * j) - (int32_t)m;
+        const int32_t xo0 = (int32_t)(NO * j) - (int32_t)(m / kBinX);
+        if (xin0 >= wb) return;
+
+        if (vec && xin0 >= 0 && xin0 + (int32_t)U <= wb) {
+            const uint32_t T = S * bin_y;                       // the rows (s, dy) in the contract's order
+            const float* rp = src + xin0;
+            uint32_t t = 0, s = 0, dy = 0;
+            float4 va[kAreaRows][NV], vb[kAreaRows][NV];
+            double wa[kAreaRows], wb_[kAreaRows];
+            double acc[NO];
+#pragma unroll
+            for (uint32_t e = 0; e < NO; ++e) acc[e] = -0.0;
+            const auto fetch = [&](float4 (&v)[kAreaRows][NV], double (&w)[kAreaRows]) {
+#pragma unroll
+                for (uint32_t r = 0; r < kAreaRows; ++r) {
+                    if (t < T) {
+#pragma unroll
+                        for (uint32_t k = 0; k < NV; ++k) v[r][k] = *reinterpret_cast<const float4*>(rp + 4u * k);
+                        w[r] = tab.w[s];
+                        ++t, ++dy;
+                        rp += Wb;
+                        if (dy == bin_y) dy = 0u, ++s, rp += plane - bin_y * Wb;
+                    }
+                }
+            };
+            const auto sum = [&](const float4 (&v)[kAreaRows][NV], const double (&w)[kAreaRows], uint32_t t0) {
+#pragma unroll
+                for (uint32_t r = 0; r < kAreaRows; ++r) {
+                    if (t0 + r < T) {
+#pragma unroll
+                        for (uint32_t k = 0; k < NV; ++k) {
+                            const float c[4] = {v[r][k].x, v[r][k].y, v[r][k].z, v[r][k].w};
+#pragma unroll
+                            for (uint32_t e = 0; e < 4u; ++e)
+                                acc[(4u * k + e) / kBinX] = lsf_step(w[r], (double)c[e], acc[(4u * k + e) / kBinX]);
+                        }
+                    }
+                }
+            };
+            fetch(va, wa);
+            for (uint32_t t0 = 0; t0 < T; t0 += 2u * kAreaRows) {
+                fetch(vb, wb_);
+                sum(va, wa, t0);
+                fetch(va, wa);
+                sum(vb, wb_, t0 + kAreaRows);
+            }
+            float o[NO];
+#pragma unroll
+            for (uint32_t e = 0; e < NO; ++e) o[e] = area_finish(acc[e], tab.wsum);
+            const size_t at = o_row + (uint32_t)xo0;
+            if (outp) {
+                float* dst = outp + at;
+                bool stored = false;                            // an aligned run of outputs goes as one store
+                if constexpr (NO == 4u) {
+                    if ((stored = (reinterpret_cast<uintptr_t>(dst) & 15u) == 0u))
+                        *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                } else if constexpr (NO == 2u) {
+                    if ((stored = (reinterpret_cast<uintptr_t>(dst) & 7u) == 0u))
+                        *reinterpret_cast<float2*>(dst) = make_float2(o[0], o[1]);
+                }
+                if (!stored) {
+#pragma unroll
+                    for (uint32_t e = 0; e < NO; ++e) dst[e] = o[e];
+                }
+            }
+            if (out_u8) {
+#pragma unroll
+                for (uint32_t e = 0; e < NO; ++e) out_u8[at + e] = lut_u8(o[e]);
+            }
+            return;
+        }
+        // a ragged end, or a row whose misalignment cuts an output: pixel by pixel
+        for (uint32_t e = 0; e < NO; ++e) {
+            const int32_t x = xo0 + (int32_t)e;
+            if (x >= 0 && x < (int32_t)W) put((uint32_t)x, pixel((uint32_t)x));
+        }
+    }
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -2972,6 +2972,68 @@ int xrt_debug_poisson_batch(xrt_context* ctx, const double* lam, const uint32_t*
     return s.finish();
 }
 
+// --- area sampling ---------------------------------------------
+
+#include "xrt_area_host.inc"
+
+// The launch of k_area_integrate (validated arguments, device pointers).
+static int launch_area_integrate(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t bin_x, uint32_t bin_y,
+                                 uint32_t num_sources, uint32_t num_planes, const float* weight, const float* d_image,
+                                 float* d_out, uint8_t* d_out_u8, hipStream_t stream)
+{
+    AreaWeights tab;                    // by value: the launch owns its copy (no context state, no wait)
+    area_weights_set(tab, weight, num_sources, bin_x, bin_y);
+    const AreaPlan plan = area_plan(width, (uint64_t)num_planes * height, bin_x, bin_y, num_sources, height);
+    const bool wide = plan.lanes_log2 == kAreaThreadsLog2;
+    auto kernel = wide ? k_area_integrate<0, true> : k_area_integrate<0, false>;
+    switch (plan.vector) {
+    case 1: kernel = wide ? k_area_integrate<1, true> : k_area_integrate<1, false>; break;
+    case 2: kernel = wide ? k_area_integrate<2, true> : k_area_integrate<2, false>; break;
+    case 4: kernel = wide ? k_area_integrate<4, true> : k_area_integrate<4, false>; break;
+    case 8: kernel = wide ? k_area_integrate<8, true> : k_area_integrate<8, false>; break;
+    default: break;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.blocks), dim3(kAreaThreads), 0, stream, d_image, d_out, d_out_u8, width,
+                       height, num_planes, bin_x, bin_y, num_sources, plan.lanes_log2, plan.chunks, tab);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_area_integrate_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t bin_x, uint32_t bin_y,
+                              uint32_t num_sources, uint32_t num_planes, const float* weight, const float* d_image,
+                              float* d_out, uint8_t* d_out_u8, void* stream)
+{
+    if (const char* why = area_arguments(width, height, bin_x, bin_y, num_sources, num_planes, weight, d_image, d_out,
+                                         d_out_u8))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_area_integrate(ctx, width, height, bin_x, bin_y, num_sources, num_planes, weight, d_image, d_out,
+                                 d_out_u8, (hipStream_t)stream);
+}
+
+int xrt_area_integrate(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t bin_x, uint32_t bin_y,
+                       uint32_t num_sources, uint32_t num_planes, const float* weight, const float* image, float* out,
+                       uint8_t* out_u8)
+{
+    if (const char* why = area_arguments(width, height, bin_x, bin_y, num_sources, num_planes, weight, image, out, out_u8))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)width * height * num_planes, n_in = n * bin_x * bin_y * num_sources;
+    DeviceScratch s(ctx, ctx->host_stream, "area integration");
+    const float* din = s.upload(image, n_in);
+    float* dout = s.alloc<float>(n, out != nullptr);
+    uint8_t* du8 = s.alloc<uint8_t>(n, out_u8 != nullptr);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_area_integrate(ctx, width, height, bin_x, bin_y, num_sources, num_planes, weight, din, dout, du8,
+                                       ctx->host_stream))
+        return rc;
+    s.download(out, dout, n);
+    s.download(out_u8, du8, n);
+    return s.finish();
+}
+
 // Render of the L-buffer plane and the fork's hole fill over it, into host buffers.
 static int render_and_fill(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
                            uint8_t* image_u8, xrt_stats* stats)
