@@ -1768,31 +1768,14 @@ constexpr uint32_t kCounterStride = 32;
 constexpr uint32_t kBinBatch = XRT_BIN_BATCH;  // queued pairs per lane per commit round (their atomics in flight together)
 constexpr uint32_t kBinSmall = 64;           // region rectangles up to this many cells are flattened over the wave
 constexpr uint32_t kBinQueue = XRT_BIN_QUEUE;  // passing (region, triangle) pairs queued per wave before a commit
-// Launch slots of a k_prep wave's regions cached in LDS (0: off): when the
-// union of the wave's region rectangles has at most this many cells, the
-// wave DMAs their region -> slot entries into LDS before its cell tests, so
-// the commit reads LDS instead of a dependent global load.
-#ifndef XRT_PREP_RANK_LDS
-#define XRT_PREP_RANK_LDS 0
-#endif
-constexpr uint32_t kRankCache = XRT_PREP_RANK_LDS;
-static_assert(kRankCache % 64u == 0u, "whole DMA rounds");
-// k_prep's commit through buffer instructions (range-checked, no per-lane
-// branches around the memory ops; 0: plain guarded loads and atomics)
-#ifndef XRT_PREP_BUFFER_OPS
-#define XRT_PREP_BUFFER_OPS 1
-#endif
-// Per-wave aggregation of the commit's count atomics (0: off): when the union
-// of the wave's region rectangles has at most kAggCells cells, the wave's pairs
+// Per-wave aggregation of the commit's count atomics: when the union of the
+// wave's region rectangles has at most kAggCells cells, the wave's pairs
 // first count per cell in LDS (each pair's offset in its cell from an LDS
 // atomic), then ONE global atomic per cell with pairs returns the cell's base
 // -- a wave's triangles are mesh-adjacent, so its pairs share few regions.
-#ifndef XRT_PREP_AGG
-#define XRT_PREP_AGG 1
-#endif
+// Both commits go through buffer instructions (range-checked, no per-lane
+// branches around the memory ops).
 constexpr uint32_t kAggCells = 256;
-static_assert(!(XRT_PREP_AGG && XRT_PREP_RANK_LDS), "one cell-indexed queue layout at a time");
-static_assert(!XRT_PREP_AGG || XRT_PREP_BUFFER_OPS, "the aggregated commit uses the buffer-op tables");
 // raw buffer atomic OR (no clang builtin for it; the LLVM intrinsic, whose
 // no-return form is selected when the result is unused)
 __device__ int buffer_atomic_or_i32(int v, __amdgpu_buffer_rsrc_t r, int off, int soff, int aux)
@@ -1919,9 +1902,6 @@ __device__ __forceinline__ void load_slot(const BinBuffers& bins, uint32_t slot,
     live = d.w;
 }
 
-#ifndef XRT_TILE_MASK
-#define XRT_TILE_MASK 1   // k_prep ORs each pair's box tile mask into its slot; the render skips tiles outside it
-#endif
 // The 8x8 tiles a footprint box meets by box_overlaps' test, as a span of
 // strip tile columns and rows (tile column j: pixels 8j .. 8j + 7; tile row i:
 // strip rows 8i .. 8i + 7): column j meets [xmin, xmax] iff j runs from
@@ -1950,9 +1930,6 @@ __device__ __forceinline__ uint32_t span_tile_mask(uint2 span, uint32_t rx, uint
     return rows & (cols * 0x1111u);
 }
 
-#ifndef XRT_BIN_TIGHT
-#define XRT_BIN_TIGHT 1   // the region rectangle of a footprint box: exactly the regions the box meets
-#endif
 // Region rectangle [x0,x1] x [y0,y1] (strip-relative region indices) that a
 // footprint box may touch; false when it touches none.
 __device__ __forceinline__ bool footprint_regions(float4 bb, const RenderParams& p,
@@ -1970,13 +1947,8 @@ __device__ __forceinline__ bool footprint_regions(float4 bb, const RenderParams&
     // integer -- every integer here is a float -- so the computed first region is
     // never past the exact one.)  Round 1-5 took floor for the first one too: one
     // region column and row more than the box meets for nearly every footprint.
-#if XRT_BIN_TIGHT
     int ix0 = (int)ceilf((xmin - 31.0f) * (1.0f / 32.0f));
     int iy0 = (int)ceilf((ymin - 31.0f) * (1.0f / 32.0f));
-#else
-    int ix0 = (int)floorf((xmin - 31.0f) * (1.0f / 32.0f));
-    int iy0 = (int)floorf((ymin - 31.0f) * (1.0f / 32.0f));
-#endif
     int ix1 = (int)floorf(xmax * (1.0f / 32.0f));
     int iy1 = (int)floorf(ymax * (1.0f / 32.0f));
     ix0 = max(ix0, 0);
@@ -2018,12 +1990,6 @@ __device__ __forceinline__ bool bin_rect(float4 bb, float reach, const RenderPar
 // k_prep runs beside the previous frame's render: single-wave workgroups fit
 // the holes that retiring render waves leave (a 4-wave one needs a free slot
 // on all four SIMDs of a CU at once).
-#ifndef XRT_PREP_PRIO
-#define XRT_PREP_PRIO 0   // k_prep's wave priority (s_setprio; 0: the render's)
-#endif
-#ifndef XRT_PREP_LATE_STORES
-#define XRT_PREP_LATE_STORES 1   // k_prep's global stores after its binning (1) or before it (0)
-#endif
 constexpr uint32_t kPrepThreads = XRT_PREP_THREADS;
 constexpr uint32_t kPrepWaves = kPrepThreads / 64u;
 #ifndef XRT_PREP_TRIS
@@ -2037,6 +2003,22 @@ static_assert(kPrepTris >= 1u && kPrepTris <= 64u, "kPrepTris");
 // frames lose 1.6 us with 64, so small meshes keep kPrepTris).
 constexpr uint32_t kPrepBigMesh = 1u << 18;
 __host__ __device__ constexpr uint32_t prep_tris_for(uint64_t T) { return T >= kPrepBigMesh ? 64u : kPrepTris; }
+
+// The union of a wave's region rectangles (the lanes with `has`): its first
+// column and row, its width and its cells, wave-uniform; left as they are when
+// no lane has a rectangle.
+__device__ __forceinline__ void wave_rect_union(bool has, uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1,
+                                                uint32_t& ux0, uint32_t& uy0, uint32_t& uw, uint32_t& ucells)
+{
+    if (__ballot(has) != 0ull) {
+        ux0 = ~wave_reduce_u32<true>(has ? ~x0 : 0u);
+        uy0 = ~wave_reduce_u32<true>(has ? ~y0 : 0u);
+        const uint32_t ux1 = wave_reduce_u32<true>(has ? x1 : 0u);
+        const uint32_t uy1 = wave_reduce_u32<true>(has ? y1 : 0u);
+        uw = ux1 - ux0 + 1u;
+        ucells = uw * (uy1 - uy0 + 1u);
+    }
+}
 
 __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__ tris, uint32_t T,
                                               RenderParams p, CullParams cp,
@@ -2072,9 +2054,6 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
     // i: the thread's index over the grid (pixel-offset tables, counter
     // clears); tri: its triangle -- p.prep_tris per wave (fewer than 64 spreads
     // the binning's cells and commits of a frame over more waves).
-#if XRT_PREP_PRIO
-    __builtin_amdgcn_s_setprio(XRT_PREP_PRIO);
-#endif
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t tri_lane = threadIdx.x & 63u;
     const uint32_t tri = (blockIdx.x * kPrepWaves + (threadIdx.x >> 6)) * p.prep_tris + tri_lane;
@@ -2113,13 +2092,13 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
             fp.e0.w = __uint_as_float(tri);          // the region entries carry the id (make_entry's layout)
         }
     }
-    // The wave's global stores -- records, cull planes, the frame's pixel
+    // ---- The late stores.  The wave's global stores -- records, cull planes, the frame's pixel
     // offsets, the other counter half's clears -- are issued at its
     // END, after the binning: on gfx9 a store holds the vector-memory counter
     // until it is acknowledged, and the binning's first wait for a load (its
     // commit's slot loads, a loop's conservative wait) would otherwise wait
     // for every one of them (2048^2: ~1-2 us per wave beside the render).
-    auto store_outputs = [&]() __attribute__((always_inline)) {
+    auto store_prep_outputs = [&]() __attribute__((always_inline)) {
         if (offsets_out) {                         // v_off of every row, then u_off of every column
             if (i < p.height) offsets_out[i] = pixel_offset(p.spacing, i, p.height);
             else if (i - p.height < p.width) offsets_out[i] = pixel_offset(p.spacing, i - p.height, p.width);
@@ -2139,19 +2118,14 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
             if (i < sizeof(BinState) / sizeof(uint32_t)) (bins.clear - kCounterStride)[i] = 0u;
         }
     };
-#if !XRT_PREP_LATE_STORES
-    store_outputs();                               // (A/B: the stores before the binning)
-#endif
     stamp(2);
     if (!bins.counts) {                            // kernel-uniform
-#if XRT_PREP_LATE_STORES
-        store_outputs();
-#endif
+        store_prep_outputs();
         stamp_end();
         return;
     }
 
-    // Binning, per wave, in two phases.  (1) Test: every cell of the wave's
+    // ---- Binning, per wave, in two phases.  (1) Test: every cell of the wave's
     // 64 region rectangles against its triangle's relaxed edges -- VALU and
     // LDS only; the cells of rectangles up to kBinSmall cells are flattened
     // over the wave (inclusive scan of the counts, a binary search per cell),
@@ -2165,10 +2139,9 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
     __shared__ uint32_t s_cum[kPrepWaves][64];     // inclusive prefix of the small cell counts
     __shared__ uint32_t s_qreg[kPrepWaves][kBinQueue];   // passing pairs: region
     __shared__ uint8_t s_qown[kPrepWaves][kBinQueue];    //                owner lane
-#if XRT_TILE_MASK
     __shared__ uint16_t s_qmask[kPrepWaves][kBinQueue];  //                box tile mask
     __shared__ uint2 s_tspan[kPrepWaves][64];      // the lane's box_tile_span
-#endif
+    // ---- Staging and scan: the lane's rectangle, entry and tile span to LDS; the prefix of the small cell counts.
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0;
     bool global = false;
@@ -2195,54 +2168,22 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
     s_fp[wave][2][lane] = fp.e2;
     s_fp[wave][3][lane] = fp.bbox;
     s_rect[wave][lane] = make_uint2(x0 | (x1 << 16), y0 | (y1 << 16));
-#if XRT_TILE_MASK
     const bool masks = bins.box_masks != 0u;       // kernel-uniform
     if (masks) s_tspan[wave][lane] = box_tile_span(fp.bbox, p.row_begin);
-#endif
     s_cum[wave][lane] = cum;
-    // The slots of the union of the wave's rectangles (mesh-adjacent triangles
-    // bin to neighbouring regions), DMAed into LDS under phase 1 when few.
+    // enqueue's copies of agg, ax0, ay0 and aw (below): folding the two sets into one
+    // changes the kernel's register allocation, so both stay until k_prep is retimed.
     bool cached = false;
     uint32_t ux0 = 0, uy0 = 0, uw = 0;
-#if XRT_PREP_RANK_LDS
-    __shared__ uint32_t s_rank[kPrepWaves][kRankCache];
-    if (__ballot(has) != 0ull) {
-        ux0 = ~wave_reduce_u32<true>(has ? ~x0 : 0u);
-        uy0 = ~wave_reduce_u32<true>(has ? ~y0 : 0u);
-        const uint32_t ux1 = wave_reduce_u32<true>(has ? x1 : 0u);
-        const uint32_t uy1 = wave_reduce_u32<true>(has ? y1 : 0u);
-        uw = ux1 - ux0 + 1u;
-        const uint32_t ucells = uw * (uy1 - uy0 + 1u);
-        cached = ucells <= kRankCache;
-        if (cached) {
-            for (uint32_t c0 = 0; c0 < ucells; c0 += 64u) {
-                const uint32_t c = c0 + lane;
-                if (c < ucells)
-                    __builtin_amdgcn_global_load_lds((const void*)(bins.rank + (uy0 + c / uw) * bins.regions_x + ux0 +
-                                                                   c % uw),
-                                                     (__attribute__((address_space(3))) void*)&s_rank[wave][c0], 4, 0,
-                                                     0);
-            }
-        }
-    }
-#endif
-    bool rank_waited = false;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     stamp(3);
 
-#if XRT_PREP_AGG
-    // the union of the wave's rectangles (wave-uniform)
+    // ---- The union of the wave's rectangles (wave-uniform; mesh-adjacent triangles bin to
+    // neighbouring regions): at most kAggCells cells, and the wave's commits are aggregated per cell.
     uint32_t ax0 = 0, ay0 = 0, aw = 0, acells = 0;
-    if (__ballot(has) != 0ull) {
-        ax0 = ~wave_reduce_u32<true>(has ? ~x0 : 0u);
-        ay0 = ~wave_reduce_u32<true>(has ? ~y0 : 0u);
-        const uint32_t ax1 = wave_reduce_u32<true>(has ? x1 : 0u);
-        const uint32_t ay1 = wave_reduce_u32<true>(has ? y1 : 0u);
-        aw = ax1 - ax0 + 1u;
-        acells = aw * (ay1 - ay0 + 1u);
-    }
+    wave_rect_union(has, x0, x1, y0, y1, ax0, ay0, aw, acells);
     const bool agg = acells <= kAggCells;
     __shared__ uint32_t s_acnt[kPrepWaves][kAggCells];   // per cell: its pairs' count, then its base slot
     __shared__ uint32_t s_alb[kPrepWaves][kAggCells];    //           its list's base
@@ -2252,12 +2193,10 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
     ux0 = ax0;
     uy0 = ay0;
     uw = aw;
-#endif
     // No lists (the sizing pass of a new geometry, DESIGN.md "List sizing"):
     // the pairs are counted, nothing is stored, nothing can overflow.
     stamp(4);
     const uint32_t count_only = wave_uniform(bins.list == nullptr ? 1u : 0u);
-#if XRT_PREP_BUFFER_OPS
     // the commit's tables as buffers (range-checked: kBufferOut is past all of them)
     const uint32_t n_regions = bins.regions_x * bins.regions_y;
     const __amdgpu_buffer_rsrc_t r_rank =
@@ -2266,12 +2205,10 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
         __builtin_amdgcn_make_buffer_rsrc(bins.counts, 0, (int)(n_regions * kCounterStride * 4u), kBufferWord3);
     const __amdgpu_buffer_rsrc_t r_desc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<SlotDesc*>(bins.desc), 0, (int)(n_regions * (uint32_t)sizeof(SlotDesc)), kBufferWord3);
-#endif
     const uint32_t tri_base = (blockIdx.x * kPrepWaves + wave) * p.prep_tris;   // the triangle of lane 0
     uint32_t my_max = 0;                           // 1 + the largest slot this lane took
     bool over = false;                             // a slot past its list's capacity
     uint32_t queued = 0;                           // wave-uniform queue length
-#if XRT_PREP_AGG
     // Device sizing (BinBuffers::pairs), aggregated commit: every queued pair
     // as (slot, its index in the slot's list, triangle) -- s_alb[c] holds the
     // cell's slot, s_acnt[c] its base index, s_qoff the pair's offset in its
@@ -2290,25 +2227,23 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
                                                 tri_base + s_qown[wave][q], 0u);
         }
     };
-#endif
+    // ---- (2) Commit, in one of two forms, chosen per wave.  They stay two arms
+    // of one lambda: split into two, the kernel compiles to other instructions.
     auto commit = [&]() __attribute__((always_inline)) {
-#if XRT_PREP_AGG
+        // -- commit_cells, the aggregated commit: the queue holds cell indices in the union; the pairs counted
+        // per cell in LDS (a), one global count atomic per cell with pairs (b), the entries (c).
         if (agg) {
             // (a) per-cell counts in LDS; each pair's offset in its cell
             // (and per cell the OR of its pairs' tile masks, in s_alc until (b) reads it)
             for (uint32_t c = lane; c < acells; c += 64u) s_acnt[wave][c] = 0u;
-#if XRT_TILE_MASK
             if (masks)
                 for (uint32_t c = lane; c < acells; c += 64u) s_alc[wave][c] = 0u;
-#endif
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             for (uint32_t q = lane; q < queued; q += 64u) {
                 s_qoff[wave][q] = (uint8_t)atomicAdd(&s_acnt[wave][s_qreg[wave][q]], 1u);
-#if XRT_TILE_MASK
                 if (masks) atomicOr(&s_alc[wave][s_qreg[wave][q]], (uint32_t)s_qmask[wave][q]);
-#endif
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -2326,11 +2261,9 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
             }
 #pragma unroll
             for (uint32_t k = 0; k < kAggRounds; ++k) cs[k] = cn[k] ? cs[k] : kEmpty;
-#if XRT_TILE_MASK
             uint32_t cm[kAggRounds];               // the cells' tile masks
 #pragma unroll
             for (uint32_t k = 0; k < kAggRounds; ++k) cm[k] = masks ? s_alc[wave][k * 64u + lane] : 0u;
-#endif
             bool planned_empty = false;            // pairs for a region the fill plan fills
 #pragma unroll
             for (uint32_t k = 0; k < kAggRounds; ++k) planned_empty |= cs[k] != kEmpty && cs[k] >= bins.tile_slots;
@@ -2348,7 +2281,6 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
                 clb[k] = bc[0];
                 clc[k] = bc[1];
             }
-#if XRT_TILE_MASK
             // the masks' atomics last (no return value; issued after the loads and
             // atomics whose results the wave waits for, they do not delay them)
             if (masks) {
@@ -2357,7 +2289,6 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
                     buffer_atomic_or_i32((int)cm[k], r_cnt,
                                          cs[k] != kEmpty ? cs[k] * (kCounterStride * 4u) + 4u : kBufferOut, 0, 0);
             }
-#endif
             if (count_only) {                       // the sizing pass: counts only
                 if (bins.pairs) {                   // (device sizing: and the pairs)
 #pragma unroll
@@ -2402,16 +2333,10 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
             queued = 0;
             return;
         }
-#endif
-#if XRT_PREP_RANK_LDS
-        if (cached && !rank_waited) {              // the slots' DMA has landed (issued before phase 1)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            rank_waited = true;
-        }
-#endif
+        // -- commit_pairs, the per-pair commit (a union over kAggCells cells): the queue holds regions,
+        // dealt kBinBatch pairs per lane per round, one count atomic per pair.
         for (uint32_t base = 0; base < queued; base += 64u * kBinBatch) {
             uint32_t reg[kBinBatch], own[kBinBatch], slot[kBinBatch];
-#if XRT_PREP_BUFFER_OPS
             // Buffer loads and atomics with an out-of-range offset for the lanes
             // without a pair (a load returns 0, an atomic does nothing): no
             // exec-masked branch around each memory op, so the round's four
@@ -2428,38 +2353,16 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
                 own[b] = s_qown[wave][qq];
             }
 #pragma unroll
-            for (uint32_t b = 0; b < kBinBatch; ++b) {
-#if XRT_PREP_RANK_LDS
-                if (cached) reg[b] = val[b] ? s_rank[wave][reg[b]] : kEmpty;
-                else
-#endif
+            for (uint32_t b = 0; b < kBinBatch; ++b)
                 reg[b] = __builtin_amdgcn_raw_buffer_load_b32(r_rank, val[b] ? reg[b] * 4u : kBufferOut, 0, 0);
-            }
 #pragma unroll
             for (uint32_t b = 0; b < kBinBatch; ++b) reg[b] = val[b] ? reg[b] : kEmpty;
-#else
-#pragma unroll
-            for (uint32_t b = 0; b < kBinBatch; ++b) {
-                const uint32_t q = base + b * 64u + lane;
-                reg[b] = kEmpty;
-                own[b] = 0u;
-                if (q < queued) {
-#if XRT_PREP_RANK_LDS
-                    reg[b] = cached ? s_rank[wave][s_qreg[wave][q]] : bins.rank[s_qreg[wave][q]];
-#else
-                    reg[b] = bins.rank[s_qreg[wave][q]];
-#endif
-                    own[b] = s_qown[wave][q];
-                }
-            }
-#endif
             bool planned_empty = false;            // a pair for a region the fill plan fills
 #pragma unroll
             for (uint32_t b = 0; b < kBinBatch; ++b) planned_empty |= reg[b] != kEmpty && reg[b] >= bins.tile_slots;
             if (__builtin_expect(bins.plan_miss != nullptr && __ballot(planned_empty) != 0ull, 0) && lane == 0)
                 *bins.plan_miss = 1u;
             uint32_t lbase[kBinBatch], lcap[kBinBatch];
-#if XRT_PREP_BUFFER_OPS
 #pragma unroll
             for (uint32_t b = 0; b < kBinBatch; ++b)
                 slot[b] = (uint32_t)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(
@@ -2471,7 +2374,6 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
                 lbase[b] = bc[0];
                 lcap[b] = bc[1];
             }
-#if XRT_TILE_MASK
             if (masks) {
 #pragma unroll
                 for (uint32_t b = 0; b < kBinBatch; ++b) {   // the pairs' tile masks, last (no return value)
@@ -2480,22 +2382,6 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
                                          reg[b] != kEmpty ? reg[b] * (kCounterStride * 4u) + 4u : kBufferOut, 0, 0);
                 }
             }
-#endif
-#else
-#pragma unroll
-            for (uint32_t b = 0; b < kBinBatch; ++b) {
-                slot[b] = reg[b] != kEmpty ? atomicAdd(&bins.counts[(size_t)reg[b] * kCounterStride], 1u) : 0u;
-#if XRT_TILE_MASK
-                if (masks && reg[b] != kEmpty)
-                    atomicOr(&bins.counts[(size_t)reg[b] * kCounterStride + 1u],
-                             (uint32_t)s_qmask[wave][min(base + b * 64u + lane, kBinQueue - 1u)]);
-#endif
-                const uint2 bc = reg[b] != kEmpty && count_only == 0u
-                                     ? *reinterpret_cast<const uint2*>(bins.desc + reg[b]) : make_uint2(0u, 0u);
-                lbase[b] = bc.x;
-                lcap[b] = bc.y;
-            }
-#endif
             if (count_only) {                      // the sizing pass: counts only
                 if (bins.pairs) {                  // (device sizing: and the pairs)
 #pragma unroll
@@ -2529,7 +2415,8 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
         __builtin_amdgcn_wave_barrier();          // the queue is refilled after every lane read it
         queued = 0;
     };
-    // append the passing cells of one round (pass, region rx/ry, owner) to the queue
+    // ---- (1) Test.  enqueue: append the passing cells of one round (pass, region
+    // rx/ry, owner) to the queue, committing first when it is full.
     auto enqueue = [&](bool pass, uint32_t rx, uint32_t ry, uint32_t owner) {
         const unsigned long long m = __ballot(pass);
         if (!m) return;
@@ -2541,15 +2428,14 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
         if (pass) {
             const uint32_t q = queued + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            // the cached slot's index, or the region
+            // the cell's index in the union (the aggregated commit), or the region
             s_qreg[wave][q] = cached ? (ry - uy0) * uw + (rx - ux0) : ry * bins.regions_x + rx;
             s_qown[wave][q] = (uint8_t)owner;
-#if XRT_TILE_MASK
             if (masks) s_qmask[wave][q] = (uint16_t)span_tile_mask(s_tspan[wave][owner], rx, ry);
-#endif
         }
         queued += (uint32_t)__popcll(m);
     };
+    // cell_pass: the owner's relaxed edges against the centre of region (rx, ry)
     auto cell_pass = [&](uint32_t owner, uint32_t rx, uint32_t ry) {
         const float xc = (float)(rx * kRegion) + 15.5f;
         const float yc = (float)(p.row_begin + ry * kRegion) + 15.5f;
@@ -2604,9 +2490,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const float* __restrict__
         atomicOr(&bs->overflow, 1u);
         if (bins.plan_miss) bins.plan_miss[1] = 1u;  // the host re-sizes for the next frame
     }
-#if XRT_PREP_LATE_STORES
-    store_outputs();
-#endif
+    store_prep_outputs();
     stamp_end();
 }
 
@@ -2757,9 +2641,6 @@ __device__ __forceinline__ void stage_survivor_records(RecStage& st, const TriRe
     }
 }
 
-#ifndef XRT_PUSH_BALLOT
-#define XRT_PUSH_BALLOT 1
-#endif
 // TriRec: e1 (a0.xyz), e2 (a0.w, a1.xy), tvec (a1.zw, a2.x), qvec (a2.yzw), tnum (q[3].x)
 __device__ __forceinline__ void test_rec(float4 a0, float4 a1, float4 a2, float tnum, float dx, float dy, float dz,
                                          HitList& hl)
@@ -2773,13 +2654,9 @@ __device__ __forceinline__ void test_rec(float4 a0, float4 a1, float4 a2, float 
     if (__builtin_expect(__ballot(!rcp_newton_exact_for(det)) != 0ull, 0)) inv = inv_det_of(det);
     bool h;
     const float t = mt_finish_inv(det, inv, u, v, tnum, h);
-#if XRT_PUSH_BALLOT
     // a survivor of the conservative tile cull often hits none of the tile's
     // rays: its insert (kMaxHits v_med3) skipped behind one wave-uniform branch
     if (__ballot(h)) hl.push_if(h, t);
-#else
-    hl.push_if(h, t);
-#endif
 }
 
 __device__ __forceinline__ void test_staged_one(const RecStage& st, uint32_t k, float dx, float dy, float dz,
@@ -2915,11 +2792,8 @@ __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restri
     // k_prep's OR over its pairs; the global list's entries are not in it):
     // no candidate can pass its tile test -- its misses, the same way.  Both
     // halves of a split tile skip alike.
-    const bool planned_dead = (!kSigned && bins.tile_plan && split == kSplitNone && !((d_live >> tile) & 1u))
-#if XRT_TILE_MASK
-                              || (bins.box_masks && n_glob == 0u && !((box_mask >> tile) & 1u))
-#endif
-        ;
+    const bool planned_dead = (!kSigned && bins.tile_plan && split == kSplitNone && !((d_live >> tile) & 1u)) ||
+                              (bins.box_masks && n_glob == 0u && !((box_mask >> tile) & 1u));
 
     float dx = 1.0f, dy = 0.0f, dz = 0.0f;
     float sx = 1.0f, sy = 0.0f, sz = 0.0f;         // kSigned: the once-normalised direction

@@ -64,14 +64,6 @@ constexpr double kTicksPerMs = 1e5;
 #define XRT_FRAME_SETS 4
 #endif
 constexpr int kFrameSets = XRT_FRAME_SETS;
-#ifndef XRT_DEV_SIZE_ON_PREP
-// Where a device-sized frame's k_size_lists / k_scatter_pairs run: 0 on the
-// render's stream (behind that stream's previous render), 1 on the prep stream
-// (behind the count pass: the prep chain grows), 2 on the device's host stream
-// after the count pass's event (idle in a device-pointer pipeline; no extra
-// queue): 2048^2 moving frames 47.0 / 57.5 / 41.1 us (profiles/r06ac, r06ae).
-#define XRT_DEV_SIZE_ON_PREP 2
-#endif
 // LDS a k_prep workgroup holds (its own + dynamic padding): the CU's LDS left
 // beside a render at full occupancy (XRT_RENDER_WAVES waves per SIMD, each
 // with its record stage), split over kPrepPerCu workgroups, so no more of
@@ -302,18 +294,6 @@ struct PendingFrame {
     Outputs out;
     BinBuffers bins = {};
     BinState* bin_ctl = nullptr;
-    // A device-sized frame (a moving camera): k_size_lists and k_scatter_pairs
-    // run on the render's stream ahead of the render (the prep stream holds
-    // only the count passes, so the next frame's k_prep is not queued behind them).
-    struct DevSize {
-        bool on = false;
-        uint32_t n_slots = 0, pool = 0;
-        const SlotDesc* fixed = nullptr;
-        uint32_t* flag = nullptr;
-        uint32_t* counts = nullptr;        // the count pass's counter lines (the base layout's order)
-        SlotDesc* plan_desc = nullptr;     // the device fill plan's layout (null: none)
-        uint32_t* plan_counts = nullptr;
-    } dev_size;
     HostClock::time_point t_call;
 };
 
@@ -1453,15 +1433,17 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
             flag[1] = 0u;
             fs.lazy_flags = true;
         }
-        // k_size_lists and k_scatter_pairs: launch_frame, on the render's stream
-        pf.dev_size.on = true;
-        pf.dev_size.n_slots = n_regions;
-        pf.dev_size.pool = pool;
-        pf.dev_size.fixed = bins.desc;
-        pf.dev_size.flag = flag;
-        pf.dev_size.counts = bins.counts;
-        pf.dev_size.plan_desc = dev_plan ? fs.plan_desc : nullptr;
-        pf.dev_size.plan_counts = dev_plan ? fs.plan_counts : nullptr;
+        // The lists of the frame: k_size_lists and k_scatter_pairs on the device's
+        // host stream (idle in a device-pointer pipeline, no extra queue) after
+        // the count pass's event, the preparation's event after them.  (Measured
+        // and dropped: on the render's stream they queue behind that stream's
+        // previous render, on the prep stream the next frame's k_prep queues
+        // behind them -- 2048^2 moving frames 47.0 / 57.5 us against 41.1,
+        // profiles/r06ac, r06ae.)
+        uint32_t* const pass_counts = bins.counts;     // the count pass's counter lines (the base layout's order)
+        const SlotDesc* const fixed = bins.desc;
+        SlotDesc* const plan_desc = dev_plan ? fs.plan_desc : nullptr;   // the device fill plan's layout (null: none)
+        uint32_t* const plan_counts = dev_plan ? fs.plan_counts : nullptr;
         bins.list = list;
         bins.desc = dev_plan ? fs.plan_desc : fs.dyn_desc;
         if (dev_plan) {                                // the render reads the plan's order
@@ -1470,28 +1452,17 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
         }
         bins.pairs = nullptr;
         bins.clear = nullptr;
-#if XRT_DEV_SIZE_ON_PREP
-        // k_size_lists and k_scatter_pairs behind the count pass on the prep
-        // stream (on a render stream they queue behind that stream's previous
-        // render), the preparation's event after them
-        {
-            // (2: on the device's host stream -- idle in a device-pointer
-            // pipeline, no extra queue -- after the count pass's event)
-            const hipStream_t ss = XRT_DEV_SIZE_ON_PREP == 2 ? ctx->host_stream : ps;
-            if (ss != ps) XRT_HIP(ctx, hipStreamWaitEvent(ss, prep_done, 0));
-            const PendingFrame::DevSize& d = pf.dev_size;
-            hipLaunchKernelGGL(k_size_lists, dim3((d.n_slots + 255) / 256), dim3(256), 0, ss, d.counts, d.fixed,
-                               fs.dyn_desc, d.n_slots, d.pool, bin_ctl, d.plan_desc, d.plan_counts);
-            XRT_HIP(ctx, hipGetLastError());
-            const uint32_t scatter_blocks = (uint32_t)std::min<uint64_t>((d.pool + 255u) / 256u, 2048u);
-            hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, ss, (const uint4*)fs.pairs,
-                               (const BinState*)bin_ctl, d.pool, (const SlotDesc*)fs.dyn_desc,
-                               (const float4*)fs.cull, (uint32_t)T, bins.list, d.flag);
-            XRT_HIP(ctx, hipGetLastError());
-            XRT_HIP(ctx, hipEventRecord(prep_done, ss));
-            pf.dev_size.on = false;
-        }
-#endif
+        const hipStream_t ss = ctx->host_stream;
+        if (ss != ps) XRT_HIP(ctx, hipStreamWaitEvent(ss, prep_done, 0));
+        hipLaunchKernelGGL(k_size_lists, dim3((n_regions + 255) / 256), dim3(256), 0, ss, pass_counts, fixed,
+                           fs.dyn_desc, n_regions, pool, bin_ctl, plan_desc, plan_counts);
+        XRT_HIP(ctx, hipGetLastError());
+        const uint32_t scatter_blocks = (uint32_t)std::min<uint64_t>((pool + 255u) / 256u, 2048u);
+        hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, ss, (const uint4*)fs.pairs,
+                           (const BinState*)bin_ctl, pool, (const SlotDesc*)fs.dyn_desc, (const float4*)fs.cull,
+                           (uint32_t)T, bins.list, flag);
+        XRT_HIP(ctx, hipGetLastError());
+        XRT_HIP(ctx, hipEventRecord(prep_done, ss));
     }
     if (rows > 0 && !device_sized && (rc = launch_prep(ctx, fs, p, cp, culled, bins, bin_ctl, ps, prep_done)))
         return rc;
@@ -1678,17 +1649,6 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
         if (q == hipSuccess) ++ctx->hp_launch_nowait;
         else if (q == hipErrorNotReady) XRT_HIP(ctx, hipStreamWaitEvent(stream, pf.prep_done, 0));
         else XRT_HIP(ctx, q);
-    }
-    if (pf.dev_size.on) {                          // a device-sized frame's lists (prepare_frame)
-        const PendingFrame::DevSize& d = pf.dev_size;
-        hipLaunchKernelGGL(k_size_lists, dim3((d.n_slots + 255) / 256), dim3(256), 0, stream, d.counts, d.fixed,
-                           fs.dyn_desc, d.n_slots, d.pool, bin_ctl, d.plan_desc, d.plan_counts);
-        XRT_HIP(ctx, hipGetLastError());
-        const uint32_t scatter_blocks = (uint32_t)std::min<uint64_t>((d.pool + 255u) / 256u, 2048u);
-        hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, stream, (const uint4*)fs.pairs,
-                           (const BinState*)bin_ctl, d.pool, (const SlotDesc*)fs.dyn_desc, (const float4*)fs.cull,
-                           p.num_triangles, pf.bins.list, d.flag);
-        XRT_HIP(ctx, hipGetLastError());
     }
     dim3 grid = pf.grid;
     BinBuffers bins = pf.bins;

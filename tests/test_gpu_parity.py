@@ -702,6 +702,81 @@ def test_box_masks_moving_camera_exact(dragon, monkeypatch):
     assert g["reused"] >= 6, g
 
 
+_COMMIT_CASES = {}
+
+
+def _commit_case(form, dragon):
+    """(triangles, base camera, [first, same, moved] cameras, their brute-force
+    frames, the cells of every k_prep wave's rectangle union), made once a form."""
+    if form in _COMMIT_CASES:
+        return _COMMIT_CASES[form]
+    if form == "cells":
+        tris, W = dragon, 512
+    else:
+        tris, W = np.ascontiguousarray(dragon[np.random.default_rng(7).permutation(len(dragon))]), 1024
+    H, T = W, len(tris)
+    lo, hi = xrt.mesh_bbox(tris)
+    centre = 0.5 * (np.asarray(lo, np.float64) + np.asarray(hi, np.float64))
+    base = xrt.camera_for_mesh(tris, W, H)
+    cams = [base, base, orbit_camera(base, centre, 1.0)]
+    with xrt.Context(0) as brute:
+        brute.set_kernel(xrt.XRT_KERNEL_BRUTE)
+        brute.upload_mesh(tris)
+        refs = [brute.render_rows(c) for c in cams]
+        _, fp = brute.probe_prep(base, T)
+    # footprint_regions: region r meets [min, max] iff ceil((min - 31) / 32) <= r <= floor(max / 32),
+    # clamped to the grid (32 x 32 regions at most here, so no footprint goes to the global list)
+    bb = fp[:, 0:4].astype(np.float64)
+    grid = -(-W // 32)
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(bb).all(axis=1) & (bb[:, 0] <= bb[:, 1]) & (bb[:, 2] <= bb[:, 3])
+        first = np.maximum(np.ceil((bb[:, (0, 2)] - 31.0) / 32.0), 0.0)
+        last = np.minimum(np.floor(bb[:, (1, 3)] / 32.0), grid - 1.0)
+        ok &= (first <= last).all(axis=1)
+    unions = []
+    for t0 in range(0, T, 32):                     # prep_tris = 32 below 2^18 triangles
+        k = ok[t0:t0 + 32]
+        if not k.any():
+            unions.append(0)
+            continue
+        f, l = first[t0:t0 + 32][k].min(axis=0), last[t0:t0 + 32][k].max(axis=0)
+        unions.append(int((l[0] - f[0] + 1) * (l[1] - f[1] + 1)))
+    _COMMIT_CASES[form] = (tris, cams, refs, np.asarray(unions))
+    return _COMMIT_CASES[form]
+
+
+@pytest.mark.parametrize("box_masks", ["0", "2"])
+@pytest.mark.parametrize("form", ["cells", "pairs"])
+def test_prep_commit_paths_exact(dragon, monkeypatch, form, box_masks):
+    """k_prep's two commit forms, each taken by every wave of a frame: the
+    aggregated commit (the union of the wave's region rectangles has at most
+    kAggCells = 256 cells: the dragon in file order at 512^2) and the per-pair
+    commit (more: its triangles shuffled at 1024^2) -- checked from the device's
+    own footprints, a union per 32 consecutive triangles.  With box masks off and
+    forced on, a geometry's first frame (sized on the device: the count pass
+    with its pair buffer, k_size_lists, k_scatter_pairs), the same camera again
+    and a moved one equal a fresh brute-force render bit for bit, image, L-buffer
+    and u8, and in their hit statistics."""
+    assert len(dragon) < 1 << 18
+    tris, cams, refs, unions = _commit_case(form, dragon)
+    if form == "cells":
+        assert unions.max() <= 256, unions.max()
+    else:
+        assert unions.min() > 256, unions.min()
+    monkeypatch.setenv("XRT_BOX_MASKS", box_masks)
+    with xrt.Context(0) as c:
+        c.set_kernel(xrt.XRT_KERNEL_BINNED)
+        c.upload_mesh(tris)
+        for k, cam in enumerate(cams):
+            got = c.render_rows(cam)
+            if k == 0:
+                assert c.first_frames()["device_sized"] == 1
+            for x, y in zip(got[:3], refs[k][:3]):
+                assert np.array_equal(bits(x), bits(y)), (form, box_masks, k)
+            for f in ("rays", "hits", "hit_rays", "odd_rays", "max_hits"):
+                assert getattr(got[3], f) == getattr(refs[k][3], f), (form, box_masks, k, f)
+
+
 @pytest.mark.parametrize("devices", [[0, 0]])
 def test_multi_strips_orbit_exact(dragon, devices):
     """xrt_render_rows_multi under a moving camera: its contexts size

@@ -3,7 +3,7 @@
 # config, the rocprofv3 kernel-trace means of k_prep and the render (a short
 # bench under the tracer) and the bench's own step without the tracer; then a
 # parity check of each variant (the binned-vs-brute GPU tests through XRT_LIB).
-# Usage: VARIANTS="base rank256" tools/gpu_prep_ab.sh TAG
+# Usage: VARIANTS="base batch8" tools/gpu_prep_ab.sh TAG   (batch8: built with -DXRT_BIN_BATCH=8)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
