@@ -687,6 +687,78 @@ int xrt_camera_supersample(const xrt_camera* cam, uint32_t bin, xrt_camera* out)
 int xrt_focal_spot(const xrt_camera* cam, float size_u, float size_v, uint32_t nu, uint32_t nv, xrt_camera* cams,
                    float* weight);
 
+/* --- the spectral detector: per-bin counts into energy channels ----------- */
+
+/*
+ * A detector that sees the beam's energy bins one by one (DESIGN.md section
+ * 10.9): per pixel and bin a photon count, then a num_channels x num_bins
+ * response matrix into num_channels output planes.  A row of bin energies is
+ * an energy-integrating panel, rows of 0/1 windows are a photon-counting
+ * detector.  `paths`, `open`, `weight`, `mu` and `num_bins` are exactly
+ * xrt_apply_spectrum's: num_meshes planes of num_pixels f32 path lengths, the
+ * uint16 masks (may be NULL: none set) and the table, `weight` and `mu` in HOST
+ * memory in both forms.  `response` is HOST memory in both forms too:
+ * num_channels rows of num_bins f32, each finite and >= 0 (a row of zeros is
+ * allowed).  `out` is num_channels f32 planes of num_pixels.  Pixel i has the
+ * global index g = first_index + i.  Per pixel, in f64 unless written
+ * otherwise, every operation rounded on its own (nothing is fused):
+ *   if open && open[i] != 0:  out[c][i] = -1.0f for every c     (the hole fill's marker, as L = -1)
+ *   else:
+ *     acc[c] = 0.0 for every c
+ *     for e in 0..num_bins-1:
+ *       x = 0; for m in 0..num_meshes-1: x = x + (double)mu[m][e] * ((double)paths[m][i] * 0.1)
+ *       lam = ((double)weight[e] * exp(-x)) * (double)gain      (exp as the spectrum model's)
+ *       N   = draw_mode == XRT_DETECT_NOISY ? the Poisson count of mean lam under the word w_e : lam
+ *       for c: acc[c] = acc[c] + (double)response[c * num_bins + e] * N
+ *     if read_noise > 0:  for c: acc[c] = acc[c] + (double)read_noise * z(v_c)
+ *     out[c][i] = XRT_DETECT_COUNTS ? (float)acc[c] : (float)(acc[c] / (double)gain)
+ * The count is xrt_photon_noise's sampler on the f64 mean (the search below 64,
+ * the AS241 deviate with the Cornish-Fisher term from there on), z its normal
+ * deviate.  w_e is word e & 3 of Philox4x32-10 at the counter (lo32(g),
+ * hi32(g), e >> 2, 1) under the key (lo32(seed), hi32(seed)); v_c is word c & 3
+ * at the counter (lo32(g), hi32(g), c >> 2, 2).  xrt_photon_noise's counters
+ * end in (0, 0): under one seed the three streams are disjoint, and the bins
+ * of a pixel are independent draws.  read_noise is additive Gaussian
+ * (electronic) noise in counts, added before the division by gain; a channel
+ * may go negative and is kept so.  A NaN path length propagates to every
+ * channel of its pixel; the NaN's sign and payload are unspecified.
+ *
+ * Two consequences.  Under XRT_DETECT_EXPECTED and XRT_DETECT_COUNTS with gain
+ * 1, one channel and a response of ones, `out` is xrt_apply_spectrum's
+ * L-buffer bit for bit wherever that is no NaN (the products by 1.0 are exact
+ * and the chain is the same).  With a 0/1 response and XRT_DETECT_COUNTS (no
+ * read noise) the noisy channel planes are exact integers while the sums stay
+ * below 2^24, and disjoint windows add up to the channel of all their bins
+ * exactly.
+ *
+ * XRT_ERR_ARGUMENT, with xrt_last_error naming the argument, for a NULL paths,
+ * weight, mu, response or out; what xrt_set_spectrum refuses in the table;
+ * num_channels outside 1..XRT_MAX_CHANNELS; a response that is NaN, infinite or
+ * negative; a gain that is not finite or not > 0; a read_noise that is not
+ * finite, negative, or not 0 under XRT_DETECT_EXPECTED; an unknown draw_mode or
+ * out_mode; num_pixels of 0 or more than one launch's 2^31 - 1 workgroups of
+ * 256 pixels hold; first_index + num_pixels overflowing 64 bits; an out that
+ * overlaps paths or open anywhere.  All of that is checked before the context
+ * is looked at.  xrt_spectral_detector: host buffers, synchronous.  _device:
+ * device buffers, asynchronous on `stream`; the table and the response travel
+ * with the launch, so the next call may bring others at once.  Neither touches
+ * the context's model, scene or frames in flight.  There is no xrt_multi_ form.
+ */
+#define XRT_MAX_CHANNELS 8
+#define XRT_DETECT_EXPECTED 0   /* N_e = lam_e: no draw, seed ignored, read_noise must be 0 */
+#define XRT_DETECT_NOISY    1
+#define XRT_DETECT_COUNTS    0  /* out = (float)acc */
+#define XRT_DETECT_INTENSITY 1  /* out = (float)(acc / (double)gain) */
+int xrt_spectral_detector(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* paths,
+                          const uint16_t* open, const float* weight, const float* mu, uint32_t num_bins,
+                          const float* response, uint32_t num_channels, float gain, float read_noise, uint64_t seed,
+                          uint64_t first_index, int draw_mode, int out_mode, float* out);
+int xrt_spectral_detector_device(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* d_paths,
+                                 const uint16_t* d_open, const float* weight, const float* mu, uint32_t num_bins,
+                                 const float* response, uint32_t num_channels, float gain, float read_noise,
+                                 uint64_t seed, uint64_t first_index, int draw_mode, int out_mode, float* d_out,
+                                 void* stream);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

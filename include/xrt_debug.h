@@ -292,6 +292,17 @@ int xrt_host_area_integrate(uint32_t width, uint32_t height, uint32_t bin_x, uin
                             uint32_t num_planes, const float* weight, const float* image, float* out, uint8_t* out_u8);
 
 /*
+ * Test hook of the spectral detector.  Host code, no device:
+ * xrt_spectral_detector's pixel function -- the one k_spectral_detector calls,
+ * compiled for the host -- over whole buffers, arguments and checks as
+ * xrt_spectral_detector's, host buffers.
+ */
+int xrt_host_spectral_detector(uint64_t num_pixels, uint32_t num_meshes, const float* paths, const uint16_t* open,
+                               const float* weight, const float* mu, uint32_t num_bins, const float* response,
+                               uint32_t num_channels, float gain, float read_noise, uint64_t seed, uint64_t first_index,
+                               int draw_mode, int out_mode, float* out);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -33,6 +33,8 @@ __all__ = [
     "XRT_MAX_LSF_TAPS", "lsf_gaussian", "host_lsf", "detector_response",
     "XRT_ORDER_PROJECTIONS", "XRT_ORDER_SINOGRAMS", "host_logf", "host_log_projection", "log_projection",
     "XRT_NOISE_INTENSITY", "XRT_NOISE_COUNTS", "host_philox4x32", "host_poisson", "host_photon_noise", "photon_noise",
+    "XRT_MAX_CHANNELS", "XRT_DETECT_EXPECTED", "XRT_DETECT_NOISY", "XRT_DETECT_COUNTS", "XRT_DETECT_INTENSITY",
+    "host_spectral_detector", "spectral_detector",
     "XRT_MAX_SOURCES", "XRT_MAX_BIN", "supersampled_camera", "focal_spot", "host_area_integrate", "area_integrate",
 ]
 
@@ -411,6 +413,57 @@ def area_integrate(image, bin=1, weights=None, u8=False, device: int = 0):
         return ctx.area_integrate(image, bin, weights, u8)
 
 
+def _detector_arrays(paths, open, weights, mu, response):
+    """The spectral detector's host arguments: (paths (M, ...) f32, open uint16 of a plane's shape or None,
+    weights (K,), mu (M, K), response (C, K))."""
+    w, mu = _spectrum_arrays(weights, mu)
+    p = np.ascontiguousarray(paths, dtype=np.float32)
+    if p.ndim < 1 or p.shape[0] != mu.shape[0]:
+        raise ValueError(f"paths must hold {mu.shape[0]} planes, got shape {p.shape}")
+    o = None if open is None else np.ascontiguousarray(open, dtype=np.uint16)
+    if o is not None and o.shape != p.shape[1:]:
+        raise ValueError(f"open must have a plane's shape {p.shape[1:]}, got {o.shape}")
+    r = _detector_response_rows(response, w.size)
+    return p, o, w, mu, r
+
+
+def _detector_response_rows(response, num_bins):
+    r = np.ascontiguousarray(response, dtype=np.float32)
+    if r.ndim == 1:
+        r = r.reshape(1, -1)
+    if r.ndim != 2 or r.shape[1] != num_bins:
+        raise ValueError(f"response must be (channels, {num_bins}), got shape {r.shape}")
+    return r
+
+
+def _detector_modes(noisy, counts):
+    return (_abi.XRT_DETECT_NOISY if noisy else _abi.XRT_DETECT_EXPECTED,
+            _abi.XRT_DETECT_COUNTS if counts else _abi.XRT_DETECT_INTENSITY)
+
+
+def host_spectral_detector(paths, open, weights, mu, response, gain=1.0, seed=0, noisy=True, counts=True,
+                           read_noise=0.0, first_index=0) -> np.ndarray:
+    """Context.spectral_detector in the device's arithmetic on the host (xrt_host_spectral_detector, a test
+    hook)."""
+    p, o, w, mu, r = _detector_arrays(paths, open, weights, mu, response)
+    out = np.empty((r.shape[0],) + p.shape[1:], np.float32)
+    draw, mode = _detector_modes(noisy, counts)
+    rc = _abi.load().xrt_host_spectral_detector(
+        out[0].size, mu.shape[0], _fptr(p), _u16ptr(o) if o is not None else None, _fptr(w), _fptr(mu), w.size,
+        _fptr(r), r.shape[0], float(gain), float(read_noise), int(seed), int(first_index), draw, mode, _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_spectral_detector")
+    return out
+
+
+def spectral_detector(paths, open, weights, mu, response, gain=1.0, seed=0, noisy=True, counts=True,
+                      read_noise=0.0, first_index=0, device: int = 0) -> np.ndarray:
+    """The channel planes of Context.spectral_detector, on a context of its own on `device`."""
+    with Context(device) as ctx:
+        return ctx.spectral_detector(paths, open, weights, mu, response, gain, seed, noisy, counts, read_noise,
+                                     first_index)
+
+
 class Context:
     """One xrt_context (one device).  Not thread-safe."""
 
@@ -599,6 +652,36 @@ class Context:
                                                  d_open or None, _fptr(w), _fptr(mu), w.size, d_lbuffer or None,
                                                  stream or None)
         self._check(rc, "xrt_apply_spectrum_device")
+
+    def spectral_detector(self, paths, open, weights, mu, response, gain=1.0, seed=0, noisy=True, counts=True,
+                          read_noise=0.0, first_index=0):
+        """The spectral detector over render_paths' planes ((M, ...) f32 and the masks, or None) under the table
+        (weights[K], mu[M, K]) and the response (C, K): per pixel and bin a Poisson count of mean gain *
+        weight * exp(-x) -- noisy=False: the mean itself --, drawn from (seed, first_index + the pixel's flat
+        index, the bin) alone, summed into C channels under the response, plus read_noise (counts, Gaussian)
+        a channel; as counts or -- counts=False -- divided by gain.  -1 where the mask is set.  (C, ...)."""
+        p, o, w, mu, r = _detector_arrays(paths, open, weights, mu, response)
+        out = np.empty((r.shape[0],) + p.shape[1:], np.float32)
+        draw, mode = _detector_modes(noisy, counts)
+        self._check(self._lib.xrt_spectral_detector(
+            self._ctx, out[0].size, mu.shape[0], _fptr(p), _u16ptr(o) if o is not None else None, _fptr(w), _fptr(mu),
+            w.size, _fptr(r), r.shape[0], float(gain), float(read_noise), int(seed), int(first_index), draw, mode,
+            _fptr(out)), "xrt_spectral_detector")
+        return out
+
+    def spectral_detector_device(self, num_pixels: int, d_paths: int, d_open: int, weights, mu, response, d_out: int,
+                                 gain: float = 1.0, seed: int = 0, noisy: bool = True, counts: bool = True,
+                                 read_noise: float = 0.0, first_index: int = 0, stream: int = 0):
+        """spectral_detector over device buffers (raw pointers; d_out holds C planes of num_pixels; the table
+        and the response are host data and travel with the launch); asynchronous on `stream`."""
+        w, mu = _spectrum_arrays(weights, mu)
+        r = _detector_response_rows(response, w.size)
+        draw, mode = _detector_modes(noisy, counts)
+        rc = self._lib.xrt_spectral_detector_device(
+            self._ctx, int(num_pixels), mu.shape[0], d_paths or None, d_open or None, _fptr(w), _fptr(mu), w.size,
+            _fptr(r), r.shape[0], float(gain), float(read_noise), int(seed), int(first_index), draw, mode,
+            d_out or None, stream or None)
+        self._check(rc, "xrt_spectral_detector_device")
 
     def detector_response(self, image, lsf_x, lsf_y=None, out=True, u8=True):
         """The detector's line-spread function over an (H, W) image or a (P, H, W) stack of them (taps as

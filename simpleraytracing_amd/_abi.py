@@ -46,6 +46,11 @@ XRT_ORDER_PROJECTIONS = 0
 XRT_ORDER_SINOGRAMS = 1
 XRT_NOISE_INTENSITY = 0
 XRT_NOISE_COUNTS = 1
+XRT_MAX_CHANNELS = 8
+XRT_DETECT_EXPECTED = 0
+XRT_DETECT_NOISY = 1
+XRT_DETECT_COUNTS = 0
+XRT_DETECT_INTENSITY = 1
 XRT_MAX_SOURCES = 64
 XRT_MAX_BIN = 8
 
@@ -193,6 +198,13 @@ XRT_SYMBOLS = {
     "xrt_photon_noise": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),
     "xrt_photon_noise_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, ctypes.c_float, _u64, _u64, ctypes.c_int, _vp,
                                                _vp]),
+    "xrt_spectral_detector": (ctypes.c_int, [_CtxP, _u64, _u32, _fp, _u16p, _fp, _fp, _u32, _fp, _u32, ctypes.c_float,
+                                             ctypes.c_float, _u64, _u64, ctypes.c_int, ctypes.c_int, _fp]),
+    "xrt_spectral_detector_device": (ctypes.c_int, [_CtxP, _u64, _u32, _vp, _vp, _fp, _fp, _u32, _fp, _u32,
+                                                    ctypes.c_float, ctypes.c_float, _u64, _u64, ctypes.c_int,
+                                                    ctypes.c_int, _vp, _vp]),
+    "xrt_host_spectral_detector": (ctypes.c_int, [_u64, _u32, _fp, _u16p, _fp, _fp, _u32, _fp, _u32, ctypes.c_float,
+                                                  ctypes.c_float, _u64, _u64, ctypes.c_int, ctypes.c_int, _fp]),
     "xrt_host_philox4x32": (None, [_u32p, _u32p, _u32p]),
     "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
     "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),

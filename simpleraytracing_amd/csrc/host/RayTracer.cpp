@@ -410,6 +410,41 @@ void applySpectrum(Image& image, const std::vector<std::vector<float>>& paths, c
           "xrt_hole_fill");
 }
 
+void applySpectralDetector(std::vector<Image>& channels, const std::vector<std::vector<float>>& paths,
+                           const std::vector<unsigned short>& open, const std::vector<float>& weight,
+                           const std::vector<float>& mu, const std::vector<float>& response, float gain, float read_noise,
+                           unsigned long long seed, unsigned long long first_index, bool noisy)
+{
+    if (channels.empty()) throw std::invalid_argument("applySpectralDetector: no channel images");
+    const unsigned width = channels[0].getWidth(), height = channels[0].getHeight();
+    const size_t n = (size_t)width * height;
+    for (const Image& channel : channels)
+        if (channel.getWidth() != width || channel.getHeight() != height)
+            throw std::invalid_argument("applySpectralDetector: the channel images differ in size");
+    if (weight.empty() || paths.empty() || mu.size() != paths.size() * weight.size())
+        throw std::invalid_argument("applySpectralDetector: one coefficient per mesh and bin");
+    if (response.size() != channels.size() * weight.size())
+        throw std::invalid_argument("applySpectralDetector: one response per channel and bin");
+    if (open.size() != n) throw std::invalid_argument("applySpectralDetector: the mask is not of the images' size");
+    std::vector<float> planes;
+    planes.reserve(n * paths.size());
+    for (const std::vector<float>& plane : paths) {
+        if (plane.size() != n) throw std::invalid_argument("applySpectralDetector: a plane is not of the images' size");
+        planes.insert(planes.end(), plane.begin(), plane.end());
+    }
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    std::vector<float> out(n * channels.size());
+    check(ctx, xrt_spectral_detector(ctx, n, (uint32_t)paths.size(), planes.data(), open.data(), weight.data(), mu.data(),
+                                     (uint32_t)weight.size(), response.data(), (uint32_t)channels.size(), gain,
+                                     read_noise, seed, first_index, noisy ? XRT_DETECT_NOISY : XRT_DETECT_EXPECTED,
+                                     XRT_DETECT_INTENSITY, out.data()),
+          "xrt_spectral_detector");
+    for (size_t c = 0; c < channels.size(); ++c)
+        check(ctx, xrt_hole_fill(ctx, width, height, out.data() + c * n, channels[c].getData(), nullptr), "xrt_hole_fill");
+}
+
 void applyDetectorResponse(Image& image, const std::vector<float>& lsf_x, const std::vector<float>& lsf_y)
 {
     const size_t n = (size_t)image.getWidth() * image.getHeight();

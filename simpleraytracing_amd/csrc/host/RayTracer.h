@@ -133,6 +133,22 @@ void applySpectrum(Image& output_image, const std::vector<std::vector<float>>& p
                    const std::vector<unsigned short>& open, const std::vector<float>& weight,
                    const std::vector<float>& mu, std::vector<float>* lbuffer = nullptr);
 
+// The spectral detector (xrt_spectral_detector, XRT_DETECT_INTENSITY) over such
+// planes: per pixel and energy bin a photon count of mean gain * weight *
+// exp(-x) -- drawn when `noisy`, from seed, first_index + the pixel's index and
+// the bin alone; the mean itself otherwise, and then read_noise must be 0 --,
+// summed into channels.size() channels under `response` (one row of
+// weight.size() values per channel, one after another), plus read_noise
+// (additive Gaussian noise, in counts) a channel, divided by gain.  Every
+// channel image must come with the planes' width and height; the hole fill
+// runs on each as applySpectrum's does on its image.  Projection p of a scan
+// of W x H images passes first_index = p * W * H.  One device.
+void applySpectralDetector(std::vector<Image>& channels, const std::vector<std::vector<float>>& paths,
+                           const std::vector<unsigned short>& open, const std::vector<float>& weight,
+                           const std::vector<float>& mu, const std::vector<float>& response, float gain = 1.0f,
+                           float read_noise = 0.0f, unsigned long long seed = 0, unsigned long long first_index = 0,
+                           bool noisy = false);
+
 // The detector response (xrt_detector_response): the image under a separable
 // line-spread function, lsf_x along the rows and lsf_y down the columns (odd
 // counts, at most XRT_MAX_LSF_TAPS; applied as written -- a correlation --,

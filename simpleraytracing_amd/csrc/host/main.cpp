@@ -87,6 +87,22 @@
 //                              --log-projection and --sinogram follow in their order.
 //                              Refused with -g N, --rows, --batch, --paths and --lbuffer
 //                              (an integrated frame has no single L-buffer)
+//       --detector FILE        the spectral detector, with --paths --spectrum FILE2: per
+//                              pixel and energy bin a photon count, summed into energy
+//                              channels.  FILE is text: one line of K responses (finite,
+//                              >= 0) per channel, at most 8 ('#' starts a comment); a
+//                              line of bin energies is an energy-integrating panel, lines
+//                              of 0/1 windows a photon-counting detector.  Writes
+//                              NAME.c<c>.EXT per channel, after the model's hole fill;
+//                              NAME.EXT stays what --paths --spectrum writes.  Without
+//                              --noise: the expected values at gain 1.  With --noise
+//                              GAIN[:SEED] the draw happens inside the detector, a count
+//                              per bin, and the channels are divided by GAIN; projection
+//                              p of --turntable draws the noise of pixels p*W*H onwards.
+//                              Not with --lsf, --lsf-gaussian, --log-projection,
+//                              --sinogram, --supersample, --focal-spot, -g, --rows, --batch
+//       --read-noise SIGMA     with --detector and --noise: additive Gaussian (electronic)
+//                              noise of SIGMA counts (finite, >= 0) on every channel
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -140,6 +156,8 @@ void showUsage(const std::string& prog)
               << "\t--noise GAIN[:SEED]\t\tPhoton noise on the written image: each pixel a Poisson count of mean I * GAIN, divided by GAIN (after --lsf, before --log-projection; SEED defaults to 0); --u8 and --lbuffer stay as rendered\n"
               << "\t--supersample B\t\t\tPixel-area integration: render W*B x H*B samples (B in 1..8) and write each pixel's mean over its B x B samples; -s stays the written size\n"
               << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
+              << "\t--detector FILE\t\t\tSpectral detector, with --paths --spectrum: FILE holds one line of K responses per energy channel (at most 8); writes NAME.c<c>.EXT per channel; with --noise GAIN[:SEED] a Poisson count per bin, divided by GAIN, otherwise the expected values at gain 1\n"
+              << "\t--read-noise SIGMA\t\tWith --detector and --noise: additive Gaussian noise of SIGMA counts on every channel\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -180,6 +198,10 @@ struct Options {
     bool focal_spot = false;                   // --focal-spot UxV[:NUxNV]
     float spot_u = 0.0f, spot_v = 0.0f;
     unsigned spot_nu = 3, spot_nv = 3;
+    bool detector = false;                     // --detector FILE: one row of K responses per channel
+    std::vector<std::vector<float>> detector_rows;
+    bool read_noise_set = false;               // --read-noise SIGMA
+    float read_noise = 0.0f;
 };
 
 // A whole, non-negative decimal number.
@@ -313,6 +335,55 @@ void read_spectrum(const std::string& path, std::vector<float>& weight, std::vec
     }
     if (weight.empty()) throw std::runtime_error("--spectrum: " + path + " holds no weights");
     if (mu.empty()) throw std::runtime_error("--spectrum: " + path + " holds no mesh's coefficients");
+}
+
+// --detector FILE: every data line is one channel's responses ('#' starts a
+// comment, blank lines are skipped).  The lines' length is checked against the
+// spectrum's bins once every option is read.
+void read_detector(const std::string& path, std::vector<std::vector<float>>& rows)
+{
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("--detector: cannot read " + path);
+    std::string line;
+    for (unsigned n = 1; std::getline(in, line); ++n) {
+        line = line.substr(0, line.find('#'));
+        std::istringstream fields(line);
+        std::vector<float> row;
+        for (std::string f; fields >> f;) {
+            size_t used = 0;
+            float v = 0.0f;
+            try {
+                v = std::stof(f, &used);
+            } catch (const std::exception&) {
+                used = 0;
+            }
+            if (used != f.size() || !std::isfinite(v) || v < 0.0f)
+                throw std::runtime_error("--detector: " + path + ":" + std::to_string(n) + ": '" + f +
+                                         "' is not a response (a finite number, >= 0)");
+            row.push_back(v);
+        }
+        if (row.empty()) continue;
+        if (rows.size() == XRT_MAX_CHANNELS)
+            throw std::runtime_error("--detector: " + path + ":" + std::to_string(n) + ": more than " +
+                                     std::to_string(XRT_MAX_CHANNELS) + " channels");
+        rows.push_back(row);
+    }
+    if (rows.empty()) throw std::runtime_error("--detector: " + path + " holds no channel");
+}
+
+// --read-noise SIGMA
+float parse_read_noise(const std::string& arg)
+{
+    size_t used = 0;
+    float v = 0.0f;
+    try {
+        v = std::stof(arg, &used);
+    } catch (const std::exception&) {
+        used = 0;
+    }
+    if (arg.empty() || used != arg.size() || !std::isfinite(v) || v < 0.0f)
+        throw std::runtime_error("--read-noise SIGMA: SIGMA is a finite number of counts, >= 0");
+    return v;
 }
 
 // A tap count the library takes.
@@ -518,6 +589,13 @@ Options processCmd(int argc, char** argv)
                 throw std::runtime_error("--supersample B: '" + b + "' is not a factor in 1.." + std::to_string(XRT_MAX_BIN));
         } else if (a == "--focal-spot") {
             parse_focal_spot(parse_str(argv[0], argc, argv, i), o);
+        } else if (a == "--detector") {
+            o.detector = true;
+            o.detector_rows.clear();
+            read_detector(parse_str(argv[0], argc, argv, i), o.detector_rows);
+        } else if (a == "--read-noise") {
+            o.read_noise = parse_read_noise(parse_str(argv[0], argc, argv, i));
+            o.read_noise_set = true;
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -550,7 +628,20 @@ Options processCmd(int argc, char** argv)
         throw std::runtime_error("--paths, --signed and --materials are three models: give one");
     if (o.paths && (o.rows || o.batch || o.gpus > 1))
         throw std::runtime_error("--paths renders whole frames on one GPU");
-    if (o.turntable && (o.paths || o.batch || o.gpus > 1))
+    if (o.detector) {                           // (the channels do not go through the rest of the chain yet)
+        if (!o.paths || !o.spectrum) throw std::runtime_error("--detector needs --paths --spectrum FILE: it reads the planes under the table");
+        if (!o.lsf_x.empty() || o.log_projection || !o.sinogram.empty() || o.supersample || o.focal_spot || o.gpus > 1 ||
+            o.rows || o.batch)
+            throw std::runtime_error("--detector writes its channels as detected: not with --lsf, --lsf-gaussian, "
+                                     "--log-projection, --sinogram, --supersample, --focal-spot, -g N, --rows or --batch");
+        for (const std::vector<float>& row : o.detector_rows)
+            if (row.size() != o.spectrum_weight.size())
+                throw std::runtime_error("--detector: " + std::to_string(row.size()) + " responses in a line, " +
+                                         std::to_string(o.spectrum_weight.size()) + " bins in --spectrum's table");
+    }
+    if (o.read_noise_set && (!o.detector || !o.noise))
+        throw std::runtime_error("--read-noise needs --detector FILE and --noise GAIN[:SEED]: it is added to the drawn channels");
+    if (o.turntable && ((o.paths && !o.detector) || o.batch || o.gpus > 1))
         throw std::runtime_error("--turntable renders on one GPU, without --paths, --batch and -g");
     if (o.lsf_file && o.lsf_gauss) throw std::runtime_error("--lsf and --lsf-gaussian are two detector responses: give one");
     if (!o.lsf_x.empty() && (o.gpus > 1 || o.rows))
@@ -714,6 +805,16 @@ int main(int argc, char** argv)
                 plane.saveTextFile(stem + ".open" + suffix);
                 if (opt.spectrum)                     // (without a table the planes are the output)
                     applySpectrum(image, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.lbuffer.empty() ? nullptr : &lb);
+                if (opt.detector) {                   // the channels beside the image; a scan's projection draws its own
+                    std::vector<float> response;
+                    for (const std::vector<float>& row : opt.detector_rows) response.insert(response.end(), row.begin(), row.end());
+                    std::vector<Image> channels(opt.detector_rows.size(), Image(opt.width, opt.height, 0.0f));
+                    applySpectralDetector(channels, planes, open, opt.spectrum_weight, opt.spectrum_mu, response,
+                                          opt.noise ? opt.noise_gain : 1.0f, opt.noise ? opt.read_noise : 0.0f,
+                                          opt.noise_seed, (unsigned long long)projection * opt.width * opt.height, opt.noise);
+                    for (size_t c = 0; c < channels.size(); ++c)
+                        channels[c].saveTextFile(stem + ".c" + std::to_string(c) + suffix);
+                }
             } else if (area) {                        // every sub-source at the finer size, then one integration
                 std::vector<RayTracerInfo> sources(1, info);
                 if (opt.focal_spot) sources = focalSpotSources(info, opt.spot_u, opt.spot_v, opt.spot_nu, opt.spot_nv);
@@ -749,7 +850,7 @@ int main(int argc, char** argv)
                 out = &strip;
             }
             if (opt.paths && !opt.spectrum) return 0;
-            if (opt.log_projection || opt.noise) {    // (whole frames: out is the image)
+            if (opt.log_projection || (opt.noise && !opt.detector)) {    // (whole frames: out is the image)
                 // the 8-bit image is the rendered intensity's (the 0..80 window means nothing for line integrals)
                 if (!opt.u8.empty()) image.savePGMFile(opt.u8, 0.0f, 80.0f);
                 Image written(image);

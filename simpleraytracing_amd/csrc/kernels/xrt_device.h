@@ -1269,4 +1269,214 @@ inline AreaPlan area_plan(uint32_t W, uint64_t rows, uint32_t bin_x, uint32_t bi
     return plan;
 }
 
+// ---------------------------------------------------------------------------
+// The spectral detector (the contract is include/xrt.h's): per
+// pixel and energy bin a count of mean gain * weight * exp(-x), then a
+// channels x bins response matrix into channel sums, in f64, every step rounded
+// on its own.  The bins go a quad at a time: one Philox evaluation gives a
+// quad's four words, and a quad's four exp run side by side.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMaxChannels = 8;
+constexpr uint32_t kDetectorThreads = 256;
+
+// What k_spectral_detector takes by value (a launch owns its tables).  The
+// spectrum, quad by quad -- the coefficients of mesh m for the four bins of
+// quad q are neighbours, mu[(q * kMaxMeshes + m) * 4 + r] for bin 4 q + r:
+// one 16-byte scalar load at an offset known at compile time, used up by the
+// mesh's four sums before the next mesh's is needed -- and +0.0f past the
+// scene's meshes and past num_bins; weight +0.0f past num_bins.  The response
+// with a row stride of kMaxBins (rows past num_channels and bins past num_bins
+// are +0.0f), the scalars, and what every channel of a pixel without a hit
+// gets under XRT_DETECT_EXPECTED (the host's own run of detector_pixel over
+// zero distances).
+struct DetectorSpectrum {
+    float weight[kMaxBins];
+    float mu[kMaxBins * kMaxMeshes];           // [detector_mu_index(m, e)]
+    uint32_t num_bins;
+};
+__host__ __device__ constexpr uint32_t detector_mu_index(uint32_t m, uint32_t e)
+{
+    return ((e >> 2) * kMaxMeshes + m) * 4u + (e & 3u);
+}
+struct DetectorTable {
+    float response[kMaxChannels * kMaxBins];   // [c * kMaxBins + e]
+    float miss[kMaxChannels];
+    float gain;
+    float read_noise;
+    uint32_t num_channels;
+    uint32_t counts;                           // XRT_DETECT_COUNTS: 1
+    // what the kernel needs only behind its bin loop, read from the argument segment there and so in no register
+    // across the loop: the masks again, the output planes, their stride in pixels, and the seed again for the
+    // read noise
+    const uint16_t* open;
+    float* out;
+    uint64_t plane;
+    uint64_t seed;
+};
+static_assert(sizeof(DetectorSpectrum) + sizeof(DetectorTable) + 64u <= 4096u, "k_spectral_detector's argument segment");
+
+// Four xrt_exp at once, bit for bit xrt_exp of each: the main path of all four
+// first and without a branch -- the table index is masked, so it is formed and
+// loaded for any argument, and the four pairs of loads are in flight together
+// --, then each value's class picks its result as xrt_exp's branches do: below
+// 2^-54 in magnitude 1 + x, from 512 on the special case, from 1024 on the
+// limits (0 for a negative argument, -inf included; +inf for a positive one;
+// 1 + x for a NaN).
+__host__ __device__ __forceinline__ void xrt_exp_quad(const double (&x)[4], double (&y)[4])
+{
+    constexpr double kInvLn2N = 0x1.71547652b82fep0 * 128;
+    constexpr double kNegLn2hiN = -0x1.62e42fefa0000p-8;
+    constexpr double kNegLn2loN = -0x1.cf79abc9e3b3ap-47;
+    constexpr double kShift = 0x1.8p52;
+    constexpr double kC2 = 0x1.ffffffffffdbdp-2;
+    constexpr double kC3 = 0x1.555555555543cp-3;
+    constexpr double kC4 = 0x1.55555cf172b91p-5;
+    constexpr double kC5 = 0x1.1111167a4d017p-7;
+    uint64_t ki[4], top[4], tail_bits[4], scale_bits[4];
+    double r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double kd = __builtin_fma(kInvLn2N, x[j], kShift);
+        ki[j] = xrt_double_as_u64(kd);
+        kd -= kShift;
+        r[j] = __builtin_fma(kd, kNegLn2loN, __builtin_fma(kd, kNegLn2hiN, x[j]));
+        top[j] = ki[j] << 45;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t idx = 2u * (uint32_t)(ki[j] & 127u);
+        tail_bits[j] = xrt_exp_tab(idx);
+        scale_bits[j] = xrt_exp_tab(idx + 1u);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint64_t sbits = scale_bits[j] + top[j];
+        const double r2 = r[j] * r[j];
+        const double tmp = __builtin_fma(r2 * r2, __builtin_fma(r[j], kC5, kC4),
+                                         __builtin_fma(r2, __builtin_fma(r[j], kC3, kC2), xrt_u64_as_double(tail_bits[j]) + r[j]));
+        const double scale = xrt_u64_as_double(sbits);
+        double v = __builtin_fma(scale, tmp, scale);
+        // the class by t = the exponent field less 0x3c9, against 0, 63 and 64 alone: below 0 |x| < 2^-54, from
+        // 63 on |x| >= 512, from 64 on |x| >= 1024, inf or NaN (few constants: they sit in scalar registers)
+        const int32_t t = (int32_t)((uint32_t)(xrt_double_as_u64(x[j]) >> 52) & 0x7ffu) - 0x3c9;
+        v = t < 0 ? 1.0 + x[j] : v;
+        if (t >= 63) {
+            if (t >= 64)                               // xrt_exp's limits: 0 below, +inf above, 1 + x for a NaN
+                v = x[j] < 0.0 ? 0.0 : x[j] != x[j] ? 1.0 + x[j] : __builtin_inf();
+            else
+                v = xrt_exp_special(tmp, sbits, ki[j]);
+        }
+        y[j] = v;
+    }
+}
+
+// Four counts at once, each xrt_poisson_from_word of its mean and word: the
+// means of 64 and above go through the normal branch one after another, those
+// below 64 through ONE search loop stepped together as k_photon_noise steps its
+// four pixels -- step k divides by the same (double)k for each and a mean drops
+// out where the contract's loop ends --, their four exp(-lam) side by side.
+__host__ __device__ __forceinline__ void xrt_poisson_quad(const double (&lam)[4], const uint32_t (&w)[4], double (&N)[4])
+{
+    bool small[4], any_small = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        small[e] = lam[e] >= 0.0 && lam[e] < kNoiseSmallMean;
+        any_small |= small[e];
+        N[e] = lam[e] >= 0.0 ? lam[e] : __builtin_nan("");              // +inf stays; a finite mean's is set below
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (lam[e] >= kNoiseSmallMean && lam[e] != __builtin_inf()) N[e] = xrt_poisson_normal(lam[e], w[e]);
+    if (any_small) {
+        // a mean that takes no part searches under u = 0, which no sum is below: whether a mean is still in the
+        // search is u > s, formed where it is asked and kept in no register between the steps
+        double u[4], p[4], s[4], neg[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) neg[e] = small[e] ? -lam[e] : 0.0;
+        xrt_exp_quad(neg, p);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            u[e] = small[e] ? xrt_uniform_from_word(w[e]) : 0.0;
+            s[e] = p[e];
+            if (small[e]) N[e] = 0.0;
+        }
+        for (uint32_t k = 1; k <= kNoiseSearchCap; ++k) {
+            if (!((u[0] > s[0]) | (u[1] > s[1]) | (u[2] > s[2]) | (u[3] > s[3]))) break;
+            const double kd = (double)k;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (!(u[e] > s[e])) continue;
+                p[e] = (p[e] * lam[e]) / kd;
+                s[e] = s[e] + p[e];
+                N[e] = kd;
+            }
+        }
+    }
+}
+
+// One pixel's channel sums acc[0 .. kC) before the output conversion, for the
+// pixel of global index g whose mask is clear.  quad_x(q, x) adds to x[0..3]
+// (+0.0 on entry) the path sums of the bins 4 q .. 4 q + 3, each bin's meshes
+// in ascending order: x[r] = x[r] + (double)mu * ((double)distance * 0.1), one
+// mesh after another -- the caller knows where its distances are (registers,
+// LDS, host arrays); a mesh of distance +0.0f may be left out (exact, as
+// apply_bins').  kC >= the channels is a compile-time bound, so that the sums
+// keep static indices: resp(c, e) is +0.0f past the channels and bins (acc
+// starts at +0.0 and +0.0 * N = +0.0 leaves it as it is), weight(e) +0.0f for a
+// bin past num_bins in the last quad: its x is dropped (an infinite path makes
+// it 0 * inf), its mean and its count are 0.  read_noise() and tail_seed() are
+// asked after the bins, where they are needed.
+template <uint32_t kC, bool kNoisy, typename QuadX, typename Weight, typename Resp, typename ReadNoise, typename TailSeed>
+__host__ __device__ __forceinline__ void detector_pixel(uint32_t num_bins, QuadX quad_x, Weight weight, Resp resp, float gain,
+                                                        uint64_t seed, uint64_t g, ReadNoise read_noise, TailSeed tail_seed,
+                                                        double (&acc)[kC])
+{
+    const double gd = (double)gain;
+#pragma unroll
+    for (uint32_t c = 0; c < kC; ++c) acc[c] = 0.0;
+    for (uint32_t q = 0; 4u * q < num_bins; ++q) {
+        double nx[4], y[4], N[4];
+        double x[4] = {0.0, 0.0, 0.0, 0.0};
+        quad_x(q, x);
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) nx[r] = 4u * q + r < num_bins ? -x[r] : -0.0;   // (0 * inf past num_bins)
+        xrt_exp_quad(nx, y);
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) N[r] = ((double)weight(4u * q + r) * y[r]) * gd;
+        if (kNoisy) {
+            uint32_t w[4];
+            xrt_philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), q, 1u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+            double lam[4];
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) lam[r] = N[r];
+            xrt_poisson_quad(lam, w, N);
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {
+#pragma unroll
+            for (uint32_t c = 0; c < kC; ++c) acc[c] = acc[c] + (double)resp(c, 4u * q + r) * N[r];
+        }
+    }
+    if (kNoisy) {
+        const float rn = read_noise();
+        if (rn > 0.0f) {
+            const uint64_t s2 = tail_seed();
+#pragma unroll
+            for (uint32_t c4 = 0; 4u * c4 < kC; ++c4) {
+                uint32_t v[4];
+                xrt_philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), c4, 2u, (uint32_t)s2, (uint32_t)(s2 >> 32), v);
+#pragma unroll
+                for (uint32_t r = 0; r < 4 && 4u * c4 + r < kC; ++r)
+                    acc[4u * c4 + r] = acc[4u * c4 + r] + (double)rn * xrt_normal_from_word(v[r]);
+            }
+        }
+    }
+}
+
+// One channel's output from its sum: XRT_DETECT_COUNTS or XRT_DETECT_INTENSITY.
+__host__ __device__ __forceinline__ float xrt_detector_output(double acc, float gain, bool counts)
+{
+    return counts ? (float)acc : (float)(acc / (double)gain);
+}
+
 }  // namespace XRT_KERNEL_NS

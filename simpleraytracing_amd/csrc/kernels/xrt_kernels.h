@@ -4083,4 +4083,105 @@ __global__ __launch_bounds__(kAreaThreads) void k_area_integrate(const float* __
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_spectral_detector: the spectral detector over the paths
+// model's planes, in k_apply_spectrum's shape: one lane a pixel, the wave's
+// live meshes parked in its LDS in scene order, their count bounded at compile
+// time so that the distances keep static register indices.  kM bounds the
+// scene's meshes (4 or kMaxMeshes: the host picks by num_meshes, and a scene
+// of at most four meshes gets a kernel sized for four -- fewer registers, more
+// waves); under kM = kMaxMeshes a wave with at most four live meshes still
+// takes the chain of four, and one with more loops over its parked meshes,
+// each distance read from the LDS where it is used.  What is needed only
+// behind the bin loop (the output planes, their stride, the channel count, the
+// read noise's seed and, in a noisy wave, the masks) is read from
+// DetectorTable there, so that it occupies no scalar register across the loop,
+// which is full of hoisted constants.  detector_pixel takes the bins a quad at a time: a
+// quad's coefficients, weights and responses are scalar loads from the
+// argument segment (both tables travel by value: a launch owns them), its four
+// exp run side by side with their table loads in flight together, one Philox
+// evaluation gives its four words and its small means share one search loop.
+// kC bounds the channels (1, 4 or 8; rows past num_channels are zero and are
+// not stored), kNoisy is the draw mode.  A wave with no live mesh and no mask
+// stores det.miss without an exp -- under XRT_DETECT_EXPECTED only: a noisy
+// miss still draws.  Indices are 64-bit.  No scratch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kDetectorFewMeshes = 4;
+
+template <uint32_t kM, uint32_t kC, bool kNoisy>
+__global__ __launch_bounds__(kDetectorThreads) void k_spectral_detector(const float* __restrict__ paths,
+                                                                        const uint16_t* __restrict__ open, size_t n,
+                                                                        uint32_t M, const DetectorSpectrum tab,
+                                                                        const DetectorTable det, uint64_t seed,
+                                                                        uint64_t first_index)
+{
+    static_assert(kM == kDetectorFewMeshes || kM == kMaxMeshes, "the two mesh bounds");
+    __shared__ float s_park[kDetectorThreads / 64u][kM * 64u];
+    const uint32_t lane = threadIdx.x & 63u;
+    float* park = s_park[wave_in_block()];
+    const size_t i = (size_t)blockIdx.x * kDetectorThreads + threadIdx.x;
+    if (i >= n) return;                               // (no barrier below: the wave goes on with its lanes inside)
+    const uint32_t flags = !kNoisy && open ? open[i] : 0u;     // (a noisy wave reads its masks behind the bins)
+    unsigned long long meshes = 0ull;                 // wave-uniform: the parked meshes' indices
+    uint32_t n_live = 0;
+    for (uint32_t m = 0; m < M && m < kM; ++m) {      // wave-uniform (M <= kM: the host's choice of kM)
+        const float d = paths[m * n + i];
+        if (!__ballot(__float_as_uint(d) != 0u)) continue;
+        park[n_live * 64u + lane] = d;
+        meshes |= (unsigned long long)m << (4u * n_live);
+        ++n_live;
+    }
+    if (!kNoisy && n_live == 0u && !__ballot(flags != 0u)) {     // the wave's every pixel is a miss
+        const uint32_t C = det.num_channels;
+#pragma unroll
+        for (uint32_t c = 0; c < kC; ++c)
+            if (c < C) det.out[c * det.plane + i] = det.miss[c];
+        return;
+    }
+    double acc[kC];
+    const uint64_t g = first_index + i;
+    const auto weight = [&](uint32_t e) { return tab.weight[e]; };
+    const auto resp = [&](uint32_t c, uint32_t e) { return det.response[c * kMaxBins + e]; };
+    const auto read_noise = [&]() { return det.read_noise; };
+    const auto tail_seed = [&]() { return det.seed; };
+    if (kM == kDetectorFewMeshes || n_live <= kDetectorFewMeshes) {
+        // at most four live meshes: their distances in registers, in scene order; past n_live mesh 0's
+        // coefficients, times +0.0
+        double path[kDetectorFewMeshes];
+#pragma unroll
+        for (uint32_t j = 0; j < kDetectorFewMeshes; ++j) path[j] = (double)(j < n_live ? park[j * 64u + lane] : 0.0f) * 0.1;
+        const uint32_t few = (uint32_t)meshes;
+        detector_pixel<kC, kNoisy>(
+            tab.num_bins,
+            [&](uint32_t q, double (&x)[4]) {
+#pragma unroll
+                for (uint32_t j = 0; j < kDetectorFewMeshes; ++j) {
+#pragma unroll
+                    for (uint32_t r = 0; r < 4; ++r)
+                        x[r] = x[r] + (double)tab.mu[detector_mu_index((few >> (4u * j)) & 15u, 4u * q + r)] * path[j];
+                }
+            },
+            weight, resp, det.gain, seed, g, read_noise, tail_seed, acc);
+    } else {
+        // more: a loop over the parked meshes, each distance read from the LDS where it is used -- no register
+        // array whatever the count, and a mesh that is not live costs nothing
+        detector_pixel<kC, kNoisy>(
+            tab.num_bins,
+            [&](uint32_t q, double (&x)[4]) {
+                for (uint32_t j = 0; j < n_live; ++j) {
+                    const uint32_t m = (uint32_t)(meshes >> (4u * j)) & 15u;
+                    const double pd = (double)park[j * 64u + lane] * 0.1;
+#pragma unroll
+                    for (uint32_t r = 0; r < 4; ++r) x[r] = x[r] + (double)tab.mu[detector_mu_index(m, 4u * q + r)] * pd;
+                }
+            },
+            weight, resp, det.gain, seed, g, read_noise, tail_seed, acc);
+    }
+    const uint32_t C = det.num_channels;
+    const uint32_t flagged = kNoisy ? (det.open ? det.open[i] : 0u) : flags;
+#pragma unroll
+    for (uint32_t c = 0; c < kC; ++c)
+        if (c < C) det.out[c * det.plane + i] = flagged ? -1.0f : xrt_detector_output(acc[c], det.gain, det.counts != 0u);
+}
+
 }  // namespace XRT_KERNEL_NS

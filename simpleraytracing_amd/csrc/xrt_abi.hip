@@ -2492,20 +2492,9 @@ int xrt_set_materials(xrt_context* ctx, const float* mu, uint32_t num_meshes)
     return upload_materials(ctx);
 }
 
-// The argument checks of xrt_set_spectrum (no device needed); null when they pass.
-static const char* spectrum_arguments(const float* weight, const float* mu, uint32_t num_meshes,
-                                      uint32_t num_bins)
-{
-    if (num_meshes < 1 || num_meshes > XRT_MAX_MESHES) return "1 to XRT_MAX_MESHES meshes";
-    if (num_bins < 1 || num_bins > XRT_MAX_BINS) return "1 to XRT_MAX_BINS energy bins";
-    if (!weight) return "weight is NULL";
-    if (!mu) return "mu is NULL";
-    for (uint32_t e = 0; e < num_bins; ++e)
-        if (!std::isfinite(weight[e]) || !(weight[e] > 0.0f)) return "a weight must be finite and > 0";
-    for (uint32_t i = 0; i < num_meshes * num_bins; ++i)
-        if (!std::isfinite(mu[i]) || mu[i] < 0.0f) return "a coefficient must be finite and >= 0";
-    return nullptr;
-}
+// The argument checks of xrt_set_spectrum (spectrum_arguments; no device needed) and the host pieces of the
+// spectral detector, which rest on them.
+#include "xrt_detector_host.inc"
 
 int xrt_set_spectrum(xrt_context* ctx, const float* weight, const float* mu, uint32_t num_meshes,
                      uint32_t num_bins)
@@ -2729,6 +2718,87 @@ int xrt_apply_spectrum(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshe
     if (s.rc()) return s.rc();
     if ((rc = launch_apply_spectrum(ctx, n, num_meshes, dp, dopen, weight, mu, num_bins, dl, ctx->host_stream))) return rc;
     s.download(lbuffer, dl, n);
+    return s.finish();
+}
+
+// --- the spectral detector -----------------------------------
+
+// The launch of k_spectral_detector (validated arguments, device pointers): the instantiation of the smallest
+// mesh and channel bounds that hold num_meshes and num_channels, and of the draw mode.
+static int launch_spectral_detector(xrt_context* ctx, uint64_t n, uint32_t num_meshes, const float* d_paths,
+                                    const uint16_t* d_open, const float* weight, const float* mu, uint32_t num_bins,
+                                    const float* response, uint32_t num_channels, float gain, float read_noise,
+                                    uint64_t seed, uint64_t first_index, int draw_mode, int out_mode, float* d_out,
+                                    hipStream_t stream)
+{
+    DetectorSpectrum tab;               // both tables by value: the launch owns its copies (no context state, no wait)
+    DetectorTable det;
+    detector_tables(weight, mu, num_meshes, num_bins, response, num_channels, gain, read_noise, draw_mode, out_mode, &tab,
+                    &det);
+    det.open = d_open;
+    det.out = d_out;
+    det.plane = n;
+    det.seed = seed;
+    const dim3 grid((unsigned)((n + kDetectorThreads - 1u) / kDetectorThreads)), block(kDetectorThreads);
+    const bool noisy = draw_mode == XRT_DETECT_NOISY;
+#define XRT_DETECT_LAUNCH(C, NOISY)                                                                              \
+    do {                                                                                                         \
+        if (num_meshes <= kDetectorFewMeshes)                                                                    \
+            hipLaunchKernelGGL((k_spectral_detector<kDetectorFewMeshes, C, NOISY>), grid, block, 0, stream, d_paths, \
+                               d_open, (size_t)n, num_meshes, tab, det, seed, first_index);                      \
+        else                                                                                                     \
+            hipLaunchKernelGGL((k_spectral_detector<kMaxMeshes, C, NOISY>), grid, block, 0, stream, d_paths, d_open, \
+                               (size_t)n, num_meshes, tab, det, seed, first_index);                              \
+    } while (0)
+    if (num_channels <= 1u) {
+        if (noisy) XRT_DETECT_LAUNCH(1, true); else XRT_DETECT_LAUNCH(1, false);
+    } else if (num_channels <= 4u) {
+        if (noisy) XRT_DETECT_LAUNCH(4, true); else XRT_DETECT_LAUNCH(4, false);
+    } else {
+        if (noisy) XRT_DETECT_LAUNCH(8, true); else XRT_DETECT_LAUNCH(8, false);
+    }
+#undef XRT_DETECT_LAUNCH
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_spectral_detector_device(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* d_paths,
+                                 const uint16_t* d_open, const float* weight, const float* mu, uint32_t num_bins,
+                                 const float* response, uint32_t num_channels, float gain, float read_noise,
+                                 uint64_t seed, uint64_t first_index, int draw_mode, int out_mode, float* d_out,
+                                 void* stream)
+{
+    if (const char* why = detector_arguments(num_pixels, num_meshes, d_paths, d_open, weight, mu, num_bins, response,
+                                             num_channels, gain, read_noise, first_index, draw_mode, out_mode, d_out))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_spectral_detector(ctx, num_pixels, num_meshes, d_paths, d_open, weight, mu, num_bins, response,
+                                    num_channels, gain, read_noise, seed, first_index, draw_mode, out_mode, d_out,
+                                    (hipStream_t)stream);
+}
+
+int xrt_spectral_detector(xrt_context* ctx, uint64_t num_pixels, uint32_t num_meshes, const float* paths,
+                          const uint16_t* open, const float* weight, const float* mu, uint32_t num_bins,
+                          const float* response, uint32_t num_channels, float gain, float read_noise, uint64_t seed,
+                          uint64_t first_index, int draw_mode, int out_mode, float* out)
+{
+    if (const char* why = detector_arguments(num_pixels, num_meshes, paths, open, weight, mu, num_bins, response,
+                                             num_channels, gain, read_noise, first_index, draw_mode, out_mode, out))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)num_pixels;
+    DeviceScratch s(ctx, ctx->host_stream, "spectral detector");
+    const float* dp = s.upload(paths, n * num_meshes);
+    const uint16_t* dopen = s.upload(open, n);
+    float* dout = s.alloc<float>(n * num_channels);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_spectral_detector(ctx, n, num_meshes, dp, dopen, weight, mu, num_bins, response, num_channels,
+                                          gain, read_noise, seed, first_index, draw_mode, out_mode, dout,
+                                          ctx->host_stream))
+        return rc;
+    s.download(out, dout, n * num_channels);
     return s.finish();
 }
 
