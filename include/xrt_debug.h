@@ -204,9 +204,22 @@ int xrt_debug_tile_plan(xrt_context* ctx, uint64_t counters[2]);
  * Host code (no device): the cull's direction grid of `camera` (DESIGN.md
  * section 5, step 0) as the library computes it -- grids[0], a bisection per
  * axis -- and by a scan of every row or column, grids[1].  Equal for every
- * camera (the test's claim).
+ * camera (the test's claim).  An axis on which up and right are both nonzero
+ * has no scan: both take its O(1) lower bound, which tests/test_camera_cpu.py
+ * holds against every pixel's direction instead.
  */
 int xrt_debug_direction_grid(const xrt_camera* camera, int grids[2]);
+
+/*
+ * Test hook (host code, no device): the tile cull's footprints of n triangles
+ * (tris[9*i] = p1, p2, p3) under `camera` -- the records as k_prep forms
+ * them, the cull parameters as the library forms them, compute_footprint
+ * compiled for the host -- in xrt_probe_prep's layout: footprint16[16*i] = box
+ * (xmin, xmax, ymin, ymax) and the three relaxed edges (a, b, c, .).  The
+ * device's reciprocal square root differs from the host's by an ulp, so the
+ * edges of the two agree closely, not bit for bit.
+ */
+int xrt_host_footprints(const xrt_camera* camera, const float* tris, uint64_t n, float* footprint16);
 
 /* Turns the tile plan on (1) or off (0) for later frames. */
 int xrt_debug_set_tile_plan(xrt_context* ctx, int on);

@@ -204,19 +204,19 @@ __device__ __forceinline__ uint32_t wave_uniform(uint32_t v)
 }
 __device__ __forceinline__ uint32_t wave_in_block() { return wave_uniform(threadIdx.x >> 6); }
 
-__device__ __forceinline__ void cross_d(const double a[3], const double b[3], double o[3])
+__host__ __device__ __forceinline__ void cross_d(const double a[3], const double b[3], double o[3])
 {
     o[0] = a[1] * b[2] - a[2] * b[1];
     o[1] = a[2] * b[0] - a[0] * b[2];
     o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-__device__ __forceinline__ double dot_d(const double a[3], const double b[3])
+__host__ __device__ __forceinline__ double dot_d(const double a[3], const double b[3])
 {
     return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
 }
 
-__device__ __forceinline__ double l1_d(const double a[3])
+__host__ __device__ __forceinline__ double l1_d(const double a[3])
 {
     return fabs(a[0]) + fabs(a[1]) + fabs(a[2]);
 }
@@ -1496,6 +1496,47 @@ struct Footprint {
     float4 bbox, e0, e1, e2;
 };
 
+// compute_footprint also compiles for the host (xrt_host_footprints: the CPU
+// suite checks the cull without a device).  Its three device instructions
+// have host twins: v_rsq_f32 (1 ulp) against a correctly rounded 1 / sqrtf,
+// the f32 sqrt builtin against sqrtf, and the rounding-up conversion against
+// a cast stepped up where it fell below.  The footprints may so differ in
+// their last bits between the two; both are conservative.
+template <typename T>
+__host__ __device__ __forceinline__ bool footprint_isfinite(T x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return isfinite(x);
+#else
+    return std::isfinite(x);
+#endif
+}
+__host__ __device__ __forceinline__ float footprint_rsqrt(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rsqf(x);
+#else
+    return 1.0f / sqrtf(x);
+#endif
+}
+__host__ __device__ __forceinline__ float footprint_sqrt(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_sqrtf(x);
+#else
+    return sqrtf(x);
+#endif
+}
+__host__ __device__ __forceinline__ float footprint_round_up(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __double2float_ru(x);
+#else
+    const float f = (float)x;
+    return (double)f < x ? nextafterf(f, __builtin_inff()) : f;
+#endif
+}
+
 // Box of the loosened triangle when it is unbounded (its inward normals do not
 // positively span the plane, e.g. a sliver seen edge-on): the bounding box of
 // {A_k x + B_k y + C_k >= 0, k < 3} inside the image rectangle [-1, W] x
@@ -1505,12 +1546,16 @@ struct Footprint {
 // Leaves `box` unchanged (unbounded: never culled by the box) if none is found.
 // One of three doubles by a uniform index, as bit masks (a select chain the
 // optimiser would turn into an indexed table in scratch memory).
-__device__ __forceinline__ double pick3(uint32_t k, double x0, double x1, double x2)
+__host__ __device__ __forceinline__ double pick3(uint32_t k, double x0, double x1, double x2)
 {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    return k == 0u ? x0 : k == 1u ? x1 : x2;      // (the host build: xrt_host_footprints)
+#else
     const uint64_t m0 = 0ull - (uint64_t)(k == 0u), m1 = 0ull - (uint64_t)(k == 1u), m2 = 0ull - (uint64_t)(k == 2u);
     return __longlong_as_double((long long)(((uint64_t)__double_as_longlong(x0) & m0) |
                                             ((uint64_t)__double_as_longlong(x1) & m1) |
                                             ((uint64_t)__double_as_longlong(x2) & m2)));
+#endif
 }
 
 struct ClipEdges {
@@ -1519,8 +1564,8 @@ struct ClipEdges {
 
 // Line k of the seven: k < 3 the edge (A_k x + B_k y + C_k >= 0), then the
 // image rectangle's x >= -1, x <= W, y >= -1, y <= H.
-__device__ __forceinline__ void clip_line(uint32_t k, const ClipEdges& e, double W, double H, double& la,
-                                          double& lb, double& lc)
+__host__ __device__ __forceinline__ void clip_line(uint32_t k, const ClipEdges& e, double W, double H, double& la,
+                                                   double& lb, double& lc)
 {
     if (k < 3u) {
         la = pick3(k, e.a0, e.a1, e.a2);
@@ -1536,8 +1581,8 @@ __device__ __forceinline__ void clip_line(uint32_t k, const ClipEdges& e, double
 // The 21 pairs are walked in a rolled loop (lines selected, not indexed): this
 // rare path (unbounded footprints) fully unrolled set the kernel's register
 // footprint (112 VGPRs; 72 without it).
-__device__ __forceinline__ void clipped_box(const double A[3], const double B[3], const double C[3], double W,
-                                            double H, float4& box)
+__host__ __device__ __forceinline__ void clipped_box(const double A[3], const double B[3], const double C[3],
+                                                     double W, double H, float4& box)
 {
     const ClipEdges e = {A[0], A[1], A[2], B[0], B[1], B[2], C[0], C[1], C[2]};
     double xmin = __builtin_inf(), xmax = -__builtin_inf();
@@ -1557,7 +1602,7 @@ __device__ __forceinline__ void clipped_box(const double A[3], const double B[3]
         if (!(fabs(det) > 1e-9 * scale)) continue;           // parallel (or NaN)
         const double x = (lb_ * mc - mb * lc) / det;
         const double y = (ma * lc - la * mc) / det;
-        bool ok = isfinite(x) && isfinite(y);
+        bool ok = footprint_isfinite(x) && footprint_isfinite(y);
 #pragma unroll
         for (uint32_t k = 0; k < 7u; ++k) {
             double qa, qb, qc;
@@ -1578,7 +1623,7 @@ __device__ __forceinline__ void clipped_box(const double A[3], const double B[3]
     box = make_float4((float)(xmin - sx), (float)(xmax + sx), (float)(ymin - sy), (float)(ymax + sy));
 }
 
-__device__ Footprint compute_footprint(const TriRec& r, const RenderParams& p, const CullParams& cp)
+__host__ __device__ Footprint compute_footprint(const TriRec& r, const RenderParams& p, const CullParams& cp)
 {
     const float kInf = __builtin_inff();
     Footprint c;
@@ -1588,7 +1633,8 @@ __device__ Footprint compute_footprint(const TriRec& r, const RenderParams& p, c
     c.e2 = c.e0;
     c.e2.w = kInf;     // the regions the footprint reaches: unknown (bin_rect)
 
-    bool finite = isfinite(r.tnum) && isfinite(r.qvx) && isfinite(r.qvy) && isfinite(r.qvz);
+    bool finite = footprint_isfinite(r.tnum) && footprint_isfinite(r.qvx) && footprint_isfinite(r.qvy) &&
+                  footprint_isfinite(r.qvz);
     if (finite && r.tnum == 0.0f) {
         // t = 0 * inv_det is never > 1e-7: the triangle never contributes.
         c.bbox = make_float4(kInf, -kInf, kInf, -kInf);
@@ -1658,7 +1704,7 @@ __device__ Footprint compute_footprint(const TriRec& r, const RenderParams& p, c
         const double nn = beta * beta + gamma * gamma;
         double nrm, inv_nrm;
         if (nn > 0x1p-120 && nn < 0x1p120) {
-            inv_nrm = (double)__builtin_amdgcn_rsqf((float)nn);
+            inv_nrm = (double)footprint_rsqrt((float)nn);
             nrm = 1.0 / inv_nrm;
         } else {
             nrm = sqrt(nn);
@@ -1686,7 +1732,7 @@ __device__ Footprint compute_footprint(const TriRec& r, const RenderParams& p, c
         eb[k] = (float)b;
         c_edge[k] = (double)(float)cc;
         // stored with an 8x8 tile's half-width folded in (edge_tile), rounded up
-        ec[k] = __double2float_ru(cc + (double)kTileHalf * (fabs((double)ea[k]) + fabs((double)eb[k])));
+        ec[k] = footprint_round_up(cc + (double)kTileHalf * (fabs((double)ea[k]) + fabs((double)eb[k])));
     }
     c.e0 = make_float4(ea[0], eb[0], ec[0], 0.0f);
     c.e1 = make_float4(ea[1], eb[1], ec[1], 0.0f);
@@ -1716,7 +1762,8 @@ __device__ Footprint compute_footprint(const TriRec& r, const RenderParams& p, c
             double ymin = fmin(vy[0], fmin(vy[1], vy[2])), ymax = fmax(vy[0], fmax(vy[1], vy[2]));
             double sx = 0.01 + 1e-4 * (fabs(xmin) + fabs(xmax));
             double sy = 0.01 + 1e-4 * (fabs(ymin) + fabs(ymax));
-            if (isfinite(xmin) && isfinite(xmax) && isfinite(ymin) && isfinite(ymax)) {
+            if (footprint_isfinite(xmin) && footprint_isfinite(xmax) && footprint_isfinite(ymin) &&
+                footprint_isfinite(ymax)) {
                 c.bbox = make_float4((float)(xmin - sx), (float)(xmax + sx), (float)(ymin - sy),
                                      (float)(ymax + sy));
                 // Regions the loosened triangle can touch, by its size rather than
@@ -1732,7 +1779,7 @@ __device__ Footprint compute_footprint(const TriRec& r, const RenderParams& p, c
                                          iw * ih);
                 double perim = 0.0;         // (a size estimate: f32 square roots serve)
                 for (int q = 0; q < 3; ++q)
-                    perim += (double)__builtin_amdgcn_sqrtf(
+                    perim += (double)footprint_sqrt(
                         (float)((vx[pj[q]] - vx[q]) * (vx[pj[q]] - vx[q]) + (vy[pj[q]] - vy[q]) * (vy[pj[q]] - vy[q])));
                 perim = fmin(perim, 2.0 * (iw + ih));
                 c.e2.w = (float)(area / (kRegion * kRegion) + 2.0 * perim / kRegion + 8.0);

@@ -811,157 +811,7 @@ int render_soup(xrt_context* ctx, const float*& soup)
     return XRT_OK;
 }
 
-RenderParams make_params(const xrt_camera& c, uint32_t row_begin, uint32_t row_end, uint64_t T,
-                         uint32_t capacity)
-{
-    RenderParams p;
-    p.ox = c.origin[0]; p.oy = c.origin[1]; p.oz = c.origin[2];
-    p.cx = c.detector[0]; p.cy = c.detector[1]; p.cz = c.detector[2];
-    p.ux = c.up[0]; p.uy = c.up[1]; p.uz = c.up[2];
-    p.rx = c.right[0]; p.ry = c.right[1]; p.rz = c.right[2];
-    p.spacing = c.pixel_spacing;
-    p.width = c.width;
-    p.height = c.height;
-    p.row_begin = row_begin;
-    p.row_end = row_end;
-    p.num_triangles = (uint32_t)T;
-    p.hit_capacity = capacity;
-    p.prep_tris = prep_tris_for(T);
-    return p;
-}
-
-// Grid exponent shared by every float of magnitude >= m > 0 (their ulps are
-// at least 2^(floor(log2 m) - 23); 2^-149 at worst).
-inline int grid_floor(double m)
-{
-    if (!(m > 0.0) || !std::isfinite(m)) return -149;
-    return std::max(std::ilogb(m) - 23, -149);
-}
-
-// The f32 pixel offset of make_ray (main.cxx:655-656).
-inline float pixel_offset(float spacing, uint32_t i, uint32_t n)
-{
-    return (float)((double)spacing * ((0.5 + (double)i) - (double)n / 2.0));
-}
-
-// Smallest nonzero |X_k| over the image, X_k = ((detector_k + up_k v) +
-// right_k u) - origin_k in f32 as make_ray forms it (main.cxx:659): exact over
-// the rows (right_k == 0) or the columns (up_k == 0) it varies with.  When it
-// varies with both, a grid bound: X_k is a rounded sum of multiples of the
-// grids of its terms, every nonzero offset being >= spacing / 2.  0 when X_k
-// is 0 at every pixel.
-// Smallest nonzero |x(i)| over i < n of a monotone sequence (non-decreasing or
-// non-increasing; NaN-free): the last element below 0 and the first above 0,
-// found by bisection -- O(log n) instead of a scan.
-template <typename F>
-double min_nonzero_monotone(uint32_t n, F x)
-{
-    double best = std::numeric_limits<double>::infinity();
-    if (n == 0) return best;
-    const bool up = x(0) <= x(n - 1);
-    // first index whose value is past 0 in the sequence's direction (n if none)
-    auto first = [&](auto past) {
-        uint32_t lo = 0, hi = n;
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (past(x(mid))) hi = mid; else lo = mid + 1;
-        }
-        return lo;
-    };
-    // up: the first x > 0, and the last x < 0 (one before the first x >= 0)
-    const uint32_t i_pos = up ? first([](float v) { return v > 0.0f; }) : first([](float v) { return v <= 0.0f; });
-    const uint32_t i_neg = up ? first([](float v) { return v >= 0.0f; }) : first([](float v) { return v < 0.0f; });
-    if (up) {
-        if (i_pos < n) best = std::min(best, (double)std::fabs(x(i_pos)));
-        if (i_neg > 0) best = std::min(best, (double)std::fabs(x(i_neg - 1)));
-    } else {                                           // positives first, then zeros, then negatives
-        if (i_pos > 0) best = std::min(best, (double)std::fabs(x(i_pos - 1)));
-        if (i_neg < n) best = std::min(best, (double)std::fabs(x(i_neg)));
-    }
-    return best;
-}
-
-double min_nonzero_x(const xrt_camera& c, int k, bool scan = false)
-{
-    const float cu = c.up[k], cr = c.right[k], cc = c.detector[k], co = c.origin[k];
-    auto x_of = [&](float v, float u) { return ((cc + cu * v) + cr * u) - co; };
-    const uint32_t kMaxScan = 1u << 20;
-    double best = std::numeric_limits<double>::infinity();
-    auto take = [&](float x) {
-        if (x != 0.0f) best = std::min(best, (double)std::fabs(x));
-    };
-    // Along one axis x is monotone in the pixel index (pixel_offset and each
-    // rounded f32 operation are monotone), so its smallest nonzero magnitude is
-    // next to its sign change: a bisection per camera instead of a scan of
-    // every row or column (xrt_debug_direction_grid compares the two).
-    const bool finite = std::isfinite(cu) && std::isfinite(cr) && std::isfinite(cc) && std::isfinite(co) &&
-                        std::isfinite(c.pixel_spacing);
-    if (cr == 0.0f && c.height <= kMaxScan) {
-        const float u0 = pixel_offset(c.pixel_spacing, 0, c.width);
-        auto xr = [&](uint32_t row) { return x_of(pixel_offset(c.pixel_spacing, row, c.height), u0); };
-        if (!scan && finite) best = min_nonzero_monotone(c.height, xr);
-        else for (uint32_t row = 0; row < c.height; ++row) take(xr(row));
-    } else if (cu == 0.0f && c.width <= kMaxScan) {
-        const float v0 = pixel_offset(c.pixel_spacing, 0, c.height);
-        auto xc = [&](uint32_t col) { return x_of(v0, pixel_offset(c.pixel_spacing, col, c.width)); };
-        if (!scan && finite) best = min_nonzero_monotone(c.width, xc);
-        else for (uint32_t col = 0; col < c.width; ++col) take(xc(col));
-    } else {
-        const double ps = std::fabs((double)c.pixel_spacing);
-        const int goff = ps > 0.0 ? grid_floor(0.5 * ps * (1.0 - 0x1p-23)) : kNoGrid;
-        int gx = std::min(grid_exp(cc), grid_exp(co));
-        if (cu != 0.0f && goff != kNoGrid) gx = std::min(gx, std::max(grid_exp(cu) + goff, -149));
-        if (cr != 0.0f && goff != kNoGrid) gx = std::min(gx, std::max(grid_exp(cr) + goff, -149));
-        if (gx != kNoGrid) best = std::ldexp(1.0, gx);
-    }
-    return std::isfinite(best) ? best : 0.0;
-}
-
-// A grid 2^g such that every nonzero component of every ray direction of the
-// image (make_ray: main.cxx:652-661 and Ray.inl:80-84) is a multiple of it:
-// the two normalisations divide X_k by |X| <= dmax and by ~1, so a nonzero
-// component is >= min|X_k| / (1.001 dmax), a float whose ulp is the grid.
-int direction_grid(const xrt_camera& c, double dmax, bool scan = false)
-{
-    int g = kNoGrid;
-    for (int k = 0; k < 3; ++k) {
-        const double xmin = min_nonzero_x(c, k, scan);
-        if (xmin > 0.0) g = std::min(g, grid_floor(xmin / (1.001 * dmax)));
-    }
-    return g;
-}
-
-// Bounds used by the cull derivation (DESIGN.md "Tile cull"): over every pixel
-// of the image, |D| <= dmax and the terms summed into D are <= mag.
-CullParams make_cull_params(const xrt_camera& c)
-{
-    double ps = std::fabs((double)c.pixel_spacing);
-    double vmax = ps * ((double)c.height / 2.0 + 1.0);
-    double umax = ps * ((double)c.width / 2.0 + 1.0);
-    double d2 = 0.0, mag = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        double cterm = std::fabs((double)c.detector[k] - (double)c.origin[k]);
-        double spread = std::fabs((double)c.up[k]) * vmax + std::fabs((double)c.right[k]) * umax;
-        d2 += (cterm + spread) * (cterm + spread);
-        mag = std::max(mag, std::fabs((double)c.detector[k]) + spread + std::fabs((double)c.origin[k]));
-    }
-    CullParams cp;
-    cp.dmax = std::sqrt(d2) * (1.0 + 1e-6);
-    cp.mag = mag;
-    cp.width = c.width;
-    cp.height = c.height;
-    cp.dir_grid = direction_grid(c, cp.dmax);
-    cp.pad = 0;
-    for (int k = 0; k < 3; ++k) {
-        cp.cvec[k] = (double)c.detector[k] - (double)c.origin[k];
-        cp.up[k] = c.up[k];
-        cp.rt[k] = c.right[k];
-    }
-    cp.ps = c.pixel_spacing;
-    cp.cv = cp.ps * (0.5 - cp.height / 2.0);
-    cp.cu = cp.ps * (0.5 - cp.width / 2.0);
-    return cp;
-}
+#include "xrt_cull_host.inc"
 
 int check_camera(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, uint32_t row_end)
 {
@@ -3356,6 +3206,16 @@ int xrt_debug_direction_grid(const xrt_camera* camera, int grids[2])
     const CullParams cp = make_cull_params(*camera);
     grids[0] = cp.dir_grid;
     grids[1] = direction_grid(*camera, cp.dmax, true);
+    return XRT_OK;
+}
+
+// Host evaluation of the tile cull's footprints (compute_footprint, same
+// source, host-compiled): the CPU suite checks them against every hit of the
+// oracle without a GPU.
+int xrt_host_footprints(const xrt_camera* camera, const float* tris, uint64_t n, float* footprint16)
+{
+    if (!camera || (n && (!tris || !footprint16))) return XRT_ERR_ARGUMENT;
+    host_footprints(*camera, tris, n, footprint16);
     return XRT_OK;
 }
 
