@@ -759,6 +759,81 @@ int xrt_spectral_detector_device(xrt_context* ctx, uint64_t num_pixels, uint32_t
                                  uint64_t seed, uint64_t first_index, int draw_mode, int out_mode, float* d_out,
                                  void* stream);
 
+/* --- voxel phantoms: a labelled volume traced into paths planes ----------- */
+
+/*
+ * A voxel object: u8 labels[nz][ny][nx] (x fastest; dims = {nx, ny, nz}),
+ * label 0 empty, label L in 1..num_labels traced into plane L - 1, and an
+ * optional f32 density of the same shape (NULL: 1 everywhere).  origin is the
+ * minimum corner of voxel (0, 0, 0), spacing the voxel's size, both in x, y, z
+ * order; the volume is axis-aligned in scene space and has no pose (turn the
+ * camera).  Per ray and label, the length of the ray inside voxels of that
+ * label, each segment times its voxel's density, is a paths plane in the sense
+ * of xrt_render_paths: xrt_apply_spectrum and xrt_spectral_detector take the
+ * planes as they are, with open = NULL.
+ *
+ * xrt_upload_volume copies the arrays to the device and replaces any earlier
+ * volume; labels = NULL or num_labels = 0 frees it.  XRT_ERR_ARGUMENT, with
+ * xrt_last_error naming the fault, before any device work and before the
+ * context is looked at, unless 1 <= dims[a] <= 2048, 1 <= num_labels <=
+ * XRT_MAX_MESHES, every spacing is finite and > 0, the origin and the far
+ * corner are finite in f32, every label is <= num_labels (the first offending
+ * voxel is named) and every density is finite.  XRT_ERR_DEVICE for a volume
+ * that does not fit device memory.  xrt_volume_bbox is host arithmetic: lower
+ * = origin, upper[a] = (float)((double)origin[a] + (double)dims[a] *
+ * (double)spacing[a]); a camera then comes from xrt_camera_from_bbox, of this
+ * box or of its union with xrt_scene_bbox's.
+ *
+ * xrt_volume_paths[_device] trace the rows [row_begin, row_end) of the camera
+ * into num_labels planes of (row_end - row_begin) * width f32, one after
+ * another.  num_labels is the caller's statement of its buffer: a value other
+ * than the uploaded volume's fails with XRT_ERR_ARGUMENT; without a volume the
+ * call fails with XRT_ERR_NO_MESH.  Every plane of every pixel is written; a
+ * ray that misses the volume writes +0.0f.  xrt_volume_paths: host buffers,
+ * synchronous.  _device: device buffers, asynchronous on `stream`.  Neither
+ * looks at or changes the context's model, meshes, poses, prepared-ahead
+ * frames or state generation: a mesh render and a volume trace of one context
+ * may be enqueued back to back on one stream.  There is no xrt_multi_ form.
+ *
+ * The ray, all in f64, every operation rounded on its own (nothing is fused;
+ * every min and max is the written comparison):  O = camera origin, d = the
+ * render's ray direction (the twice-normalised f32 direction, widened),
+ * plane(a, i) = origin[a] + (double)i * spacing[a].
+ *   te = 0, tx = +inf
+ *   for a in x, y, z:
+ *     d[a] == 0:  a miss unless plane(a, 0) <= O[a] < plane(a, n[a])
+ *     otherwise:  inv[a] = 1 / d[a]; t0 = (plane(a, 0) - O[a]) * inv[a]; t1 = (plane(a, n[a]) - O[a]) * inv[a]
+ *                 te = max(te, min(t0, t1)); tx = min(tx, max(t0, t1))
+ *   a miss unless te < tx
+ *   idx[a] = floor(((O[a] + te * d[a]) - origin[a]) / spacing[a]) clamped to [0, n[a] - 1]
+ *   tnext(a) = d[a] == 0 ? +inf : (plane(a, idx[a] + (d[a] > 0 ? 1 : 0)) - O[a]) * inv[a]
+ *   tc = te; then, at most nx + ny + nz + 3 times:
+ *     a = the axis of the least tnext (ties: x before y before z); t = tnext(a)
+ *     tend = min(t, tx); seg = tend - tc
+ *     a run is the consecutive steps of one label: its sum `run` starts at 0 and is added to
+ *     acc[label - 1] when the label changes and at the end
+ *     if label != 0 and seg > 0:  run = run + (density ? seg * (double)density[idx] : seg)
+ *     if seg > 0:  tc = tend
+ *     stop unless t < tx;  idx[a] += d[a] > 0 ? 1 : -1;  stop when idx[a] leaves the volume
+ *   paths[m][pixel] = (float)acc[m]
+ *
+ * Stacking.  Mesh planes and volume planes may share one buffer and one
+ * spectrum table: render a mesh scene's M1 planes with
+ * xrt_render_paths_device into the front of a buffer of M1 + M2 planes of
+ * num_pixels, trace the volume's M2 planes with xrt_volume_paths_device into
+ * d_paths + M1 * num_pixels, and call xrt_apply_spectrum_device (or
+ * xrt_spectral_detector_device) with num_meshes = M1 + M2 <= XRT_MAX_MESHES,
+ * a table of M1 + M2 rows (the meshes' first) and the mesh scene's open plane.
+ */
+int xrt_upload_volume(xrt_context* ctx, const uint8_t* labels, const float* density, const uint32_t dims[3],
+                      const float origin[3], const float spacing[3], uint32_t num_labels);
+int xrt_volume_bbox(const uint32_t dims[3], const float origin[3], const float spacing[3], float lower[3],
+                    float upper[3]);
+int xrt_volume_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                     uint32_t num_labels, float* paths);
+int xrt_volume_paths_device(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                            uint32_t num_labels, float* d_paths, void* stream);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

@@ -316,6 +316,24 @@ int xrt_host_spectral_detector(uint64_t num_pixels, uint32_t num_meshes, const f
                                int draw_mode, int out_mode, float* out);
 
 /*
+ * Test hook of the voxel trace.  Host code, no device: xrt_volume_paths' ray
+ * function -- volume_ray, the one k_volume_paths calls, compiled for the host
+ * -- over whole host buffers.  The volume's arrays are taken directly
+ * (arguments and checks as xrt_upload_volume's), the camera, strip and planes
+ * as xrt_volume_paths'.
+ */
+int xrt_host_volume_paths(const xrt_camera* camera, uint32_t row_begin, uint32_t row_end, const uint8_t* labels,
+                          const float* density, const uint32_t dims[3], const float origin[3], const float spacing[3],
+                          uint32_t num_labels, float* paths);
+
+/*
+ * The shape of k_volume_paths' waves, for the A/B its layout rests on
+ * (tools/volume_timing.py): rows = 0, the default, 8 x 8 pixel tiles; rows != 0,
+ * 64 x 1 row segments.  The planes are the same bit for bit.
+ */
+int xrt_debug_volume_wave_shape(xrt_context* ctx, int rows);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -31,6 +31,24 @@ int xrt_host_load_meshes(const char* path, float** triangles, uint64_t** mesh_tr
 void xrt_host_free(void* p);
 
 /*
+ * A MetaImage volume (loadMetaImage of the host API): a text header -- NDims =
+ * 3, DimSize, ElementSpacing, Offset (or Origin), ElementType = MET_UCHAR
+ * (labels) or MET_FLOAT (a density), ElementDataFile = NAME.raw beside the
+ * header -- and its raw little-endian data, x fastest.  *data is malloc'd
+ * (free with xrt_host_free) and holds dims[0] * dims[1] * dims[2] elements of
+ * *element_type; dims, origin and spacing are in x, y, z order, as
+ * xrt_upload_volume takes them.  XRT_ERR_IO when a file cannot be opened,
+ * XRT_ERR_FORMAT for a missing or malformed key and for what the loader
+ * refuses: compressed data, another element type, a TransformMatrix that is
+ * not the identity, big-endian data, a data file shorter than the volume.
+ * xrt_host_last_error names the key (this thread's last failed load).
+ */
+enum { XRT_VOLUME_U8 = 0, XRT_VOLUME_F32 = 1 };
+int xrt_host_load_volume(const char* path, void** data, int* element_type, uint32_t dims[3], float origin[3],
+                         float spacing[3]);
+const char* xrt_host_last_error(void);
+
+/*
  * Ray::intersect (src/Ray.cxx:72-124) of the drop-in host class for n pairs:
  * rays[6*i] = origin, direction (normalised by the Ray constructor as
  * include/Ray.inl:74-85); triangles[9*i] = p1, p2, p3.  hit[i] = 0/1, t[i] =

@@ -34,7 +34,7 @@ __all__ = [
     "XRT_ORDER_PROJECTIONS", "XRT_ORDER_SINOGRAMS", "host_logf", "host_log_projection", "log_projection",
     "XRT_NOISE_INTENSITY", "XRT_NOISE_COUNTS", "host_philox4x32", "host_poisson", "host_photon_noise", "photon_noise",
     "XRT_MAX_CHANNELS", "XRT_DETECT_EXPECTED", "XRT_DETECT_NOISY", "XRT_DETECT_COUNTS", "XRT_DETECT_INTENSITY",
-    "host_spectral_detector", "spectral_detector",
+    "host_spectral_detector", "spectral_detector", "volume_bbox", "host_volume_paths", "load_volume",
     "XRT_MAX_SOURCES", "XRT_MAX_BIN", "supersampled_camera", "focal_spot", "host_area_integrate", "area_integrate",
 ]
 
@@ -464,6 +464,73 @@ def spectral_detector(paths, open, weights, mu, response, gain=1.0, seed=0, nois
                                      first_index)
 
 
+def _volume_arrays(labels, spacing, origin, density, num_labels):
+    """A voxel volume as xrt_upload_volume takes it: (labels (nz, ny, nx) uint8, density f32 of that shape or
+    None, dims (nx, ny, nz) uint32, origin f32[3], spacing f32[3], num_labels)."""
+    lab = np.ascontiguousarray(labels, dtype=np.uint8)
+    if lab.ndim != 3:
+        raise ValueError(f"labels must have shape (nz, ny, nx), got {lab.shape}")
+    den = None if density is None else np.ascontiguousarray(density, dtype=np.float32)
+    if den is not None and den.shape != lab.shape:
+        raise ValueError(f"density must have the labels' shape {lab.shape}, got {den.shape}")
+    dims = np.array(lab.shape[::-1], np.uint32)
+    org = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1)
+    spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+    if org.size != 3:
+        raise ValueError("origin must hold 3 values (x, y, z)")
+    m = int(lab.max()) if num_labels is None and lab.size else int(num_labels or 0)
+    return lab, den, dims, org, spc, m
+
+
+def load_volume(path: str):
+    """A MetaImage volume (xrt_host_load_volume): (data (nz, ny, nx) uint8 -- MET_UCHAR labels -- or float32 --
+    a MET_FLOAT density --, spacing f32[3], origin f32[3]), both in x, y, z order, as upload_volume takes them."""
+    host = _abi.load_host()
+    data, kind = ctypes.c_void_p(), ctypes.c_int()
+    dims, org, spc = np.zeros(3, np.uint32), np.zeros(3, np.float32), np.zeros(3, np.float32)
+    rc = host.xrt_host_load_volume(path.encode(), ctypes.byref(data), ctypes.byref(kind), _u32ptr(dims), _fptr(org),
+                                   _fptr(spc))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, f"xrt_host_load_volume({path}): {host.xrt_host_last_error().decode()}")
+    try:
+        n = int(dims[0]) * int(dims[1]) * int(dims[2])
+        ctype, dtype = (ctypes.c_uint8, np.uint8) if kind.value == _abi.XRT_VOLUME_U8 else (ctypes.c_float, np.float32)
+        arr = np.ctypeslib.as_array(ctypes.cast(data, ctypes.POINTER(ctype)), shape=(n,)).astype(dtype, copy=True)
+    finally:
+        host.xrt_host_free(data)
+    return arr.reshape(int(dims[2]), int(dims[1]), int(dims[0])), spc, org
+
+
+def volume_bbox(dims, spacing, origin=(0.0, 0.0, 0.0)):
+    """(lower, upper) of a volume of dims (nx, ny, nz) voxels of `spacing` whose minimum corner is `origin`
+    (xrt_volume_bbox)."""
+    d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(-1)
+    org = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1)
+    spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+    if d.size != 3 or org.size != 3:
+        raise ValueError("dims and origin must hold 3 values (x, y, z)")
+    lo, hi = np.empty(3, np.float32), np.empty(3, np.float32)
+    rc = _abi.load().xrt_volume_bbox(_u32ptr(d), _fptr(org), _fptr(spc), _fptr(lo), _fptr(hi))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_volume_bbox")
+    return lo, hi
+
+
+def host_volume_paths(cam: Camera, labels, spacing, origin=(0.0, 0.0, 0.0), density=None, num_labels=None,
+                      row_begin: int = 0, row_end: int | None = None) -> np.ndarray:
+    """Context.volume_paths in the device's arithmetic on the host (xrt_host_volume_paths, a test hook)."""
+    lab, den, dims, org, spc, m = _volume_arrays(labels, spacing, origin, density, num_labels)
+    if row_end is None:
+        row_end = cam.height
+    out = np.empty((max(m, 1), max(row_end - row_begin, 0), cam.width), np.float32)
+    rc = _abi.load().xrt_host_volume_paths(ctypes.byref(cam), row_begin, row_end, _u8ptr(lab),
+                                           _fptr(den) if den is not None else None, _u32ptr(dims), _fptr(org),
+                                           _fptr(spc), m, _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_volume_paths")
+    return out
+
+
 class Context:
     """One xrt_context (one device).  Not thread-safe."""
 
@@ -471,6 +538,7 @@ class Context:
         self._lib = _abi.load()
         self._ctx = _abi._CtxP()
         self._num_meshes = 0               # of the uploaded scene (render_paths' planes)
+        self._num_labels = 0               # of the uploaded volume (volume_paths' planes)
         rc = self._lib.xrt_create(device, ctypes.byref(self._ctx))
         if rc != _abi.XRT_OK:
             raise XrtError(rc, self._lib.xrt_last_error(None).decode())
@@ -682,6 +750,46 @@ class Context:
             _fptr(r), r.shape[0], float(gain), float(read_noise), int(seed), int(first_index), draw, mode,
             d_out or None, stream or None)
         self._check(rc, "xrt_spectral_detector_device")
+
+    def upload_volume(self, labels, spacing, origin=(0.0, 0.0, 0.0), density=None, num_labels=None):
+        """A voxel volume: labels (nz, ny, nx) uint8 (0: empty, L into plane L - 1), voxels of `spacing` (one
+        value or (x, y, z)), the minimum corner at `origin`, an optional f32 density of the labels' shape.
+        num_labels defaults to labels.max().  Replaces any earlier volume; labels=None frees it."""
+        if labels is None:
+            self._check(self._lib.xrt_upload_volume(self._ctx, None, None, None, None, None, 0), "xrt_upload_volume")
+            self._num_labels = 0
+            return
+        lab, den, dims, org, spc, m = _volume_arrays(labels, spacing, origin, density, num_labels)
+        if m == 0:                         # (num_labels = 0 would free the volume)
+            raise ValueError("the volume has no label above 0: give num_labels")
+        self._check(self._lib.xrt_upload_volume(self._ctx, _u8ptr(lab), _fptr(den) if den is not None else None,
+                                                _u32ptr(dims), _fptr(org), _fptr(spc), m), "xrt_upload_volume")
+        self._num_labels = m
+
+    def volume_paths(self, cam: Camera, row_begin: int = 0, row_end: int | None = None, num_labels: int | None = None):
+        """The uploaded volume's planes over the strip: (M, rows, W) f32, plane m the length of each ray inside
+        label m + 1 (times the voxels' density).  M is the uploaded volume's label count (num_labels overrides
+        the buffer's size as stated to the library, which checks it against the volume)."""
+        if row_end is None:
+            row_end = cam.height
+        m = self._num_labels if num_labels is None else int(num_labels)
+        paths = np.empty((max(m, 1), max(row_end - row_begin, 0), cam.width), np.float32)
+        self._check(self._lib.xrt_volume_paths(self._ctx, ctypes.byref(cam), row_begin, row_end, m, _fptr(paths)),
+                    "xrt_volume_paths")
+        return paths
+
+    def volume_paths_device(self, cam: Camera, row_begin: int, row_end: int, num_labels: int, d_paths: int,
+                            stream: int = 0):
+        """Device-buffer volume trace (a raw device pointer: num_labels f32 planes of the strip, one after
+        another); asynchronous on `stream`."""
+        rc = self._lib.xrt_volume_paths_device(self._ctx, ctypes.byref(cam), row_begin, row_end, int(num_labels),
+                                               d_paths or None, stream or None)
+        self._check(rc, "xrt_volume_paths_device")
+
+    def volume_wave_shape(self, rows: bool):
+        """k_volume_paths' waves as 64 x 1 row segments (rows=True) or 8 x 8 tiles (the default): a timing A/B,
+        the planes are the same (xrt_debug_volume_wave_shape)."""
+        self._check(self._lib.xrt_debug_volume_wave_shape(self._ctx, int(bool(rows))), "xrt_debug_volume_wave_shape")
 
     def detector_response(self, image, lsf_x, lsf_y=None, out=True, u8=True):
         """The detector's line-spread function over an (H, W) image or a (P, H, W) stack of them (taps as

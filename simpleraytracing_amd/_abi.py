@@ -69,6 +69,9 @@ XRT_IMAGE_TGA = 1
 XRT_IMAGE_PGM = 2
 XRT_IMAGE_JPEG = 3
 
+XRT_VOLUME_U8 = 0
+XRT_VOLUME_F32 = 1
+
 _f = ctypes.c_float
 _fp = ctypes.POINTER(ctypes.c_float)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -205,6 +208,13 @@ XRT_SYMBOLS = {
                                                     ctypes.c_int, _vp, _vp]),
     "xrt_host_spectral_detector": (ctypes.c_int, [_u64, _u32, _fp, _u16p, _fp, _fp, _u32, _fp, _u32, ctypes.c_float,
                                                   ctypes.c_float, _u64, _u64, ctypes.c_int, ctypes.c_int, _fp]),
+    "xrt_upload_volume": (ctypes.c_int, [_CtxP, _u8p, _fp, _u32p, _fp, _fp, _u32]),
+    "xrt_volume_bbox": (ctypes.c_int, [_u32p, _fp, _fp, _fp, _fp]),
+    "xrt_volume_paths": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _u32, _u32, _u32, _fp]),
+    "xrt_volume_paths_device": (ctypes.c_int, [_CtxP, ctypes.POINTER(Camera), _u32, _u32, _u32, _vp, _vp]),
+    "xrt_host_volume_paths": (ctypes.c_int, [ctypes.POINTER(Camera), _u32, _u32, _u8p, _fp, _u32p, _fp, _fp, _u32,
+                                             _fp]),
+    "xrt_debug_volume_wave_shape": (ctypes.c_int, [_CtxP, ctypes.c_int]),
     "xrt_host_philox4x32": (None, [_u32p, _u32p, _u32p]),
     "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
     "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),
@@ -283,6 +293,9 @@ XRT_HOST_SYMBOLS = {
     "xrt_host_load_meshes": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_fp), ctypes.POINTER(_u64p),
                                             ctypes.POINTER(_u32)]),
     "xrt_host_free": (None, [_vp]),
+    "xrt_host_load_volume": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int), _u32p, _fp,
+                                            _fp]),
+    "xrt_host_last_error": (ctypes.c_char_p, []),
     "xrt_host_intersect_batch": (None, [_fp, _fp, _u64, _u8p, _fp]),
     "xrt_host_save_image": (ctypes.c_int, [_fp, _u32, _u32, ctypes.c_char_p, ctypes.c_int, _f, _f]),
 }

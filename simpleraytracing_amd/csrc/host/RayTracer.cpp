@@ -22,6 +22,7 @@ namespace {
 int g_kernel = -1;
 int g_device = -1;
 std::vector<std::array<float, 12>> g_poses;   // setMeshPoses (empty: every mesh at rest)
+unsigned g_volume_labels = 0;                 // uploadVolume's label count (renderLoopVolumePaths' planes)
 
 int kernel_choice()
 {
@@ -184,12 +185,13 @@ namespace {
 
 // Camera for a render: RayTracerInfo + the pixel spacing of renderLoop's
 // prologue (main.cxx:634-641), from the bbox of all meshes.
+// (range: the box's; null: the meshes' own, as renderLoop forms it)
 xrt_camera camera_for(const Image& image, const std::vector<TriangleMesh>& meshes,
-                      const RayTracerInfo& info)
+                      const RayTracerInfo& info, const Vec3* info_range = nullptr)
 {
     Vec3 upper, lower;
-    getBBox(meshes, upper, lower);
-    Vec3 range = upper - lower;
+    if (!info_range) getBBox(meshes, upper, lower);
+    Vec3 range = info_range ? *info_range : upper - lower;
     float res1 = range[2] / image.getWidth();
     float res2 = range[1] / image.getHeight();
     xrt_camera cam;
@@ -367,11 +369,12 @@ unsigned long long renderLoopSpectrum(Image& image, const std::vector<TriangleMe
 }
 
 unsigned long long renderLoopPaths(std::vector<std::vector<float>>& paths, std::vector<unsigned short>& open,
-                                   const Image& frame, const std::vector<TriangleMesh>& meshes, RayTracerInfo& info)
+                                   const Image& frame, const std::vector<TriangleMesh>& meshes, RayTracerInfo& info,
+                                   bool info_range)
 {
     if (meshes.empty() || meshes.size() > XRT_MAX_MESHES)
         throw std::invalid_argument("renderLoopPaths: 1 to XRT_MAX_MESHES meshes");
-    xrt_camera cam = camera_for(frame, meshes, info);
+    xrt_camera cam = camera_for(frame, meshes, info, info_range ? &info.range : nullptr);
     SceneRender r(meshes, kEveryMesh, kSignedModel);
     check(r.ctx, xrt_set_paths(r.ctx), "xrt_set_paths");
     const size_t n = (size_t)frame.getWidth() * frame.getHeight();
@@ -383,6 +386,40 @@ unsigned long long renderLoopPaths(std::vector<std::vector<float>>& paths, std::
     paths.resize(meshes.size());
     for (size_t m = 0; m < meshes.size(); ++m) paths[m].assign(planes.begin() + m * n, planes.begin() + (m + 1) * n);
     return stats.odd_rays;
+}
+
+void getVolumeBBox(const Volume& volume, Vec3& upper, Vec3& lower)
+{
+    float lo[3], hi[3];
+    if (xrt_volume_bbox(volume.dims, volume.origin, volume.spacing, lo, hi) != XRT_OK)
+        throw std::invalid_argument("getVolumeBBox: dims of 1 to 2048, a finite origin and spacings above 0");
+    lower = Vec3(lo[0], lo[1], lo[2]);
+    upper = Vec3(hi[0], hi[1], hi[2]);
+}
+
+void uploadVolume(const Volume& volume)
+{
+    const size_t n = (size_t)volume.dims[0] * volume.dims[1] * volume.dims[2];
+    if (volume.labels.size() != n || (!volume.density.empty() && volume.density.size() != n))
+        throw std::invalid_argument("uploadVolume: the arrays are not of the volume's dims");
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    g_volume_labels = volume.num_labels;
+    check(slot.ctx, xrt_upload_volume(slot.ctx, volume.labels.data(), volume.density.empty() ? nullptr : volume.density.data(),
+                                      volume.dims, volume.origin, volume.spacing, volume.num_labels),
+          "xrt_upload_volume");
+}
+
+void renderLoopVolumePaths(std::vector<std::vector<float>>& planes, const Image& frame, const RayTracerInfo& info)
+{
+    const xrt_camera cam = camera_for(frame, std::vector<TriangleMesh>(), info, &info.range);
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    const size_t n = (size_t)frame.getWidth() * frame.getHeight(), M = g_volume_labels;
+    std::vector<float> all(n * std::max<size_t>(M, 1));
+    check(slot.ctx, xrt_volume_paths(slot.ctx, &cam, 0, cam.height, (uint32_t)M, all.data()), "xrt_volume_paths");
+    planes.resize(M);
+    for (size_t m = 0; m < M; ++m) planes[m].assign(all.begin() + m * n, all.begin() + (m + 1) * n);
 }
 
 void applySpectrum(Image& image, const std::vector<std::vector<float>>& paths, const std::vector<unsigned short>& open,
@@ -730,3 +767,41 @@ extern "C" int xrt_host_load_meshes(const char* path, float** triangles, uint64_
 }
 
 extern "C" void xrt_host_free(void* p) { std::free(p); }
+
+namespace {
+thread_local std::string t_host_error;
+}
+
+extern "C" const char* xrt_host_last_error(void) { return t_host_error.c_str(); }
+
+extern "C" int xrt_host_load_volume(const char* path, void** data, int* element_type, uint32_t dims[3], float origin[3],
+                                    float spacing[3])
+{
+    if (!path || !data || !element_type || !dims || !origin || !spacing) {
+        t_host_error = "xrt_host_load_volume: NULL argument";
+        return XRT_ERR_ARGUMENT;
+    }
+    *data = nullptr;
+    try {
+        const MetaImage img = loadMetaImage(path);
+        const bool u8 = !img.u8.empty();
+        const size_t bytes = u8 ? img.u8.size() : img.f32.size() * sizeof(float);
+        void* out = std::malloc(bytes);
+        if (!out) {
+            t_host_error = "xrt_host_load_volume: out of memory";
+            return XRT_ERR_ARGUMENT;
+        }
+        std::memcpy(out, u8 ? static_cast<const void*>(img.u8.data()) : static_cast<const void*>(img.f32.data()), bytes);
+        *data = out;
+        *element_type = u8 ? XRT_VOLUME_U8 : XRT_VOLUME_F32;
+        for (int a = 0; a < 3; ++a) {
+            dims[a] = img.dims[a];
+            origin[a] = img.origin[a];
+            spacing[a] = img.spacing[a];
+        }
+        return XRT_OK;
+    } catch (const VolumeError& e) {
+        t_host_error = e.what();
+        return e.code;
+    }
+}

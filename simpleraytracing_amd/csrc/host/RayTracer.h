@@ -19,6 +19,7 @@
 #include "Material.h"
 #include "TriangleMesh.h"
 #include "Vec3.h"
+#include "VolumeLoader.h"
 
 struct xrt_stats;
 
@@ -127,8 +128,12 @@ unsigned long long renderLoopSpectrumMultiGPU(Image& output_image, const std::ve
 // and mu) and runs the hole fill into output_image: what renderLoopSpectrum
 // writes for the same scene, view and table, without tracing again.  One
 // device (there is no multi-GPU form yet).
+// With info_range the pixel spacing comes from info.range -- the box the camera
+// was made for, which may hold more than the meshes (a volume) -- and not from
+// the meshes' own box.
 unsigned long long renderLoopPaths(std::vector<std::vector<float>>& paths, std::vector<unsigned short>& open,
-                                   const Image& frame, const std::vector<TriangleMesh>& meshes, RayTracerInfo& info);
+                                   const Image& frame, const std::vector<TriangleMesh>& meshes, RayTracerInfo& info,
+                                   bool info_range = false);
 void applySpectrum(Image& output_image, const std::vector<std::vector<float>>& paths,
                    const std::vector<unsigned short>& open, const std::vector<float>& weight,
                    const std::vector<float>& mu, std::vector<float>* lbuffer = nullptr);
@@ -148,6 +153,21 @@ void applySpectralDetector(std::vector<Image>& channels, const std::vector<std::
                            const std::vector<float>& mu, const std::vector<float>& response, float gain = 1.0f,
                            float read_noise = 0.0f, unsigned long long seed = 0, unsigned long long first_index = 0,
                            bool noisy = false);
+
+// Voxel volumes (xrt_upload_volume).  getVolumeBBox: the
+// volume's box (xrt_volume_bbox), to pass to initialiseRayTracing alone or in
+// union with getBBox's.  uploadVolume: the volume onto the render device,
+// replacing any earlier one (it stays there between renders, apart from the
+// meshes).  renderLoopVolumePaths: one trace of the uploaded volume into one
+// plane per label (planes[L - 1], row-major, of frame's size -- only its size
+// is read), the path length of each ray inside label L times the voxels'
+// density; the pixel spacing comes from info.range.  Such planes go behind
+// renderLoopPaths' in applySpectrum's and applySpectralDetector's `paths`
+// (the table's rows: the meshes', then the labels'; the mask is the meshes').
+// The volume has no pose: setMeshPoses does not move it.  One device.
+void getVolumeBBox(const Volume& volume, Vec3& upper, Vec3& lower);
+void uploadVolume(const Volume& volume);
+void renderLoopVolumePaths(std::vector<std::vector<float>>& planes, const Image& frame, const RayTracerInfo& info);
 
 // The detector response (xrt_detector_response): the image under a separable
 // line-spread function, lsf_x along the rows and lsf_y down the columns (odd

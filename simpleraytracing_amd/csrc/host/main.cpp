@@ -103,6 +103,18 @@
 //                              --sinogram, --supersample, --focal-spot, -g, --rows, --batch
 //       --read-noise SIGMA     with --detector and --noise: additive Gaussian (electronic)
 //                              noise of SIGMA counts (finite, >= 0) on every channel
+//       --volume FILE.mhd      with --paths: a voxel phantom beside the meshes (or alone:
+//                              -i may then be omitted).  FILE.mhd is a MetaImage header
+//                              of MET_UCHAR labels (0: empty) with its raw file beside
+//                              it.  The camera is fitted to the union of the scene's box
+//                              and the volume's; label L's plane of path lengths is
+//                              written to NAME.m<k>.EXT behind the meshes' (k = meshes +
+//                              L - 1), and --spectrum's table holds one row per mesh,
+//                              then one per label.  The volume has no pose.  Not with
+//                              -g, --rows, --batch, --supersample, --focal-spot,
+//                              --turntable, --pose
+//       --volume-density FILE.mhd  with --volume: a MET_FLOAT density per voxel, of the
+//                              volume's dims; a segment counts times its voxel's density
 //       --lbuffer FILE         also write the L-buffer as raw little-endian f32
 //       --u8 FILE              also write the 8-bit image (LUT 0..80) as PGM
 //       --time                 print render wall-clock and Mrays/s
@@ -158,6 +170,8 @@ void showUsage(const std::string& prog)
               << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
               << "\t--detector FILE\t\t\tSpectral detector, with --paths --spectrum: FILE holds one line of K responses per energy channel (at most 8); writes NAME.c<c>.EXT per channel; with --noise GAIN[:SEED] a Poisson count per bin, divided by GAIN, otherwise the expected values at gain 1\n"
               << "\t--read-noise SIGMA\t\tWith --detector and --noise: additive Gaussian noise of SIGMA counts on every channel\n"
+              << "\t--volume FILE.mhd\t\tWith --paths: a voxel phantom (MetaImage header, MET_UCHAR labels, raw file beside it) beside the meshes or alone (no -i); one plane per label behind the meshes' (NAME.m<k>.EXT), one --spectrum row per mesh, then per label; not with -g, --rows, --batch, --supersample, --focal-spot, --turntable, --pose\n"
+              << "\t--volume-density FILE.mhd\tWith --volume: a MET_FLOAT density per voxel, of the volume's dims\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
               << "\t--u8 FILE\t\t\tWrite the 8-bit image (0..80 keV LUT) as PGM\n"
               << "\t--time\t\t\t\tPrint render time and Mrays/s\n"
@@ -202,6 +216,7 @@ struct Options {
     std::vector<std::vector<float>> detector_rows;
     bool read_noise_set = false;               // --read-noise SIGMA
     float read_noise = 0.0f;
+    std::string volume, volume_density;        // --volume FILE.mhd, --volume-density FILE.mhd
 };
 
 // A whole, non-negative decimal number.
@@ -596,6 +611,10 @@ Options processCmd(int argc, char** argv)
         } else if (a == "--read-noise") {
             o.read_noise = parse_read_noise(parse_str(argv[0], argc, argv, i));
             o.read_noise_set = true;
+        } else if (a == "--volume") {
+            o.volume = parse_str(argv[0], argc, argv, i);
+        } else if (a == "--volume-density") {
+            o.volume_density = parse_str(argv[0], argc, argv, i);
         } else if (a == "--time") {
             o.time = true;
         } else if (a == "--rows") {
@@ -619,7 +638,16 @@ Options processCmd(int argc, char** argv)
             std::exit(EXIT_FAILURE);
         }
     }
-    if (o.inputs.empty()) o.inputs.push_back("./dragon.ply");
+    if (o.inputs.empty() && o.volume.empty()) o.inputs.push_back("./dragon.ply");
+    if (!o.volume_density.empty() && o.volume.empty())
+        throw std::runtime_error("--volume-density needs --volume FILE.mhd: it is the density of that volume's voxels");
+    if (!o.volume.empty()) {
+        if (!o.paths) throw std::runtime_error("--volume needs --paths: a volume is traced into path-length planes");
+        const char* with = o.gpus > 1 ? "-g" : o.rows ? "--rows" : o.batch ? "--batch" : o.supersample ? "--supersample"
+                           : o.focal_spot ? "--focal-spot" : o.turntable ? "--turntable" : !o.poses.empty() ? "--pose" : nullptr;
+        if (with)
+            throw std::runtime_error(std::string("--volume traces whole frames on one GPU and has no pose: not with ") + with);
+    }
     if (o.rows && (o.row_begin >= o.row_end || o.row_end > o.height))
         throw std::out_of_range("--rows A:B must satisfy 0 <= A < B <= image height");
     if ((o.rows || o.batch) && (o.signed_model || !o.materials.empty() || o.spectrum || o.gpus > 1))
@@ -688,8 +716,31 @@ int main(int argc, char** argv)
         std::cout << "Loading polygon meshes... " << std::endl;
         auto t0 = std::chrono::high_resolution_clock::now();
         std::vector<TriangleMesh> meshes;
-        loadMeshes(opt.inputs[0], meshes);
+        if (!opt.inputs.empty()) loadMeshes(opt.inputs[0], meshes);
         for (size_t f = 1; f < opt.inputs.size(); ++f) appendMeshes(opt.inputs[f], meshes);
+        Volume volume;                                // --volume: every check before a device is opened
+        if (!opt.volume.empty()) {
+            try {
+                loadVolume(opt.volume, volume);
+            } catch (const VolumeError& e) {
+                throw std::runtime_error(std::string("--volume: ") + e.what());
+            }
+            try {
+                if (!opt.volume_density.empty()) loadVolumeDensity(opt.volume_density, volume);
+            } catch (const VolumeError& e) {
+                throw std::runtime_error(std::string("--volume-density: ") + e.what());
+            }
+            if (volume.num_labels == 0) throw std::runtime_error("--volume: " + opt.volume + " holds no label above 0");
+            if (meshes.size() + volume.num_labels > XRT_MAX_MESHES)
+                throw std::runtime_error("--volume: " + std::to_string(meshes.size()) + " meshes and " +
+                                         std::to_string(volume.num_labels) + " labels are more than " +
+                                         std::to_string(XRT_MAX_MESHES) + " planes");
+            if (opt.spectrum && opt.spectrum_mu.size() / opt.spectrum_weight.size() != meshes.size() + volume.num_labels)
+                throw std::runtime_error("--spectrum takes one row of coefficients per mesh, then one per label of --volume: " +
+                                         std::to_string(meshes.size()) + " meshes and " + std::to_string(volume.num_labels) +
+                                         " labels loaded, " +
+                                         std::to_string(opt.spectrum_mu.size() / opt.spectrum_weight.size()) + " rows");
+        }
         auto t1 = std::chrono::high_resolution_clock::now();
         std::cout << "Loading meshes took: " << std::chrono::duration<double>(t1 - t0).count()
                   << " seconds" << std::endl
@@ -707,6 +758,14 @@ int main(int argc, char** argv)
         std::cout << "Getting scene bbox... " << std::endl;
         Vec3 lower, upper;
         getBBox(meshes, upper, lower);
+        if (!opt.volume.empty()) {                    // the union of the scene's box and the volume's
+            Vec3 vlower, vupper;
+            getVolumeBBox(volume, vupper, vlower);
+            for (unsigned k = 0; k < 3; ++k) {
+                lower[k] = std::min(lower[k], vlower[k]);
+                upper[k] = std::max(upper[k], vupper[k]);
+            }
+        }
         float lut = 0.0f;
         Image image(opt.width, opt.height, lut);
         RayTracerInfo info = initialiseRayTracing(meshes, upper, lower, opt.height, opt.width, image, lut);
@@ -785,13 +844,23 @@ int main(int argc, char** argv)
                 renderLoopRows(image, meshes, info, rb, re, nullptr, nullptr, &st);
                 for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
             } else if (opt.paths) {
-                if (opt.spectrum && opt.spectrum_mu.size() / opt.spectrum_weight.size() != meshes.size())
+                const bool with_volume = !opt.volume.empty();
+                if (!with_volume && opt.spectrum && opt.spectrum_mu.size() / opt.spectrum_weight.size() != meshes.size())
                     throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
                                              " meshes loaded, " +
                                              std::to_string(opt.spectrum_mu.size() / opt.spectrum_weight.size()) + " rows");
                 std::vector<std::vector<float>> planes;
                 std::vector<unsigned short> open;
-                renderLoopPaths(planes, open, image, meshes, info);
+                if (!with_volume) {
+                    renderLoopPaths(planes, open, image, meshes, info);
+                } else {                              // the meshes' planes (if any), then the labels', under one camera
+                    if (!meshes.empty()) renderLoopPaths(planes, open, image, meshes, info, true);
+                    else open.assign((size_t)opt.width * opt.height, 0);
+                    std::vector<std::vector<float>> labels;
+                    uploadVolume(volume);
+                    renderLoopVolumePaths(labels, image, info);
+                    planes.insert(planes.end(), labels.begin(), labels.end());
+                }
                 const size_t dot = opt.output.find_last_of("./");
                 const bool ext = dot != std::string::npos && opt.output[dot] == '.';
                 const std::string stem = ext ? opt.output.substr(0, dot) : opt.output;

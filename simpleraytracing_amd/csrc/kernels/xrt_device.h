@@ -194,25 +194,27 @@ struct PixelOffsets {
 };
 
 // P: RenderParams in any address space (kernel argument or constant memory).
+// Callable from host code too (xrt_host_volume_paths): the same f32 sequence,
+// with the host's correctly rounded sqrtf and division.
 template <typename P>
-__device__ __forceinline__ void make_ray(const P& p, uint32_t row, uint32_t col,
-                                         float& dx, float& dy, float& dz);
+__host__ __device__ __forceinline__ void make_ray(const P& p, uint32_t row, uint32_t col, float& dx, float& dy,
+                                                  float& dz);
 
 template <typename P>
-__device__ __forceinline__ void make_ray_from(const P& p, float v_off, float u_off, float& dx,
-                                              float& dy, float& dz, float& sx, float& sy, float& sz);
+__host__ __device__ __forceinline__ void make_ray_from(const P& p, float v_off, float u_off, float& dx, float& dy,
+                                                       float& dz, float& sx, float& sy, float& sz);
 
 template <typename P>
-__device__ __forceinline__ void make_ray_from(const P& p, float v_off, float u_off, float& dx,
-                                              float& dy, float& dz)
+__host__ __device__ __forceinline__ void make_ray_from(const P& p, float v_off, float u_off, float& dx, float& dy,
+                                                       float& dz)
 {
     float sx, sy, sz;
     make_ray_from(p, v_off, u_off, dx, dy, dz, sx, sy, sz);
 }
 
 template <typename P>
-__device__ __forceinline__ void make_ray(const P& p, uint32_t row, uint32_t col,
-                                         float& dx, float& dy, float& dz)
+__host__ __device__ __forceinline__ void make_ray(const P& p, uint32_t row, uint32_t col, float& dx, float& dy,
+                                                  float& dz)
 {
     make_ray_from(p, pixel_offset(p.spacing, row, p.height), pixel_offset(p.spacing, col, p.width), dx,
                   dy, dz);
@@ -220,8 +222,8 @@ __device__ __forceinline__ void make_ray(const P& p, uint32_t row, uint32_t col,
 
 // The same ray with the offsets read from the frame's tables.
 template <typename P>
-__device__ __forceinline__ void make_ray(const P& p, const PixelOffsets& off, uint32_t row,
-                                         uint32_t col, float& dx, float& dy, float& dz)
+__host__ __device__ __forceinline__ void make_ray(const P& p, const PixelOffsets& off, uint32_t row, uint32_t col,
+                                                  float& dx, float& dy, float& dz)
 {
     make_ray_from(p, off.v[row], off.u[col], dx, dy, dz);
 }
@@ -230,8 +232,8 @@ __device__ __forceinline__ void make_ray(const P& p, const PixelOffsets& off, ui
 // L-buffer fork takes sign(direction . normal) with it, not with the Ray's
 // twice-normalised copy (main-pthreads-lbuffer.cxx:761-762, :791).
 template <typename P>
-__device__ __forceinline__ void make_ray_from(const P& p, float v_off, float u_off, float& dx,
-                                              float& dy, float& dz, float& sx, float& sy, float& sz)
+__host__ __device__ __forceinline__ void make_ray_from(const P& p, float v_off, float u_off, float& dx, float& dy,
+                                                       float& dz, float& sx, float& sy, float& sz)
 {
     // :659  detector + up*v + right*u - origin  (Vec3 ops left to right, f32)
     float X = ((p.cx + p.ux * v_off) + p.rx * u_off) - p.ox;
@@ -1477,6 +1479,111 @@ __host__ __device__ __forceinline__ void detector_pixel(uint32_t num_bins, QuadX
 __host__ __device__ __forceinline__ float xrt_detector_output(double acc, float gain, bool counts)
 {
     return counts ? (float)acc : (float)(acc / (double)gain);
+}
+
+// ---------------------------------------------------------------------------
+// Voxel phantoms: a labelled, axis-aligned volume traced into
+// paths planes.  volume_ray is the contract: k_volume_paths calls it on the
+// device and xrt_host_volume_paths compiled for the host, and
+// tests/volume_ref.py restates it.  All of it is f64, every operation rounded
+// on its own (no FMA), every min or max the written select (no fmin / fmax:
+// a NaN takes the same branch on both sides), no register array with a
+// dynamic index.
+// ---------------------------------------------------------------------------
+// The volume, by value in k_volume_paths' arguments.  labels[(z * ny + y) * nx
+// + x], label 0 empty, label L in 1..num_labels into plane L - 1; density of
+// the same shape or null (1).
+struct VolumeDesc {
+    const uint8_t* __restrict__ labels;
+    const float* __restrict__ density;
+    uint32_t n[3];          // nx, ny, nz
+    uint32_t num_labels;
+    float origin[3];        // the minimum corner of voxel (0, 0, 0)
+    float spacing[3];       // > 0
+};
+
+constexpr uint32_t kMaxVolumeDim = 2048;
+
+// Grid plane i of an axis: from the index every time, so nothing drifts.
+__host__ __device__ __forceinline__ double volume_plane(double lo, double s, uint32_t i) { return lo + (double)i * s; }
+
+// One axis of the slab test against [p0, pn): narrows [te, tx]; false when a
+// ray parallel to the axis lies outside the slab.
+__host__ __device__ __forceinline__ bool volume_slab(double O, double d, double p0, double pn, double& inv, double& te,
+                                                     double& tx)
+{
+    inv = 0.0;
+    if (d == 0.0) return O >= p0 && O < pn;
+    inv = 1.0 / d;
+    const double t0 = (p0 - O) * inv, t1 = (pn - O) * inv;
+    const double mn = t0 < t1 ? t0 : t1, mx = t0 < t1 ? t1 : t0;
+    te = mn > te ? mn : te;
+    tx = mx < tx ? mx : tx;
+    return true;
+}
+
+// The voxel index of the entry point on one axis, clamped into the volume (a
+// NaN goes to 0).
+__host__ __device__ __forceinline__ int32_t volume_start(double O, double te, double d, double lo, double s, uint32_t n)
+{
+    double f = floor(((O + te * d) - lo) / s);
+    const double top = (double)(n - 1u);
+    f = f >= 0.0 ? f : 0.0;
+    f = f <= top ? f : top;
+    return (int32_t)f;
+}
+
+// The ray O + t d through the volume: add(m, run) is called once per run of
+// consecutive steps in label m + 1 with the run's f64 sum of segment lengths
+// (times the voxel's density), in ray order -- the association of the plane's
+// sum.  A ray that misses calls nothing.  At most nx + ny + nz + 3 steps.
+template <typename Add>
+__host__ __device__ __forceinline__ void volume_ray(const VolumeDesc& v, double Ox, double Oy, double Oz, double dx,
+                                                    double dy, double dz, Add&& add)
+{
+    const double inf = __builtin_huge_val();
+    const uint32_t nx = v.n[0], ny = v.n[1], nz = v.n[2];
+    const double lox = (double)v.origin[0], loy = (double)v.origin[1], loz = (double)v.origin[2];
+    const double sx = (double)v.spacing[0], sy = (double)v.spacing[1], sz = (double)v.spacing[2];
+    double te = 0.0, tx = inf, ivx, ivy, ivz;
+    if (!volume_slab(Ox, dx, volume_plane(lox, sx, 0u), volume_plane(lox, sx, nx), ivx, te, tx)) return;
+    if (!volume_slab(Oy, dy, volume_plane(loy, sy, 0u), volume_plane(loy, sy, ny), ivy, te, tx)) return;
+    if (!volume_slab(Oz, dz, volume_plane(loz, sz, 0u), volume_plane(loz, sz, nz), ivz, te, tx)) return;
+    if (!(te < tx)) return;
+    int32_t ix = volume_start(Ox, te, dx, lox, sx, nx);
+    int32_t iy = volume_start(Oy, te, dy, loy, sy, ny);
+    int32_t iz = volume_start(Oz, te, dz, loz, sz, nz);
+    const int32_t stx = dx > 0.0 ? 1 : -1, sty = dy > 0.0 ? 1 : -1, stz = dz > 0.0 ? 1 : -1;
+    const int32_t upx = dx > 0.0 ? 1 : 0, upy = dy > 0.0 ? 1 : 0, upz = dz > 0.0 ? 1 : 0;
+    double tc = te, run = 0.0;
+    uint32_t cur = 0;
+    const uint32_t limit = nx + ny + nz + 3u;
+    for (uint32_t k = 0; k < limit; ++k) {
+        const double tnx = dx == 0.0 ? inf : (volume_plane(lox, sx, (uint32_t)(ix + upx)) - Ox) * ivx;
+        const double tny = dy == 0.0 ? inf : (volume_plane(loy, sy, (uint32_t)(iy + upy)) - Oy) * ivy;
+        const double tnz = dz == 0.0 ? inf : (volume_plane(loz, sz, (uint32_t)(iz + upz)) - Oz) * ivz;
+        double t = tnx;                 // ties: the lower axis first
+        int32_t a = 0;
+        if (tny < t) { t = tny; a = 1; }
+        if (tnz < t) { t = tnz; a = 2; }
+        const double tend = t < tx ? t : tx;
+        const double seg = tend - tc;
+        const uint64_t vox = ((uint64_t)(uint32_t)iz * ny + (uint32_t)iy) * nx + (uint32_t)ix;
+        const uint32_t L = v.labels[vox];
+        if (L != cur) {
+            if (cur) add(cur - 1u, run);
+            run = 0.0;
+            cur = L;
+        }
+        if (L != 0u && seg > 0.0) run = run + (v.density ? seg * (double)v.density[vox] : seg);
+        if (seg > 0.0) tc = tend;
+        if (!(t < tx)) break;
+        ix += a == 0 ? stx : 0;
+        iy += a == 1 ? sty : 0;
+        iz += a == 2 ? stz : 0;
+        if ((uint32_t)ix >= nx || (uint32_t)iy >= ny || (uint32_t)iz >= nz) break;
+    }
+    if (cur) add(cur - 1u, run);
 }
 
 }  // namespace XRT_KERNEL_NS

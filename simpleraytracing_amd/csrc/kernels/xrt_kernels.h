@@ -4231,4 +4231,55 @@ __global__ __launch_bounds__(kDetectorThreads) void k_spectral_detector(const fl
         if (c < C) det.out[c * det.plane + i] = flagged ? -1.0f : xrt_detector_output(acc[c], det.gain, det.counts != 0u);
 }
 
+// ---------------------------------------------------------------------------
+// k_volume_paths: the voxel trace.  One lane a pixel, one
+// single-wave workgroup an 8x8 pixel tile, as the binned render tiles its
+// rays: neighbouring rays walk the same voxels, so their label and density
+// loads share cache lines.  Each lane runs volume_ray for its pixel.  kM
+// bounds the labels (1, 4 or kMaxMeshes: the host picks the smallest that
+// holds the volume's).  Under kM = 1 the plane's sum stays in a register and
+// there is no LDS; otherwise the per-label f64 sums, which need a dynamic
+// index, are parked in the wave's LDS as acc[m * 64 + lane] (a lane reads only
+// what it wrote: no barrier) and touched only when a run ends.  Every plane of
+// every pixel of the strip is written (a miss: +0.0f).  A lane outside the
+// frame or the strip leaves at once.  Indices into the volume and the planes
+// are 64-bit.  No scratch.  tile_shift is the wave's shape, 2^tile_shift
+// pixels wide and 64 >> tile_shift high: kVolumeTileShift (8 x 8) in every
+// product call; 6 (a 64 x 1 row segment) is the other leg of the layout's A/B
+// (xrt_debug_volume_wave_shape, tools/volume_timing.py).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kVolumeTileShift = 3;
+constexpr uint32_t kVolumeFewLabels = 4;
+
+template <uint32_t kM>
+__global__ __launch_bounds__(64) void k_volume_paths(const RenderParams p, const VolumeDesc vol, uint32_t tiles_x,
+                                                     uint32_t tile_shift, float* __restrict__ paths)
+{
+    static_assert(kM == 1u || kM == kVolumeFewLabels || kM == kMaxMeshes, "the three label bounds");
+    const uint32_t lane = threadIdx.x;
+    const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const uint32_t col = (tile_x << tile_shift) + (lane & ((1u << tile_shift) - 1u));
+    const uint32_t row = p.row_begin + tile_y * (64u >> tile_shift) + (lane >> tile_shift);
+    if (col >= p.width || row >= p.row_end) return;   // (no barrier below)
+    float dx, dy, dz;
+    make_ray(p, row, col, dx, dy, dz);
+    const size_t plane = (size_t)(p.row_end - p.row_begin) * p.width;
+    const size_t pix = (size_t)(row - p.row_begin) * p.width + col;
+    if constexpr (kM == 1u) {
+        double acc = 0.0;
+        volume_ray(vol, (double)p.ox, (double)p.oy, (double)p.oz, (double)dx, (double)dy, (double)dz,
+                   [&](uint32_t, double run) { acc = acc + run; });
+        paths[pix] = (float)acc;
+    } else {
+        __shared__ double s_acc[kM * 64u];
+        const uint32_t M = vol.num_labels < kM ? vol.num_labels : kM;
+        for (uint32_t m = 0; m < M; ++m) s_acc[m * 64u + lane] = 0.0;
+        volume_ray(vol, (double)p.ox, (double)p.oy, (double)p.oz, (double)dx, (double)dy, (double)dz,
+                   [&](uint32_t m, double run) {
+                       if (m < M) s_acc[m * 64u + lane] = s_acc[m * 64u + lane] + run;
+                   });
+        for (uint32_t m = 0; m < M; ++m) paths[m * plane + pix] = (float)s_acc[m * 64u + lane];
+    }
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -536,6 +536,15 @@ struct xrt_context {
     std::vector<Pose> posed_written;
     uint64_t pose_gen = 0;             // bumped by every pose change
     uint64_t hp_pose_launches = 0, hp_pose_tris = 0;   // k_pose launches and the triangles they wrote
+
+    // The voxel volume (xrt_upload_volume): apart from the
+    // meshes, the model and the frames.  vol.labels is null while there is
+    // none.  vol_ev marks the last trace enqueued (on the caller's stream):
+    // the next upload waits for it before it frees the arrays.
+    VolumeDesc vol = {};
+    hipEvent_t vol_ev = nullptr;
+    bool vol_busy = false;
+    uint32_t vol_tile_shift = kVolumeTileShift;        // xrt_debug_volume_wave_shape
 };
 
 inline double seconds_since(HostClock::time_point t)
@@ -2082,6 +2091,10 @@ void xrt_destroy(xrt_context* ctx)
     (void)hipFree(ctx->d_spectrum);
     (void)hipFree(ctx->d_path_ends);
     (void)hipFree(ctx->d_prep_times);
+    if (ctx->vol_busy) (void)hipEventSynchronize(ctx->vol_ev);
+    (void)hipFree(const_cast<uint8_t*>(ctx->vol.labels));
+    (void)hipFree(const_cast<float*>(ctx->vol.density));
+    if (ctx->vol_ev) (void)hipEventDestroy(ctx->vol_ev);
     for (auto& c : ctx->tchunks) (void)hipFree(c.p);
     lap(1);
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
@@ -2649,6 +2662,124 @@ int xrt_spectral_detector(xrt_context* ctx, uint64_t num_pixels, uint32_t num_me
                                           ctx->host_stream))
         return rc;
     s.download(out, dout, n * num_channels);
+    return s.finish();
+}
+
+// --- voxel phantoms -----------------------------------------
+
+#include "xrt_volume_host.inc"
+
+// Frees the context's volume once its last trace is through.
+static int free_volume(xrt_context* ctx)
+{
+    if (ctx->vol_busy) {
+        XRT_HIP(ctx, hipEventSynchronize(ctx->vol_ev));
+        ctx->vol_busy = false;
+    }
+    (void)hipFree(const_cast<uint8_t*>(ctx->vol.labels));
+    (void)hipFree(const_cast<float*>(ctx->vol.density));
+    ctx->vol = VolumeDesc{};
+    return XRT_OK;
+}
+
+int xrt_upload_volume(xrt_context* ctx, const uint8_t* labels, const float* density, const uint32_t dims[3],
+                      const float origin[3], const float spacing[3], uint32_t num_labels)
+{
+    const bool release = !labels || num_labels == 0;
+    if (!release) {
+        const std::string why = volume_arguments(labels, density, dims, origin, spacing, num_labels);
+        if (!why.empty()) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    }
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = free_volume(ctx)) return rc;
+    if (release) return XRT_OK;
+    const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+    uint8_t* d_labels = nullptr;
+    float* d_density = nullptr;
+    hipError_t e = hipMalloc((void**)&d_labels, n);
+    if (e == hipSuccess && density) e = hipMalloc((void**)&d_density, n * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d_labels, labels, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && density) e = hipMemcpy(d_density, density, n * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d_labels);
+        (void)hipFree(d_density);
+        (void)hipGetLastError();
+        return fail(ctx, XRT_ERR_DEVICE, std::string("xrt_upload_volume: ") + hipGetErrorString(e));
+    }
+    ctx->vol = volume_desc(d_labels, d_density, dims, origin, spacing, num_labels);
+    return XRT_OK;
+}
+
+// The checks both traces share, the arguments' first (no context needed).
+static int volume_paths_arguments(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                                  uint32_t num_labels, const float* paths)
+{
+    if (const char* why = volume_trace_arguments(camera, row_begin, row_end, num_labels, paths))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (!ctx->vol.labels) return fail(ctx, XRT_ERR_NO_MESH, "no volume uploaded (xrt_upload_volume)");
+    if (num_labels != ctx->vol.num_labels)
+        return fail(ctx, XRT_ERR_ARGUMENT, "num_labels differs from the uploaded volume's");
+    return XRT_OK;
+}
+
+// The launch of k_volume_paths (validated arguments, a strip of at least one row): the instantiation of the
+// smallest label bound that holds the volume's.
+static int launch_volume_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                               float* d_paths, hipStream_t stream)
+{
+    const RenderParams p = volume_params(*camera, row_begin, row_end);
+    const uint32_t shift = ctx->vol_tile_shift, tw = 1u << shift, th = 64u >> shift;
+    const uint64_t tiles_x = ((uint64_t)p.width + tw - 1u) / tw;
+    const uint64_t tiles_y = ((uint64_t)(row_end - row_begin) + th - 1u) / th;
+    // (8 x 8 tiles: at most 2^32 / 64 tiles and a ragged edge's; only the row-shaped debug leg can exceed a launch)
+    if (tiles_x * tiles_y > 0x7FFFFFFFull) return fail(ctx, XRT_ERR_ARGUMENT, "the strip needs more than 2^31 - 1 workgroups");
+    const dim3 grid((unsigned)(tiles_x * tiles_y)), block(64);
+    const uint32_t M = ctx->vol.num_labels;
+    if (M <= 1u)
+        hipLaunchKernelGGL((k_volume_paths<1u>), grid, block, 0, stream, p, ctx->vol, (uint32_t)tiles_x, shift, d_paths);
+    else if (M <= kVolumeFewLabels)
+        hipLaunchKernelGGL((k_volume_paths<kVolumeFewLabels>), grid, block, 0, stream, p, ctx->vol, (uint32_t)tiles_x,
+                           shift, d_paths);
+    else
+        hipLaunchKernelGGL((k_volume_paths<kMaxMeshes>), grid, block, 0, stream, p, ctx->vol, (uint32_t)tiles_x, shift,
+                           d_paths);
+    XRT_HIP(ctx, hipGetLastError());
+    if (!ctx->vol_ev) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->vol_ev, hipEventDisableTiming));
+    XRT_HIP(ctx, hipEventRecord(ctx->vol_ev, stream));
+    ctx->vol_busy = true;
+    return XRT_OK;
+}
+
+int xrt_debug_volume_wave_shape(xrt_context* ctx, int rows)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    ctx->vol_tile_shift = rows ? 6u : kVolumeTileShift;
+    return XRT_OK;
+}
+
+int xrt_volume_paths_device(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                            uint32_t num_labels, float* d_paths, void* stream)
+{
+    int rc = volume_paths_arguments(ctx, camera, row_begin, row_end, num_labels, d_paths);
+    if (rc || row_begin == row_end) return rc;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_volume_paths(ctx, camera, row_begin, row_end, d_paths, (hipStream_t)stream);
+}
+
+int xrt_volume_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
+                     uint32_t num_labels, float* paths)
+{
+    int rc = volume_paths_arguments(ctx, camera, row_begin, row_end, num_labels, paths);
+    if (rc || row_begin == row_end) return rc;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)(row_end - row_begin) * camera->width * num_labels;
+    DeviceScratch s(ctx, ctx->host_stream, "volume paths");
+    float* dp = s.alloc<float>(n);
+    if (s.rc()) return s.rc();
+    if ((rc = launch_volume_paths(ctx, camera, row_begin, row_end, dp, ctx->host_stream))) return rc;
+    s.download(paths, dp, n);
     return s.finish();
 }
 
