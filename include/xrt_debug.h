@@ -225,6 +225,30 @@ int xrt_host_footprints(const xrt_camera* camera, const float* tris, uint64_t n,
 int xrt_debug_set_tile_plan(xrt_context* ctx, int on);
 
 /*
+ * The ray table ("Ray table"): an attenuation BINNED
+ * frame that repeats the previous one's camera, image size and strip has the
+ * camera's ray directions tabulated once on the device, and the frames after
+ * it read them instead of generating them (bit for bit the same rays).  On by
+ * default within XRT_RAY_CACHE_MB megabytes (256; 0 = never), read from the
+ * environment at xrt_create.  xrt_debug_set_ray_table turns it off (0) or on
+ * (1) for later frames.  counters: [0] fills launched, [1] frames rendered
+ * from the table, [2] frames in its scope that computed their rays (no fill
+ * yet, a fill postponed behind renders in flight, over the budget, or off),
+ * [3] bytes held.
+ */
+int xrt_debug_set_ray_table(xrt_context* ctx, int on);
+int xrt_debug_ray_table_counters(xrt_context* ctx, uint64_t counters[4]);
+
+/*
+ * Host code (no device): where the table of a width x height image's strip
+ * [row_begin, row_end) keeps dx of pixel (row, col), in floats -- dy and dz lie
+ * 64 and 128 floats further --, by the function the two kernels use; *floats
+ * (may be NULL) receives the table's size in floats.
+ */
+int xrt_debug_ray_table_index(uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_end, uint32_t row,
+                              uint32_t col, uint64_t* index, uint64_t* floats);
+
+/*
  * Diagnostics: k_prep's per-wave timestamps.  enable 1 / 0 turns the records
  * on / off for later launches (-1 leaves it); *n_waves = the waves of the last
  * recorded launch; with dst, waits for the context's work and copies up to

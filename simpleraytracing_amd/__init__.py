@@ -36,6 +36,7 @@ __all__ = [
     "XRT_MAX_CHANNELS", "XRT_DETECT_EXPECTED", "XRT_DETECT_NOISY", "XRT_DETECT_COUNTS", "XRT_DETECT_INTENSITY",
     "host_spectral_detector", "spectral_detector", "volume_bbox", "host_volume_paths", "load_volume",
     "XRT_MAX_SOURCES", "XRT_MAX_BIN", "supersampled_camera", "focal_spot", "host_area_integrate", "area_integrate",
+    "ray_table_index",
 ]
 
 
@@ -340,6 +341,18 @@ def photon_noise(image, gain, seed, counts=False, first_index=0, device: int = 0
     """The noisy image(s) of Context.photon_noise, on a context of its own on `device`."""
     with Context(device) as ctx:
         return ctx.photon_noise(image, gain, seed, counts, first_index)
+
+
+def ray_table_index(width: int, height: int, row_begin: int, row_end: int, row: int, col: int):
+    """(index, floats): where the ray table of the strip [row_begin, row_end) of a width x height image keeps
+    dx of pixel (row, col) -- dy and dz lie 64 and 128 floats on -- and the table's size in floats
+    (xrt_debug_ray_table_index: host code, the kernels' own function)."""
+    index, floats = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = _abi.load().xrt_debug_ray_table_index(int(width), int(height), int(row_begin), int(row_end), int(row),
+                                               int(col), ctypes.byref(index), ctypes.byref(floats))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_debug_ray_table_index: the pixel must lie in the strip and the strip in the image")
+    return int(index.value), int(floats.value)
 
 
 def supersampled_camera(cam: Camera, bin: int) -> Camera:
@@ -1001,6 +1014,17 @@ class Context:
     def set_tile_plan(self, on: bool):
         """The tile plan on / off for later frames (off by default: xrt_debug_set_tile_plan)."""
         self._check(self._lib.xrt_debug_set_tile_plan(self._ctx, 1 if on else 0), "xrt_debug_set_tile_plan")
+
+    def set_ray_table(self, on: bool):
+        """The ray table on / off for later frames (on by default: xrt_debug_set_ray_table)."""
+        self._check(self._lib.xrt_debug_set_ray_table(self._ctx, 1 if on else 0), "xrt_debug_set_ray_table")
+
+    def ray_table_counters(self) -> dict:
+        """Fills launched, frames rendered from the ray table, frames in its scope that
+        computed their rays, bytes held (xrt_debug_ray_table_counters)."""
+        c = (ctypes.c_uint64 * 4)()
+        self._check(self._lib.xrt_debug_ray_table_counters(self._ctx, c), "xrt_debug_ray_table_counters")
+        return dict(zip(("fills", "frames", "computed", "bytes"), (int(v) for v in c)))
 
     def pipeline_counters(self) -> dict:
         """Frames rendered from a preparation made ahead, preparations dropped, renders

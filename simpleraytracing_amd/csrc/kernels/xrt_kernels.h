@@ -122,6 +122,10 @@ struct Outputs {
         const __attribute__((address_space(4))) uint32_t* path_ends;
     };
     uint32_t num_meshes;
+    // The camera's ray table (k_ray_table; ray_table_tile): the twice-normalised
+    // direction of every pixel of the strip, tile-major.  Null: the tile waves
+    // compute their rays.  Read by k_render_binned_rays only.
+    const float* rays;
 };
 // (the hit layout has its own instantiation of the binned render, kHits: its
 // stores in the ordinary render cost 10-35% of the kernel's time)
@@ -2663,6 +2667,38 @@ constexpr uint32_t kRoundSlots = kBinStage / 64u;
 static_assert(kBinStage % 64u == 0u && kRoundSlots >= 1u && kRoundSlots <= 4u, "64 to 256 candidates per round");
 static_assert(16u % kTileWaves == 0u, "a workgroup's waves render tiles of one region");
 
+// The ray table of one camera and strip (k_ray_table writes it, the tile waves
+// of k_render_binned_rays read it): tile-major over the render's own 8x8
+// tiles, tile rows and columns padded to whole regions.  Tile (tx, ty) -- the
+// columns 8 * tx .., the rows row_begin + 8 * ty .. -- owns kRayTileFloats
+// contiguous floats: the dx, dy and dz planes, 64 floats each, in render_tile's
+// lane order.  A tile wave's address is a wave-uniform base plus its lane.
+constexpr uint32_t kRayTileFloats = 3u * 64u;
+__host__ __device__ __forceinline__ uint32_t ray_table_tiles_x(uint32_t width)
+{
+    return (width + kRegion - 1u) / kRegion * (kRegion / 8u);
+}
+__host__ __device__ __forceinline__ uint32_t ray_table_tiles_y(uint32_t row_begin, uint32_t row_end)
+{
+    return (row_end - row_begin + kRegion - 1u) / kRegion * (kRegion / 8u);
+}
+__host__ __device__ __forceinline__ uint64_t ray_table_floats(uint32_t width, uint32_t row_begin, uint32_t row_end)
+{
+    return (uint64_t)ray_table_tiles_x(width) * ray_table_tiles_y(row_begin, row_end) * kRayTileFloats;
+}
+// First float (lane 0's dx) of tile (tx, ty).
+__host__ __device__ __forceinline__ uint64_t ray_table_tile(uint32_t width, uint32_t tx, uint32_t ty)
+{
+    return ((uint64_t)ty * ray_table_tiles_x(width) + tx) * kRayTileFloats;
+}
+// dx of pixel (row, col) of the strip that begins at row_begin; dy and dz lie 64 and 128 floats on.
+__host__ __device__ __forceinline__ uint64_t ray_table_index(uint32_t width, uint32_t row_begin, uint32_t row,
+                                                             uint32_t col)
+{
+    const uint32_t r = row - row_begin;
+    return ray_table_tile(width, col / 8u, r / 8u) + (r & 7u) * 8u + (col & 7u);
+}
+
 // One tile wave's staged records: q[0..3][L] = the TriRec of lane L's
 // candidate, written by that lane's DMA when the candidate survived the tile
 // test, read back as a broadcast by the survivor loop.  Private to the wave:
@@ -2793,7 +2829,7 @@ __device__ __forceinline__ void merge_half(const RecStage& other, HitList& hl, u
     tests += wave_uniform(__float_as_uint(d.y));
 }
 
-template <uint32_t kModel, bool kHits>
+template <uint32_t kModel, bool kHits, bool kRays = false>
 __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restrict__ recs,
                                             const float4* __restrict__ culls, const RenderParams& p,
                                             const Outputs& out, const BinBuffers& bins, uint32_t n_glob,
@@ -2847,8 +2883,13 @@ __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restri
     bool have_ray = false;                         // wave-uniform
     // the tile's pixel offsets, loaded beside the first footprints: a tile with
     // survivors generates its rays without another memory round trip
-    const float pre_v = out.off.v[min(row, p.height - 1u)];
-    const float pre_u = out.off.u[min(col, p.width - 1u)];
+    // (kRays: the rays come from the camera's table instead, below)
+    static_assert(!kRays || (!kSigned && !kHits), "the ray table holds the twice-normalised direction only");
+    float pre_v = 0.0f, pre_u = 0.0f;
+    if constexpr (!kRays) {
+        pre_v = out.off.v[min(row, p.height - 1u)];
+        pre_u = out.off.u[min(col, p.width - 1u)];
+    }
     typename std::conditional<kSigned, SignedHits, HitList>::type hl;
     hl.init();
     uint32_t tests = 0;
@@ -2895,7 +2936,16 @@ __device__ __forceinline__ void render_tile(RecStage& st, const TriRec* __restri
             // the survivors' records into the wave's stage (DMA, no registers)
             if (mm) stage_survivor_records(st, recs, (mm >> lane) & 1ull, id[r]);
             if (!have_ray) {                       // under the records' DMA
-                make_ray_from(*out.frame, pre_v, pre_u, dx, dy, dz, sx, sy, sz);
+                if constexpr (kRays) {
+                    // the tile's three planes, 256 B each: issued beside the DMA, landed by the same wait
+                    const float* __restrict__ t =
+                        out.rays + ray_table_tile(p.width, tx0 / 8u, (ty0 - p.row_begin) / 8u);
+                    dx = t[lane];
+                    dy = t[64u + lane];
+                    dz = t[128u + lane];
+                } else {
+                    make_ray_from(*out.frame, pre_v, pre_u, dx, dy, dz, sx, sy, sz);
+                }
                 have_ray = true;
             }
             if (!mm) continue;
@@ -3005,7 +3055,7 @@ __device__ __forceinline__ void fill_region_rows(const RenderParams& p, const Ou
 // launches a plan that this frame's k_prep confirmed (no pair binned past
 // tile_slots, an empty global list: BinBuffers::plan_miss); otherwise every
 // region renders as tiles.  The signed model always renders tiles.
-template <uint32_t kModel, bool kHits>
+template <uint32_t kModel, bool kHits, bool kRays = false>
 __device__ __forceinline__ void render_binned(RecStage* st, const TriRec* __restrict__ recs,
                                               const float4* __restrict__ culls, const RenderParams& p,
                                               const Outputs& out, const BinBuffers& bins,
@@ -3074,7 +3124,7 @@ __device__ __forceinline__ void render_binned(RecStage* st, const TriRec* __rest
         slot = g / kWavesPerRegion;                  // workgroup-uniform
         tile = g % kWavesPerRegion;
     }
-    render_tile<kModel, kHits>(st[wave], recs, culls, p, out, bins, n_glob, slot, tile, ws, cand, split, partner);
+    render_tile<kModel, kHits, kRays>(st[wave], recs, culls, p, out, bins, n_glob, slot, tile, ws, cand, split, partner);
     // one record per tile (a split tile's by half 0); candidates are counted
     // once per region (by the wave holding tile 0)
     if (split != kSplitHalf1)
@@ -3098,6 +3148,45 @@ __global__ __launch_bounds__(64 * kTileWaves) __attribute__((amdgpu_waves_per_eu
 {
     __shared__ RecStage st[kTileWaves];
     render_binned<kModelAttenuation, true>(st, recs, culls, p, out, bins, bs);
+}
+
+// The same render with its rays read from the camera's table (Outputs::rays,
+// launch_frame): a tile wave with a survivor loads its tile's three planes
+// where the other instantiation runs make_ray_from.  Its own kernel, as the hit
+// layout's: both paths in one would cost registers and instruction cache.
+__global__ __launch_bounds__(64 * kTileWaves) __attribute__((amdgpu_waves_per_eu(XRT_RENDER_WAVES, 8))) void k_render_binned_rays(
+    const TriRec* __restrict__ recs, const float4* __restrict__ culls, RenderParams p, Outputs out,
+    BinBuffers bins, const BinState* __restrict__ bs)
+{
+    __shared__ RecStage st[kTileWaves];
+    render_binned<kModelAttenuation, false, true>(st, recs, culls, p, out, bins, bs);
+}
+
+// ---------------------------------------------------------------------------
+// k_ray_table: fills a camera's ray table (ray_table_tile), one wave per 8x8
+// tile of the padded strip.  Each lane runs render_tile's own ray generation
+// for its pixel -- make_ray_from over pixel_offset of the row and column
+// clamped into the image, as k_prep tabulates them -- so a partial tile,
+// its lanes outside the image included, holds exactly what the computing wave
+// would have in its registers.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ray_table(RenderParams p, float* __restrict__ table)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tiles_x = ray_table_tiles_x(p.width);
+    const uint32_t tile = blockIdx.x * (blockDim.x / 64u) + wave_in_block();
+    if (tile >= tiles_x * ray_table_tiles_y(p.row_begin, p.row_end)) return;
+    const uint32_t tx = tile % tiles_x, ty = tile / tiles_x;
+    const uint32_t col = tx * 8u + (lane & 7u);
+    const uint32_t row = p.row_begin + ty * 8u + (lane >> 3);
+    const float v_off = pixel_offset(p.spacing, min(row, p.height - 1u), p.height);
+    const float u_off = pixel_offset(p.spacing, min(col, p.width - 1u), p.width);
+    float dx, dy, dz;
+    make_ray_from(p, v_off, u_off, dx, dy, dz);
+    float* __restrict__ t = table + ray_table_tile(p.width, tx, ty);
+    t[lane] = dx;
+    t[64u + lane] = dy;
+    t[128u + lane] = dz;
 }
 
 // ---------------------------------------------------------------------------

@@ -188,6 +188,7 @@ struct FrameSet {
     hipEvent_t done = nullptr;         // render end (a stop event on the render's dispatch)
     hipEvent_t done_ev = nullptr;      // the event that marks the set's last render complete
     bool done_valid = false;
+    bool ray_reader = false;           // the set's last render reads the context's ray table
     // k_prep's flags (BinBuffers::plan_miss): [0] the fill plan did not hold,
     // [1] a list overflowed.  Host-mapped, cleared by the host before k_prep,
     // read after the host has waited for k_prep's completion.
@@ -545,6 +546,34 @@ struct xrt_context {
     hipEvent_t vol_ev = nullptr;
     bool vol_busy = false;
     uint32_t vol_tile_shift = kVolumeTileShift;        // xrt_debug_volume_wave_shape
+
+    // Ray table (DESIGN.md "Ray table"): the ray directions of one camera and
+    // strip, filled by k_ray_table on the prep stream when an attenuation
+    // BINNED frame repeats the previous one's RayKey, and read by
+    // k_render_binned_rays in place of make_ray_from while the key stays.  The
+    // rays depend on nothing else: the mesh, the poses and the lists may change
+    // under a valid table.
+    struct RayKey {
+        float cam[13];                 // RenderParams' camera floats
+        uint32_t width, height, row_begin, row_end;
+        bool same(const RayKey& o) const   // field by field, the floats by bits
+        {
+            return std::memcmp(cam, o.cam, sizeof cam) == 0 && width == o.width && height == o.height &&
+                   row_begin == o.row_begin && row_end == o.row_end;
+        }
+    };
+    float* d_rays = nullptr;
+    size_t rays_cap = 0;               // bytes allocated
+    RayKey ray_key = {};               // the table's, while ray_valid
+    bool ray_valid = false;            // a fill for ray_key is enqueued (or complete)
+    hipEvent_t ray_filled = nullptr;   // that fill's end (prep stream)
+    bool ray_fill_done = false;        // ray_filled has passed: readers need no wait
+    std::vector<hipStream_t> ray_waited;   // the streams already ordered after the fill
+    RayKey ray_call_key = {};          // the previous eligible frame's key
+    bool ray_call_valid = false;
+    bool ray_enabled = true;           // xrt_debug_set_ray_table
+    size_t ray_budget = (size_t)256 << 20;   // XRT_RAY_CACHE_MB (0: no table)
+    uint64_t hp_ray_fills = 0, hp_ray_frames = 0, hp_ray_computed = 0;
 };
 
 inline double seconds_since(HostClock::time_point t)
@@ -1123,6 +1152,7 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     out.wave_times = nullptr;          // launch_frame
     out.hit_tiles = 0u;
     out.hit_off = nullptr;
+    out.rays = nullptr;                // launch_frame
     if (ctx->packed_cap || ctx->hits_cap) {        // xrt_set_transit_layout / _hits
         if (!binned || signed_model || d_image || d_u8)
             return fail(ctx, XRT_ERR_ARGUMENT,
@@ -1480,6 +1510,86 @@ double records_span_ms(const std::vector<uint2>& t)
     return hi > lo ? (double)(hi - lo) / kTicksPerMs : 0.0;
 }
 
+// The ray table for an attenuation BINNED frame about to be launched on
+// `stream`, or null when the frame computes its rays (xrt_context::RayKey).
+// A frame whose key repeats the previous frame's starts the fill (the trigger
+// of prepare-ahead: an orbit or a one-shot frame never pays for one); the
+// frames until then, a frame over the budget and a context with the table off
+// compute.  The render is ordered after the fill on the device, one wait per
+// stream and fill and none once the fill's event has passed; the host never
+// waits.  A table that launched renders may still read is not refilled: the
+// new key's frames compute until those renders' completion events have passed.
+int frame_rays(xrt_context* ctx, const RenderParams& p, hipStream_t stream, const float*& rays)
+{
+    rays = nullptr;
+    xrt_context::RayKey key = {};
+    const float cam[13] = {p.ox, p.oy, p.oz, p.cx, p.cy, p.cz, p.ux, p.uy, p.uz, p.rx, p.ry, p.rz, p.spacing};
+    std::memcpy(key.cam, cam, sizeof cam);
+    key.width = p.width;
+    key.height = p.height;
+    key.row_begin = p.row_begin;
+    key.row_end = p.row_end;
+    const bool repeated = ctx->ray_call_valid && key.same(ctx->ray_call_key);
+    ctx->ray_call_key = key;
+    ctx->ray_call_valid = true;
+    if (ctx->ray_valid && !key.same(ctx->ray_key)) ctx->ray_valid = false;
+    const uint64_t bytes = ray_table_floats(p.width, p.row_begin, p.row_end) * sizeof(float);
+    if (!ctx->ray_enabled || bytes > ctx->ray_budget) {
+        ++ctx->hp_ray_computed;
+        return XRT_OK;
+    }
+    if (!ctx->ray_valid && repeated) {
+        // renders in flight over the old table (a set is reused only after its
+        // last render is complete, so each set's last event speaks for it), and
+        // an old fill still running before the buffer is freed for a larger one
+        bool busy = false;
+        for (FrameSet& fs : ctx->sets) {
+            if (!fs.ray_reader) continue;
+            if (!fs.done_valid || hipEventQuery(fs.done_ev) == hipSuccess) fs.ray_reader = false;
+            else busy = true;
+        }
+        if (!busy && bytes > ctx->rays_cap && ctx->d_rays && !ctx->ray_fill_done) {
+            if (hipEventQuery(ctx->ray_filled) == hipSuccess) ctx->ray_fill_done = true;
+            else busy = true;
+        }
+        if (!busy) {
+            if (bytes > ctx->rays_cap) {
+                (void)hipFree(ctx->d_rays);
+                ctx->d_rays = nullptr;
+                ctx->rays_cap = 0;
+                XRT_HIP(ctx, hipMalloc(&ctx->d_rays, bytes));
+                ctx->rays_cap = bytes;
+            }
+            if (!ctx->ray_filled) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->ray_filled, hipEventDisableTiming));
+            const uint32_t tiles = ray_table_tiles_x(p.width) * ray_table_tiles_y(p.row_begin, p.row_end);
+            hipLaunchKernelGGL(k_ray_table, dim3((tiles + 3u) / 4u), dim3(256), 0, ctx->prep_stream, p, ctx->d_rays);
+            XRT_HIP(ctx, hipGetLastError());
+            XRT_HIP(ctx, hipEventRecord(ctx->ray_filled, ctx->prep_stream));
+            ctx->ray_key = key;
+            ctx->ray_valid = true;
+            ctx->ray_fill_done = false;
+            ctx->ray_waited.clear();
+            ++ctx->hp_ray_fills;
+        }
+    }
+    if (!ctx->ray_valid) {
+        ++ctx->hp_ray_computed;
+        return XRT_OK;
+    }
+    if (!ctx->ray_fill_done) {
+        const hipError_t q = hipEventQuery(ctx->ray_filled);
+        if (q == hipSuccess) ctx->ray_fill_done = true;
+        else if (q != hipErrorNotReady) XRT_HIP(ctx, q);
+        else if (std::find(ctx->ray_waited.begin(), ctx->ray_waited.end(), stream) == ctx->ray_waited.end()) {
+            XRT_HIP(ctx, hipStreamWaitEvent(stream, ctx->ray_filled, 0));
+            ctx->ray_waited.push_back(stream);
+        }
+    }
+    ++ctx->hp_ray_frames;
+    rays = ctx->d_rays;
+    return XRT_OK;
+}
+
 int launch_frame(xrt_context* ctx, PendingFrame& pf)
 {
     FrameSet& fs = *pf.fs;
@@ -1592,6 +1702,15 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
         const bool mat = p.model == kModelMaterials;
         const bool spc = p.model == kModelSpectrum;
         const bool pth = p.model == kModelPaths;
+        // the attenuation BINNED render takes its rays from the camera's table
+        // when there is one for this frame (the other models need the
+        // once-normalised direction, and the hit layout keeps its own kernel)
+        const bool ray_scope = kernel != XRT_KERNEL_BRUTE && kernel != XRT_KERNEL_TILED && binned && !sgn &&
+                               out.packed != kLayoutHits;
+        if (ray_scope) {
+            if (int rc = frame_rays(ctx, p, stream, out.rays)) return rc;
+        }
+        fs.ray_reader = out.rays != nullptr;
         const auto t_launch = HostClock::now();
         if (kernel == XRT_KERNEL_BRUTE)
             hipExtLaunchKernelGGL(pth   ? k_render_brute<kModelPaths>
@@ -1609,6 +1728,7 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
                                   : mat ? k_render_binned<kModelMaterials>
                                   : sgn ? k_render_binned<kModelSigned>
                                   : out.packed == kLayoutHits ? k_render_binned_hits
+                                  : out.rays                  ? k_render_binned_rays
                                                               : k_render_binned<kModelAttenuation>, grid, dim3(64 * kTileWaves),
                                   0, stream, t0, t1, 0, fs.recs, fs.cull, p, out, bins, (const BinState*)bin_ctl);
         XRT_HIP(ctx, hipGetLastError());
@@ -1983,6 +2103,7 @@ int xrt_create(int device, xrt_context** out)
     if (const char* bm = std::getenv("XRT_BOX_MASKS")) ctx->box_masks = std::atoi(bm);
     if (const char* df = std::getenv("XRT_DEVICE_FILL")) ctx->device_fill = std::atoi(df) != 0;
     if (const char* dq = std::getenv("XRT_DEVICE_FIRST")) ctx->device_first = std::atoi(dq) != 0;
+    if (const char* rc = std::getenv("XRT_RAY_CACHE_MB")) ctx->ray_budget = (size_t)std::strtoull(rc, nullptr, 10) << 20;
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu <= 0)
         n_cu = 256;
@@ -2091,6 +2212,8 @@ void xrt_destroy(xrt_context* ctx)
     (void)hipFree(ctx->d_spectrum);
     (void)hipFree(ctx->d_path_ends);
     (void)hipFree(ctx->d_prep_times);
+    (void)hipFree(ctx->d_rays);
+    if (ctx->ray_filled) (void)hipEventDestroy(ctx->ray_filled);
     if (ctx->vol_busy) (void)hipEventSynchronize(ctx->vol_ev);
     (void)hipFree(const_cast<uint8_t*>(ctx->vol.labels));
     (void)hipFree(const_cast<float*>(ctx->vol.density));
@@ -3363,6 +3486,34 @@ int xrt_debug_tile_plan(xrt_context* ctx, uint64_t counters[2])
     if (!ctx || !counters) return XRT_ERR_ARGUMENT;
     counters[0] = ctx->hp_tile_plan_frames;
     counters[1] = ctx->hp_tile_plans;
+    return XRT_OK;
+}
+
+int xrt_debug_set_ray_table(xrt_context* ctx, int on)
+{
+    if (!ctx) return XRT_ERR_ARGUMENT;
+    ctx->ray_enabled = on != 0;        // read at every launch; a table kept while off stays valid for its key
+    return XRT_OK;
+}
+
+int xrt_debug_ray_table_counters(xrt_context* ctx, uint64_t counters[4])
+{
+    if (!ctx || !counters) return XRT_ERR_ARGUMENT;
+    counters[0] = ctx->hp_ray_fills;
+    counters[1] = ctx->hp_ray_frames;
+    counters[2] = ctx->hp_ray_computed;
+    counters[3] = ctx->rays_cap;
+    return XRT_OK;
+}
+
+int xrt_debug_ray_table_index(uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_end, uint32_t row,
+                              uint32_t col, uint64_t* index, uint64_t* floats)
+{
+    if (!width || !height || row_begin >= row_end || row_end > height || row < row_begin || row >= row_end ||
+        col >= width || !index)
+        return XRT_ERR_ARGUMENT;
+    *index = ray_table_index(width, row_begin, row, col);
+    if (floats) *floats = ray_table_floats(width, row_begin, row_end);
     return XRT_OK;
 }
 
