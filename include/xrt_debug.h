@@ -249,6 +249,17 @@ int xrt_debug_ray_table_index(uint32_t width, uint32_t height, uint32_t row_begi
                               uint32_t col, uint64_t* index, uint64_t* floats);
 
 /*
+ * The valid table's contents: waits on the host for its fill and copies the
+ * whole table -- xrt_debug_ray_table_index's *floats for its key, padding
+ * included -- into dst; dims (may be NULL) = the key's width, height,
+ * row_begin, row_end.  XRT_ERR_NO_MESH while no table is valid (none filled
+ * yet, or a frame of another key came since); XRT_ERR_ARGUMENT for a NULL dst
+ * or `floats` below the table's size ([3] bytes held / 4 always suffices).
+ * Changes nothing that decides how later frames take their rays.
+ */
+int xrt_debug_ray_table_read(xrt_context* ctx, float* dst, uint64_t floats, uint32_t dims[4]);
+
+/*
  * Diagnostics: k_prep's per-wave timestamps.  enable 1 / 0 turns the records
  * on / off for later launches (-1 leaves it); *n_waves = the waves of the last
  * recorded launch; with dst, waits for the context's work and copies up to

@@ -1026,6 +1026,17 @@ class Context:
         self._check(self._lib.xrt_debug_ray_table_counters(self._ctx, c), "xrt_debug_ray_table_counters")
         return dict(zip(("fills", "frames", "computed", "bytes"), (int(v) for v in c)))
 
+    def read_ray_table(self):
+        """(table, (width, height, row_begin, row_end)): the valid ray table's floats, padding included, in
+        ray_table_index's layout, and its key's sizes (xrt_debug_ray_table_read; XrtError while none is valid)."""
+        cap = max(self.ray_table_counters()["bytes"] // 4, 1)
+        out = np.zeros(cap, np.float32)
+        dims = (ctypes.c_uint32 * 4)()
+        self._check(self._lib.xrt_debug_ray_table_read(self._ctx, out.ctypes.data, cap, dims),
+                    "xrt_debug_ray_table_read")
+        W, H, r0, r1 = (int(v) for v in dims)
+        return out[:ray_table_index(W, H, r0, r1, r0, 0)[1]].copy(), (W, H, r0, r1)
+
     def pipeline_counters(self) -> dict:
         """Frames rendered from a preparation made ahead, preparations dropped, renders
         launched with no wait, renders launched after a host wait (xrt_debug_pipeline_counters)."""

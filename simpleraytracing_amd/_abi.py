@@ -245,6 +245,7 @@ XRT_SYMBOLS = {
     "xrt_debug_set_ray_table": (ctypes.c_int, [_CtxP, ctypes.c_int]),
     "xrt_debug_ray_table_counters": (ctypes.c_int, [_CtxP, ctypes.POINTER(ctypes.c_uint64)]),
     "xrt_debug_ray_table_index": (ctypes.c_int, [_u32, _u32, _u32, _u32, _u32, _u32, _u64p, _u64p]),
+    "xrt_debug_ray_table_read": (ctypes.c_int, [_CtxP, _vp, _u64, ctypes.POINTER(_u32)]),
     "xrt_debug_direction_grid": (ctypes.c_int, [ctypes.POINTER(Camera), ctypes.POINTER(ctypes.c_int)]),
     "xrt_host_footprints": (ctypes.c_int, [ctypes.POINTER(Camera), _fp, _u64, _fp]),
     "xrt_debug_prep_times": (ctypes.c_int, [_CtxP, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,

@@ -3506,6 +3506,26 @@ int xrt_debug_ray_table_counters(xrt_context* ctx, uint64_t counters[4])
     return XRT_OK;
 }
 
+int xrt_debug_ray_table_read(xrt_context* ctx, float* dst, uint64_t floats, uint32_t dims[4])
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (!ctx->ray_valid) return fail(ctx, XRT_ERR_NO_MESH, "no ray table is valid");
+    const xrt_context::RayKey& k = ctx->ray_key;
+    const uint64_t n = ray_table_floats(k.width, k.row_begin, k.row_end);
+    if (!dst || floats < n) return fail(ctx, XRT_ERR_ARGUMENT, "dst is NULL or smaller than the table");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    XRT_HIP(ctx, hipEventSynchronize(ctx->ray_filled));
+    ctx->ray_fill_done = true;
+    XRT_HIP(ctx, hipMemcpy(dst, ctx->d_rays, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (dims) {
+        dims[0] = k.width;
+        dims[1] = k.height;
+        dims[2] = k.row_begin;
+        dims[3] = k.row_end;
+    }
+    return XRT_OK;
+}
+
 int xrt_debug_ray_table_index(uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_end, uint32_t row,
                               uint32_t col, uint64_t* index, uint64_t* floats)
 {

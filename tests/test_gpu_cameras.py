@@ -12,40 +12,20 @@ import materials_ref
 import simpleraytracing_amd as xrt
 from simpleraytracing_amd import _abi
 from oracle import oracle
+from camera_refs import reference
 from conftest import bits
-from scene_kit import corner_soup, second_mesh_for, striped_sheets, synthetic_soup
+from scene_kit import second_mesh_for, striped_sheets, synthetic_soup
 from test_camera_cpu import assert_footprints_contain_hits, host_footprints, never_cull
 from test_gpu_parity import KERNELS, KNAME, assert_same
 
 pytestmark = pytest.mark.gpu
 
 
-def scene(name, dragon):
-    """(triangles, W, H, base camera, centre of the turn)."""
-    if name == "dragon":
-        tris, W, H = dragon, 67, 45
-    elif name == "soup":
-        tris, W, H = synthetic_soup(seed=9, n=2000), 80, 72
-    elif name == "corner":
-        tris, W, H = corner_soup(), 33, 31
-    else:                                       # the source inside the soup
-        tris, W, H = synthetic_soup(), 64, 48
-        return tris, W, H, ck.inside_source_camera(tris, W, H), ck.scene_centre([tris[:200]])
-    return tris, W, H, oracle.camera_for_mesh(tris, W, H), ck.scene_centre([tris])
-
-
 @pytest.fixture(scope="module")
 def references(dragon):
-    """The oracle's frame of every (scene, case), computed once and shared."""
-    cache = {}
-
-    def get(name, case):
-        if (name, case) not in cache:
-            tris, W, H, base, centre = scene(name, dragon)
-            c13 = ck.general_camera(base, centre, W, H, **ck.CASES[case])
-            cache[name, case] = (tris, W, H, c13, oracle.render_rows(tris, c13, W, H))
-        return cache[name, case]
-    return get
+    """The oracle's frame of every (scene, case), computed once and shared
+    (camera_refs: with the ray table's suite too)."""
+    return lambda name, case: reference(name, case, dragon)
 
 
 # --------------------------------------------------------------------------- a. parity

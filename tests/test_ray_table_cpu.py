@@ -48,6 +48,50 @@ def test_rejects_pixels_outside_the_strip():
             xrt.ray_table_index(*args)
 
 
+@pytest.mark.parametrize("W,H,r0,r1", CASES + [(1, 1, 0, 1), (67, 45, 0, 45), (100, 37, 5, 30), (96, 128, 40, 41)])
+def test_numpy_restatement_of_the_layout(W, H, r0, r1):
+    """ray_table_kit.table_indices (the GPU suite builds the whole expected
+    table with it) agrees with the kernels' function at every pixel of the
+    strip, and covers the padded table's every float exactly once."""
+    import ray_table_kit as rk
+    idx, r, c = rk.table_indices(W, r0, r1)
+    assert idx.shape == (rk.pad32(r1 - r0), rk.pad32(W))
+    floats = xrt.ray_table_index(W, H, r0, r1, r0, 0)[1]
+    assert floats == 3 * idx.size
+    for row in range(r0, r1):
+        for col in range(W):
+            assert xrt.ray_table_index(W, H, r0, r1, row, col)[0] == idx[row - r0, col]
+    every = np.concatenate([idx.ravel() + 64 * k for k in range(3)])
+    assert np.array_equal(np.sort(every), np.arange(floats))
+
+
+def test_degenerate_cameras_have_the_expected_nan_pattern():
+    """The two degenerate cameras of the GPU suite, on the CPU: the source on
+    the detector's centre has NaN at the centre pixel only, the underflowing
+    camera everywhere; neither reaches the second normalisation's zero-length
+    branch (no direction is (0, 0, 0)).  The random cameras are all finite."""
+    import camera_kit as ck
+    import ray_table_kit as rk
+    c13, W, H = rk.source_on_detector_camera()
+    d = ck.ray_directions(c13, W, H)
+    nan = np.isnan(d)
+    assert nan[H // 2, W // 2].all() and nan.sum() == 3 and np.isfinite(d[~nan]).all()
+    assert not (d == 0).all(axis=2).any()
+    c13, W, H = rk.underflow_camera()
+    d = ck.ray_directions(c13, W, H)
+    assert np.isnan(d).all()
+    raw = c13[3:6] - c13[0:3]
+    assert (np.abs(raw) > np.finfo(np.float32).tiny).all() and (raw * raw == 0).all()
+    for c13, W, H in rk.random_cameras():
+        assert np.isfinite(ck.ray_directions(c13, W, H)).all()
+
+
+def test_reader_refuses_without_a_context():
+    from simpleraytracing_amd import _abi
+    buf = np.zeros(4, np.float32)
+    assert _abi.load().xrt_debug_ray_table_read(None, buf.ctypes.data, 4, None) == _abi.XRT_ERR_ARGUMENT
+
+
 def test_cached_render_keeps_eight_waves_without_scratch():
     """k_render_binned_rays keeps 8 waves per SIMD -- at most 64 VGPRs of 512, 8 KB of
     LDS for its four waves -- and spills nothing into scratch, as the computing
