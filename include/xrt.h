@@ -834,6 +834,100 @@ int xrt_volume_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_be
 int xrt_volume_paths_device(xrt_context* ctx, const xrt_camera* camera, uint32_t row_begin, uint32_t row_end,
                             uint32_t num_labels, float* d_paths, void* stream);
 
+/* --- FDK reconstruction: ramp filter and cone-beam backprojector ---------- */
+
+/*
+ * What consumes the line integrals of xrt_log_projection (DESIGN.md section
+ * 10.11): a row filter and a voxel-driven backprojector, which together are
+ * FDK for a full turn about an axis parallel to the detector's `up`; the
+ * backprojector alone is the adjoint-style operator of iterative methods.
+ * Neither looks at or changes the context's model, scene, poses, frames in
+ * flight or state generation.  There is no xrt_multi_ form.
+ *
+ * xrt_fdk_filter[_device].  image: num_planes row-major f32 planes of width x
+ * height; weight: one such plane, or NULL; taps[num_taps], num_taps odd and in
+ * 1..2 * XRT_MAX_RAMP_WIDTH - 1, r = (num_taps - 1) / 2; width <=
+ * XRT_MAX_RAMP_WIDTH.  Per plane
+ *   pw[y][x]  = weight ? image[y][x] * weight[y][x] : image[y][x]     (one f32 product)
+ *   out[y][x] = (float)s,  s = +0.0 in f64, then for k = 0 .. num_taps - 1 in this order, only
+ *               where 0 <= x + k - r < width:  s = s + (double)taps[k] * (double)pw[y][x + k - r]
+ * every operation rounded on its own.  A correlation, as xrt_detector_response
+ * is; nothing is normalised; pixels outside the row are skipped, not
+ * replicated.  XRT_ERR_ARGUMENT, before the context is looked at, for a NULL
+ * image, taps or out, an even or out-of-range tap count, a tap that is not
+ * finite (the host form only: the device form cannot read its taps), a width,
+ * height or num_planes of 0, a width above the limit (or 2^30 rows and more),
+ * and an out that overlaps image, weight or taps.  xrt_fdk_filter: host
+ * buffers, synchronous.  _device: device pointers for image, weight, taps and
+ * out (8191 taps do not fit a launch's arguments), asynchronous on `stream`.
+ *
+ * xrt_backproject[_device].  proj: num_planes planes of width x height, pixel
+ * (row, col) centred on integer coordinates; matrices[num_planes][12], each a
+ * row-major 3 x 4 f64 matrix A taking a voxel index to homogeneous detector
+ * coordinates; the volume is f32 [nz][ny][nx], x fastest, dims = {nx, ny, nz}
+ * as xrt_upload_volume's, each 1..2048.  Only the slabs k in [slab_begin,
+ * slab_end) are written, into (slab_end - slab_begin) * ny * nx floats (an
+ * empty range: success, nothing written).  Per voxel (i, j, k), exact doubles,
+ * and per plane p = 0 .. num_planes - 1 in this order, A = matrices[p]:
+ *   a = A[0]*i + ((A[1]*j + A[2]*k) + A[3])       f64, every product and sum rounded on its own
+ *   b = A[4]*i + ((A[5]*j + A[6]*k) + A[7])
+ *   c = A[8]*i + ((A[9]*j + A[10]*k) + A[11])
+ *   contributes only if c > 0                      (a NaN compares false)
+ *   w = 1.0 / c;  col = a * w;  row = b * w        f64, IEEE division
+ *   contributes only if col > -1 && col < width && row > -1 && row < height
+ *   x0 = floor(col), y0 = floor(row);  fx = (float)(col - x0), fy = (float)(row - y0)
+ *   s(y, x) = proj[p][y][x] inside the plane, +0.0f outside
+ *   top = s(y0,x0)   + fx * (s(y0,x0+1)   - s(y0,x0))       f32, separately rounded
+ *   bot = s(y0+1,x0) + fx * (s(y0+1,x0+1) - s(y0+1,x0))
+ *   v   = top + fy * (bot - top)
+ *   acc = acc + (double)v * (w * w)                f64; acc starts at +0.0
+ *   out = accumulate ? (float)((double)old + acc * scale) : (float)(acc * scale)
+ * XRT_ERR_ARGUMENT, before the context is looked at, for a NULL pointer, a
+ * width, height or num_planes of 0 (or a width or height above 2^31 - 1, or a
+ * plane of more than 2^40 pixels), more than 65535 planes, a dims[a] outside 1..2048, slab_begin > slab_end or
+ * slab_end > nz, a scale that is not finite, a matrix entry that is not finite
+ * (the host form only) and a volume that overlaps the projections or the
+ * matrices.  xrt_backproject: host buffers, synchronous.  _device: device
+ * buffers, asynchronous on `stream`.
+ *
+ * Host arithmetic in f64 (no device):
+ * xrt_backprojection_matrix: the matrix of a camera for a voxel grid.  A voxel
+ * centre is X = origin + (idx + 0.5) * spacing in the rest frame, Xw = pose X
+ * in the world (xrt_set_pose's layout; NULL: the identity), (a', b', c) =
+ * M^-1 (Xw - S) with S the source and M's columns right, up, detector - S;
+ * rows 0 and 1 become pixel coordinates of the render's pixel formula:
+ * A_row0 = a'-row / pixel_spacing + (width / 2 - 0.5) * c-row, A_row1 likewise
+ * with up's row and the height.  XRT_ERR_ARGUMENT for a singular or
+ * non-finite M or a non-finite result.
+ * xrt_fdk_weights: weight[y][x] = the cosine between pixel (y, x)'s ray and the
+ * central ray detector - origin, rounded once.
+ * xrt_ramp_filter: XRT_RAMP_RAMLAK g[0] = 1/4, g[n] = -1 / (pi^2 n^2) for odd
+ * n, 0 for even n; XRT_RAMP_HANN (g[n-1] / 4 + g[n] / 2) + g[n+1] / 4, the Hann
+ * window's closed form in space; taps[k] = (float)g[k - r], dimensionless.
+ * xrt_fdk_scale: pi / P * (SOD / SDD) / (pixel_spacing * |right|), SDD =
+ * |detector - origin|, SOD the component of axis_point - origin along the
+ * central ray: the full-turn FDK constant, with which a uniform object of
+ * mu = 1 reconstructs to 1.
+ */
+#define XRT_MAX_RAMP_WIDTH 4096
+#define XRT_RAMP_RAMLAK 0
+#define XRT_RAMP_HANN 1
+int xrt_fdk_filter(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* image,
+                   const float* weight, const float* taps, uint32_t num_taps, float* out);
+int xrt_fdk_filter_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_image,
+                          const float* d_weight, const float* d_taps, uint32_t num_taps, float* d_out, void* stream);
+int xrt_backproject(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* proj,
+                    const double* matrices, const uint32_t dims[3], uint32_t slab_begin, uint32_t slab_end, double scale,
+                    int accumulate, float* volume);
+int xrt_backproject_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                           const double* d_matrices, const uint32_t dims[3], uint32_t slab_begin, uint32_t slab_end,
+                           double scale, int accumulate, float* d_volume, void* stream);
+int xrt_backprojection_matrix(const xrt_camera* camera, const float pose[12], const float origin[3],
+                              const float spacing[3], double A[12]);
+int xrt_fdk_weights(const xrt_camera* camera, float* weight);
+int xrt_ramp_filter(uint32_t num_taps, int window, float* taps);
+int xrt_fdk_scale(const xrt_camera* camera, const float axis_point[3], uint32_t num_projections, double* scale);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

@@ -369,6 +369,19 @@ int xrt_host_volume_paths(const xrt_camera* camera, uint32_t row_begin, uint32_t
 int xrt_debug_volume_wave_shape(xrt_context* ctx, int rows);
 
 /*
+ * Test hooks of FDK reconstruction.  Host code, no device: xrt_fdk_filter's
+ * contract as include/xrt.h writes it, and xrt_backproject's per-plane
+ * arithmetic -- backproject_term, the one k_backproject calls, compiled for
+ * the host -- over whole host buffers.  Arguments and checks as the host
+ * forms'.
+ */
+int xrt_host_fdk_filter(uint32_t width, uint32_t height, uint32_t num_planes, const float* image, const float* weight,
+                        const float* taps, uint32_t num_taps, float* out);
+int xrt_host_backproject(uint32_t width, uint32_t height, uint32_t num_planes, const float* proj, const double* matrices,
+                         const uint32_t dims[3], uint32_t slab_begin, uint32_t slab_end, double scale, int accumulate,
+                         float* volume);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -49,6 +49,17 @@ int xrt_host_load_volume(const char* path, void** data, int* element_type, uint3
 const char* xrt_host_last_error(void);
 
 /*
+ * Writes a f32 volume (saveVolume of the host API): `path` must end in .mhd and
+ * receives the MetaImage header (ElementType = MET_FLOAT, uncompressed); the
+ * raw data, data[(z * ny + y) * nx + x] with dims = {nx, ny, nz}, goes to
+ * NAME.raw beside it.  xrt_host_load_volume reads both back bit for bit.
+ * XRT_ERR_ARGUMENT for another extension, a size outside 1..2048 or a spacing
+ * that is not above 0; XRT_ERR_IO when a file cannot be written.
+ */
+int xrt_host_save_volume(const char* path, const float* data, const uint32_t dims[3], const float origin[3],
+                         const float spacing[3]);
+
+/*
  * Ray::intersect (src/Ray.cxx:72-124) of the drop-in host class for n pairs:
  * rays[6*i] = origin, direction (normalised by the Ray constructor as
  * include/Ray.inl:74-85); triangles[9*i] = p1, p2, p3.  hit[i] = 0/1, t[i] =

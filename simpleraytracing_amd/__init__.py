@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_MAX_SOURCES, XRT_MAX_BIN, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_MAX_SOURCES, XRT_MAX_BIN, XRT_MAX_RAMP_WIDTH, XRT_RAMP_RAMLAK, XRT_RAMP_HANN, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -36,7 +36,8 @@ __all__ = [
     "XRT_MAX_CHANNELS", "XRT_DETECT_EXPECTED", "XRT_DETECT_NOISY", "XRT_DETECT_COUNTS", "XRT_DETECT_INTENSITY",
     "host_spectral_detector", "spectral_detector", "volume_bbox", "host_volume_paths", "load_volume",
     "XRT_MAX_SOURCES", "XRT_MAX_BIN", "supersampled_camera", "focal_spot", "host_area_integrate", "area_integrate",
-    "ray_table_index",
+    "ray_table_index", "XRT_MAX_RAMP_WIDTH", "XRT_RAMP_RAMLAK", "XRT_RAMP_HANN", "ramp_filter", "fdk_weights",
+    "fdk_scale", "backprojection_matrix", "save_volume", "host_fdk_filter", "host_backproject",
 ]
 
 
@@ -514,6 +515,21 @@ def load_volume(path: str):
     return arr.reshape(int(dims[2]), int(dims[1]), int(dims[0])), spc, org
 
 
+def save_volume(path: str, data, spacing, origin=(0.0, 0.0, 0.0)):
+    """A (nz, ny, nx) f32 volume as a MetaImage (xrt_host_save_volume): `path` (NAME.mhd) and NAME.raw beside it;
+    load_volume reads it back bit for bit."""
+    host = _abi.load_host()
+    a = np.ascontiguousarray(data, dtype=np.float32)
+    if a.ndim != 3:
+        raise ValueError(f"a volume is (nz, ny, nx), got shape {a.shape}")
+    dims = np.array(a.shape[::-1], np.uint32)
+    org = np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+    spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+    rc = host.xrt_host_save_volume(str(path).encode(), _fptr(a), _u32ptr(dims), _fptr(org), _fptr(spc))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, f"xrt_host_save_volume({path}): {host.xrt_host_last_error().decode()}")
+
+
 def volume_bbox(dims, spacing, origin=(0.0, 0.0, 0.0)):
     """(lower, upper) of a volume of dims (nx, ny, nz) voxels of `spacing` whose minimum corner is `origin`
     (xrt_volume_bbox)."""
@@ -542,6 +558,102 @@ def host_volume_paths(cam: Camera, labels, spacing, origin=(0.0, 0.0, 0.0), dens
     if rc != _abi.XRT_OK:
         raise XrtError(rc, "xrt_host_volume_paths")
     return out
+
+
+def ramp_filter(num_taps: int, window: int = _abi.XRT_RAMP_RAMLAK) -> np.ndarray:
+    """`num_taps` (odd) samples of the band-limited ramp at unit sample distance, plain (XRT_RAMP_RAMLAK) or
+    under a Hann window (XRT_RAMP_HANN), as f32 (xrt_ramp_filter)."""
+    out = np.empty(max(int(num_taps), 1), np.float32)
+    rc = _abi.load().xrt_ramp_filter(int(num_taps), int(window), _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_ramp_filter: num_taps odd and in 1..2*XRT_MAX_RAMP_WIDTH-1, window RAMLAK or HANN")
+    return out
+
+
+def fdk_weights(cam: Camera) -> np.ndarray:
+    """The (H, W) f32 cosine weights of FDK for a camera (xrt_fdk_weights)."""
+    out = np.empty((cam.height, cam.width), np.float32)
+    rc = _abi.load().xrt_fdk_weights(ctypes.byref(cam), _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_fdk_weights")
+    return out
+
+
+def fdk_scale(cam: Camera, axis_point, num_projections: int) -> float:
+    """The full-turn FDK constant of a scan of `num_projections` about an axis through `axis_point`
+    (xrt_fdk_scale)."""
+    q = np.ascontiguousarray(axis_point, dtype=np.float32).reshape(3)
+    out = ctypes.c_double(0.0)
+    rc = _abi.load().xrt_fdk_scale(ctypes.byref(cam), _fptr(q), int(num_projections), ctypes.byref(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_fdk_scale")
+    return out.value
+
+
+def backprojection_matrix(cam: Camera, origin, spacing, pose=None) -> np.ndarray:
+    """The (3, 4) f64 matrix taking a voxel index (i, j, k) of the grid whose voxel (0, 0, 0) has its minimum
+    corner at `origin` (voxels of `spacing`, one value or (x, y, z)), posed by `pose` (None: the identity), to the
+    camera's homogeneous (col, row, 1) * c (xrt_backprojection_matrix)."""
+    org = np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+    spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+    q = _pose_array(pose)
+    out = np.empty(12, np.float64)
+    rc = _abi.load().xrt_backprojection_matrix(ctypes.byref(cam), _fptr(q) if q is not None else None, _fptr(org),
+                                               _fptr(spc), _dptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_backprojection_matrix: the camera's axes must be finite and independent")
+    return out.reshape(3, 4)
+
+
+def _fdk_filter_arrays(image, weight, taps):
+    """xrt_fdk_filter's arguments from an (H, W) image or a (P, H, W) stack: (image, weight or None, taps, P, H, W)."""
+    a, p, h, w = _lsf_planes(image)
+    if weight is not None:
+        weight = np.ascontiguousarray(weight, dtype=np.float32)
+        if weight.shape != (h, w):
+            raise ValueError(f"weight is one (H, W) = ({h}, {w}) plane, got shape {weight.shape}")
+    return a, weight, np.ascontiguousarray(taps, dtype=np.float32).reshape(-1), p, h, w
+
+
+def _backproject_arrays(proj, matrices, dims, slabs, volume, accumulate):
+    """xrt_backproject's arguments: (projections, matrices (P, 12) f64, dims u32[3], slab range, volume)."""
+    a, p, h, w = _lsf_planes(proj)
+    m = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 12)
+    if m.shape[0] != p:
+        raise ValueError(f"{p} projections need {p} matrices, got {m.shape[0]}")
+    d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+    lo, hi = (0, int(d[2])) if slabs is None else (int(slabs[0]), int(slabs[1]))
+    shape = (max(hi - lo, 0), int(d[1]), int(d[0]))
+    if accumulate:
+        if volume is None:
+            raise ValueError("accumulate needs the volume to add to")
+        volume = np.array(volume, dtype=np.float32, order="C")
+        if volume.shape != shape:
+            raise ValueError(f"the volume to add to must have shape {shape}, got {volume.shape}")
+    else:
+        volume = np.empty(shape, np.float32)
+    return a, m, d, lo, hi, volume, p, h, w
+
+
+def host_fdk_filter(image, taps, weight=None) -> np.ndarray:
+    """Context.fdk_filter's contract on the host (xrt_host_fdk_filter, a test hook)."""
+    a, wt, t, p, h, w = _fdk_filter_arrays(image, weight, taps)
+    out = np.empty_like(a)
+    rc = _abi.load().xrt_host_fdk_filter(w, h, p, _fptr(a), _fptr(wt) if wt is not None else None, _fptr(t), t.size,
+                                         _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_fdk_filter")
+    return out
+
+
+def host_backproject(proj, matrices, dims, scale=1.0, slabs=None, volume=None, accumulate=False) -> np.ndarray:
+    """Context.backproject in the device's arithmetic on the host (xrt_host_backproject, a test hook)."""
+    a, m, d, lo, hi, vol, p, h, w = _backproject_arrays(proj, matrices, dims, slabs, volume, accumulate)
+    rc = _abi.load().xrt_host_backproject(w, h, p, _fptr(a), _dptr(m), _u32ptr(d), lo, hi, float(scale),
+                                          int(bool(accumulate)), _fptr(vol))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_backproject")
+    return vol
 
 
 class Context:
@@ -803,6 +915,67 @@ class Context:
         """k_volume_paths' waves as 64 x 1 row segments (rows=True) or 8 x 8 tiles (the default): a timing A/B,
         the planes are the same (xrt_debug_volume_wave_shape)."""
         self._check(self._lib.xrt_debug_volume_wave_shape(self._ctx, int(bool(rows))), "xrt_debug_volume_wave_shape")
+
+    def fdk_filter(self, image, taps, weight=None) -> np.ndarray:
+        """The row filter of FDK over an (H, W) image or a (P, H, W) stack: every row of image * weight (one
+        (H, W) plane or None) correlated with `taps` (odd count) in f64, pixels outside the row skipped.  The
+        image's shape."""
+        a, wt, t, p, h, w = _fdk_filter_arrays(image, weight, taps)
+        out = np.empty_like(a)
+        self._check(self._lib.xrt_fdk_filter(self._ctx, w, h, p, _fptr(a), _fptr(wt) if wt is not None else None,
+                                             _fptr(t), t.size, _fptr(out)), "xrt_fdk_filter")
+        return out
+
+    def fdk_filter_device(self, width: int, height: int, num_planes: int, d_image: int, d_taps: int, num_taps: int,
+                          d_out: int, d_weight: int = 0, stream: int = 0):
+        """fdk_filter over device buffers (raw pointers, the taps and the weight plane too); asynchronous on
+        `stream`."""
+        rc = self._lib.xrt_fdk_filter_device(self._ctx, int(width), int(height), int(num_planes), d_image or None,
+                                             d_weight or None, d_taps or None, int(num_taps), d_out or None,
+                                             stream or None)
+        self._check(rc, "xrt_fdk_filter_device")
+
+    def backproject(self, proj, matrices, dims, scale=1.0, slabs=None, volume=None, accumulate=False) -> np.ndarray:
+        """The cone-beam backprojection of a (P, H, W) stack (or one (H, W) plane) under P (3, 4) f64 matrices
+        into the slabs [slabs[0], slabs[1]) (None: all) of a grid of dims = (nx, ny, nz): (slabs, ny, nx) f32,
+        each voxel's sum times `scale`; accumulate=True adds it to `volume` (a copy is returned)."""
+        a, m, d, lo, hi, vol, p, h, w = _backproject_arrays(proj, matrices, dims, slabs, volume, accumulate)
+        self._check(self._lib.xrt_backproject(self._ctx, w, h, p, _fptr(a), _dptr(m), _u32ptr(d), lo, hi, float(scale),
+                                              int(bool(accumulate)), _fptr(vol)), "xrt_backproject")
+        return vol
+
+    def backproject_device(self, width: int, height: int, num_planes: int, d_proj: int, d_matrices: int, dims,
+                           slab_begin: int, slab_end: int, scale: float, accumulate: bool, d_volume: int,
+                           stream: int = 0):
+        """backproject over device buffers (raw pointers: f32 planes, f64 matrices, the f32 slabs); asynchronous
+        on `stream`."""
+        d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+        rc = self._lib.xrt_backproject_device(self._ctx, int(width), int(height), int(num_planes), d_proj or None,
+                                              d_matrices or None, _u32ptr(d), int(slab_begin), int(slab_end),
+                                              float(scale), int(bool(accumulate)), d_volume or None, stream or None)
+        self._check(rc, "xrt_backproject_device")
+
+    def fdk(self, projections, camera: Camera, poses, dims, origin, spacing, axis_point,
+            window: int = _abi.XRT_RAMP_RAMLAK) -> np.ndarray:
+        """FDK over a full turn: the (P, H, W) line integrals `projections`, taken by `camera` -- one Camera, or
+        P of them for a turning source -- of an object under `poses` (P poses, or None: at rest), into the grid of
+        dims = (nx, ny, nz) voxels of `spacing` with its minimum corner at `origin`, about the axis through
+        `axis_point` parallel to the detector's up.  Weights, the ramp (2 W - 1 taps under `window`), the
+        matrices and the backprojection: (nz, ny, nx) f32."""
+        a, p, h, w = _lsf_planes(projections)
+        cams = [camera] * p if isinstance(camera, Camera) else list(camera)
+        poses = [None] * p if poses is None else list(poses)
+        if len(cams) != p or len(poses) != p:
+            raise ValueError(f"{p} projections need one camera or {p}, and {p} poses or None")
+        taps = ramp_filter(2 * w - 1, window)
+        mats = np.stack([backprojection_matrix(c, origin, spacing, q) for c, q in zip(cams, poses)])
+        same = all(bytes(c) == bytes(cams[0]) for c in cams)
+        if same:
+            filtered = self.fdk_filter(a, taps, fdk_weights(cams[0]))
+        else:
+            filtered = np.stack([self.fdk_filter(a.reshape(p, h, w)[i], taps, fdk_weights(c))
+                                 for i, c in enumerate(cams)])
+        return self.backproject(filtered.reshape(p, h, w), mats, dims, fdk_scale(cams[0], axis_point, p))
 
     def detector_response(self, image, lsf_x, lsf_y=None, out=True, u8=True):
         """The detector's line-spread function over an (H, W) image or a (P, H, W) stack of them (taps as

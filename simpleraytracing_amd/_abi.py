@@ -53,6 +53,9 @@ XRT_DETECT_COUNTS = 0
 XRT_DETECT_INTENSITY = 1
 XRT_MAX_SOURCES = 64
 XRT_MAX_BIN = 8
+XRT_MAX_RAMP_WIDTH = 4096
+XRT_RAMP_RAMLAK = 0
+XRT_RAMP_HANN = 1
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -215,6 +218,19 @@ XRT_SYMBOLS = {
     "xrt_host_volume_paths": (ctypes.c_int, [ctypes.POINTER(Camera), _u32, _u32, _u8p, _fp, _u32p, _fp, _fp, _u32,
                                              _fp]),
     "xrt_debug_volume_wave_shape": (ctypes.c_int, [_CtxP, ctypes.c_int]),
+    "xrt_fdk_filter": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _fp, _fp, _u32, _fp]),
+    "xrt_fdk_filter_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "xrt_backproject": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _dp, _u32p, _u32, _u32, ctypes.c_double,
+                                       ctypes.c_int, _fp]),
+    "xrt_backproject_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _vp, _u32p, _u32, _u32, ctypes.c_double,
+                                              ctypes.c_int, _vp, _vp]),
+    "xrt_backprojection_matrix": (ctypes.c_int, [ctypes.POINTER(Camera), _fp, _fp, _fp, _dp]),
+    "xrt_fdk_weights": (ctypes.c_int, [ctypes.POINTER(Camera), _fp]),
+    "xrt_ramp_filter": (ctypes.c_int, [_u32, ctypes.c_int, _fp]),
+    "xrt_fdk_scale": (ctypes.c_int, [ctypes.POINTER(Camera), _fp, _u32, _dp]),
+    "xrt_host_fdk_filter": (ctypes.c_int, [_u32, _u32, _u32, _fp, _fp, _fp, _u32, _fp]),
+    "xrt_host_backproject": (ctypes.c_int, [_u32, _u32, _u32, _fp, _dp, _u32p, _u32, _u32, ctypes.c_double, ctypes.c_int,
+                                            _fp]),
     "xrt_host_philox4x32": (None, [_u32p, _u32p, _u32p]),
     "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
     "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),
@@ -300,6 +316,7 @@ XRT_HOST_SYMBOLS = {
     "xrt_host_load_volume": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int), _u32p, _fp,
                                             _fp]),
     "xrt_host_last_error": (ctypes.c_char_p, []),
+    "xrt_host_save_volume": (ctypes.c_int, [ctypes.c_char_p, _fp, _u32p, _fp, _fp]),
     "xrt_host_intersect_batch": (None, [_fp, _fp, _u64, _u8p, _fp]),
     "xrt_host_save_image": (ctypes.c_int, [_fp, _u32, _u32, ctypes.c_char_p, ctypes.c_int, _f, _f]),
 }

@@ -568,6 +568,41 @@ void logProjectionSinograms(const std::vector<float>& stack, unsigned width, uns
           "xrt_log_projection");
 }
 
+void reconstructFDK(std::vector<float>& volume, const std::vector<float>& projections, unsigned num_projections,
+                    const Image& frame, const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                    const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                    const float spacing[3], const float axis_point[3], int window)
+{
+    const unsigned W = frame.getWidth(), H = frame.getHeight();
+    if (num_projections == 0 || projections.size() != (size_t)W * H * num_projections)
+        throw std::runtime_error("reconstructFDK: the stack does not hold num_projections images");
+    if (!poses.empty() && poses.size() != num_projections)
+        throw std::runtime_error("reconstructFDK: one pose per projection, or none");
+    if (W > XRT_MAX_RAMP_WIDTH) throw std::runtime_error("reconstructFDK: the image is wider than XRT_MAX_RAMP_WIDTH");
+    const xrt_camera cam = camera_for(frame, meshes, info);
+    std::vector<float> weight((size_t)W * H), taps(2u * W - 1u);
+    std::vector<double> matrices((size_t)num_projections * 12u);
+    double scale = 0.0;
+    if (xrt_fdk_weights(&cam, weight.data()) != XRT_OK || xrt_ramp_filter((uint32_t)taps.size(), window, taps.data()) != XRT_OK ||
+        xrt_fdk_scale(&cam, axis_point, num_projections, &scale) != XRT_OK)
+        throw std::runtime_error("reconstructFDK: the camera is not finite, or the window is not one of XRT_RAMP_*");
+    for (unsigned p = 0; p < num_projections; ++p)
+        if (xrt_backprojection_matrix(&cam, poses.empty() ? nullptr : poses[p].data(), origin, spacing,
+                                      matrices.data() + 12u * p) != XRT_OK)
+            throw std::runtime_error("reconstructFDK: the camera's axes are not independent, or the grid is not finite");
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    std::vector<float> filtered(projections.size());
+    check(ctx, xrt_fdk_filter(ctx, W, H, num_projections, projections.data(), weight.data(), taps.data(),
+                              (uint32_t)taps.size(), filtered.data()),
+          "xrt_fdk_filter");
+    volume.assign((size_t)dims[0] * dims[1] * dims[2], 0.0f);
+    check(ctx, xrt_backproject(ctx, W, H, num_projections, filtered.data(), matrices.data(), dims, 0, dims[2], scale, 0,
+                               volume.data()),
+          "xrt_backproject");
+}
+
 namespace {
 
 // One multi-device context per device list for the process lifetime: the
@@ -799,6 +834,23 @@ extern "C" int xrt_host_load_volume(const char* path, void** data, int* element_
             origin[a] = img.origin[a];
             spacing[a] = img.spacing[a];
         }
+        return XRT_OK;
+    } catch (const VolumeError& e) {
+        t_host_error = e.what();
+        return e.code;
+    }
+}
+
+extern "C" int xrt_host_save_volume(const char* path, const float* data, const uint32_t dims[3], const float origin[3],
+                                    const float spacing[3])
+{
+    if (!path || !data || !dims || !origin || !spacing) {
+        t_host_error = "xrt_host_save_volume: NULL argument";
+        return XRT_ERR_ARGUMENT;
+    }
+    try {
+        const unsigned d[3] = {dims[0], dims[1], dims[2]};
+        saveVolume(path, d, origin, spacing, data);
         return XRT_OK;
     } catch (const VolumeError& e) {
         t_host_error = e.what();

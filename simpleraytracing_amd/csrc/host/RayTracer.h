@@ -193,6 +193,21 @@ void applyPhotonNoise(Image& output_image, float gain, unsigned long long seed, 
 void logProjectionSinograms(const std::vector<float>& stack, unsigned width, unsigned height, unsigned num_projections,
                             float flat_value, float t_min, std::vector<float>& sinograms);
 
+// FDK reconstruction (xrt_fdk_filter and xrt_backproject) of a
+// full-turn scan: `projections` holds num_projections line-integral images
+// (applyLogProjection's) of frame's size one after another, all taken by the
+// camera of `info` over `meshes` (as renderLoop forms it) while the object
+// stood under poses[p] (one row-major 3x4 pose per projection; empty: at rest,
+// a scan that turns nothing).  `volume` receives dims[0] * dims[1] * dims[2]
+// f32, x fastest, of the grid whose voxel (0, 0, 0) has its minimum corner at
+// `origin` in the object's rest frame; axis_point lies on the turn axis, which
+// is parallel to info.up.  window: XRT_RAMP_RAMLAK or XRT_RAMP_HANN over 2 W - 1
+// taps.  One device.
+void reconstructFDK(std::vector<float>& volume, const std::vector<float>& projections, unsigned num_projections,
+                    const Image& frame, const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                    const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                    const float spacing[3], const float axis_point[3], int window = 0);
+
 // Area sampling (xrt_area_integrate).  focalSpotSources: the
 // sub-sources of a uniform rectangular focal spot of size_u x size_v (the
 // scene's length unit, along info.right and info.up), at the centres of an

@@ -6,6 +6,8 @@
 #include <cmath>
 #include <cstring>
 #include <fstream>
+#include <iomanip>
+#include <limits>
 #include <sstream>
 
 #include "xrt.h"
@@ -154,4 +156,35 @@ void loadVolumeDensity(const std::string& path, Volume& volume)
                                     std::to_string(volume.dims[0]) + " " + std::to_string(volume.dims[1]) + " " +
                                     std::to_string(volume.dims[2]));
     volume.density = std::move(img.f32);
+}
+
+void saveVolume(const std::string& path, const unsigned dims[3], const float origin[3], const float spacing[3],
+                const float* data)
+{
+    if (path.size() < 5 || path.compare(path.size() - 4, 4, ".mhd") != 0)
+        throw VolumeError(XRT_ERR_ARGUMENT, path + ": a volume is written as NAME.mhd");
+    if (!dims || !origin || !spacing || !data) throw VolumeError(XRT_ERR_ARGUMENT, path + ": NULL argument");
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1u || dims[a] > 2048u) throw VolumeError(XRT_ERR_ARGUMENT, path + ": a size is not 1 to 2048");
+        if (!(spacing[a] > 0.0f) || !std::isfinite(spacing[a]) || !std::isfinite(origin[a]))
+            throw VolumeError(XRT_ERR_ARGUMENT, path + ": a spacing is not above 0 or the origin is not finite");
+    }
+    const std::string raw = path.substr(0, path.size() - 4) + ".raw";
+    const size_t slash = raw.find_last_of('/');
+    {
+        std::ofstream out(raw, std::ios::binary);
+        out.write(reinterpret_cast<const char*>(data), (std::streamsize)((size_t)dims[0] * dims[1] * dims[2] * sizeof(float)));
+        if (!out) throw VolumeError(XRT_ERR_IO, "Cannot write the file " + raw);
+    }
+    std::ofstream head(path);
+    head << std::setprecision(std::numeric_limits<float>::max_digits10);         // (a f32 survives the text)
+    head << "ObjectType = Image\nNDims = 3\nBinaryData = True\nBinaryDataByteOrderMSB = False\nCompressedData = False\n"
+         << "TransformMatrix = 1 0 0 0 1 0 0 0 1\n"
+         << "Offset = " << origin[0] << ' ' << origin[1] << ' ' << origin[2] << "\n"
+         << "ElementSpacing = " << spacing[0] << ' ' << spacing[1] << ' ' << spacing[2] << "\n"
+         << "DimSize = " << dims[0] << ' ' << dims[1] << ' ' << dims[2] << "\n"
+         << "ElementType = MET_FLOAT\n"
+         << "ElementDataFile = " << (slash == std::string::npos ? raw : raw.substr(slash + 1)) << "\n";
+    head.close();
+    if (!head) throw VolumeError(XRT_ERR_IO, "Cannot write the file " + path);
 }

@@ -53,3 +53,14 @@ MetaImage loadMetaImage(const std::string& path);
 // a MET_FLOAT file of the same dims as volume's density.
 void loadVolume(const std::string& path, Volume& volume);
 void loadVolumeDensity(const std::string& path, Volume& volume);
+
+// Writes a f32 volume (data[(z * ny + y) * nx + x], dims = {nx, ny, nz}, the
+// minimum corner of voxel (0, 0, 0) and the voxel's size) as `path` -- a .mhd
+// header with ElementType = MET_FLOAT, uncompressed -- and its raw
+// little-endian data in NAME.raw beside it: what loadMetaImage (and
+// loadVolumeDensity) reads back bit for bit, a reconstruction's way out.
+// Throws VolumeError: XRT_ERR_ARGUMENT for a path that does not end in .mhd, a
+// size outside 1..2048 or a spacing that is not above 0, XRT_ERR_IO when a file
+// cannot be written.
+void saveVolume(const std::string& path, const unsigned dims[3], const float origin[3], const float spacing[3],
+                const float* data);

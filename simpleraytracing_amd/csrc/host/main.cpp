@@ -53,6 +53,16 @@
 //                              given (the detector blurs intensity); every model, every
 //                              projection of --turntable.  --u8, --lbuffer, NAME.m<m>
 //                              and NAME.open stay as rendered
+//       --reconstruct FILE.mhd[:N]  with --turntable N and --log-projection: the scan's line
+//                              integrals reconstructed by FDK (the ramp filter and the
+//                              cone-beam backprojector on the device) into an N x N x N grid
+//                              (default 128; 1 to 2048) of float32 attenuation per scene
+//                              length unit, a cube about the turntable's centre whose side
+//                              is the scene box's diagonal, written as FILE.mhd (MetaImage,
+//                              MET_FLOAT) and FILE.raw beside it.  The turntable must turn
+//                              every mesh about an axis parallel to the detector's up (--turntable N:z):
+//                              another axis is refused once the meshes are loaded and the
+//                              camera is known, before a projection is rendered.
 //       --sinogram FILE        with --turntable N and --log-projection: also write the N
 //                              projections' line integrals as one sinogram per detector
 //                              row, raw little-endian f32 in (height, N, width) order
@@ -165,6 +175,7 @@ void showUsage(const std::string& prog)
               << "\t--lsf-gaussian SIGMA[:TAPS]\tThe same with a normalised Gaussian of SIGMA pixels (TAPS odd, default 2*ceil(4*SIGMA)+1, at most 129)\n"
               << "\t--log-projection I0\t\tLine integrals: write -ln(I / I0) (I0 finite and > 0; after --lsf) instead of the intensity I; --u8 and --lbuffer stay as rendered\n"
               << "\t--sinogram FILE\t\t\tWith --turntable N and --log-projection: also write the line integrals as raw float32 sinograms, (height, N, width)\n"
+              << "\t--reconstruct FILE.mhd[:N]\tWith --turntable N:z (every mesh, about the detector's up) and --log-projection: reconstruct the scan by FDK into an N^3 grid (default 128) about the turntable's centre, its side the scene box's diagonal; writes FILE.mhd (MET_FLOAT) and FILE.raw\n"
               << "\t--noise GAIN[:SEED]\t\tPhoton noise on the written image: each pixel a Poisson count of mean I * GAIN, divided by GAIN (after --lsf, before --log-projection; SEED defaults to 0); --u8 and --lbuffer stay as rendered\n"
               << "\t--supersample B\t\t\tPixel-area integration: render W*B x H*B samples (B in 1..8) and write each pixel's mean over its B x B samples; -s stays the written size\n"
               << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
@@ -205,6 +216,8 @@ struct Options {
     bool log_projection = false;               // --log-projection I0
     float flat_value = 0.0f;                   // I0
     std::string sinogram;                      // --sinogram FILE
+    std::string reconstruct;                   // --reconstruct FILE.mhd[:N]
+    unsigned reconstruct_n = 128;              // N: the grid is N x N x N
     bool noise = false;                        // --noise GAIN[:SEED]
     float noise_gain = 0.0f;
     unsigned long long noise_seed = 0;
@@ -596,6 +609,12 @@ Options processCmd(int argc, char** argv)
             o.log_projection = true;
         } else if (a == "--sinogram") {
             o.sinogram = parse_str(argv[0], argc, argv, i);
+        } else if (a == "--reconstruct") {
+            const std::vector<std::string> parts = split(parse_str(argv[0], argc, argv, i), ':');
+            if (parts.empty() || parts.size() > 2 || parts[0].size() < 5 || parts[0].substr(parts[0].size() - 4) != ".mhd" ||
+                (parts.size() == 2 && (!parse_index(parts[1], o.reconstruct_n) || o.reconstruct_n < 1 || o.reconstruct_n > 2048)))
+                throw std::runtime_error("--reconstruct FILE.mhd[:N]: a MetaImage header's name and a grid size of 1 to 2048");
+            o.reconstruct = parts[0];
         } else if (a == "--noise") {
             parse_noise(parse_str(argv[0], argc, argv, i), o);
         } else if (a == "--supersample") {
@@ -680,6 +699,10 @@ Options processCmd(int argc, char** argv)
                                  " with --paths needs --spectrum: the planes stay as rendered, there is no image to spread");
     if (!o.sinogram.empty() && (!o.turntable || !o.log_projection))
         throw std::runtime_error("--sinogram needs --turntable N and --log-projection I0: it stacks a scan's line integrals");
+    if (!o.reconstruct.empty() && (!o.turntable || !o.log_projection))
+        throw std::runtime_error("--reconstruct needs --turntable N and --log-projection I0: it reconstructs a scan's line integrals");
+    if (!o.reconstruct.empty() && !o.turn_meshes.empty())
+        throw std::runtime_error("--reconstruct needs a --turntable that turns every mesh: the scene is reconstructed as one object");
     if (o.log_projection && (o.gpus > 1 || o.rows))
         throw std::runtime_error("--log-projection needs whole frames on one GPU: not with -g N or --rows");
     if (o.log_projection && o.paths && !o.spectrum)
@@ -770,6 +793,17 @@ int main(int argc, char** argv)
         Image image(opt.width, opt.height, lut);
         RayTracerInfo info = initialiseRayTracing(meshes, upper, lower, opt.height, opt.width, image, lut);
 
+        if (!opt.reconstruct.empty()) {               // before a projection is rendered: the scan is of no use otherwise
+            float axis[3] = {0.0f, 0.0f, 0.0f};
+            axis[opt.turn_axis] = 1.0f;
+            const Vec3 turn_axis(axis[0], axis[1], axis[2]);
+            if (std::fabs(turn_axis.dotProduct(info.right)) > 1e-6f * info.right.getLength() ||
+                std::fabs(turn_axis.dotProduct(info.detector_position - info.origin)) >
+                    1e-6f * (info.detector_position - info.origin).getLength())
+                throw std::runtime_error("--reconstruct: the turntable's axis must be parallel to the detector's up, --turntable N:z "
+                                         "(the filter runs along the detector's rows)");
+        }
+
         // the poses: --pose's, and over them each projection's turn of --turntable's meshes
         const std::array<float, 12> rest = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
         std::vector<std::array<float, 12>> poses;
@@ -777,6 +811,8 @@ int main(int argc, char** argv)
         for (const auto& q : opt.poses) poses[q.first] = q.second;
         const std::string name = opt.output, lbuffer_name = opt.lbuffer, u8_name = opt.u8;
         std::vector<float> scan;                      // --sinogram: the projections' intensity images
+        std::vector<float> integrals;                 // --reconstruct: the projections' line integrals
+        std::vector<std::array<float, 12>> turns;     //                and the turntable's pose under each
         for (unsigned projection = 0; projection < std::max(opt.turntable, 1u); ++projection) {
             if (opt.turntable) {
                 // the rest scene's box centre, as initialiseRayTracing forms it (main.cxx:575-578)
@@ -786,6 +822,7 @@ int main(int argc, char** argv)
                 std::array<float, 12> turn;
                 if (xrt_pose_rotation(axis, projection * 360.0 / opt.turntable, centre, turn.data()) != XRT_OK)
                     throw std::runtime_error("--turntable: the scene's box is not finite");
+                if (!opt.reconstruct.empty()) turns.push_back(turn);
                 for (size_t m = 0; m < meshes.size(); ++m)
                     if (opt.turn_meshes.empty() ||
                         std::find(opt.turn_meshes.begin(), opt.turn_meshes.end(), (unsigned)m) != opt.turn_meshes.end())
@@ -928,6 +965,8 @@ int main(int argc, char** argv)
                                      (unsigned long long)projection * opt.width * opt.height);
                 if (!opt.sinogram.empty()) scan.insert(scan.end(), written.getData(), written.getData() + (size_t)opt.width * opt.height);
                 if (opt.log_projection) applyLogProjection(written, opt.flat_value);
+                if (!opt.reconstruct.empty())
+                    integrals.insert(integrals.end(), written.getData(), written.getData() + (size_t)opt.width * opt.height);
                 written.saveTextFile(opt.output);
             } else {
                 out->saveTextFile(opt.output);
@@ -952,6 +991,27 @@ int main(int argc, char** argv)
             if (!f) throw std::runtime_error("Cannot create the file " + opt.sinogram);
             std::fwrite(sinograms.data(), sizeof(float), sinograms.size(), f);
             std::fclose(f);
+        }
+        if (!opt.reconstruct.empty()) {
+            // an N^3 cube about the turntable's centre whose side is the scene box's diagonal: it holds the
+            // scene under every turn
+            float centre[3], origin[3], spacing[3];
+            double diagonal = 0.0;
+            for (unsigned k = 0; k < 3; ++k) diagonal += (double)(upper[k] - lower[k]) * (double)(upper[k] - lower[k]);
+            diagonal = std::sqrt(diagonal);
+            const unsigned dims[3] = {opt.reconstruct_n, opt.reconstruct_n, opt.reconstruct_n};
+            for (unsigned k = 0; k < 3; ++k) {
+                centre[k] = lower[k] + (float)((double)(upper[k] - lower[k]) / 2.0);
+                spacing[k] = (float)(diagonal / opt.reconstruct_n);
+                origin[k] = (float)((double)centre[k] - diagonal / 2.0);
+            }
+            std::vector<float> reconstruction;
+            reconstructFDK(reconstruction, integrals, opt.turntable, image, meshes, info, turns, dims, origin, spacing, centre);
+            try {
+                saveVolume(opt.reconstruct, dims, origin, spacing, reconstruction.data());
+            } catch (const VolumeError& e) {
+                throw std::runtime_error(std::string("--reconstruct: ") + e.what());
+            }
         }
     } catch (const std::exception& e) {
         std::cerr << "ERROR: " << e.what() << std::endl;

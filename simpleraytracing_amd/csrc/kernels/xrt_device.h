@@ -1586,4 +1586,53 @@ __host__ __device__ __forceinline__ void volume_ray(const VolumeDesc& v, double 
     if (cur) add(cur - 1u, run);
 }
 
+// ---------------------------------------------------------------------------
+// FDK reconstruction: the arithmetic that k_backproject and its
+// host restatement (xrt_host_backproject) share.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMaxRampWidth = 4096;            // XRT_MAX_RAMP_WIDTH
+
+// The (j, k) part of one line of a projection matrix, A = that line's four
+// entries: a voxel's homogeneous coordinate is A[0] * i + backproject_bracket.
+__host__ __device__ __forceinline__ double backproject_bracket(const double* A, double j, double k)
+{
+    return (A[1] * j + A[2] * k) + A[3];
+}
+
+// A projection sample: the pixel inside the plane, +0.0f outside (W and H are at most 2^31 - 1: the
+// callers' argument check).
+__host__ __device__ __forceinline__ float backproject_sample(const float* plane, uint32_t W, uint32_t H, int32_t y,
+                                                             int32_t x)
+{
+    return x >= 0 && y >= 0 && (uint32_t)x < W && (uint32_t)y < H ? plane[(size_t)y * W + (size_t)x] : 0.0f;
+}
+
+// One plane's contribution to one voxel whose homogeneous detector
+// coordinates are (a, b, c): nothing unless c > 0 and the point lies within
+// one pixel of the plane; else the bilinear sample (f32, every operation
+// rounded on its own) times 1 / c^2, added to acc in f64.
+__host__ __device__ __forceinline__ void backproject_term(const float* plane, uint32_t W, uint32_t H, double a, double b,
+                                                          double c, double& acc)
+{
+    if (!(c > 0.0)) return;                          // (a NaN compares false)
+    const double w = 1.0 / c;
+    const double col = a * w, row = b * w;
+    if (!(col > -1.0 && col < (double)W && row > -1.0 && row < (double)H)) return;
+    const double fc = floor(col), fr = floor(row);
+    const float fx = (float)(col - fc), fy = (float)(row - fr);
+    const int32_t x0 = (int32_t)fc, y0 = (int32_t)fr;          // -1 .. W - 1 and -1 .. H - 1
+    const float s00 = backproject_sample(plane, W, H, y0, x0), s01 = backproject_sample(plane, W, H, y0, x0 + 1);
+    const float s10 = backproject_sample(plane, W, H, y0 + 1, x0), s11 = backproject_sample(plane, W, H, y0 + 1, x0 + 1);
+    const float top = s00 + fx * (s01 - s00);
+    const float bot = s10 + fx * (s11 - s10);
+    const float v = top + fy * (bot - top);
+    acc = acc + (double)v * (w * w);
+}
+
+// What a voxel's sum becomes in the volume.
+__host__ __device__ __forceinline__ float backproject_output(double acc, double scale, bool accumulate, float old)
+{
+    return accumulate ? (float)((double)old + acc * scale) : (float)(acc * scale);
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -4371,4 +4371,299 @@ __global__ __launch_bounds__(64) void k_volume_paths(const RenderParams p, const
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_fdk_filter: the row filter of FDK.  A workgroup of five
+// waves owns a segment of kFilterSegment outputs of one row of one plane; the
+// pixels its sums meet, times the weight plane (one f32 product), lie in LDS
+// widened to f64, with zeros where the row has no pixel.  A sum starts at +0.0
+// and the taps are finite, so a product with such a zero adds +-0.0 and
+// changes no bit: the padded row gives what skipping gives.  A lane owns
+// kFilterOut = 7 adjacent outputs in registers (an odd count: the lanes' LDS
+// addresses, 7 doubles apart, fall on different banks).  The tap loop is
+// unrolled by 7, so the window of pixels slides through registers by
+// renaming: per tap a lane reads one new pixel from LDS and one tap -- a
+// scalar load, the index is wave-uniform -- for 7 sums.  A wave runs only the
+// taps that meet a pixel of the row for one of its 448 outputs, at most
+// W + 447 of them.
+// The contract's s = s + t * px, each operation rounded on its own, is one
+// fma here, bit for bit: t and px are widened f32 values, so their product
+// has at most 48 significant bits and an exponent within +-300 -- exact in
+// f64, neither overflow nor underflow -- and rounding it changes nothing;
+// fma(t, px, s) then rounds the same exact sum once, as the addition would
+// (0 * inf and inf - inf are NaN either way; (+0.0) + (-0.0) is +0.0 either
+// way).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kFilterOut = 7;
+constexpr uint32_t kFilterWaves = 5;
+constexpr uint32_t kFilterThreads = 64u * kFilterWaves;
+constexpr uint32_t kFilterWaveOut = 64u * kFilterOut;
+constexpr uint32_t kFilterSegment = kFilterWaves * kFilterWaveOut;
+// the row's pixels, a wave's overhang to the left (kFilterWaveOut - 1) and to the right (the last lane's window and
+// the look-ahead of the last group of taps)
+constexpr uint32_t kFilterTail = kFilterWaveOut + 7u;
+constexpr uint32_t kFilterLds = kMaxRampWidth + (kFilterWaveOut - 1u) + kFilterTail;
+
+// kFilterOut taps (kFull) or the first `count` of them over the window win and the pixels behind it.
+template <bool kFull>
+__device__ __forceinline__ void fdk_filter_group(const float* __restrict__ taps, uint32_t count, const double* next,
+                                                 double (&win)[kFilterOut], double (&s)[kFilterOut])
+{
+    double nw[kFilterOut];
+#pragma unroll
+    for (uint32_t i = 0; i < kFilterOut; ++i) nw[i] = next[i];
+#pragma unroll
+    for (uint32_t u = 0; u < kFilterOut; ++u) {
+        if (kFull || u < count) {
+            const double t = (double)taps[u];
+#pragma unroll
+            for (uint32_t j = 0; j < kFilterOut; ++j) {
+                const double px = j + u < kFilterOut ? win[j + u] : nw[j + u - kFilterOut];
+                s[j] = __builtin_fma(t, px, s[j]);     // = s[j] + t * px: the product is exact (above)
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kFilterOut; ++i) win[i] = nw[i];
+}
+
+__global__ __launch_bounds__(kFilterThreads) void k_fdk_filter(const float* __restrict__ image,
+                                                               const float* __restrict__ weight,
+                                                               const float* __restrict__ taps, float* __restrict__ out,
+                                                               uint32_t width, uint32_t height, uint32_t num_taps,
+                                                               uint32_t segments)
+{
+    __shared__ double s_row[kFilterLds];
+    const uint32_t seg = blockIdx.x % segments;
+    const size_t row = blockIdx.x / segments;         // plane * height + y
+    const uint32_t y = (uint32_t)(row % height);
+    const int32_t W = (int32_t)width, r = (int32_t)((num_taps - 1u) / 2u);
+    const int32_t x0 = (int32_t)(seg * kFilterSegment);
+    // the pixels [lo, hi) that some wave of this workgroup reads (outside the row: zeros)
+    const int32_t lo = max(x0 - r, -(int32_t)(kFilterWaveOut - 1u));
+    const int32_t hi = min(W - 1, x0 + (int32_t)(kFilterSegment - kFilterWaveOut) + r) + (int32_t)kFilterTail;
+    const uint32_t count = min((uint32_t)(hi - lo), kFilterLds);
+    const float* src = image + row * width;
+    const float* wrow = weight ? weight + (size_t)y * width : nullptr;
+    for (uint32_t m = threadIdx.x; m < count; m += kFilterThreads) {
+        const int32_t px = lo + (int32_t)m;
+        float v = 0.0f;
+        if (px >= 0 && px < W) {
+            v = src[px];
+            if (wrow) v = v * wrow[px];
+        }
+        s_row[m] = (double)v;
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const int32_t xa = x0 + (int32_t)(wave_in_block() * kFilterWaveOut);     // the wave's first output
+    if (xa >= W) return;
+    const int32_t x_last = min(xa + (int32_t)kFilterWaveOut - 1, W - 1);
+    const int32_t k_lo = max(0, r - x_last), k_hi = min((int32_t)num_taps - 1, r - xa + W - 1);
+    const uint32_t nt = (uint32_t)(k_hi - k_lo + 1);
+    const double* L = s_row + (xa + k_lo - r - lo) + (int32_t)(kFilterOut * lane);
+    const float* tp = taps + k_lo;
+    double win[kFilterOut], s[kFilterOut];
+#pragma unroll
+    for (uint32_t i = 0; i < kFilterOut; ++i) {
+        win[i] = L[i];
+        s[i] = 0.0;
+    }
+    const uint32_t groups = nt / kFilterOut, rest = nt - groups * kFilterOut;
+    for (uint32_t q = 0; q < groups; ++q)
+        fdk_filter_group<true>(tp + q * kFilterOut, kFilterOut, L + (q + 1u) * kFilterOut, win, s);
+    if (rest) fdk_filter_group<false>(tp + groups * kFilterOut, rest, L + (groups + 1u) * kFilterOut, win, s);
+    const int32_t x = xa + (int32_t)(kFilterOut * lane);
+    float* dst = out + row * width;
+#pragma unroll
+    for (uint32_t j = 0; j < kFilterOut; ++j)
+        if (x + (int32_t)j < W) dst[x + (int32_t)j] = (float)s[j];
+}
+
+// ---------------------------------------------------------------------------
+// k_fdk_filter_wide: the same filter where the table is as long as a ramp's,
+// num_taps >= 2 W - 1, so that every pixel of the row meets every output under
+// a tap of the table (k = i - x + r lies in 0 .. num_taps - 1 for all i and x).
+// The sums then run over the pixels i = 0 .. W - 1 -- for one output the same
+// terms in the same order as k ascending -- and every lane of a wave is at
+// the same pixel at the same time: exactly W steps an output, where
+// k_fdk_filter's waves, aligned by tap, run W + 447.  A workgroup of four
+// waves owns a segment of 2048 outputs of two rows.  Its LDS holds the two
+// weighted rows widened to f64 (read by all lanes at one address: a
+// broadcast), and the taps its outputs meet widened to f64 once, zeros where
+// the table has no tap (they meet only the rows' padding zeros and the lanes
+// past the row's end).  A lane owns 8 adjacent outputs of both rows; per pixel
+// it reads one new tap -- the window of 8 + 8 taps slides by renaming, two
+// groups of 8 pixels an iteration so that no register is copied -- for 16
+// fma (exact products, as above).  The table is skewed by one double in
+// eight: the lanes' reads, 8 taps apart, fall on different banks.
+// A ramp's table is half zeros: the Ram-Lak taps at even distances n = k - r
+// from the centre, the centre apart.  Where a workgroup finds, while it fills
+// its LDS, that every such tap it holds is +-0.0 and that every pixel of its
+// two rows is finite, the terms under those taps are s + (+-0.0) -- s itself,
+// bit for bit: s starts at +0.0 and a sum never becomes -0.0 -- and are left
+// out (kOdd): n = i - x has the parity of u - j for every lane, so the half
+// that stays is the same for a whole wave.  The centre term falls on the
+// group q = x / 8 of a lane's outputs: a wave runs those 64 of its groups in
+// full.  A table with another tap at an even distance (a Hann window's), or
+// a row with a NaN or an infinity (0 * inf is NaN, not 0), runs every term.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kWideOut = 8;
+constexpr uint32_t kWideThreads = 256;
+constexpr uint32_t kWideSegment = kWideThreads * kWideOut;
+
+// the groups of 8 pixels of a row, and the bytes of LDS of a launch: the skewed taps, then two rows
+__host__ __device__ constexpr uint32_t fdk_wide_groups(uint32_t width) { return (width + 7u) / 8u; }
+__host__ __device__ constexpr size_t fdk_wide_lds_bytes(uint32_t width)
+{
+    return ((size_t)9u * (fdk_wide_groups(width) + kWideThreads) + (size_t)16u * fdk_wide_groups(width)) * sizeof(double);
+}
+
+// 8 pixels of both rows over the window `a` and the 8 taps behind it, which are read into `b`: b is the next window.
+template <bool kOdd>
+__device__ __forceinline__ void fdk_wide_group(const double* next, const double* p0, const double* p1,
+                                               const double (&a)[kWideOut], double (&b)[kWideOut],
+                                               double (&s0)[kWideOut], double (&s1)[kWideOut])
+{
+#pragma unroll
+    for (uint32_t t = 0; t < kWideOut; ++t) b[t] = next[t];
+#pragma unroll
+    for (uint32_t u = 0; u < kWideOut; ++u) {
+        const double x0 = p0[u], x1 = p1[u];
+#pragma unroll
+        for (uint32_t j = 0; j < kWideOut; ++j) {
+            if (kOdd && ((u ^ j) & 1u) == 0u) continue;     // a tap at an even distance: +-0.0 (the caller's check)
+            const uint32_t idx = kWideOut - 1u + u - j;
+            const double t = idx < kWideOut ? a[idx] : b[idx - kWideOut];
+            s0[j] = __builtin_fma(t, x0, s0[j]);
+            s1[j] = __builtin_fma(t, x1, s1[j]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kWideThreads) void k_fdk_filter_wide(const float* __restrict__ image,
+                                                                  const float* __restrict__ weight,
+                                                                  const float* __restrict__ taps, float* __restrict__ out,
+                                                                  uint32_t width, uint32_t height, uint64_t rows,
+                                                                  uint32_t num_taps, uint32_t segments)
+{
+    extern __shared__ double s_wide[];
+    const uint32_t groups = fdk_wide_groups(width);
+    double* tab = s_wide;                                   // 9 * (groups + 256) doubles, skewed
+    double* row0 = s_wide + 9u * (groups + kWideThreads);   // 8 * groups doubles each
+    double* row1 = row0 + 8u * groups;
+    const uint32_t seg = blockIdx.x % segments;
+    const uint64_t r0 = (uint64_t)(blockIdx.x / segments) * 2u;      // plane * height + y of the first row
+    const int32_t W = (int32_t)width, r = (int32_t)((num_taps - 1u) / 2u);
+    const int32_t x0 = (int32_t)(seg * kWideSegment);
+    // table entry m holds tap k_min + m: the lowest tap that lane 255's first window reads is entry 0
+    const int32_t k_min = r - x0 - (int32_t)(kWideSegment - 1u);
+    int dense = 0;                      // a tap or a pixel that forbids leaving out the even distances
+    for (uint32_t m = threadIdx.x; m < 8u * (groups + kWideThreads); m += kWideThreads) {
+        const int32_t k = k_min + (int32_t)m;
+        const float t = k >= 0 && k < (int32_t)num_taps ? taps[k] : 0.0f;
+        if (k != r && ((k - r) & 1) == 0 && t != 0.0f) dense = 1;
+        tab[m + (m >> 3)] = (double)t;
+    }
+    for (uint32_t h = 0; h < 2u; ++h) {
+        double* dst = h ? row1 : row0;
+        const uint64_t row = r0 + h;
+        const float* src = image + row * width;
+        const float* wrow = weight ? weight + (size_t)(row % height) * width : nullptr;
+        for (uint32_t i = threadIdx.x; i < 8u * groups; i += kWideThreads) {
+            float v = 0.0f;
+            if (row < rows && (int32_t)i < W) {
+                v = src[i];
+                if (wrow) v = v * wrow[i];
+            }
+            if (!(fabsf(v) <= 3.40282347e+38f)) dense = 1;          // a NaN or an infinity
+            dst[i] = (double)v;
+        }
+    }
+    const bool odd = !__syncthreads_or(dense);
+    const int32_t x = x0 + (int32_t)(kWideOut * threadIdx.x);        // the lane's first output
+    if (x0 + (int32_t)((threadIdx.x & ~63u) * kWideOut) >= W) return;   // the wave's first output: past the row's end
+    // the lane's taps of group q (pixels 8 q .. 8 q + 7 bring in the taps 8 (q - lane + 256) + t): 9 (q - lane + 256) + t
+    const double* lane_tab = tab + 9u * (kWideThreads - threadIdx.x);
+    double a[kWideOut], b[kWideOut], s0[kWideOut], s1[kWideOut];
+#pragma unroll
+    for (uint32_t t = 0; t < kWideOut; ++t) {
+        a[t] = lane_tab[(int32_t)t - 9];
+        s0[t] = 0.0;
+        s1[t] = 0.0;
+    }
+    // the groups that hold the centre terms of this wave's outputs: q = x / 8 of its 64 lanes
+    const uint32_t centre = wave_uniform(seg * kWideThreads + (threadIdx.x & ~63u));
+    const auto group = [&](uint32_t g, const double (&from)[kWideOut], double (&to)[kWideOut]) {
+        if (odd && g - centre >= 64u)
+            fdk_wide_group<true>(lane_tab + 9u * g, row0 + 8u * g, row1 + 8u * g, from, to, s0, s1);
+        else
+            fdk_wide_group<false>(lane_tab + 9u * g, row0 + 8u * g, row1 + 8u * g, from, to, s0, s1);
+    };
+    uint32_t q = 0;
+    for (; q + 2u <= groups; q += 2u) {
+        group(q, a, b);
+        group(q + 1u, b, a);
+    }
+    if (q < groups) group(q, a, b);
+#pragma unroll
+    for (uint32_t j = 0; j < kWideOut; ++j)
+        if (x + (int32_t)j < W) {
+            out[r0 * width + (uint32_t)(x + (int32_t)j)] = (float)s0[j];
+            if (r0 + 1u < rows) out[(r0 + 1u) * width + (uint32_t)(x + (int32_t)j)] = (float)s1[j];
+        }
+}
+
+// ---------------------------------------------------------------------------
+// k_backproject: the cone-beam backprojector.  A wave owns
+// kBackprojectChunks * 64 voxels of one row (j, k) of the volume, lanes along
+// x: a lane keeps the sums of the voxels i = x0 + lane + 64 c across the loop
+// over the planes, so one fetch of a plane's matrix -- scalar loads, the
+// address is wave-uniform -- and one evaluation of the three (j, k) brackets
+// serve all of them, and a lane adds its A * i.  Neighbouring lanes project
+// to neighbouring detector pixels: the four gathers and the store coalesce.
+// Offsets into the planes and the volume are 64-bit.  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kBackprojectThreads = 256;
+constexpr uint32_t kBackprojectChunks = 4;
+constexpr uint32_t kBackprojectSpan = 64u * kBackprojectChunks;
+
+__global__ __launch_bounds__(kBackprojectThreads) void k_backproject(const float* __restrict__ proj,
+                                                                     const double* __restrict__ matrices, uint32_t width,
+                                                                     uint32_t height, uint32_t num_planes, uint32_t nx,
+                                                                     uint32_t ny, uint32_t slab_begin, uint64_t rows,
+                                                                     uint32_t spans, double scale, uint32_t accumulate,
+                                                                     float* volume)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t g = (uint64_t)blockIdx.x * (kBackprojectThreads / 64u) + wave_in_block();
+    const uint64_t row = g / spans;                   // (k - slab_begin) * ny + j
+    if (row >= rows) return;                          // (no barrier below)
+    const uint32_t x0 = (uint32_t)(g - row * spans) * kBackprojectSpan + lane;
+    const double dj = (double)(uint32_t)(row % ny), dk = (double)(slab_begin + (uint32_t)(row / ny));
+    double acc[kBackprojectChunks], di[kBackprojectChunks];
+#pragma unroll
+    for (uint32_t c = 0; c < kBackprojectChunks; ++c) {
+        acc[c] = 0.0;
+        di[c] = (double)(x0 + 64u * c);
+    }
+    const size_t plane = (size_t)width * height;
+    for (uint32_t p = 0; p < num_planes; ++p) {
+        const double* A = matrices + (size_t)p * 12u;
+        const double ba = backproject_bracket(A, dj, dk), bb = backproject_bracket(A + 4, dj, dk),
+                     bc = backproject_bracket(A + 8, dj, dk);
+        const double a0 = A[0], a4 = A[4], a8 = A[8];
+        const float* img = proj + (size_t)p * plane;
+#pragma unroll
+        for (uint32_t c = 0; c < kBackprojectChunks; ++c)
+            if (x0 + 64u * c < nx)
+                backproject_term(img, width, height, a0 * di[c] + ba, a4 * di[c] + bb, a8 * di[c] + bc, acc[c]);
+    }
+    float* dst = volume + row * nx;
+#pragma unroll
+    for (uint32_t c = 0; c < kBackprojectChunks; ++c) {
+        const uint32_t x = x0 + 64u * c;
+        if (x < nx) dst[x] = backproject_output(acc[c], scale, accumulate != 0u, accumulate ? dst[x] : 0.0f);
+    }
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -2906,6 +2906,119 @@ int xrt_volume_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_be
     return s.finish();
 }
 
+// --- FDK reconstruction ----------------------------------------
+
+#include "xrt_fdk_host.inc"
+
+// The launch of k_fdk_filter (validated arguments, device pointers).
+static int launch_fdk_filter(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_image,
+                             const float* d_weight, const float* d_taps, uint32_t num_taps, float* d_out,
+                             hipStream_t stream)
+{
+    if (num_taps >= 2u * width - 1u) {   // a table as long as a ramp's: every lane at the same pixel, W steps an output
+        const uint32_t segments = (width + kWideSegment - 1u) / kWideSegment;
+        const uint64_t rows = (uint64_t)height * num_planes;
+        const size_t lds = fdk_wide_lds_bytes(width);
+        if (lds > 64u * 1024u)          // past the default limit of a launch's dynamic LDS
+            XRT_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fdk_filter_wide),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_fdk_filter_wide, dim3((unsigned)((rows + 1u) / 2u * segments)), dim3(kWideThreads), lds, stream,
+                           d_image, d_weight, d_taps, d_out, width, height, rows, num_taps, segments);
+        XRT_HIP(ctx, hipGetLastError());
+        return XRT_OK;
+    }
+    const uint32_t segments = (width + kFilterSegment - 1u) / kFilterSegment;
+    const uint64_t blocks = (uint64_t)height * num_planes * segments;
+    hipLaunchKernelGGL(k_fdk_filter, dim3((unsigned)blocks), dim3(kFilterThreads), 0, stream, d_image, d_weight, d_taps,
+                       d_out, width, height, num_taps, segments);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_fdk_filter_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_image,
+                          const float* d_weight, const float* d_taps, uint32_t num_taps, float* d_out, void* stream)
+{
+    if (const char* why = fdk_filter_arguments(width, height, num_planes, d_image, d_weight, d_taps, num_taps, d_out, false))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_fdk_filter(ctx, width, height, num_planes, d_image, d_weight, d_taps, num_taps, d_out,
+                             (hipStream_t)stream);
+}
+
+int xrt_fdk_filter(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* image,
+                   const float* weight, const float* taps, uint32_t num_taps, float* out)
+{
+    if (const char* why = fdk_filter_arguments(width, height, num_planes, image, weight, taps, num_taps, out, true))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t plane = (size_t)width * height, all = plane * num_planes;
+    DeviceScratch s(ctx, ctx->host_stream, "FDK filter");
+    const float* din = s.upload(image, all);
+    const float* dweight = s.upload(weight, plane);
+    const float* dtaps = s.upload(taps, (size_t)num_taps);
+    float* dout = s.alloc<float>(all);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_fdk_filter(ctx, width, height, num_planes, din, dweight, dtaps, num_taps, dout, ctx->host_stream))
+        return rc;
+    s.download(out, dout, all);
+    return s.finish();
+}
+
+// The launch of k_backproject (validated arguments, device pointers, a slab range that is not empty).
+static int launch_backproject(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                              const double* d_matrices, const uint32_t dims[3], uint32_t slab_begin, uint32_t slab_end,
+                              double scale, int accumulate, float* d_volume, hipStream_t stream)
+{
+    const uint32_t spans = (dims[0] + kBackprojectSpan - 1u) / kBackprojectSpan;
+    const uint64_t rows = (uint64_t)(slab_end - slab_begin) * dims[1];
+    const uint64_t waves = rows * spans, per_block = kBackprojectThreads / 64u;
+    hipLaunchKernelGGL(k_backproject, dim3((unsigned)((waves + per_block - 1u) / per_block)), dim3(kBackprojectThreads), 0,
+                       stream, d_proj, d_matrices, width, height, num_planes, dims[0], dims[1], slab_begin, rows, spans,
+                       scale, (uint32_t)(accumulate != 0), d_volume);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_backproject_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                           const double* d_matrices, const uint32_t dims[3], uint32_t slab_begin, uint32_t slab_end,
+                           double scale, int accumulate, float* d_volume, void* stream)
+{
+    if (const char* why = backproject_arguments(width, height, num_planes, d_proj, d_matrices, dims, slab_begin, slab_end,
+                                                scale, d_volume, false))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (slab_begin == slab_end) return XRT_OK;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_backproject(ctx, width, height, num_planes, d_proj, d_matrices, dims, slab_begin, slab_end, scale,
+                              accumulate, d_volume, (hipStream_t)stream);
+}
+
+int xrt_backproject(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* proj,
+                    const double* matrices, const uint32_t dims[3], uint32_t slab_begin, uint32_t slab_end, double scale,
+                    int accumulate, float* volume)
+{
+    if (const char* why = backproject_arguments(width, height, num_planes, proj, matrices, dims, slab_begin, slab_end,
+                                                scale, volume, true))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (slab_begin == slab_end) return XRT_OK;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t all = (size_t)width * height * num_planes;
+    const size_t voxels = (size_t)(slab_end - slab_begin) * dims[1] * dims[0];
+    DeviceScratch s(ctx, ctx->host_stream, "backprojection");
+    const float* dproj = s.upload(proj, all);
+    const double* dmat = s.upload(matrices, (size_t)num_planes * 12u);
+    float* dvol = accumulate ? s.upload(volume, voxels) : s.alloc<float>(voxels);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_backproject(ctx, width, height, num_planes, dproj, dmat, dims, slab_begin, slab_end, scale,
+                                    accumulate, dvol, ctx->host_stream))
+        return rc;
+    s.download(volume, dvol, voxels);
+    return s.finish();
+}
+
 int xrt_hole_fill_device(xrt_context* ctx, uint32_t width, uint32_t height, const float* d_lbuffer,
                          float* d_image, uint8_t* d_u8, void* stream)
 {
