@@ -52,7 +52,8 @@ typedef enum xrt_status {
     XRT_ERR_NO_MESH = 3,    /* render before xrt_upload_mesh */
     XRT_ERR_OVERFLOW = 4,   /* internal capacity exceeded */
     XRT_ERR_IO = 5,         /* file could not be read / written */
-    XRT_ERR_FORMAT = 6      /* malformed input file */
+    XRT_ERR_FORMAT = 6,     /* malformed input file */
+    XRT_ERR_MEMORY = 7      /* a device working set could not be allocated (xrt_sirt) */
 } xrt_status;
 
 /* Kernel selection. */
@@ -927,6 +928,125 @@ int xrt_backprojection_matrix(const xrt_camera* camera, const float pose[12], co
 int xrt_fdk_weights(const xrt_camera* camera, float* weight);
 int xrt_ramp_filter(uint32_t num_taps, int window, float* taps);
 int xrt_fdk_scale(const xrt_camera* camera, const float axis_point[3], uint32_t num_projections, double* scale);
+
+/* --- SIRT / OS-SART: a matrix-driven forward projector and solver ---------- */
+
+/*
+ * The iterative side of reconstruction: a forward
+ * projector of a device-resident f32 volume under the backprojector's own
+ * matrices, a voxel update, and the loop over both and xrt_backproject that
+ * is SIRT (one subset) or OS-SART (several).  None of them looks at or
+ * changes the context's model, scene, poses, frames in flight or state
+ * generation.  There is no xrt_multi_ form.
+ *
+ * xrt_ray_matrix (host arithmetic in f64, no device).  A = [A3 | a4] is a
+ * matrix of xrt_backproject; R = [N | -N a4] with N = A3^-1 by cofactors:
+ *   C[i][j] = A3[i1][j1] * A3[i2][j2] - A3[i1][j2] * A3[i2][j1],  i1 = (i+1)%3, i2 = (i+2)%3, j likewise
+ *   det     = (A3[0][0] * C[0][0] + A3[0][1] * C[0][1]) + A3[0][2] * C[0][2]
+ *   N[i][j] = C[j][i] / det
+ *   R[4i+j] = N[i][j],  R[4i+3] = -((N[i][0] * a4[0] + N[i][1] * a4[1]) + N[i][2] * a4[2])
+ * every operation rounded on its own.  In centre-index coordinates (voxel i
+ * occupies [i - 0.5, i + 0.5]) column 3 of R is the source s, and the ray of
+ * pixel (row, col) is s + t d with
+ *   d_a = R[4a] * col + (R[4a+1] * row + R[4a+2])
+ * A (s + t d, 1) = t (col, row, 1): t is the backprojector's c, and forward is
+ * t > 0, the half-space the backprojector accepts.  XRT_ERR_ARGUMENT for a
+ * NULL pointer, an input that is not finite, a determinant that is zero or not
+ * finite, and a result that is not finite.
+ *
+ * xrt_forward_project[_device].  volume: f32 [nz][ny][nx], dims = {nx, ny, nz}
+ * as xrt_backproject's, each 1..2048; spacing[3] the voxel's size, each finite
+ * and > 0; rays[num_planes][12] f64 ray matrices; meas (XRT_FP_RESIDUAL: needed;
+ * XRT_FP_PROJECT: not read) and out: num_planes planes of width x height.  Per
+ * pixel (row, col) of plane p, R = rays[p], all in f64, every operation
+ * rounded on its own (no FMA), every min or max the written select, the grid
+ * lo = -0.5, s = 1 with plane(i) = -0.5 + (double)i * 1.0 from the index every
+ * time, n = (nx, ny, nz):
+ *   O = (R[3], R[7], R[11]);  d as above with (double)row, (double)col
+ *   te = 0, tx = +inf;  per axis a in x, y, z order:
+ *     d_a == 0:  a miss unless O_a >= plane(0) && O_a < plane(n_a)
+ *     else       inv_a = 1 / d_a;  t0 = (plane(0) - O_a) * inv_a;  t1 = (plane(n_a) - O_a) * inv_a
+ *                mn = t0 < t1 ? t0 : t1;  mx = t0 < t1 ? t1 : t0
+ *                te = mn > te ? mn : te;  tx = mx < tx ? mx : tx
+ *   a miss unless te < tx
+ *   i_a = floor(((O_a + te * d_a) - (-0.5)) / 1.0), then f >= 0 ? f : 0 and f <= n_a - 1 ? f : n_a - 1
+ *   step_a = d_a > 0 ? 1 : -1;  up_a = d_a > 0 ? 1 : 0
+ *   tnext_a = d_a == 0 ? +inf : (plane(i_a + up_a) - O_a) * inv_a
+ *   tc = te, acc = +0.0; at most nx + ny + nz + 3 times:
+ *     t = tnext_x, a = x;  if (tnext_y < t) t = tnext_y, a = y;  if (tnext_z < t) t = tnext_z, a = z
+ *     tend = t < tx ? t : tx;  seg = tend - tc
+ *     if (seg > 0) { acc = acc + seg * (double)volume[(i_z * ny + i_y) * nx + i_x];  tc = tend }
+ *     stop unless t < tx;  i_a += step_a;  stop when i_a leaves 0 .. n_a - 1
+ *   ell = sqrt(((sx*dx) * (sx*dx) + (sy*dy) * (sy*dy)) + (sz*dz) * (sz*dz)),  s = (double)spacing
+ *   L   = (tx - te) * ell
+ *   XRT_FP_PROJECT:   out = (float)(acc * ell); a miss: +0.0f
+ *   XRT_FP_RESIDUAL:  out = L > 0 ? (float)(((double)meas - acc * ell) / L) : +0.0f; a miss: +0.0f
+ * the residual being SART's row-normalised one.  XRT_ERR_ARGUMENT, before the
+ * context is looked at, for a NULL volume, dims, spacing, rays or out, a
+ * width, height or num_planes of 0 (or outside xrt_backproject's limits, or a
+ * plane of more than 2^26 - 1 tiles of 8 x 8 pixels), more than 65535 planes,
+ * a dims[a] outside 1..2048, a spacing that is not finite and > 0, a mode
+ * that is not one of XRT_FP_*, XRT_FP_RESIDUAL without meas, a ray matrix
+ * entry that is not finite (the host form only) and an out that overlaps the
+ * volume, the rays or meas.  xrt_forward_project: host buffers, synchronous.
+ * _device: device buffers, asynchronous on `stream`.
+ *
+ * xrt_volume_update[_device].  Per voxel i < n (n in 1..2^33), only where
+ * norm[i] > 0 (a NaN compares false):
+ *   v = (float)((double)x[i] + relax * ((double)corr[i] / (double)norm[i]))
+ *   v = v < lo ? lo : v;  v = v > hi ? hi : v;  x[i] = v
+ * elsewhere x[i] stays.  lo = -inf and hi = +inf: no clamp.  XRT_ERR_ARGUMENT,
+ * before the context is looked at, for a NULL pointer, an n of 0 or above
+ * 2^33, a relax that is not finite, a bound that is NaN, lo > hi and an x that
+ * overlaps corr or norm.
+ *
+ * xrt_sirt[_device].  proj[P][H][W]: line integrals (xrt_log_projection's);
+ * matrices[P][12]: xrt_backproject's, in host memory in both forms -- the
+ * library derives every R from its A (xrt_ray_matrix), so the two geometries
+ * agree by construction --; `volume` is the start and the result.  Subset s of
+ * S holds the planes p with p mod S == s, ascending; A_s, R_s, b_s are its
+ * matrices and measurements.  N_s = xrt_backproject of all-ones planes under
+ * A_s (scale 1, no accumulate), once.  Then for k = 0 .. iterations - 1 and
+ * s = 0 .. S - 1 in this order:
+ *   r = xrt_forward_project(volume, R_s, XRT_FP_RESIDUAL, b_s)
+ *   c = xrt_backproject(r, A_s, scale 1, no accumulate)
+ *   volume = xrt_volume_update(volume, c, N_s, relax, lo, hi)
+ * S = 1 is SIRT, S > 1 OS-SART.  XRT_ERR_ARGUMENT, before the context is
+ * looked at, for a NULL pointer, sizes outside the limits above, iterations of
+ * 0, subsets outside 1..min(P, XRT_MAX_SUBSETS), a relax that is not finite, a
+ * NaN bound, lo > hi, a matrix entry that is not finite and a volume that
+ * overlaps an input; then for a matrix without a ray matrix.  xrt_sirt: host
+ * projections and volume, synchronous.  _device: device projections and
+ * volume, asynchronous on `stream` (a call first waits for the context's
+ * previous xrt_sirt[_device], whose working set it takes over: two calls on
+ * two streams of one context run one after the other, the second's host
+ * thread blocked until the first has finished on the device; calls that are
+ * to overlap need a context each).  The working
+ * set -- the residual planes of the largest subset, one correction volume, S
+ * norm volumes and the gathered matrices -- is held by the context and reused;
+ * XRT_ERR_MEMORY, with the byte count in xrt_last_error, when it cannot be
+ * allocated.
+ */
+#define XRT_FP_PROJECT 0
+#define XRT_FP_RESIDUAL 1
+#define XRT_MAX_SUBSETS 64
+int xrt_ray_matrix(const double A[12], double R[12]);
+int xrt_forward_project(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* volume,
+                        const uint32_t dims[3], const float spacing[3], const double* rays, int mode, const float* meas,
+                        float* out);
+int xrt_forward_project_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                               const float* d_volume, const uint32_t dims[3], const float spacing[3], const double* d_rays,
+                               int mode, const float* d_meas, float* d_out, void* stream);
+int xrt_volume_update(xrt_context* ctx, uint64_t n, float* x, const float* corr, const float* norm, double relax, float lo,
+                      float hi);
+int xrt_volume_update_device(xrt_context* ctx, uint64_t n, float* d_x, const float* d_corr, const float* d_norm,
+                             double relax, float lo, float hi, void* stream);
+int xrt_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* proj,
+             const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets,
+             double relax, float lo, float hi, float* volume);
+int xrt_sirt_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                    const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
+                    uint32_t subsets, double relax, float lo, float hi, float* d_volume, void* stream);
 
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 

@@ -382,6 +382,21 @@ int xrt_host_backproject(uint32_t width, uint32_t height, uint32_t num_planes, c
                          float* volume);
 
 /*
+ * Test hooks of SIRT / OS-SART.  Host code, no device: forward_pixel and
+ * volume_update_voxel -- the functions k_forward_project and k_volume_update
+ * call, compiled for the host -- over whole host buffers, and xrt_sirt's
+ * algorithm over them and xrt_host_backproject.  Arguments and checks as the
+ * host forms'.
+ */
+int xrt_host_forward_project(uint32_t width, uint32_t height, uint32_t num_planes, const float* volume,
+                             const uint32_t dims[3], const float spacing[3], const double* rays, int mode,
+                             const float* meas, float* out);
+int xrt_host_volume_update(uint64_t n, float* x, const float* corr, const float* norm, double relax, float lo, float hi);
+int xrt_host_sirt(uint32_t width, uint32_t height, uint32_t num_planes, const float* proj, const double* matrices,
+                  const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets, double relax,
+                  float lo, float hi, float* volume);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -20,7 +20,7 @@ import numpy as np
 from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
-                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_MAX_SOURCES, XRT_MAX_BIN, XRT_MAX_RAMP_WIDTH, XRT_RAMP_RAMLAK, XRT_RAMP_HANN, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
+                   XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_MAX_SOURCES, XRT_MAX_BIN, XRT_MAX_RAMP_WIDTH, XRT_RAMP_RAMLAK, XRT_RAMP_HANN, XRT_FP_PROJECT, XRT_FP_RESIDUAL, XRT_MAX_SUBSETS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
 
 __all__ = [
@@ -38,6 +38,8 @@ __all__ = [
     "XRT_MAX_SOURCES", "XRT_MAX_BIN", "supersampled_camera", "focal_spot", "host_area_integrate", "area_integrate",
     "ray_table_index", "XRT_MAX_RAMP_WIDTH", "XRT_RAMP_RAMLAK", "XRT_RAMP_HANN", "ramp_filter", "fdk_weights",
     "fdk_scale", "backprojection_matrix", "save_volume", "host_fdk_filter", "host_backproject",
+    "XRT_FP_PROJECT", "XRT_FP_RESIDUAL", "XRT_MAX_SUBSETS", "ray_matrix", "host_forward_project", "host_volume_update",
+    "host_sirt",
 ]
 
 
@@ -656,6 +658,91 @@ def host_backproject(proj, matrices, dims, scale=1.0, slabs=None, volume=None, a
     return vol
 
 
+def ray_matrix(A) -> np.ndarray:
+    """The (3, 4) f64 ray matrix R = [A3^-1 | -A3^-1 a4] of a backprojection matrix A = [A3 | a4]: column 3 is the
+    source in centre-index coordinates and pixel (row, col)'s ray direction is R[:, 0] * col + (R[:, 1] * row +
+    R[:, 2]) (xrt_ray_matrix)."""
+    a = np.ascontiguousarray(A, dtype=np.float64).reshape(12)
+    out = np.empty(12, np.float64)
+    rc = _abi.load().xrt_ray_matrix(_dptr(a), _dptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_ray_matrix: the matrix must be finite and its left 3 x 3 block invertible")
+    return out.reshape(3, 4)
+
+
+def _forward_arrays(volume, spacing, rays, mode, meas, shape):
+    """xrt_forward_project's arguments: (volume, dims u32[3], spacing f32[3], rays (P, 12) f64, meas or None, P, H,
+    W); shape = (H, W) of a plane."""
+    v = np.ascontiguousarray(volume, dtype=np.float32)
+    if v.ndim != 3:
+        raise ValueError(f"a volume is (nz, ny, nx), got shape {v.shape}")
+    d = np.array(v.shape[::-1], np.uint32)
+    spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+    r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 12)
+    p = r.shape[0]
+    if meas is not None:
+        meas, mp, h, w = _lsf_planes(meas)
+        if mp != p:
+            raise ValueError(f"{p} ray matrices need {p} measured planes, got {mp}")
+    else:
+        if mode == _abi.XRT_FP_RESIDUAL:
+            raise ValueError("the residual mode needs meas")
+        h, w = (int(x) for x in shape)
+    return v, d, spc, r, meas, p, h, w
+
+
+def host_forward_project(volume, spacing, rays, shape=None, mode=_abi.XRT_FP_PROJECT, meas=None) -> np.ndarray:
+    """Context.forward_project in the device's arithmetic on the host (xrt_host_forward_project, a test hook)."""
+    v, d, spc, r, m, p, h, w = _forward_arrays(volume, spacing, rays, mode, meas, shape)
+    out = np.empty((p, h, w), np.float32)
+    rc = _abi.load().xrt_host_forward_project(w, h, p, _fptr(v), _u32ptr(d), _fptr(spc), _dptr(r), int(mode),
+                                              _fptr(m) if m is not None else None, _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_forward_project")
+    return out
+
+
+def _update_arrays(x, corr, norm):
+    x = np.array(x, dtype=np.float32, order="C")
+    c, n = np.ascontiguousarray(corr, dtype=np.float32), np.ascontiguousarray(norm, dtype=np.float32)
+    if c.shape != x.shape or n.shape != x.shape:
+        raise ValueError(f"x, corr and norm must share a shape, got {x.shape}, {c.shape}, {n.shape}")
+    return x, c, n
+
+
+def host_volume_update(x, corr, norm, relax=1.0, lo=-np.inf, hi=np.inf) -> np.ndarray:
+    """Context.volume_update on the host (xrt_host_volume_update, a test hook): the updated copy of x."""
+    x, c, n = _update_arrays(x, corr, norm)
+    rc = _abi.load().xrt_host_volume_update(x.size, _fptr(x), _fptr(c), _fptr(n), float(relax), float(lo), float(hi))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_volume_update")
+    return x
+
+
+def _sirt_arrays(proj, matrices, dims, spacing, start):
+    a, p, h, w = _lsf_planes(proj)
+    m = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 12)
+    if m.shape[0] != p:
+        raise ValueError(f"{p} projections need {p} matrices, got {m.shape[0]}")
+    d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+    spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+    shape = (int(d[2]), int(d[1]), int(d[0]))
+    vol = np.zeros(shape, np.float32) if start is None else np.array(start, dtype=np.float32, order="C")
+    if vol.shape != shape:
+        raise ValueError(f"the start must have shape {shape}, got {vol.shape}")
+    return a, m, d, spc, vol, p, h, w
+
+
+def host_sirt(proj, matrices, dims, spacing, iterations, subsets=1, relax=1.0, lo=0.0, hi=np.inf, start=None) -> np.ndarray:
+    """Context.sirt_matrices in the device's arithmetic on the host (xrt_host_sirt, a test hook)."""
+    a, m, d, spc, vol, p, h, w = _sirt_arrays(proj, matrices, dims, spacing, start)
+    rc = _abi.load().xrt_host_sirt(w, h, p, _fptr(a), _dptr(m), _u32ptr(d), _fptr(spc), int(iterations), int(subsets),
+                                   float(relax), float(lo), float(hi), _fptr(vol))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_sirt")
+    return vol
+
+
 class Context:
     """One xrt_context (one device).  Not thread-safe."""
 
@@ -976,6 +1063,78 @@ class Context:
             filtered = np.stack([self.fdk_filter(a.reshape(p, h, w)[i], taps, fdk_weights(c))
                                  for i, c in enumerate(cams)])
         return self.backproject(filtered.reshape(p, h, w), mats, dims, fdk_scale(cams[0], axis_point, p))
+
+    def forward_project(self, volume, spacing, rays, shape=None, mode=_abi.XRT_FP_PROJECT, meas=None) -> np.ndarray:
+        """The line integrals of a (nz, ny, nx) f32 volume of voxels of `spacing` along the rays of P (3, 4) f64 ray
+        matrices (ray_matrix), one (H, W) = `shape` plane each: (P, H, W) f32.  mode XRT_FP_RESIDUAL: (meas -
+        integral) / the ray's length inside the grid, with `meas` a (P, H, W) stack that gives the shape."""
+        v, d, spc, r, m, p, h, w = _forward_arrays(volume, spacing, rays, mode, meas, shape)
+        out = np.empty((p, h, w), np.float32)
+        self._check(self._lib.xrt_forward_project(self._ctx, w, h, p, _fptr(v), _u32ptr(d), _fptr(spc), _dptr(r), int(mode),
+                                                  _fptr(m) if m is not None else None, _fptr(out)), "xrt_forward_project")
+        return out
+
+    def forward_project_device(self, width: int, height: int, num_planes: int, d_volume: int, dims, spacing,
+                               d_rays: int, d_out: int, mode: int = _abi.XRT_FP_PROJECT, d_meas: int = 0,
+                               stream: int = 0):
+        """forward_project over device buffers (raw pointers: the f32 volume, f64 ray matrices, f32 planes);
+        asynchronous on `stream`."""
+        d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+        spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+        rc = self._lib.xrt_forward_project_device(self._ctx, int(width), int(height), int(num_planes), d_volume or None,
+                                                  _u32ptr(d), _fptr(spc), d_rays or None, int(mode), d_meas or None,
+                                                  d_out or None, stream or None)
+        self._check(rc, "xrt_forward_project_device")
+
+    def volume_update(self, x, corr, norm, relax=1.0, lo=-np.inf, hi=np.inf) -> np.ndarray:
+        """x + relax * corr / norm where norm > 0, clamped to [lo, hi]; elsewhere x: the updated copy of x."""
+        x, c, n = _update_arrays(x, corr, norm)
+        self._check(self._lib.xrt_volume_update(self._ctx, x.size, _fptr(x), _fptr(c), _fptr(n), float(relax), float(lo),
+                                                float(hi)), "xrt_volume_update")
+        return x
+
+    def volume_update_device(self, n: int, d_x: int, d_corr: int, d_norm: int, relax: float = 1.0, lo: float = -np.inf,
+                             hi: float = np.inf, stream: int = 0):
+        """volume_update over device buffers (raw pointers), in place in d_x; asynchronous on `stream`."""
+        rc = self._lib.xrt_volume_update_device(self._ctx, int(n), d_x or None, d_corr or None, d_norm or None,
+                                                float(relax), float(lo), float(hi), stream or None)
+        self._check(rc, "xrt_volume_update_device")
+
+    def sirt_matrices(self, projections, matrices, dims, spacing, iterations: int, subsets: int = 1, relax: float = 1.0,
+                      lo: float = 0.0, hi: float = np.inf, start=None) -> np.ndarray:
+        """sirt under P given (3, 4) f64 backprojection matrices in place of cameras and poses."""
+        a, m, d, spc, vol, p, h, w = _sirt_arrays(projections, matrices, dims, spacing, start)
+        self._check(self._lib.xrt_sirt(self._ctx, w, h, p, _fptr(a), _dptr(m), _u32ptr(d), _fptr(spc), int(iterations),
+                                       int(subsets), float(relax), float(lo), float(hi), _fptr(vol)), "xrt_sirt")
+        return vol
+
+    def sirt(self, projections, camera: Camera, poses, dims, origin, spacing, iterations: int, subsets: int = 1,
+             relax: float = 1.0, lo: float = 0.0, hi: float = np.inf, start=None) -> np.ndarray:
+        """SIRT (subsets = 1) or OS-SART (subsets > 1; subset s holds the projections p with p mod subsets == s) of
+        the (P, H, W) line integrals `projections`, taken by `camera` -- one Camera, or P of them -- of an object
+        under `poses` (P poses, or None: at rest), into the grid of dims = (nx, ny, nz) voxels of `spacing` with its
+        minimum corner at `origin`: `iterations` passes over every subset from `start` (None: zeros), each update
+        relaxed by `relax` and clamped to [lo, hi].  (nz, ny, nx) f32."""
+        a, p, h, w = _lsf_planes(projections)
+        cams = [camera] * p if isinstance(camera, Camera) else list(camera)
+        poses = [None] * p if poses is None else list(poses)
+        if len(cams) != p or len(poses) != p:
+            raise ValueError(f"{p} projections need one camera or {p}, and {p} poses or None")
+        mats = np.stack([backprojection_matrix(c, origin, spacing, q) for c, q in zip(cams, poses)])
+        return self.sirt_matrices(a, mats, dims, spacing, iterations, subsets, relax, lo, hi, start)
+
+    def sirt_device(self, width: int, height: int, num_planes: int, d_proj: int, matrices, dims, spacing,
+                    iterations: int, d_volume: int, subsets: int = 1, relax: float = 1.0, lo: float = 0.0,
+                    hi: float = np.inf, stream: int = 0):
+        """sirt over device buffers (raw pointers: the f32 projections and the f32 volume, start and result);
+        `matrices` is a host (P, 12) f64 array.  Asynchronous on `stream`."""
+        m = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 12)
+        d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+        spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+        rc = self._lib.xrt_sirt_device(self._ctx, int(width), int(height), int(num_planes), d_proj or None, _dptr(m),
+                                       _u32ptr(d), _fptr(spc), int(iterations), int(subsets), float(relax), float(lo),
+                                       float(hi), d_volume or None, stream or None)
+        self._check(rc, "xrt_sirt_device")
 
     def detector_response(self, image, lsf_x, lsf_y=None, out=True, u8=True):
         """The detector's line-spread function over an (H, W) image or a (P, H, W) stack of them (taps as

@@ -18,6 +18,7 @@ XRT_ERR_NO_MESH = 3
 XRT_ERR_OVERFLOW = 4
 XRT_ERR_IO = 5
 XRT_ERR_FORMAT = 6
+XRT_ERR_MEMORY = 7
 
 XRT_KERNEL_AUTO = 0
 XRT_KERNEL_BRUTE = 1
@@ -56,6 +57,9 @@ XRT_MAX_BIN = 8
 XRT_MAX_RAMP_WIDTH = 4096
 XRT_RAMP_RAMLAK = 0
 XRT_RAMP_HANN = 1
+XRT_FP_PROJECT = 0
+XRT_FP_RESIDUAL = 1
+XRT_MAX_SUBSETS = 64
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -231,6 +235,18 @@ XRT_SYMBOLS = {
     "xrt_host_fdk_filter": (ctypes.c_int, [_u32, _u32, _u32, _fp, _fp, _fp, _u32, _fp]),
     "xrt_host_backproject": (ctypes.c_int, [_u32, _u32, _u32, _fp, _dp, _u32p, _u32, _u32, ctypes.c_double, ctypes.c_int,
                                             _fp]),
+    "xrt_ray_matrix": (ctypes.c_int, [_dp, _dp]),
+    "xrt_forward_project": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _u32p, _fp, _dp, ctypes.c_int, _fp, _fp]),
+    "xrt_forward_project_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _u32p, _fp, _vp, ctypes.c_int, _vp, _vp,
+                                                  _vp]),
+    "xrt_volume_update": (ctypes.c_int, [_CtxP, _u64, _fp, _fp, _fp, ctypes.c_double, _f, _f]),
+    "xrt_volume_update_device": (ctypes.c_int, [_CtxP, _u64, _vp, _vp, _vp, ctypes.c_double, _f, _f, _vp]),
+    "xrt_sirt": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f, _fp]),
+    "xrt_sirt_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f,
+                                       _vp, _vp]),
+    "xrt_host_forward_project": (ctypes.c_int, [_u32, _u32, _u32, _fp, _u32p, _fp, _dp, ctypes.c_int, _fp, _fp]),
+    "xrt_host_volume_update": (ctypes.c_int, [_u64, _fp, _fp, _fp, ctypes.c_double, _f, _f]),
+    "xrt_host_sirt": (ctypes.c_int, [_u32, _u32, _u32, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f, _fp]),
     "xrt_host_philox4x32": (None, [_u32p, _u32p, _u32p]),
     "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
     "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),

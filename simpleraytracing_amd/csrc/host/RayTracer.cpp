@@ -605,6 +605,68 @@ void reconstructFDK(std::vector<float>& volume, const std::vector<float>& projec
 
 namespace {
 
+// The backprojection matrices of a scan: one per pose, or one at rest.
+std::vector<double> scan_matrices(const char* who, const xrt_camera& cam, const std::vector<std::array<float, 12>>& poses,
+                                  unsigned count, const float origin[3], const float spacing[3])
+{
+    std::vector<double> matrices((size_t)count * 12u);
+    for (unsigned p = 0; p < count; ++p)
+        if (xrt_backprojection_matrix(&cam, poses.empty() ? nullptr : poses[p].data(), origin, spacing,
+                                      matrices.data() + 12u * p) != XRT_OK)
+            throw std::runtime_error(std::string(who) + ": the camera's axes are not independent, or the grid is not finite");
+    return matrices;
+}
+
+}  // namespace
+
+void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& projections, unsigned num_projections,
+                     const Image& frame, const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                     const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                     const float spacing[3], unsigned iterations, unsigned subsets, double relax, float lo, float hi)
+{
+    const unsigned W = frame.getWidth(), H = frame.getHeight();
+    if (num_projections == 0 || projections.size() != (size_t)W * H * num_projections)
+        throw std::runtime_error("reconstructSIRT: the stack does not hold num_projections images");
+    if (!poses.empty() && poses.size() != num_projections)
+        throw std::runtime_error("reconstructSIRT: one pose per projection, or none");
+    const xrt_camera cam = camera_for(frame, meshes, info);
+    const std::vector<double> matrices = scan_matrices("reconstructSIRT", cam, poses, num_projections, origin, spacing);
+    const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
+    if (volume.size() != voxels) volume.assign(voxels, 0.0f);
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    check(ctx, xrt_sirt(ctx, W, H, num_projections, projections.data(), matrices.data(), dims, spacing, iterations, subsets,
+                        relax, lo, hi, volume.data()),
+          "xrt_sirt");
+}
+
+void forwardProject(std::vector<float>& projections, const std::vector<float>& volume, const Image& frame,
+                    const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                    const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                    const float spacing[3])
+{
+    const unsigned W = frame.getWidth(), H = frame.getHeight();
+    const unsigned count = poses.empty() ? 1u : (unsigned)poses.size();
+    if (volume.size() != (size_t)dims[0] * dims[1] * dims[2])
+        throw std::runtime_error("forwardProject: the volume does not hold dims[0] * dims[1] * dims[2] values");
+    const xrt_camera cam = camera_for(frame, meshes, info);
+    const std::vector<double> matrices = scan_matrices("forwardProject", cam, poses, count, origin, spacing);
+    std::vector<double> rays(matrices.size());
+    for (unsigned p = 0; p < count; ++p)
+        if (xrt_ray_matrix(matrices.data() + 12u * p, rays.data() + 12u * p) != XRT_OK)
+            throw std::runtime_error("forwardProject: a projection's matrix has no ray matrix");
+    projections.assign((size_t)W * H * count, 0.0f);
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    check(ctx, xrt_forward_project(ctx, W, H, count, volume.data(), dims, spacing, rays.data(), XRT_FP_PROJECT, nullptr,
+                                   projections.data()),
+          "xrt_forward_project");
+}
+
+namespace {
+
 // One multi-device context per device list for the process lifetime: the
 // devices 0 .. num_gpus-1, or $XRT_MULTI_DEVICES ("0,0" ...; a device listed
 // twice rehearses the strip path on one GPU).  Guarded by multi_lock().

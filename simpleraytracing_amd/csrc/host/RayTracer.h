@@ -11,6 +11,7 @@
 #pragma once
 
 #include <array>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -207,6 +208,28 @@ void reconstructFDK(std::vector<float>& volume, const std::vector<float>& projec
                     const Image& frame, const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
                     const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
                     const float spacing[3], const float axis_point[3], int window = 0);
+
+// SIRT / OS-SART (xrt_sirt) of the same scan into the same grid,
+// arguments as reconstructFDK's: `iterations` passes over `subsets` subsets
+// (1: SIRT; subset s holds the projections p with p mod subsets == s), every
+// update relaxed by `relax` and clamped to [lo, hi], from `volume` when it
+// holds the grid's dims[0] * dims[1] * dims[2] values, else from zeros.  No
+// axis is needed: any poses do.  One device.
+void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& projections, unsigned num_projections,
+                     const Image& frame, const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                     const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                     const float spacing[3], unsigned iterations, unsigned subsets = 1, double relax = 1.0, float lo = 0.0f,
+                     float hi = std::numeric_limits<float>::infinity());
+
+// The line integrals of a f32 volume (dims[0] * dims[1] * dims[2] values, x
+// fastest, the grid of reconstructFDK) along the rays of the camera of `info`
+// under every pose (empty: one projection at rest): xrt_forward_project under
+// the ray matrices of xrt_backprojection_matrix's matrices.  `projections`
+// receives poses.size() (or 1) images of frame's size one after another.
+void forwardProject(std::vector<float>& projections, const std::vector<float>& volume, const Image& frame,
+                    const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                    const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                    const float spacing[3]);
 
 // Area sampling (xrt_area_integrate).  focalSpotSources: the
 // sub-sources of a uniform rectangular focal spot of size_u x size_v (the

@@ -63,6 +63,12 @@
 //                              every mesh about an axis parallel to the detector's up (--turntable N:z):
 //                              another axis is refused once the meshes are loaded and the
 //                              camera is known, before a projection is rendered.
+//       --sirt K[:S[:RELAX]]   with --reconstruct: reconstruct by K iterations of SIRT (S = 1,
+//                              the default) or OS-SART over S subsets (1 to 64, at most the
+//                              projections; subset s holds the projections p with p mod S
+//                              == s) instead of FDK, from zeros, every update relaxed by
+//                              RELAX (default 1) and kept >= 0.  The same cube and the same
+//                              refusals as FDK's.
 //       --sinogram FILE        with --turntable N and --log-projection: also write the N
 //                              projections' line integrals as one sinogram per detector
 //                              row, raw little-endian f32 in (height, N, width) order
@@ -142,6 +148,7 @@
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -176,6 +183,7 @@ void showUsage(const std::string& prog)
               << "\t--log-projection I0\t\tLine integrals: write -ln(I / I0) (I0 finite and > 0; after --lsf) instead of the intensity I; --u8 and --lbuffer stay as rendered\n"
               << "\t--sinogram FILE\t\t\tWith --turntable N and --log-projection: also write the line integrals as raw float32 sinograms, (height, N, width)\n"
               << "\t--reconstruct FILE.mhd[:N]\tWith --turntable N:z (every mesh, about the detector's up) and --log-projection: reconstruct the scan by FDK into an N^3 grid (default 128) about the turntable's centre, its side the scene box's diagonal; writes FILE.mhd (MET_FLOAT) and FILE.raw\n"
+              << "\t--sirt K[:S[:RELAX]]\t\tWith --reconstruct: K iterations of SIRT (S = 1) or OS-SART over S subsets (1 to 64) instead of FDK, from zeros, relaxed by RELAX (default 1), kept >= 0\n"
               << "\t--noise GAIN[:SEED]\t\tPhoton noise on the written image: each pixel a Poisson count of mean I * GAIN, divided by GAIN (after --lsf, before --log-projection; SEED defaults to 0); --u8 and --lbuffer stay as rendered\n"
               << "\t--supersample B\t\t\tPixel-area integration: render W*B x H*B samples (B in 1..8) and write each pixel's mean over its B x B samples; -s stays the written size\n"
               << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
@@ -218,6 +226,9 @@ struct Options {
     std::string sinogram;                      // --sinogram FILE
     std::string reconstruct;                   // --reconstruct FILE.mhd[:N]
     unsigned reconstruct_n = 128;              // N: the grid is N x N x N
+    unsigned sirt_iterations = 0;              // --sirt K[:S[:RELAX]] (0: FDK)
+    unsigned sirt_subsets = 1;
+    double sirt_relax = 1.0;
     bool noise = false;                        // --noise GAIN[:SEED]
     float noise_gain = 0.0f;
     unsigned long long noise_seed = 0;
@@ -615,6 +626,22 @@ Options processCmd(int argc, char** argv)
                 (parts.size() == 2 && (!parse_index(parts[1], o.reconstruct_n) || o.reconstruct_n < 1 || o.reconstruct_n > 2048)))
                 throw std::runtime_error("--reconstruct FILE.mhd[:N]: a MetaImage header's name and a grid size of 1 to 2048");
             o.reconstruct = parts[0];
+        } else if (a == "--sirt") {
+            const std::vector<std::string> parts = split(parse_str(argv[0], argc, argv, i), ':');
+            bool ok = parts.size() >= 1 && parts.size() <= 3 && parse_index(parts[0], o.sirt_iterations) && o.sirt_iterations >= 1;
+            if (ok && parts.size() >= 2)
+                ok = parse_index(parts[1], o.sirt_subsets) && o.sirt_subsets >= 1 && o.sirt_subsets <= XRT_MAX_SUBSETS;
+            if (ok && parts.size() == 3) {
+                size_t used = 0;
+                try {
+                    o.sirt_relax = std::stod(parts[2], &used);
+                } catch (const std::exception&) {
+                    used = 0;
+                }
+                ok = !parts[2].empty() && used == parts[2].size() && std::isfinite(o.sirt_relax);
+            }
+            if (!ok)
+                throw std::runtime_error("--sirt K[:S[:RELAX]]: K iterations (>= 1), S subsets (1 to 64), RELAX a finite number");
         } else if (a == "--noise") {
             parse_noise(parse_str(argv[0], argc, argv, i), o);
         } else if (a == "--supersample") {
@@ -703,6 +730,10 @@ Options processCmd(int argc, char** argv)
         throw std::runtime_error("--reconstruct needs --turntable N and --log-projection I0: it reconstructs a scan's line integrals");
     if (!o.reconstruct.empty() && !o.turn_meshes.empty())
         throw std::runtime_error("--reconstruct needs a --turntable that turns every mesh: the scene is reconstructed as one object");
+    if (o.sirt_iterations && o.reconstruct.empty())
+        throw std::runtime_error("--sirt needs --reconstruct FILE.mhd: it chooses how the scan is reconstructed");
+    if (o.sirt_iterations && o.sirt_subsets > o.turntable)
+        throw std::runtime_error("--sirt K[:S[:RELAX]]: more subsets than projections");
     if (o.log_projection && (o.gpus > 1 || o.rows))
         throw std::runtime_error("--log-projection needs whole frames on one GPU: not with -g N or --rows");
     if (o.log_projection && o.paths && !o.spectrum)
@@ -1006,7 +1037,12 @@ int main(int argc, char** argv)
                 origin[k] = (float)((double)centre[k] - diagonal / 2.0);
             }
             std::vector<float> reconstruction;
-            reconstructFDK(reconstruction, integrals, opt.turntable, image, meshes, info, turns, dims, origin, spacing, centre);
+            if (opt.sirt_iterations)
+                reconstructSIRT(reconstruction, integrals, opt.turntable, image, meshes, info, turns, dims, origin, spacing,
+                                opt.sirt_iterations, opt.sirt_subsets, opt.sirt_relax, 0.0f,
+                                std::numeric_limits<float>::infinity());
+            else
+                reconstructFDK(reconstruction, integrals, opt.turntable, image, meshes, info, turns, dims, origin, spacing, centre);
             try {
                 saveVolume(opt.reconstruct, dims, origin, spacing, reconstruction.data());
             } catch (const VolumeError& e) {

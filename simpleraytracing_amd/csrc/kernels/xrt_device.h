@@ -1635,4 +1635,117 @@ __host__ __device__ __forceinline__ float backproject_output(double acc, double 
     return accumulate ? (float)((double)old + acc * scale) : (float)(acc * scale);
 }
 
+// ---------------------------------------------------------------------------
+// SIRT / OS-SART: the forward projector of a f32 volume under
+// the backprojector's matrices, and the voxel update.  forward_ray is the
+// contract: k_forward_project calls it on the device and
+// xrt_host_forward_project compiled for the host, and tests/sirt_ref.py
+// restates it.  volume_ray's rules (f64, no FMA, written selects, planes from
+// the index every time) over the grid lo = -0.5, s = 1 of centre-index
+// coordinates; no labels, no runs.
+// ---------------------------------------------------------------------------
+constexpr int kForwardProject = 0;                  // XRT_FP_PROJECT
+constexpr int kForwardResidual = 1;                 // XRT_FP_RESIDUAL
+
+// One component of pixel (row, col)'s ray direction under the ray matrix R
+// (xrt_ray_matrix), Ra = that line's four entries; Ra[3] is the source's.
+__host__ __device__ __forceinline__ double forward_direction(const double* Ra, double row, double col)
+{
+    return Ra[0] * col + (Ra[1] * row + Ra[2]);
+}
+
+// The ray O + t d, t > 0, through the grid of n voxels (voxel i occupies
+// [i - 0.5, i + 0.5]): false for a miss; else acc = the sum over the steps
+// with seg > 0 of seg * vol[voxel], in ray order, and span = tx - te, both in
+// units of t.  At most nx + ny + nz + 3 steps.  Only the stepped axis' tnext
+// is formed again after a step: the others' indices have not changed, so
+// their values would be the same.
+__host__ __device__ __forceinline__ bool forward_ray(const float* __restrict__ vol, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                     double Ox, double Oy, double Oz, double dx, double dy, double dz,
+                                                     double& acc, double& span)
+{
+    const double inf = __builtin_huge_val();
+    const double lo = -0.5, s = 1.0;
+    double te = 0.0, tx = inf, ivx, ivy, ivz;
+    if (!volume_slab(Ox, dx, volume_plane(lo, s, 0u), volume_plane(lo, s, nx), ivx, te, tx)) return false;
+    if (!volume_slab(Oy, dy, volume_plane(lo, s, 0u), volume_plane(lo, s, ny), ivy, te, tx)) return false;
+    if (!volume_slab(Oz, dz, volume_plane(lo, s, 0u), volume_plane(lo, s, nz), ivz, te, tx)) return false;
+    if (!(te < tx)) return false;
+    int32_t ix = volume_start(Ox, te, dx, lo, s, nx);
+    int32_t iy = volume_start(Oy, te, dy, lo, s, ny);
+    int32_t iz = volume_start(Oz, te, dz, lo, s, nz);
+    const int32_t stx = dx > 0.0 ? 1 : -1, sty = dy > 0.0 ? 1 : -1, stz = dz > 0.0 ? 1 : -1;
+    const int32_t upx = dx > 0.0 ? 1 : 0, upy = dy > 0.0 ? 1 : 0, upz = dz > 0.0 ? 1 : 0;
+    double tnx = dx == 0.0 ? inf : (volume_plane(lo, s, (uint32_t)(ix + upx)) - Ox) * ivx;
+    double tny = dy == 0.0 ? inf : (volume_plane(lo, s, (uint32_t)(iy + upy)) - Oy) * ivy;
+    double tnz = dz == 0.0 ? inf : (volume_plane(lo, s, (uint32_t)(iz + upz)) - Oz) * ivz;
+    double tc = te, sum = 0.0;
+    const uint32_t limit = nx + ny + nz + 3u;
+    for (uint32_t k = 0; k < limit; ++k) {
+        double t = tnx;                 // ties: the lower axis first
+        int32_t a = 0;
+        if (tny < t) { t = tny; a = 1; }
+        if (tnz < t) { t = tnz; a = 2; }
+        const double tend = t < tx ? t : tx;
+        const double seg = tend - tc;
+        const uint64_t vox = ((uint64_t)(uint32_t)iz * ny + (uint32_t)iy) * nx + (uint32_t)ix;
+        if (seg > 0.0) {
+            sum = sum + seg * (double)vol[vox];
+            tc = tend;
+        }
+        if (!(t < tx)) break;
+        if (a == 0) {
+            ix += stx;
+            if ((uint32_t)ix >= nx) break;
+            tnx = (volume_plane(lo, s, (uint32_t)(ix + upx)) - Ox) * ivx;
+        } else if (a == 1) {
+            iy += sty;
+            if ((uint32_t)iy >= ny) break;
+            tny = (volume_plane(lo, s, (uint32_t)(iy + upy)) - Oy) * ivy;
+        } else {
+            iz += stz;
+            if ((uint32_t)iz >= nz) break;
+            tnz = (volume_plane(lo, s, (uint32_t)(iz + upz)) - Oz) * ivz;
+        }
+    }
+    acc = sum;
+    span = tx - te;
+    return true;
+}
+
+// The length of the direction in the scene's unit: what a step of 1 in t is worth.
+__host__ __device__ __forceinline__ double forward_ell(double sx, double sy, double sz, double dx, double dy, double dz)
+{
+    return ::sqrt(((sx * dx) * (sx * dx) + (sy * dy) * (sy * dy)) + (sz * dz) * (sz * dz));
+}
+
+// A pixel of xrt_forward_project: the ray of (row, col) under R through the
+// volume, as the mode has it (meas: the pixel's measurement, read by the
+// residual mode only).
+__host__ __device__ __forceinline__ float forward_pixel(const float* __restrict__ vol, uint32_t nx, uint32_t ny,
+                                                        uint32_t nz, double sx, double sy, double sz, const double* R,
+                                                        uint32_t row, uint32_t col, int mode, float meas)
+{
+    const double dr = (double)row, dc = (double)col;
+    const double dx = forward_direction(R, dr, dc), dy = forward_direction(R + 4, dr, dc),
+                 dz = forward_direction(R + 8, dr, dc);
+    double acc, span;
+    if (!forward_ray(vol, nx, ny, nz, R[3], R[7], R[11], dx, dy, dz, acc, span)) return 0.0f;
+    const double ell = forward_ell(sx, sy, sz, dx, dy, dz);
+    if (mode == kForwardProject) return (float)(acc * ell);
+    const double L = span * ell;
+    return L > 0.0 ? (float)(((double)meas - acc * ell) / L) : 0.0f;
+}
+
+// A voxel of xrt_volume_update.
+__host__ __device__ __forceinline__ float volume_update_voxel(float x, float corr, float norm, double relax, float lo,
+                                                              float hi)
+{
+    if (!(norm > 0.0f)) return x;
+    float v = (float)((double)x + relax * ((double)corr / (double)norm));
+    v = v < lo ? lo : v;
+    v = v > hi ? hi : v;
+    return v;
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -4666,4 +4666,54 @@ __global__ __launch_bounds__(kBackprojectThreads) void k_backproject(const float
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_forward_project: the forward projector of a f32 volume under ray matrices
+// (DESIGN 10.12).  One lane a pixel, one single-wave workgroup an 8x8 pixel
+// tile of one plane (blockIdx.y), as k_volume_paths tiles its rays:
+// neighbouring rays walk the same voxels.  The plane's R is read through a
+// wave-uniform address -- scalar loads --, each lane forms its direction and
+// runs forward_pixel.  A lane outside the plane leaves at once (no barrier).
+// Plane p's measurement lies at meas + p * meas_stride: the solver's subsets
+// read the scan's planes where they are.  Offsets are 64-bit.  No LDS, no
+// scratch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kForwardTile = 8;
+
+__global__ __launch_bounds__(64) void k_forward_project(const float* __restrict__ vol, const double* __restrict__ rays,
+                                                        const float* __restrict__ meas, uint64_t meas_stride,
+                                                        float* __restrict__ out, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                        double sx, double sy, double sz, uint32_t width, uint32_t height,
+                                                        uint32_t tiles_x, int mode)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const uint32_t col = tile_x * kForwardTile + (lane & (kForwardTile - 1u));
+    const uint32_t row = tile_y * kForwardTile + lane / kForwardTile;
+    if (col >= width || row >= height) return;
+    const uint64_t p = blockIdx.y;
+    const double* R = rays + p * 12u;
+    const uint64_t pix = (uint64_t)row * width + col;
+    const float m = mode == kForwardResidual ? meas[p * meas_stride + pix] : 0.0f;
+    out[p * ((uint64_t)width * height) + pix] = forward_pixel(vol, nx, ny, nz, sx, sy, sz, R, row, col, mode, m);
+}
+
+// ---------------------------------------------------------------------------
+// k_volume_update: x = clamp(x + relax * corr / norm) where norm > 0, a lane a
+// voxel, then the voxel a whole grid further on: at most kUpdateBlocks
+// workgroups, so that 2^33 voxels stay within a launch's 2^32 work-items
+// (DESIGN 10.12).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kUpdateThreads = 256;
+constexpr uint32_t kUpdateBlocks = 1u << 14;         // 2^22 voxels a pass: many times the device's resident lanes
+
+__global__ __launch_bounds__(kUpdateThreads) void k_volume_update(uint64_t n, float* __restrict__ x,
+                                                                  const float* __restrict__ corr,
+                                                                  const float* __restrict__ norm, double relax, float lo,
+                                                                  float hi)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kUpdateThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kUpdateThreads + threadIdx.x; i < n; i += stride)
+        x[i] = volume_update_voxel(x[i], corr[i], norm[i], relax, lo, hi);
+}
+
 }  // namespace XRT_KERNEL_NS

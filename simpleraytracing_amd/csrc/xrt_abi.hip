@@ -547,6 +547,18 @@ struct xrt_context {
     bool vol_busy = false;
     uint32_t vol_tile_shift = kVolumeTileShift;        // xrt_debug_volume_wave_shape
 
+    // The working set of xrt_sirt[_device]: one allocation
+    // holding the gathered matrices (A then R, f64), the residual planes of
+    // the largest subset, the correction volume and the norm volumes, kept
+    // between calls.  sirt_mats is the upload's source (it must outlive the
+    // copy); sirt_ev marks the last call's end on its stream: the next call
+    // waits for it before it touches either.
+    uint8_t* d_sirt = nullptr;
+    size_t sirt_cap = 0;
+    std::vector<double> sirt_mats;
+    hipEvent_t sirt_ev = nullptr;
+    bool sirt_busy = false;
+
     // Ray table (DESIGN.md "Ray table"): the ray directions of one camera and
     // strip, filled by k_ray_table on the prep stream when an attenuation
     // BINNED frame repeats the previous one's RayKey, and read by
@@ -2218,6 +2230,9 @@ void xrt_destroy(xrt_context* ctx)
     (void)hipFree(const_cast<uint8_t*>(ctx->vol.labels));
     (void)hipFree(const_cast<float*>(ctx->vol.density));
     if (ctx->vol_ev) (void)hipEventDestroy(ctx->vol_ev);
+    if (ctx->sirt_busy) (void)hipEventSynchronize(ctx->sirt_ev);
+    (void)hipFree(ctx->d_sirt);
+    if (ctx->sirt_ev) (void)hipEventDestroy(ctx->sirt_ev);
     for (auto& c : ctx->tchunks) (void)hipFree(c.p);
     lap(1);
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
@@ -3016,6 +3031,190 @@ int xrt_backproject(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t 
                                     accumulate, dvol, ctx->host_stream))
         return rc;
     s.download(volume, dvol, voxels);
+    return s.finish();
+}
+
+// --- SIRT / OS-SART ---------------------------------------------
+
+#include "xrt_sirt_host.inc"
+
+// The launch of k_forward_project (validated arguments, device pointers); plane p's measurement lies at
+// d_meas + p * meas_stride.
+static int launch_forward_project(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                                  const float* d_volume, const uint32_t dims[3], const float spacing[3],
+                                  const double* d_rays, int mode, const float* d_meas, uint64_t meas_stride, float* d_out,
+                                  hipStream_t stream)
+{
+    const uint32_t tiles_x = (width + kForwardTile - 1u) / kForwardTile, tiles_y = (height + kForwardTile - 1u) / kForwardTile;
+    hipLaunchKernelGGL(k_forward_project, dim3(tiles_x * tiles_y, num_planes), dim3(64), 0, stream, d_volume, d_rays, d_meas,
+                       meas_stride, d_out, dims[0], dims[1], dims[2], (double)spacing[0], (double)spacing[1],
+                       (double)spacing[2], width, height, tiles_x, mode);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_forward_project_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                               const float* d_volume, const uint32_t dims[3], const float spacing[3], const double* d_rays,
+                               int mode, const float* d_meas, float* d_out, void* stream)
+{
+    if (const char* why = forward_project_arguments(width, height, num_planes, d_volume, dims, spacing, d_rays, mode, d_meas,
+                                                    d_out, false))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_forward_project(ctx, width, height, num_planes, d_volume, dims, spacing, d_rays, mode, d_meas,
+                                  (uint64_t)width * height, d_out, (hipStream_t)stream);
+}
+
+int xrt_forward_project(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* volume,
+                        const uint32_t dims[3], const float spacing[3], const double* rays, int mode, const float* meas,
+                        float* out)
+{
+    if (const char* why = forward_project_arguments(width, height, num_planes, volume, dims, spacing, rays, mode, meas, out,
+                                                    true))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t all = (size_t)width * height * num_planes;
+    DeviceScratch s(ctx, ctx->host_stream, "forward projection");
+    const float* dvol = s.upload(volume, (size_t)dims[0] * dims[1] * dims[2]);
+    const double* drays = s.upload(rays, (size_t)num_planes * 12u);
+    const float* dmeas = mode == XRT_FP_RESIDUAL ? s.upload(meas, all) : nullptr;
+    float* dout = s.alloc<float>(all);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_forward_project(ctx, width, height, num_planes, dvol, dims, spacing, drays, mode, dmeas,
+                                        (uint64_t)width * height, dout, ctx->host_stream))
+        return rc;
+    s.download(out, dout, all);
+    return s.finish();
+}
+
+static int launch_volume_update(xrt_context* ctx, uint64_t n, float* d_x, const float* d_corr, const float* d_norm,
+                                double relax, float lo, float hi, hipStream_t stream)
+{
+    const uint64_t blocks = std::min<uint64_t>((n + kUpdateThreads - 1u) / kUpdateThreads, kUpdateBlocks);
+    hipLaunchKernelGGL(k_volume_update, dim3((unsigned)blocks), dim3(kUpdateThreads), 0, stream, n, d_x, d_corr, d_norm,
+                       relax, lo, hi);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_volume_update_device(xrt_context* ctx, uint64_t n, float* d_x, const float* d_corr, const float* d_norm,
+                             double relax, float lo, float hi, void* stream)
+{
+    if (const char* why = volume_update_arguments(n, d_x, d_corr, d_norm, relax, lo, hi)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_volume_update(ctx, n, d_x, d_corr, d_norm, relax, lo, hi, (hipStream_t)stream);
+}
+
+int xrt_volume_update(xrt_context* ctx, uint64_t n, float* x, const float* corr, const float* norm, double relax, float lo,
+                      float hi)
+{
+    if (const char* why = volume_update_arguments(n, x, corr, norm, relax, lo, hi)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceScratch s(ctx, ctx->host_stream, "volume update");
+    float* dx = s.upload(x, (size_t)n);
+    const float* dcorr = s.upload(corr, (size_t)n);
+    const float* dnorm = s.upload(norm, (size_t)n);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_volume_update(ctx, n, dx, dcorr, dnorm, relax, lo, hi, ctx->host_stream)) return rc;
+    s.download(x, (const float*)dx, (size_t)n);
+    return s.finish();
+}
+
+// xrt_sirt's loop over device buffers on `stream` (validated arguments, a plan whose every matrix has its ray
+// matrix).  The working set lies in the context's d_sirt.
+static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                    SirtPlan& plan, const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets,
+                    double relax, float lo, float hi, float* d_volume, hipStream_t stream)
+{
+    if (ctx->sirt_busy) {                             // the previous call's kernels and upload are done with the set
+        XRT_HIP(ctx, hipEventSynchronize(ctx->sirt_ev));
+        ctx->sirt_busy = false;
+    }
+    const size_t plane = (size_t)width * height, voxels = (size_t)dims[0] * dims[1] * dims[2];
+    const size_t mat_bytes = (size_t)num_planes * 24u * sizeof(double);
+    const size_t bytes = mat_bytes + (plane * plan.widest + voxels * ((size_t)subsets + 1u)) * sizeof(float);
+    if (bytes > ctx->sirt_cap || !ctx->d_sirt) {
+        (void)hipFree(ctx->d_sirt);
+        ctx->d_sirt = nullptr;
+        ctx->sirt_cap = 0;
+        if (hipMalloc((void**)&ctx->d_sirt, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->d_sirt = nullptr;
+            return fail(ctx, XRT_ERR_MEMORY, "the working set of " + std::to_string(bytes) + " bytes cannot be allocated");
+        }
+        ctx->sirt_cap = bytes;
+    }
+    double* dA = reinterpret_cast<double*>(ctx->d_sirt);
+    double* dR = dA + (size_t)num_planes * 12u;
+    float* d_res = reinterpret_cast<float*>(ctx->d_sirt + mat_bytes);
+    float* d_corr = d_res + plane * plan.widest;
+    float* d_norms = d_corr + voxels;
+    ctx->sirt_mats.assign(plan.A.begin(), plan.A.end());
+    ctx->sirt_mats.insert(ctx->sirt_mats.end(), plan.R.begin(), plan.R.end());
+    if (!ctx->sirt_ev) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->sirt_ev, hipEventDisableTiming));
+    XRT_HIP(ctx, hipMemcpyAsync(dA, ctx->sirt_mats.data(), mat_bytes, hipMemcpyHostToDevice, stream));
+    ctx->sirt_busy = true;                            // from here on the set is in use until sirt_ev
+    int rc = XRT_OK;
+    // N_s: the backprojection of all-ones planes (1.0f's bits, word by word)
+    if (hipMemsetD32Async((hipDeviceptr_t)d_res, 0x3F800000, plane * plan.widest, stream) != hipSuccess)
+        rc = fail(ctx, XRT_ERR_DEVICE, "SIRT: filling the planes of ones failed");
+    for (uint32_t s = 0; s < subsets && !rc; ++s)
+        rc = launch_backproject(ctx, width, height, plan.count[s], d_res, dA + (size_t)plan.first[s] * 12u, dims, 0, dims[2],
+                                1.0, 0, d_norms + voxels * s, stream);
+    for (uint32_t k = 0; k < iterations && !rc; ++k)
+        for (uint32_t s = 0; s < subsets && !rc; ++s) {
+            // subset s's planes lie `subsets` planes apart in the scan, from plane s
+            rc = launch_forward_project(ctx, width, height, plan.count[s], d_volume, dims, spacing,
+                                        dR + (size_t)plan.first[s] * 12u, XRT_FP_RESIDUAL, d_proj + plane * s,
+                                        (uint64_t)plane * subsets, d_res, stream);
+            if (!rc)
+                rc = launch_backproject(ctx, width, height, plan.count[s], d_res, dA + (size_t)plan.first[s] * 12u, dims, 0,
+                                        dims[2], 1.0, 0, d_corr, stream);
+            if (!rc) rc = launch_volume_update(ctx, voxels, d_volume, d_corr, d_norms + voxels * s, relax, lo, hi, stream);
+        }
+    (void)hipEventRecord(ctx->sirt_ev, stream);
+    return rc;
+}
+
+int xrt_sirt_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                    const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
+                    uint32_t subsets, double relax, float lo, float hi, float* d_volume, void* stream)
+{
+    if (const char* why = sirt_arguments(width, height, num_planes, d_proj, matrices, dims, spacing, iterations, subsets, relax,
+                                         lo, hi, d_volume, false))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    SirtPlan plan;
+    if (!sirt_plan(num_planes, subsets, matrices, plan)) return fail(ctx, XRT_ERR_ARGUMENT, "a matrix has no ray matrix (xrt_ray_matrix)");
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return run_sirt(ctx, width, height, num_planes, d_proj, plan, dims, spacing, iterations, subsets, relax, lo, hi, d_volume,
+                    (hipStream_t)stream);
+}
+
+int xrt_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* proj,
+             const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets,
+             double relax, float lo, float hi, float* volume)
+{
+    if (const char* why = sirt_arguments(width, height, num_planes, proj, matrices, dims, spacing, iterations, subsets, relax,
+                                         lo, hi, volume, true))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    SirtPlan plan;
+    if (!sirt_plan(num_planes, subsets, matrices, plan)) return fail(ctx, XRT_ERR_ARGUMENT, "a matrix has no ray matrix (xrt_ray_matrix)");
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
+    DeviceScratch s(ctx, ctx->host_stream, "SIRT");
+    const float* dproj = s.upload(proj, (size_t)width * height * num_planes);
+    float* dvol = s.upload(volume, voxels);
+    if (s.rc()) return s.rc();
+    if (int rc = run_sirt(ctx, width, height, num_planes, dproj, plan, dims, spacing, iterations, subsets, relax, lo, hi, dvol,
+                          ctx->host_stream))
+        return rc;
+    s.download(volume, (const float*)dvol, voxels);
     return s.finish();
 }
 
