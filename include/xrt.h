@@ -1048,6 +1048,99 @@ int xrt_sirt_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t 
                     const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
                     uint32_t subsets, double relax, float lo, float hi, float* d_volume, void* stream);
 
+/* --- TV-regularised SIRT: a 3-D TV gradient and descent steps -------------- */
+
+/*
+ * A prior beyond the clamp: ASD-POCS without its
+ * host-side adaptation.  After every full SIRT iteration the volume takes a
+ * fixed number of normalised steepest-descent steps on a smoothed isotropic
+ * total variation, their length tied to how far the data step moved the
+ * volume.  Nothing comes back to the host inside the loop: the norms stay in
+ * device memory and the step reads them there.  Like the SIRT entries, none
+ * of these looks at or changes the context's model, scene, poses, frames in
+ * flight or state generation, and there is no xrt_multi_ form.  All
+ * arithmetic is f64, every operation rounded on its own (no FMA), every
+ * select the written one; sqrt and / are IEEE's.
+ *
+ * xrt_tv_gradient[_device].  volume, out: f32 [nz][ny][nx], dims = {nx, ny,
+ * nz} as xrt_forward_project's, each 1..2048; v(i,j,k) = (double)volume[(k *
+ * ny + j) * nx + i]; eps finite and > 0.  Per voxel p = (i, j, k):
+ *   dx(p) = i + 1 < nx ? v(i+1,j,k) - v(p) : +0.0;  dy, dz likewise
+ *   n(p)  = sqrt(((dx * dx + dy * dy) + dz * dz) + eps)
+ *   qx(p) = dx(p) / n(p);  qy(p) = dy(p) / n(p);  qz(p) = dz(p) / n(p)
+ *   bx = i > 0 ? qx(i-1,j,k) : +0.0;  by = j > 0 ? qy(i,j-1,k) : +0.0;  bz = k > 0 ? qz(i,j,k-1) : +0.0
+ *   out(p) = (float)(((bx + by) + bz) - ((qx(p) + qy(p)) + qz(p)))
+ * the exact gradient of TV(x) = sum over p of n(p), with no difference across
+ * the border.  A 1 x 1 x 1 grid gives +0.0; nz = 1 is 2-D TV.
+ * XRT_ERR_ARGUMENT, before the context is looked at, for a NULL volume, dims
+ * or out, a dims[a] outside 1..2048, an eps that is not finite and > 0 and an
+ * out that overlaps the volume.
+ *
+ * xrt_volume_sumsq[_device].  n in 1..2^33; b may be NULL.  e_i = b ?
+ * (double)a[i] - (double)b[i] : (double)a[i], w_i = e_i * e_i, and *out =
+ * reduce(w, n), whose order is part of the contract:
+ *   reduce(w, 1) = w[0]
+ *   reduce(w, m): chunk c covers w[4096 c .. 4096 c + 4095], entries from m on
+ *     being +0.0.  acc_l = +0.0 for l = 0 .. 255; for r = 0 .. 15 in turn
+ *     acc_l = acc_l + w[4096 c + 256 r + l]; then for h = 128, 64, .., 1 in
+ *     turn acc_l = acc_l + acc_(l+h) for l < h.  partial_c = acc_0, and the
+ *     result is reduce(partial, ceil(m / 4096)).
+ * At most three levels; no atomics.  The device form writes one double to
+ * device memory at d_out; the partials live in the context's working set
+ * (below).  XRT_ERR_ARGUMENT, before the context is looked at, for a NULL a or
+ * out, an n of 0 or above 2^33 and an out that overlaps an input.
+ *
+ * xrt_tv_descend[_device].  `steps` times (0: nothing), with the working
+ * set's gradient volume g:
+ *   g = xrt_tv_gradient(volume, eps);  G = xrt_volume_sumsq(g);  gn = sqrt(G)
+ *   where gn > 0 (a NaN compares false):  c = length / gn, and per voxel
+ *     v = (float)((double)x - c * (double)g);  v = v < lo ? lo : v;  v = v > hi ? hi : v;  x = v
+ *   otherwise the volume stays.
+ * XRT_ERR_ARGUMENT, before the context is looked at, for a NULL volume or
+ * dims, a dims[a] outside 1..2048, an eps that is not finite and > 0, a
+ * length that is not finite and >= 0, a NaN bound and lo > hi.
+ *
+ * xrt_sirt_tv[_device].  xrt_sirt's arguments and checks, and tv.  With tv
+ * NULL or tv->steps == 0 it is xrt_sirt, bit for bit (the other fields are
+ * not looked at).  Otherwise a_0 = tv->alpha, and iteration k is
+ *   x0 = volume;  xrt_sirt's loop over the subsets;  D = xrt_volume_sumsq(volume, x0)
+ *   xrt_tv_descend(volume, tv->eps, tv->steps, length = a_k * sqrt(D), lo, hi)
+ *   a_(k+1) = a_k * tv->reduction
+ * length being formed on the device from the resident D, the product rounded
+ * once (a D that is not finite gives what the formulas give).  XRT_ERR_ARGUMENT
+ * also for an alpha that is not finite and >= 0, a reduction that is not
+ * finite and in (0, 1] and an eps that is not finite and > 0.
+ *
+ * Host forms: host buffers, synchronous.  _device: device buffers,
+ * asynchronous on `stream`.  The working set -- the partials, the gradient
+ * volume (xrt_sirt_tv: the solver's correction volume, free after the
+ * update) and the solver's x0 -- is the context's xrt_sirt working set,
+ * ordered as xrt_sirt_device says; XRT_ERR_MEMORY, with the byte count in
+ * xrt_last_error, when it cannot be allocated.
+ */
+typedef struct xrt_tv_params {
+    uint32_t steps;      /* descent steps after every iteration; 0: none */
+    double alpha;        /* the first iteration's step length as a share of the data step's, finite and >= 0 */
+    double reduction;    /* alpha's factor from one iteration to the next, in (0, 1] */
+    double eps;          /* the smoothing under the square root, finite and > 0 */
+} xrt_tv_params;
+int xrt_tv_gradient(xrt_context* ctx, const float* volume, const uint32_t dims[3], double eps, float* out);
+int xrt_tv_gradient_device(xrt_context* ctx, const float* d_volume, const uint32_t dims[3], double eps, float* d_out,
+                           void* stream);
+int xrt_volume_sumsq(xrt_context* ctx, uint64_t n, const float* a, const float* b, double* out);
+int xrt_volume_sumsq_device(xrt_context* ctx, uint64_t n, const float* d_a, const float* d_b, double* d_out, void* stream);
+int xrt_tv_descend(xrt_context* ctx, float* volume, const uint32_t dims[3], double eps, uint32_t steps, double length,
+                   float lo, float hi);
+int xrt_tv_descend_device(xrt_context* ctx, float* d_volume, const uint32_t dims[3], double eps, uint32_t steps,
+                          double length, float lo, float hi, void* stream);
+int xrt_sirt_tv(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* proj,
+                const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
+                uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv, float* volume);
+int xrt_sirt_tv_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                       const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
+                       uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv, float* d_volume,
+                       void* stream);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

@@ -397,6 +397,20 @@ int xrt_host_sirt(uint32_t width, uint32_t height, uint32_t num_planes, const fl
                   float lo, float hi, float* volume);
 
 /*
+ * Test hooks of TV-regularised SIRT.  Host code, no device: tv_quotients,
+ * tv_voxel, sumsq_entry and tv_step_voxel -- the functions k_tv_gradient,
+ * k_sumsq_first and k_tv_step call, compiled for the host -- over whole host
+ * buffers, the sum's order as written, and xrt_sirt_tv's algorithm over
+ * them and xrt_host_sirt's pieces.  Arguments and checks as the host forms'.
+ */
+int xrt_host_tv_gradient(const float* volume, const uint32_t dims[3], double eps, float* out);
+int xrt_host_volume_sumsq(uint64_t n, const float* a, const float* b, double* out);
+int xrt_host_tv_descend(float* volume, const uint32_t dims[3], double eps, uint32_t steps, double length, float lo, float hi);
+int xrt_host_sirt_tv(uint32_t width, uint32_t height, uint32_t num_planes, const float* proj, const double* matrices,
+                     const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets, double relax,
+                     float lo, float hi, const xrt_tv_params* tv, float* volume);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -39,7 +39,7 @@ __all__ = [
     "ray_table_index", "XRT_MAX_RAMP_WIDTH", "XRT_RAMP_RAMLAK", "XRT_RAMP_HANN", "ramp_filter", "fdk_weights",
     "fdk_scale", "backprojection_matrix", "save_volume", "host_fdk_filter", "host_backproject",
     "XRT_FP_PROJECT", "XRT_FP_RESIDUAL", "XRT_MAX_SUBSETS", "ray_matrix", "host_forward_project", "host_volume_update",
-    "host_sirt",
+    "host_sirt", "host_tv_gradient", "host_volume_sumsq", "host_tv_descend",
 ]
 
 
@@ -733,14 +733,75 @@ def _sirt_arrays(proj, matrices, dims, spacing, start):
     return a, m, d, spc, vol, p, h, w
 
 
-def host_sirt(proj, matrices, dims, spacing, iterations, subsets=1, relax=1.0, lo=0.0, hi=np.inf, start=None) -> np.ndarray:
-    """Context.sirt_matrices in the device's arithmetic on the host (xrt_host_sirt, a test hook)."""
+def _tv_params(tv):
+    """xrt_tv_params from a (steps, alpha, reduction, eps) tuple; None stays None."""
+    if tv is None:
+        return None
+    steps, alpha, reduction, eps = tv
+    return _abi.TvParams(int(steps), float(alpha), float(reduction), float(eps))
+
+
+def host_sirt(proj, matrices, dims, spacing, iterations, subsets=1, relax=1.0, lo=0.0, hi=np.inf, start=None,
+              tv=None) -> np.ndarray:
+    """Context.sirt_matrices in the device's arithmetic on the host (xrt_host_sirt, or with tv xrt_host_sirt_tv; test
+    hooks)."""
     a, m, d, spc, vol, p, h, w = _sirt_arrays(proj, matrices, dims, spacing, start)
-    rc = _abi.load().xrt_host_sirt(w, h, p, _fptr(a), _dptr(m), _u32ptr(d), _fptr(spc), int(iterations), int(subsets),
-                                   float(relax), float(lo), float(hi), _fptr(vol))
+    if tv is None:
+        rc = _abi.load().xrt_host_sirt(w, h, p, _fptr(a), _dptr(m), _u32ptr(d), _fptr(spc), int(iterations), int(subsets),
+                                       float(relax), float(lo), float(hi), _fptr(vol))
+    else:
+        params = _tv_params(tv)
+        rc = _abi.load().xrt_host_sirt_tv(w, h, p, _fptr(a), _dptr(m), _u32ptr(d), _fptr(spc), int(iterations),
+                                          int(subsets), float(relax), float(lo), float(hi), ctypes.byref(params), _fptr(vol))
     if rc != _abi.XRT_OK:
         raise XrtError(rc, "xrt_host_sirt")
     return vol
+
+
+def _tv_volume(volume, copy=False):
+    """(volume f32 (nz, ny, nx), dims u32[3]) of xrt_tv_gradient and xrt_tv_descend."""
+    v = np.array(volume, dtype=np.float32, order="C") if copy else np.ascontiguousarray(volume, dtype=np.float32)
+    if v.ndim != 3:
+        raise ValueError(f"a volume is (nz, ny, nx), got shape {v.shape}")
+    return v, np.array(v.shape[::-1], np.uint32)
+
+
+def _sumsq_arrays(a, b):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if b.shape != a.shape:
+            raise ValueError(f"a and b must share a shape, got {a.shape} and {b.shape}")
+    return a, b
+
+
+def host_tv_gradient(volume, eps=1e-8) -> np.ndarray:
+    """Context.tv_gradient on the host (xrt_host_tv_gradient, a test hook)."""
+    v, d = _tv_volume(volume)
+    out = np.empty_like(v)
+    rc = _abi.load().xrt_host_tv_gradient(_fptr(v), _u32ptr(d), float(eps), _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_tv_gradient")
+    return out
+
+
+def host_volume_sumsq(a, b=None) -> float:
+    """Context.volume_sumsq on the host (xrt_host_volume_sumsq, a test hook)."""
+    a, b = _sumsq_arrays(a, b)
+    out = np.zeros(1, np.float64)
+    rc = _abi.load().xrt_host_volume_sumsq(a.size, _fptr(a), _fptr(b) if b is not None else None, _dptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_volume_sumsq")
+    return float(out[0])
+
+
+def host_tv_descend(volume, steps, length, eps=1e-8, lo=-np.inf, hi=np.inf) -> np.ndarray:
+    """Context.tv_descend on the host (xrt_host_tv_descend, a test hook): the descended copy of the volume."""
+    v, d = _tv_volume(volume, copy=True)
+    rc = _abi.load().xrt_host_tv_descend(_fptr(v), _u32ptr(d), float(eps), int(steps), float(length), float(lo), float(hi))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_tv_descend")
+    return v
 
 
 class Context:
@@ -1100,37 +1161,98 @@ class Context:
                                                 float(relax), float(lo), float(hi), stream or None)
         self._check(rc, "xrt_volume_update_device")
 
+    def tv_gradient(self, volume, eps: float = 1e-8) -> np.ndarray:
+        """The gradient of the smoothed isotropic total variation sum sqrt(dx^2 + dy^2 + dz^2 + eps) (forward
+        differences, none across the border) of a (nz, ny, nx) f32 volume: (nz, ny, nx) f32."""
+        v, d = _tv_volume(volume)
+        out = np.empty_like(v)
+        self._check(self._lib.xrt_tv_gradient(self._ctx, _fptr(v), _u32ptr(d), float(eps), _fptr(out)), "xrt_tv_gradient")
+        return out
+
+    def tv_gradient_device(self, d_volume: int, dims, d_out: int, eps: float = 1e-8, stream: int = 0):
+        """tv_gradient over device buffers (raw pointers to f32 volumes); asynchronous on `stream`."""
+        d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+        self._check(self._lib.xrt_tv_gradient_device(self._ctx, d_volume or None, _u32ptr(d), float(eps), d_out or None,
+                                                     stream or None), "xrt_tv_gradient_device")
+
+    def volume_sumsq(self, a, b=None) -> float:
+        """The sum of the squares of a's entries, or of a - b's, in f64 in the fixed order of xrt_volume_sumsq."""
+        a, b = _sumsq_arrays(a, b)
+        out = np.zeros(1, np.float64)
+        self._check(self._lib.xrt_volume_sumsq(self._ctx, a.size, _fptr(a), _fptr(b) if b is not None else None,
+                                               _dptr(out)), "xrt_volume_sumsq")
+        return float(out[0])
+
+    def volume_sumsq_device(self, n: int, d_a: int, d_b: int, d_out: int, stream: int = 0):
+        """volume_sumsq over device buffers (raw pointers; d_b 0: none); one f64 is written at d_out.  Asynchronous on
+        `stream`."""
+        self._check(self._lib.xrt_volume_sumsq_device(self._ctx, int(n), d_a or None, d_b or None, d_out or None,
+                                                      stream or None), "xrt_volume_sumsq_device")
+
+    def tv_descend(self, volume, steps: int, length: float, eps: float = 1e-8, lo: float = -np.inf,
+                   hi: float = np.inf) -> np.ndarray:
+        """`steps` steepest-descent steps of `length` each on the volume's total variation (tv_gradient, normalised),
+        clamped to [lo, hi]: the descended copy of the volume."""
+        v, d = _tv_volume(volume, copy=True)
+        self._check(self._lib.xrt_tv_descend(self._ctx, _fptr(v), _u32ptr(d), float(eps), int(steps), float(length),
+                                             float(lo), float(hi)), "xrt_tv_descend")
+        return v
+
+    def tv_descend_device(self, d_volume: int, dims, steps: int, length: float, eps: float = 1e-8, lo: float = -np.inf,
+                          hi: float = np.inf, stream: int = 0):
+        """tv_descend over a device volume (a raw pointer), in place; asynchronous on `stream`."""
+        d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+        self._check(self._lib.xrt_tv_descend_device(self._ctx, d_volume or None, _u32ptr(d), float(eps), int(steps),
+                                                    float(length), float(lo), float(hi), stream or None),
+                    "xrt_tv_descend_device")
+
     def sirt_matrices(self, projections, matrices, dims, spacing, iterations: int, subsets: int = 1, relax: float = 1.0,
-                      lo: float = 0.0, hi: float = np.inf, start=None) -> np.ndarray:
+                      lo: float = 0.0, hi: float = np.inf, start=None, tv=None) -> np.ndarray:
         """sirt under P given (3, 4) f64 backprojection matrices in place of cameras and poses."""
         a, m, d, spc, vol, p, h, w = _sirt_arrays(projections, matrices, dims, spacing, start)
-        self._check(self._lib.xrt_sirt(self._ctx, w, h, p, _fptr(a), _dptr(m), _u32ptr(d), _fptr(spc), int(iterations),
-                                       int(subsets), float(relax), float(lo), float(hi), _fptr(vol)), "xrt_sirt")
+        if tv is None:
+            self._check(self._lib.xrt_sirt(self._ctx, w, h, p, _fptr(a), _dptr(m), _u32ptr(d), _fptr(spc), int(iterations),
+                                           int(subsets), float(relax), float(lo), float(hi), _fptr(vol)), "xrt_sirt")
+        else:
+            params = _tv_params(tv)
+            self._check(self._lib.xrt_sirt_tv(self._ctx, w, h, p, _fptr(a), _dptr(m), _u32ptr(d), _fptr(spc),
+                                              int(iterations), int(subsets), float(relax), float(lo), float(hi),
+                                              ctypes.byref(params), _fptr(vol)), "xrt_sirt_tv")
         return vol
 
     def sirt(self, projections, camera: Camera, poses, dims, origin, spacing, iterations: int, subsets: int = 1,
-             relax: float = 1.0, lo: float = 0.0, hi: float = np.inf, start=None) -> np.ndarray:
+             relax: float = 1.0, lo: float = 0.0, hi: float = np.inf, start=None, tv=None) -> np.ndarray:
         """SIRT (subsets = 1) or OS-SART (subsets > 1; subset s holds the projections p with p mod subsets == s) of
         the (P, H, W) line integrals `projections`, taken by `camera` -- one Camera, or P of them -- of an object
         under `poses` (P poses, or None: at rest), into the grid of dims = (nx, ny, nz) voxels of `spacing` with its
         minimum corner at `origin`: `iterations` passes over every subset from `start` (None: zeros), each update
-        relaxed by `relax` and clamped to [lo, hi].  (nz, ny, nx) f32."""
+        relaxed by `relax` and clamped to [lo, hi].  tv = (steps, alpha, reduction, eps): after every iteration `steps`
+        descent steps on the volume's total variation (tv_gradient with `eps`), each as long as alpha times the
+        distance the iteration moved the volume, alpha multiplied by `reduction` from one iteration to the next
+        (xrt_sirt_tv; alpha above about 0.5 flattens the object's level).  (nz, ny, nx) f32."""
         a, p, h, w = _lsf_planes(projections)
         cams = [camera] * p if isinstance(camera, Camera) else list(camera)
         poses = [None] * p if poses is None else list(poses)
         if len(cams) != p or len(poses) != p:
             raise ValueError(f"{p} projections need one camera or {p}, and {p} poses or None")
         mats = np.stack([backprojection_matrix(c, origin, spacing, q) for c, q in zip(cams, poses)])
-        return self.sirt_matrices(a, mats, dims, spacing, iterations, subsets, relax, lo, hi, start)
+        return self.sirt_matrices(a, mats, dims, spacing, iterations, subsets, relax, lo, hi, start, tv)
 
     def sirt_device(self, width: int, height: int, num_planes: int, d_proj: int, matrices, dims, spacing,
                     iterations: int, d_volume: int, subsets: int = 1, relax: float = 1.0, lo: float = 0.0,
-                    hi: float = np.inf, stream: int = 0):
+                    hi: float = np.inf, stream: int = 0, tv=None):
         """sirt over device buffers (raw pointers: the f32 projections and the f32 volume, start and result);
         `matrices` is a host (P, 12) f64 array.  Asynchronous on `stream`."""
         m = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 12)
         d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
         spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+        if tv is not None:
+            params = _tv_params(tv)
+            rc = self._lib.xrt_sirt_tv_device(self._ctx, int(width), int(height), int(num_planes), d_proj or None, _dptr(m),
+                                              _u32ptr(d), _fptr(spc), int(iterations), int(subsets), float(relax), float(lo),
+                                              float(hi), ctypes.byref(params), d_volume or None, stream or None)
+            self._check(rc, "xrt_sirt_tv_device")
+            return
         rc = self._lib.xrt_sirt_device(self._ctx, int(width), int(height), int(num_planes), d_proj or None, _dptr(m),
                                        _u32ptr(d), _fptr(spc), int(iterations), int(subsets), float(relax), float(lo),
                                        float(hi), d_volume or None, stream or None)

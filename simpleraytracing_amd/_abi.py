@@ -106,6 +106,20 @@ class Camera(ctypes.Structure):
     ]
 
 
+class TvParams(ctypes.Structure):
+    """xrt_tv_params: the TV descent of xrt_sirt_tv."""
+
+    _fields_ = [
+        ("steps", _u32),
+        ("alpha", ctypes.c_double),
+        ("reduction", ctypes.c_double),
+        ("eps", ctypes.c_double),
+    ]
+
+
+_TvP = ctypes.POINTER(TvParams)
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("rays", _u64),
@@ -247,6 +261,21 @@ XRT_SYMBOLS = {
     "xrt_host_forward_project": (ctypes.c_int, [_u32, _u32, _u32, _fp, _u32p, _fp, _dp, ctypes.c_int, _fp, _fp]),
     "xrt_host_volume_update": (ctypes.c_int, [_u64, _fp, _fp, _fp, ctypes.c_double, _f, _f]),
     "xrt_host_sirt": (ctypes.c_int, [_u32, _u32, _u32, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f, _fp]),
+    "xrt_tv_gradient": (ctypes.c_int, [_CtxP, _fp, _u32p, ctypes.c_double, _fp]),
+    "xrt_tv_gradient_device": (ctypes.c_int, [_CtxP, _vp, _u32p, ctypes.c_double, _vp, _vp]),
+    "xrt_volume_sumsq": (ctypes.c_int, [_CtxP, _u64, _fp, _fp, _dp]),
+    "xrt_volume_sumsq_device": (ctypes.c_int, [_CtxP, _u64, _vp, _vp, _vp, _vp]),
+    "xrt_tv_descend": (ctypes.c_int, [_CtxP, _fp, _u32p, ctypes.c_double, _u32, ctypes.c_double, _f, _f]),
+    "xrt_tv_descend_device": (ctypes.c_int, [_CtxP, _vp, _u32p, ctypes.c_double, _u32, ctypes.c_double, _f, _f, _vp]),
+    "xrt_sirt_tv": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f, _TvP,
+                                   _fp]),
+    "xrt_sirt_tv_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f,
+                                          _TvP, _vp, _vp]),
+    "xrt_host_tv_gradient": (ctypes.c_int, [_fp, _u32p, ctypes.c_double, _fp]),
+    "xrt_host_volume_sumsq": (ctypes.c_int, [_u64, _fp, _fp, _dp]),
+    "xrt_host_tv_descend": (ctypes.c_int, [_fp, _u32p, ctypes.c_double, _u32, ctypes.c_double, _f, _f]),
+    "xrt_host_sirt_tv": (ctypes.c_int, [_u32, _u32, _u32, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f, _TvP,
+                                        _fp]),
     "xrt_host_philox4x32": (None, [_u32p, _u32p, _u32p]),
     "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
     "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),

@@ -624,6 +624,16 @@ void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& proje
                      const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
                      const float spacing[3], unsigned iterations, unsigned subsets, double relax, float lo, float hi)
 {
+    reconstructSIRT(volume, projections, num_projections, frame, meshes, info, poses, dims, origin, spacing, iterations,
+                    subsets, relax, lo, hi, TVParams());
+}
+
+void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& projections, unsigned num_projections,
+                     const Image& frame, const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                     const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                     const float spacing[3], unsigned iterations, unsigned subsets, double relax, float lo, float hi,
+                     const TVParams& tv)
+{
     const unsigned W = frame.getWidth(), H = frame.getHeight();
     if (num_projections == 0 || projections.size() != (size_t)W * H * num_projections)
         throw std::runtime_error("reconstructSIRT: the stack does not hold num_projections images");
@@ -636,9 +646,21 @@ void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& proje
     DeviceSlot& slot = device_slot(device_choice());
     std::lock_guard<std::mutex> g(slot.lock);
     xrt_context* ctx = slot.ctx;
-    check(ctx, xrt_sirt(ctx, W, H, num_projections, projections.data(), matrices.data(), dims, spacing, iterations, subsets,
-                        relax, lo, hi, volume.data()),
-          "xrt_sirt");
+    const xrt_tv_params params = {tv.steps, tv.alpha, tv.reduction, tv.eps};
+    check(ctx, xrt_sirt_tv(ctx, W, H, num_projections, projections.data(), matrices.data(), dims, spacing, iterations, subsets,
+                           relax, lo, hi, tv.steps ? &params : nullptr, volume.data()),
+          "xrt_sirt_tv");
+}
+
+void denoiseTV(std::vector<float>& volume, const unsigned dims[3], unsigned steps, double length, double eps, float lo,
+               float hi)
+{
+    if (volume.size() != (size_t)dims[0] * dims[1] * dims[2])
+        throw std::runtime_error("denoiseTV: the volume does not hold dims[0] * dims[1] * dims[2] values");
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    check(ctx, xrt_tv_descend(ctx, volume.data(), dims, eps, steps, length, lo, hi), "xrt_tv_descend");
 }
 
 void forwardProject(std::vector<float>& projections, const std::vector<float>& volume, const Image& frame,

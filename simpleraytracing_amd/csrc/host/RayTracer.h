@@ -221,6 +221,30 @@ void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& proje
                      const float spacing[3], unsigned iterations, unsigned subsets = 1, double relax = 1.0, float lo = 0.0f,
                      float hi = std::numeric_limits<float>::infinity());
 
+// TV-regularised SIRT (xrt_sirt_tv): after every iteration the
+// volume takes `steps` normalised steepest-descent steps on its smoothed
+// isotropic total variation, each alpha times as long as the distance the
+// iteration moved the volume; alpha is multiplied by `reduction` (in (0, 1])
+// from one iteration to the next and `eps` smooths the norm.  alpha above
+// about 0.5 flattens the object's level.  steps == 0: plain reconstructSIRT.
+struct TVParams {
+    unsigned steps = 0;
+    double alpha = 0.2;
+    double reduction = 1.0;
+    double eps = 1e-8;
+};
+void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& projections, unsigned num_projections,
+                     const Image& frame, const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                     const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                     const float spacing[3], unsigned iterations, unsigned subsets, double relax, float lo, float hi,
+                     const TVParams& tv);
+
+// `steps` descent steps of `length` each on the total variation of a f32
+// volume of dims[0] * dims[1] * dims[2] values (x fastest), in place, clamped
+// to [lo, hi] (xrt_tv_descend).  One device.
+void denoiseTV(std::vector<float>& volume, const unsigned dims[3], unsigned steps, double length, double eps = 1e-8,
+               float lo = -std::numeric_limits<float>::infinity(), float hi = std::numeric_limits<float>::infinity());
+
 // The line integrals of a f32 volume (dims[0] * dims[1] * dims[2] values, x
 // fastest, the grid of reconstructFDK) along the rays of the camera of `info`
 // under every pose (empty: one projection at rest): xrt_forward_project under

@@ -69,6 +69,14 @@
 //                              == s) instead of FDK, from zeros, every update relaxed by
 //                              RELAX (default 1) and kept >= 0.  The same cube and the same
 //                              refusals as FDK's.
+//       --tv STEPS[:ALPHA[:REDUCTION[:EPS]]]
+//                              with --sirt: after every iteration STEPS descent steps on the
+//                              volume's total variation, each ALPHA (default
+//                              0.2) times as long as the distance the iteration moved the
+//                              volume; ALPHA is multiplied by REDUCTION (default 1, in
+//                              (0, 1]) after every iteration and EPS (default 1e-8) smooths
+//                              the norm.  It flattens noise and keeps edges; ALPHA above
+//                              about 0.5 flattens the object's level too.
 //       --sinogram FILE        with --turntable N and --log-projection: also write the N
 //                              projections' line integrals as one sinogram per detector
 //                              row, raw little-endian f32 in (height, N, width) order
@@ -184,6 +192,7 @@ void showUsage(const std::string& prog)
               << "\t--sinogram FILE\t\t\tWith --turntable N and --log-projection: also write the line integrals as raw float32 sinograms, (height, N, width)\n"
               << "\t--reconstruct FILE.mhd[:N]\tWith --turntable N:z (every mesh, about the detector's up) and --log-projection: reconstruct the scan by FDK into an N^3 grid (default 128) about the turntable's centre, its side the scene box's diagonal; writes FILE.mhd (MET_FLOAT) and FILE.raw\n"
               << "\t--sirt K[:S[:RELAX]]\t\tWith --reconstruct: K iterations of SIRT (S = 1) or OS-SART over S subsets (1 to 64) instead of FDK, from zeros, relaxed by RELAX (default 1), kept >= 0\n"
+              << "\t--tv STEPS[:ALPHA[:REDUCTION[:EPS]]]\tWith --sirt: STEPS total-variation descent steps after every iteration, each ALPHA (default 0.2) of the iteration's move, ALPHA times REDUCTION (default 1, in (0, 1]) after every iteration, EPS (default 1e-8) under the norm; ALPHA above about 0.5 flattens the object's level\n"
               << "\t--noise GAIN[:SEED]\t\tPhoton noise on the written image: each pixel a Poisson count of mean I * GAIN, divided by GAIN (after --lsf, before --log-projection; SEED defaults to 0); --u8 and --lbuffer stay as rendered\n"
               << "\t--supersample B\t\t\tPixel-area integration: render W*B x H*B samples (B in 1..8) and write each pixel's mean over its B x B samples; -s stays the written size\n"
               << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
@@ -229,6 +238,8 @@ struct Options {
     unsigned sirt_iterations = 0;              // --sirt K[:S[:RELAX]] (0: FDK)
     unsigned sirt_subsets = 1;
     double sirt_relax = 1.0;
+    bool tv = false;                           // --tv STEPS[:ALPHA[:REDUCTION[:EPS]]]
+    TVParams tv_params;
     bool noise = false;                        // --noise GAIN[:SEED]
     float noise_gain = 0.0f;
     unsigned long long noise_seed = 0;
@@ -642,6 +653,23 @@ Options processCmd(int argc, char** argv)
             }
             if (!ok)
                 throw std::runtime_error("--sirt K[:S[:RELAX]]: K iterations (>= 1), S subsets (1 to 64), RELAX a finite number");
+        } else if (a == "--tv") {
+            const std::vector<std::string> parts = split(parse_str(argv[0], argc, argv, i), ':');
+            bool ok = parts.size() >= 1 && parts.size() <= 4 && parse_index(parts[0], o.tv_params.steps) && o.tv_params.steps >= 1;
+            double* fields[3] = {&o.tv_params.alpha, &o.tv_params.reduction, &o.tv_params.eps};
+            for (size_t f = 1; ok && f < parts.size(); ++f) {
+                size_t used = 0;
+                try {
+                    *fields[f - 1] = std::stod(parts[f], &used);
+                } catch (const std::exception&) {
+                    used = 0;
+                }
+                ok = !parts[f].empty() && used == parts[f].size() && std::isfinite(*fields[f - 1]);
+            }
+            ok = ok && o.tv_params.alpha >= 0.0 && o.tv_params.reduction > 0.0 && o.tv_params.reduction <= 1.0 && o.tv_params.eps > 0.0;
+            if (!ok)
+                throw std::runtime_error("--tv STEPS[:ALPHA[:REDUCTION[:EPS]]]: STEPS descent steps (>= 1), ALPHA finite and >= 0, REDUCTION in (0, 1], EPS finite and > 0");
+            o.tv = true;
         } else if (a == "--noise") {
             parse_noise(parse_str(argv[0], argc, argv, i), o);
         } else if (a == "--supersample") {
@@ -732,6 +760,8 @@ Options processCmd(int argc, char** argv)
         throw std::runtime_error("--reconstruct needs a --turntable that turns every mesh: the scene is reconstructed as one object");
     if (o.sirt_iterations && o.reconstruct.empty())
         throw std::runtime_error("--sirt needs --reconstruct FILE.mhd: it chooses how the scan is reconstructed");
+    if (o.tv && !o.sirt_iterations)
+        throw std::runtime_error("--tv needs --sirt K: it regularises the iterative reconstruction");
     if (o.sirt_iterations && o.sirt_subsets > o.turntable)
         throw std::runtime_error("--sirt K[:S[:RELAX]]: more subsets than projections");
     if (o.log_projection && (o.gpus > 1 || o.rows))
@@ -1040,7 +1070,7 @@ int main(int argc, char** argv)
             if (opt.sirt_iterations)
                 reconstructSIRT(reconstruction, integrals, opt.turntable, image, meshes, info, turns, dims, origin, spacing,
                                 opt.sirt_iterations, opt.sirt_subsets, opt.sirt_relax, 0.0f,
-                                std::numeric_limits<float>::infinity());
+                                std::numeric_limits<float>::infinity(), opt.tv ? opt.tv_params : TVParams());
             else
                 reconstructFDK(reconstruction, integrals, opt.turntable, image, meshes, info, turns, dims, origin, spacing, centre);
             try {

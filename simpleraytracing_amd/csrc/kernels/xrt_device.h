@@ -1748,4 +1748,76 @@ __host__ __device__ __forceinline__ float volume_update_voxel(float x, float cor
     return v;
 }
 
+// ---------------------------------------------------------------------------
+// TV-regularised SIRT: the gradient of the smoothed isotropic
+// total variation, the sum of squares' chunk order and the descent step.
+// tv_quotients and tv_voxel are the gradient's contract: k_tv_gradient calls
+// them on the device and xrt_host_tv_gradient compiled for the host, and
+// tests/tv_ref.py restates them.  f64, no FMA, written selects.
+// ---------------------------------------------------------------------------
+
+// The forward differences of a voxel of value v over its norm: vx, vy, vz are
+// its upper neighbours' values, read only where hx, hy, hz say that there is
+// one (no difference across the border).
+__host__ __device__ __forceinline__ void tv_quotients(double v, double vx, double vy, double vz, bool hx, bool hy, bool hz,
+                                                      double eps, double& qx, double& qy, double& qz)
+{
+    const double dx = hx ? vx - v : 0.0;
+    const double dy = hy ? vy - v : 0.0;
+    const double dz = hz ? vz - v : 0.0;
+    const double n = ::sqrt(((dx * dx + dy * dy) + dz * dz) + eps);
+    qx = dx / n;
+    qy = dy / n;
+    qz = dz / n;
+}
+
+// A voxel of xrt_tv_gradient from its own quotients and its lower neighbours'
+// (bx: qx of (i - 1, j, k), +0.0 where i = 0; by, bz likewise).
+__host__ __device__ __forceinline__ float tv_voxel(double bx, double by, double bz, double qx, double qy, double qz)
+{
+    return (float)(((bx + by) + bz) - ((qx + qy) + qz));
+}
+
+// The quotients of voxel (i, j, k) of the volume x read where it lies.
+__host__ __device__ __forceinline__ void tv_quotients_at(const float* __restrict__ x, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                         uint32_t i, uint32_t j, uint32_t k, double eps, double& qx,
+                                                         double& qy, double& qz)
+{
+    const uint64_t row = nx, plane = (uint64_t)nx * ny;
+    const uint64_t at = ((uint64_t)k * ny + j) * nx + i;
+    const bool hx = i + 1u < nx, hy = j + 1u < ny, hz = k + 1u < nz;
+    tv_quotients((double)x[at], hx ? (double)x[at + 1u] : 0.0, hy ? (double)x[at + row] : 0.0,
+                 hz ? (double)x[at + plane] : 0.0, hx, hy, hz, eps, qx, qy, qz);
+}
+
+// xrt_volume_sumsq's order (include/xrt.h): chunks of kSumsqChunk entries, a
+// chunk's kSumsqLanes accumulators each over kSumsqRounds entries a
+// kSumsqLanes apart, then the halving tree.
+constexpr uint32_t kSumsqLanes = 256;
+constexpr uint32_t kSumsqRounds = 16;
+constexpr uint32_t kSumsqChunk = kSumsqLanes * kSumsqRounds;   // 4096
+
+// An entry of the first level: the square of a[i], or of a[i] - b[i].
+__host__ __device__ __forceinline__ double sumsq_entry(const float* __restrict__ a, const float* __restrict__ b, uint64_t i)
+{
+    const double e = b ? (double)a[i] - (double)b[i] : (double)a[i];
+    return e * e;
+}
+
+// The descent's step length from the resident sums: scale, or scale *
+// sqrt(*moved) where the solver ties it to the data step.
+__host__ __device__ __forceinline__ double tv_step_length(double scale, const double* moved)
+{
+    return moved ? scale * ::sqrt(*moved) : scale;
+}
+
+// A voxel of a descent step under c = length / gn.
+__host__ __device__ __forceinline__ float tv_step_voxel(float x, float g, double c, float lo, float hi)
+{
+    float v = (float)((double)x - c * (double)g);
+    v = v < lo ? lo : v;
+    v = v > hi ? hi : v;
+    return v;
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -4716,4 +4716,138 @@ __global__ __launch_bounds__(kUpdateThreads) void k_volume_update(uint64_t n, fl
         x[i] = volume_update_voxel(x[i], corr[i], norm[i], relax, lo, hi);
 }
 
+// ---------------------------------------------------------------------------
+// k_tv_gradient: the gradient of the smoothed isotropic TV of a f32 volume
+// (DESIGN 10.13).  A workgroup of kTvLanesX x kTvLanesY lanes owns the
+// kTvOwnX x kTvOwnY columns of an (x, y) tile -- its lanes of column 0 and
+// row 0 are the rim, one voxel below the owned ones: they form quotients and
+// write nothing -- and marches kTvChunkZ slices along z (blockIdx.y: the
+// chunk).  Per slice a lane forms its own voxel's norm and three quotients
+// once (tv_quotients), hands qx and qy to its upper neighbours through LDS
+// -- two buffers in turn, so one barrier a slice: a buffer is written again
+// only behind the barrier of the slice in between, which every lane passes
+// after its reads -- and keeps qz in a register for the slice above.  A chunk
+// that does not start at slice 0 first forms the quotients of the slice below
+// it for that register.  The slice above is loaded once and kept as the next
+// slice's own value.  Offsets are 64-bit; no lane leaves before the last
+// barrier.  8 KB of LDS, no scratch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kTvLanesX = 32, kTvLanesY = 8;
+constexpr uint32_t kTvOwnX = kTvLanesX - 1u, kTvOwnY = kTvLanesY - 1u;
+constexpr uint32_t kTvChunkZ = 32;
+constexpr uint32_t kTvThreads = kTvLanesX * kTvLanesY;
+
+__global__ __launch_bounds__(kTvThreads) void k_tv_gradient(const float* __restrict__ x, float* __restrict__ g, uint32_t nx,
+                                                            uint32_t ny, uint32_t nz, uint32_t tiles_x, double eps)
+{
+    __shared__ double s_qx[2][kTvLanesY][kTvLanesX];
+    __shared__ double s_qy[2][kTvLanesY][kTvLanesX];
+    const uint32_t tx = threadIdx.x % kTvLanesX, ty = threadIdx.x / kTvLanesX;
+    const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    // (a rim lane of the first tile lies at -1: outside)
+    const int64_t i = (int64_t)tile_x * kTvOwnX + tx - 1, j = (int64_t)tile_y * kTvOwnY + ty - 1;
+    const bool inside = i >= 0 && i < (int64_t)nx && j >= 0 && j < (int64_t)ny;
+    const bool owns = inside && tx > 0u && ty > 0u;
+    const bool hx = inside && i + 1 < (int64_t)nx, hy = inside && j + 1 < (int64_t)ny;
+    const uint32_t k0 = blockIdx.y * kTvChunkZ;
+    const uint32_t k1 = nz - k0 < kTvChunkZ ? nz : k0 + kTvChunkZ;
+    const uint64_t row = nx, plane = (uint64_t)nx * ny;
+    uint64_t at = inside ? ((uint64_t)k0 * ny + (uint64_t)j) * nx + (uint64_t)i : 0u;
+    double below = 0.0;                               // qz of the voxel one slice down: +0.0 under slice 0
+    if (inside && k0 > 0u) {
+        double qx, qy;
+        tv_quotients_at(x, nx, ny, nz, (uint32_t)i, (uint32_t)j, k0 - 1u, eps, qx, qy, below);
+    }
+    double v = inside ? (double)x[at] : 0.0;
+    uint32_t buf = 0;
+    for (uint32_t k = k0; k < k1; ++k) {
+        const bool hz = inside && k + 1u < nz;
+        const double vz = hz ? (double)x[at + plane] : 0.0;
+        double qx = 0.0, qy = 0.0, qz = 0.0;
+        if (inside)
+            tv_quotients(v, hx ? (double)x[at + 1u] : 0.0, hy ? (double)x[at + row] : 0.0, vz, hx, hy, hz, eps, qx, qy, qz);
+        s_qx[buf][ty][tx] = qx;
+        s_qy[buf][ty][tx] = qy;
+        __syncthreads();
+        if (owns) {
+            const double bx = i > 0 ? s_qx[buf][ty][tx - 1u] : 0.0;
+            const double by = j > 0 ? s_qy[buf][ty - 1u][tx] : 0.0;
+            g[at] = tv_voxel(bx, by, below, qx, qy, qz);
+        }
+        below = qz;
+        v = vz;
+        at += plane;
+        buf ^= 1u;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_sumsq_first / k_sumsq_next: xrt_volume_sumsq's levels.  A
+// workgroup of kSumsqLanes lanes a chunk of kSumsqChunk entries: lane l adds
+// the entries 256 r + l for r = 0 .. 15 in turn -- coalesced --, then the
+// halving tree: the strides 128 and 64 through LDS across the four waves, 32
+// to 1 by shuffles inside the first; lane 0 writes the chunk's partial.  The
+// order is the contract's, so the sum does not depend on the launch.  2^33
+// entries are 2^21 chunks: 2^29 work-items.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void sumsq_tree(double acc, double* __restrict__ sh, double* __restrict__ out)
+{
+    const uint32_t l = threadIdx.x;
+    sh[l] = acc;
+    __syncthreads();
+    if (l < 128u) {
+        acc = acc + sh[l + 128u];
+        sh[l] = acc;                                  // (lanes below 128 read above 128 only)
+    }
+    __syncthreads();
+    if (l < 64u) {                                    // the first wave, whole
+        acc = acc + sh[l + 64u];
+        for (uint32_t h = 32u; h >= 1u; h >>= 1) acc = acc + __shfl_down(acc, h);
+        if (l == 0u) out[blockIdx.x] = acc;
+    }
+}
+
+__global__ __launch_bounds__(kSumsqLanes) void k_sumsq_first(uint64_t n, const float* __restrict__ a,
+                                                             const float* __restrict__ b, double* __restrict__ out)
+{
+    __shared__ double sh[kSumsqLanes];
+    const uint64_t base = (uint64_t)blockIdx.x * kSumsqChunk + threadIdx.x;
+    double acc = 0.0;
+    for (uint32_t r = 0; r < kSumsqRounds; ++r) {
+        const uint64_t i = base + (uint64_t)r * kSumsqLanes;
+        acc = acc + (i < n ? sumsq_entry(a, b, i) : 0.0);
+    }
+    sumsq_tree(acc, sh, out);
+}
+
+__global__ __launch_bounds__(kSumsqLanes) void k_sumsq_next(uint64_t m, const double* __restrict__ w, double* __restrict__ out)
+{
+    __shared__ double sh[kSumsqLanes];
+    const uint64_t base = (uint64_t)blockIdx.x * kSumsqChunk + threadIdx.x;
+    double acc = 0.0;
+    for (uint32_t r = 0; r < kSumsqRounds; ++r) {
+        const uint64_t i = base + (uint64_t)r * kSumsqLanes;
+        acc = acc + (i < m ? w[i] : 0.0);
+    }
+    sumsq_tree(acc, sh, out);
+}
+
+// ---------------------------------------------------------------------------
+// k_tv_step: one descent step, x = clamp(x - (length / sqrt(G)) g) where
+// sqrt(G) > 0, k_volume_update's grid.  G and, in the solver, the data step's
+// D are read from device memory by every lane -- a wave-uniform address --,
+// so c has the same bits everywhere and the host never waits for a norm.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kUpdateThreads) void k_tv_step(uint64_t n, float* __restrict__ x, const float* __restrict__ g,
+                                                            const double* __restrict__ G, double scale,
+                                                            const double* __restrict__ moved, float lo, float hi)
+{
+    const double gn = ::sqrt(*G);
+    if (!(gn > 0.0)) return;
+    const double c = tv_step_length(scale, moved) / gn;
+    const uint64_t stride = (uint64_t)gridDim.x * kUpdateThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kUpdateThreads + threadIdx.x; i < n; i += stride)
+        x[i] = tv_step_voxel(x[i], g[i], c, lo, hi);
+}
+
 }  // namespace XRT_KERNEL_NS

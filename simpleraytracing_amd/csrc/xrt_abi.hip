@@ -549,7 +549,9 @@ struct xrt_context {
 
     // The working set of xrt_sirt[_device]: one allocation
     // holding the gathered matrices (A then R, f64), the residual planes of
-    // the largest subset, the correction volume and the norm volumes, kept
+    // the largest subset, the correction volume and the norm volumes -- with
+    // TV also the sums' partials and x0; xrt_volume_sumsq and
+    // xrt_tv_descend lay their partials and gradient volume in it --, kept
     // between calls.  sirt_mats is the upload's source (it must outlive the
     // copy); sirt_ev marks the last call's end on its stream: the next call
     // waits for it before it touches either.
@@ -3124,19 +3126,19 @@ int xrt_volume_update(xrt_context* ctx, uint64_t n, float* x, const float* corr,
     return s.finish();
 }
 
-// xrt_sirt's loop over device buffers on `stream` (validated arguments, a plan whose every matrix has its ray
-// matrix).  The working set lies in the context's d_sirt.
-static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
-                    SirtPlan& plan, const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets,
-                    double relax, float lo, float hi, float* d_volume, hipStream_t stream)
+// --- TV-regularised SIRT ------------------------------------------
+
+#include "xrt_tv_host.inc"
+
+// The context's working set (d_sirt) for a call that needs `bytes` of it: the previous call's kernels and upload
+// are done with it, it is large enough, and sirt_ev exists.  The caller sets sirt_busy once it has enqueued work on
+// the set and records sirt_ev behind its last.
+static int sirt_working_set(xrt_context* ctx, size_t bytes)
 {
-    if (ctx->sirt_busy) {                             // the previous call's kernels and upload are done with the set
+    if (ctx->sirt_busy) {
         XRT_HIP(ctx, hipEventSynchronize(ctx->sirt_ev));
         ctx->sirt_busy = false;
     }
-    const size_t plane = (size_t)width * height, voxels = (size_t)dims[0] * dims[1] * dims[2];
-    const size_t mat_bytes = (size_t)num_planes * 24u * sizeof(double);
-    const size_t bytes = mat_bytes + (plane * plan.widest + voxels * ((size_t)subsets + 1u)) * sizeof(float);
     if (bytes > ctx->sirt_cap || !ctx->d_sirt) {
         (void)hipFree(ctx->d_sirt);
         ctx->d_sirt = nullptr;
@@ -3148,14 +3150,188 @@ static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t 
         }
         ctx->sirt_cap = bytes;
     }
+    if (!ctx->sirt_ev) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->sirt_ev, hipEventDisableTiming));
+    return XRT_OK;
+}
+
+// The doubles that the sum of n entries needs for its partials: the first level's and the second's.
+static size_t sumsq_partials(uint64_t n)
+{
+    const uint64_t m1 = sumsq_chunks(n);
+    return (size_t)(m1 + sumsq_chunks(m1));
+}
+
+static int launch_tv_gradient(xrt_context* ctx, const float* d_x, const uint32_t dims[3], double eps, float* d_g,
+                              hipStream_t stream)
+{
+    // at most 67 x 293 tiles and 64 chunks of 256 lanes: 2^28.3 work-items
+    const uint32_t tiles_x = (dims[0] + kTvOwnX - 1u) / kTvOwnX, tiles_y = (dims[1] + kTvOwnY - 1u) / kTvOwnY;
+    const uint32_t chunks = (dims[2] + kTvChunkZ - 1u) / kTvChunkZ;
+    hipLaunchKernelGGL(k_tv_gradient, dim3(tiles_x * tiles_y, chunks), dim3(kTvThreads), 0, stream, d_x, d_g, dims[0], dims[1],
+                       dims[2], tiles_x, eps);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+// *d_out = the sum of squares of the n entries of d_a (less d_b's), its levels' partials in d_partials
+// (sumsq_partials(n) doubles).
+static int launch_sumsq(xrt_context* ctx, uint64_t n, const float* d_a, const float* d_b, double* d_partials, double* d_out,
+                        hipStream_t stream)
+{
+    uint64_t m = sumsq_chunks(n);
+    double* level = d_partials;
+    hipLaunchKernelGGL(k_sumsq_first, dim3((unsigned)m), dim3(kSumsqLanes), 0, stream, n, d_a, d_b, m == 1u ? d_out : level);
+    XRT_HIP(ctx, hipGetLastError());
+    while (m > 1u) {
+        const uint64_t next = sumsq_chunks(m);
+        hipLaunchKernelGGL(k_sumsq_next, dim3((unsigned)next), dim3(kSumsqLanes), 0, stream, m, (const double*)level,
+                           next == 1u ? d_out : level + m);
+        XRT_HIP(ctx, hipGetLastError());
+        level += m;
+        m = next;
+    }
+    return XRT_OK;
+}
+
+// xrt_tv_descend's steps on `stream`: d_g a volume's worth of floats, d_sums sumsq_partials(voxels) + 1 doubles
+// (the partials, then G).  The step's length is `scale`, or scale * sqrt(*d_moved).
+static int launch_tv_descend(xrt_context* ctx, float* d_x, const uint32_t dims[3], double eps, uint32_t steps, double scale,
+                             const double* d_moved, float lo, float hi, float* d_g, double* d_sums, hipStream_t stream)
+{
+    const uint64_t voxels = (uint64_t)dims[0] * dims[1] * dims[2];
+    double* d_G = d_sums + sumsq_partials(voxels);
+    const uint64_t blocks = std::min<uint64_t>((voxels + kUpdateThreads - 1u) / kUpdateThreads, kUpdateBlocks);
+    for (uint32_t s = 0; s < steps; ++s) {
+        if (int rc = launch_tv_gradient(ctx, d_x, dims, eps, d_g, stream)) return rc;
+        if (int rc = launch_sumsq(ctx, voxels, d_g, nullptr, d_sums, d_G, stream)) return rc;
+        hipLaunchKernelGGL(k_tv_step, dim3((unsigned)blocks), dim3(kUpdateThreads), 0, stream, voxels, d_x, (const float*)d_g,
+                           (const double*)d_G, scale, d_moved, lo, hi);
+        XRT_HIP(ctx, hipGetLastError());
+    }
+    return XRT_OK;
+}
+
+int xrt_tv_gradient_device(xrt_context* ctx, const float* d_volume, const uint32_t dims[3], double eps, float* d_out,
+                           void* stream)
+{
+    if (const char* why = tv_gradient_arguments(d_volume, dims, eps, d_out)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_tv_gradient(ctx, d_volume, dims, eps, d_out, (hipStream_t)stream);
+}
+
+int xrt_tv_gradient(xrt_context* ctx, const float* volume, const uint32_t dims[3], double eps, float* out)
+{
+    if (const char* why = tv_gradient_arguments(volume, dims, eps, out)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
+    DeviceScratch s(ctx, ctx->host_stream, "TV gradient");
+    const float* dvol = s.upload(volume, voxels);
+    float* dout = s.alloc<float>(voxels);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_tv_gradient(ctx, dvol, dims, eps, dout, ctx->host_stream)) return rc;
+    s.download(out, (const float*)dout, voxels);
+    return s.finish();
+}
+
+// xrt_volume_sumsq over device buffers on `stream`, its partials in the context's working set.
+static int run_sumsq(xrt_context* ctx, uint64_t n, const float* d_a, const float* d_b, double* d_out, hipStream_t stream)
+{
+    if (int rc = sirt_working_set(ctx, std::max<size_t>(sumsq_partials(n), 1u) * sizeof(double))) return rc;
+    ctx->sirt_busy = true;
+    const int rc = launch_sumsq(ctx, n, d_a, d_b, reinterpret_cast<double*>(ctx->d_sirt), d_out, stream);
+    (void)hipEventRecord(ctx->sirt_ev, stream);
+    return rc;
+}
+
+int xrt_volume_sumsq_device(xrt_context* ctx, uint64_t n, const float* d_a, const float* d_b, double* d_out, void* stream)
+{
+    if (const char* why = sumsq_arguments(n, d_a, d_b, d_out)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return run_sumsq(ctx, n, d_a, d_b, d_out, (hipStream_t)stream);
+}
+
+int xrt_volume_sumsq(xrt_context* ctx, uint64_t n, const float* a, const float* b, double* out)
+{
+    if (const char* why = sumsq_arguments(n, a, b, out)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceScratch s(ctx, ctx->host_stream, "sum of squares");
+    const float* da = s.upload(a, (size_t)n);
+    const float* db = s.upload(b, (size_t)n);
+    double* dout = s.alloc<double>(1);
+    if (s.rc()) return s.rc();
+    if (int rc = run_sumsq(ctx, n, da, db, dout, ctx->host_stream)) return rc;
+    s.download(out, (const double*)dout, 1);
+    return s.finish();
+}
+
+// xrt_tv_descend over a device volume on `stream`: the sums, then the gradient volume, in the context's working set.
+static int run_tv_descend(xrt_context* ctx, float* d_volume, const uint32_t dims[3], double eps, uint32_t steps, double length,
+                          float lo, float hi, hipStream_t stream)
+{
+    const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
+    const size_t sums = sumsq_partials(voxels) + 1u;
+    if (int rc = sirt_working_set(ctx, sums * sizeof(double) + voxels * sizeof(float))) return rc;
+    ctx->sirt_busy = true;
+    double* d_sums = reinterpret_cast<double*>(ctx->d_sirt);
+    const int rc = launch_tv_descend(ctx, d_volume, dims, eps, steps, length, nullptr, lo, hi,
+                                     reinterpret_cast<float*>(d_sums + sums), d_sums, stream);
+    (void)hipEventRecord(ctx->sirt_ev, stream);
+    return rc;
+}
+
+int xrt_tv_descend_device(xrt_context* ctx, float* d_volume, const uint32_t dims[3], double eps, uint32_t steps,
+                          double length, float lo, float hi, void* stream)
+{
+    if (const char* why = tv_descend_arguments(d_volume, dims, eps, length, lo, hi)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return run_tv_descend(ctx, d_volume, dims, eps, steps, length, lo, hi, (hipStream_t)stream);
+}
+
+int xrt_tv_descend(xrt_context* ctx, float* volume, const uint32_t dims[3], double eps, uint32_t steps, double length,
+                   float lo, float hi)
+{
+    if (const char* why = tv_descend_arguments(volume, dims, eps, length, lo, hi)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
+    DeviceScratch s(ctx, ctx->host_stream, "TV descent");
+    float* dvol = s.upload(volume, voxels);
+    if (s.rc()) return s.rc();
+    if (int rc = run_tv_descend(ctx, dvol, dims, eps, steps, length, lo, hi, ctx->host_stream)) return rc;
+    s.download(volume, (const float*)dvol, voxels);
+    return s.finish();
+}
+
+// xrt_sirt_tv's loop over device buffers on `stream` (validated arguments, a plan whose every matrix has its ray
+// matrix; tv NULL or without steps: xrt_sirt's).  The working set lies in the context's d_sirt: the matrices, with
+// TV the sums (the partials, G, D), the residual planes, the correction volume -- the gradient's too --, the norm
+// volumes and with TV x0.
+static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                    SirtPlan& plan, const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets,
+                    double relax, float lo, float hi, const xrt_tv_params* tv, float* d_volume, hipStream_t stream)
+{
+    const bool with_tv = tv && tv->steps > 0u;
+    const size_t plane = (size_t)width * height, voxels = (size_t)dims[0] * dims[1] * dims[2];
+    const size_t mat_bytes = (size_t)num_planes * 24u * sizeof(double);
+    const size_t sums = with_tv ? sumsq_partials(voxels) + 2u : 0u;
+    const size_t bytes = mat_bytes + sums * sizeof(double) +
+                         (plane * plan.widest + voxels * ((size_t)subsets + 1u + (with_tv ? 1u : 0u))) * sizeof(float);
+    if (int rc = sirt_working_set(ctx, bytes)) return rc;
     double* dA = reinterpret_cast<double*>(ctx->d_sirt);
     double* dR = dA + (size_t)num_planes * 12u;
-    float* d_res = reinterpret_cast<float*>(ctx->d_sirt + mat_bytes);
+    double* d_sums = dR + (size_t)num_planes * 12u;
+    double* d_moved = d_sums + (sums ? sums - 1u : 0u);      // D, behind the partials and G
+    float* d_res = reinterpret_cast<float*>(d_sums + sums);
     float* d_corr = d_res + plane * plan.widest;
     float* d_norms = d_corr + voxels;
+    float* d_x0 = d_norms + voxels * subsets;
     ctx->sirt_mats.assign(plan.A.begin(), plan.A.end());
     ctx->sirt_mats.insert(ctx->sirt_mats.end(), plan.R.begin(), plan.R.end());
-    if (!ctx->sirt_ev) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->sirt_ev, hipEventDisableTiming));
     XRT_HIP(ctx, hipMemcpyAsync(dA, ctx->sirt_mats.data(), mat_bytes, hipMemcpyHostToDevice, stream));
     ctx->sirt_busy = true;                            // from here on the set is in use until sirt_ev
     int rc = XRT_OK;
@@ -3165,7 +3341,10 @@ static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t 
     for (uint32_t s = 0; s < subsets && !rc; ++s)
         rc = launch_backproject(ctx, width, height, plan.count[s], d_res, dA + (size_t)plan.first[s] * 12u, dims, 0, dims[2],
                                 1.0, 0, d_norms + voxels * s, stream);
-    for (uint32_t k = 0; k < iterations && !rc; ++k)
+    double a_k = with_tv ? tv->alpha : 0.0;
+    for (uint32_t k = 0; k < iterations && !rc; ++k) {
+        if (with_tv && hipMemcpyAsync(d_x0, d_volume, voxels * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+            rc = fail(ctx, XRT_ERR_DEVICE, "SIRT: keeping the iteration's start failed");
         for (uint32_t s = 0; s < subsets && !rc; ++s) {
             // subset s's planes lie `subsets` planes apart in the scan, from plane s
             rc = launch_forward_project(ctx, width, height, plan.count[s], d_volume, dims, spacing,
@@ -3176,32 +3355,42 @@ static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t 
                                         dims[2], 1.0, 0, d_corr, stream);
             if (!rc) rc = launch_volume_update(ctx, voxels, d_volume, d_corr, d_norms + voxels * s, relax, lo, hi, stream);
         }
+        if (with_tv && !rc) {
+            // the data step's D stays on the device: every lane of the steps forms a_k * sqrt(D) from it
+            rc = launch_sumsq(ctx, voxels, d_volume, d_x0, d_sums, d_moved, stream);
+            if (!rc) rc = launch_tv_descend(ctx, d_volume, dims, tv->eps, tv->steps, a_k, d_moved, lo, hi, d_corr, d_sums, stream);
+            a_k = a_k * tv->reduction;
+        }
+    }
     (void)hipEventRecord(ctx->sirt_ev, stream);
     return rc;
 }
 
-int xrt_sirt_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
-                    const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
-                    uint32_t subsets, double relax, float lo, float hi, float* d_volume, void* stream)
+int xrt_sirt_tv_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                       const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
+                       uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv, float* d_volume,
+                       void* stream)
 {
     if (const char* why = sirt_arguments(width, height, num_planes, d_proj, matrices, dims, spacing, iterations, subsets, relax,
                                          lo, hi, d_volume, false))
         return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (const char* why = tv_params_arguments(tv)) return fail(ctx, XRT_ERR_ARGUMENT, why);
     SirtPlan plan;
     if (!sirt_plan(num_planes, subsets, matrices, plan)) return fail(ctx, XRT_ERR_ARGUMENT, "a matrix has no ray matrix (xrt_ray_matrix)");
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
-    return run_sirt(ctx, width, height, num_planes, d_proj, plan, dims, spacing, iterations, subsets, relax, lo, hi, d_volume,
-                    (hipStream_t)stream);
+    return run_sirt(ctx, width, height, num_planes, d_proj, plan, dims, spacing, iterations, subsets, relax, lo, hi, tv,
+                    d_volume, (hipStream_t)stream);
 }
 
-int xrt_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* proj,
-             const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets,
-             double relax, float lo, float hi, float* volume)
+int xrt_sirt_tv(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* proj,
+                const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
+                uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv, float* volume)
 {
     if (const char* why = sirt_arguments(width, height, num_planes, proj, matrices, dims, spacing, iterations, subsets, relax,
                                          lo, hi, volume, true))
         return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (const char* why = tv_params_arguments(tv)) return fail(ctx, XRT_ERR_ARGUMENT, why);
     SirtPlan plan;
     if (!sirt_plan(num_planes, subsets, matrices, plan)) return fail(ctx, XRT_ERR_ARGUMENT, "a matrix has no ray matrix (xrt_ray_matrix)");
     if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
@@ -3211,11 +3400,27 @@ int xrt_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_pla
     const float* dproj = s.upload(proj, (size_t)width * height * num_planes);
     float* dvol = s.upload(volume, voxels);
     if (s.rc()) return s.rc();
-    if (int rc = run_sirt(ctx, width, height, num_planes, dproj, plan, dims, spacing, iterations, subsets, relax, lo, hi, dvol,
-                          ctx->host_stream))
+    if (int rc = run_sirt(ctx, width, height, num_planes, dproj, plan, dims, spacing, iterations, subsets, relax, lo, hi, tv,
+                          dvol, ctx->host_stream))
         return rc;
     s.download(volume, (const float*)dvol, voxels);
     return s.finish();
+}
+
+int xrt_sirt_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_proj,
+                    const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations,
+                    uint32_t subsets, double relax, float lo, float hi, float* d_volume, void* stream)
+{
+    return xrt_sirt_tv_device(ctx, width, height, num_planes, d_proj, matrices, dims, spacing, iterations, subsets, relax, lo,
+                              hi, nullptr, d_volume, stream);
+}
+
+int xrt_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* proj,
+             const double* matrices, const uint32_t dims[3], const float spacing[3], uint32_t iterations, uint32_t subsets,
+             double relax, float lo, float hi, float* volume)
+{
+    return xrt_sirt_tv(ctx, width, height, num_planes, proj, matrices, dims, spacing, iterations, subsets, relax, lo, hi,
+                       nullptr, volume);
 }
 
 int xrt_hole_fill_device(xrt_context* ctx, uint32_t width, uint32_t height, const float* d_lbuffer,
