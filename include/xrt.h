@@ -1141,6 +1141,112 @@ int xrt_sirt_tv_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32
                        uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv, float* d_volume,
                        void* stream);
 
+/* --- material decomposition: a per-pixel Newton solver -------------------- */
+
+/*
+ * The inverse of xrt_spectral_detector under XRT_DETECT_EXPECTED (DESIGN.md
+ * section 10.14): projection-domain material decomposition.  Given the
+ * num_channels channel planes of a scan and the tables that produced them, per
+ * pixel the line integrals A_b of num_basis basis materials whose expected
+ * channels match the measured ones.  `weight`, `mu` (num_basis rows of
+ * num_bins), `response` (num_channels rows of num_bins) and `gain` mean exactly
+ * what they mean to xrt_spectral_detector, with basis materials in place of
+ * meshes, and are HOST memory in both forms; `in_mode` is the out_mode the
+ * channels were written under.  `channels` is num_channels f32 planes of
+ * num_pixels, `open` the uint16 masks (may be NULL: none set), `out` num_basis
+ * f32 planes of num_pixels -- path planes again, in xrt_render_paths' units --,
+ * `iters` a uint8 plane (may be NULL) of each pixel's status: the iterations
+ * it ran, XRT_DECOMPOSE_MASKED or XRT_DECOMPOSE_FAILED.  `guess` is
+ * xrt_decompose_guess' num_basis x num_channels f64 matrix in HOST memory in
+ * both forms, or NULL to start from zero.  With B = num_basis, C =
+ * num_channels, per pixel, in f64 unless written otherwise, every operation
+ * rounded on its own (nothing is fused):
+ *   if open && open[i] != 0:  out[b][i] = +0.0f for every b; iters[i] = 254; done
+ *   y[c] = (double)channels[c][i];  if in_mode == XRT_DETECT_INTENSITY: y[c] = y[c] * (double)gain
+ *   if guess == NULL: A[b] = 0.0
+ *   else:
+ *     y0[c] = the chain below at A = 0 (every exp is 1.0; computed on the host, travels with the launch)
+ *     t = (float)(y[c] / y0[c]);  if !(t >= 1e-30f): t = 1e-30f     (zero, negative and NaN counts start at the floor)
+ *     p[c] = -(double)logf(t)                                       (logf as xrt_log_projection's)
+ *     A[b] = 0.0; for c ascending: A[b] = A[b] + guess[b * C + c] * p[c]
+ *   it = 0
+ *   while it < max_iter:
+ *     ybar[c] = 0; J[c][b] = 0
+ *     for e ascending:
+ *       x = 0; for b ascending: x = x + (double)mu[b][e] * (A[b] * 0.1)
+ *       lam = ((double)weight[e] * exp(-x)) * (double)gain          (the detector's lam)
+ *       for c: t = (double)response[c][e] * lam
+ *              ybar[c] = ybar[c] + t
+ *              for b: J[c][b] = J[c][b] + (double)mu[b][e] * t
+ *     g[b] = 0; H[b][b'] = 0 (b' >= b)
+ *     for c ascending, skipped if !(ybar[c] > 0):                   (a zero response row, or underflow)
+ *       q = y[c] / ybar[c];  r = 1.0 - q;  v = 1.0 / ybar[c]
+ *       for b: g[b] = g[b] + J[c][b] * r
+ *       for b, b' >= b: H[b][b'] = H[b][b'] + (J[c][b] * J[c][b']) * v
+ *     for b: H[b][b] = H[b][b] + H[b][b] * damping
+ *     solve H d = g by LDL^T without pivoting, in this order (B = 1, 2 are its leading blocks):
+ *       d0 = H00;  l10 = H01/d0;  l20 = H02/d0
+ *       d1 = H11 - l10*H01;  l21 = (H12 - l20*H01)/d1
+ *       d2 = (H22 - l20*H02) - l21*(l21*d1)
+ *       z0 = g0;  z1 = g1 - l10*z0;  z2 = (g2 - l20*z0) - l21*z1
+ *       x2 = z2/d2;  x1 = z1/d1 - l21*x2;  x0 = (z0/d0 - l10*x1) - l20*x2
+ *     a pivot d_k that is not > 0: iters[i] = 255, A stays as it is, done
+ *     s[b] = x_b / 0.1;  A[b] = A[b] + s[b];  it = it + 1
+ *     if every |s[b]| <= tol: break
+ *   out[b][i] = (float)A[b];  iters[i] = it
+ * This is Fisher scoring on the Poisson likelihood of the channels: exp and
+ * division only, defined for zero and negative counts (read noise makes
+ * those).  For energy-integrating rows it is a consistent estimator, not the
+ * exact likelihood.  A NaN count makes the first step, and with it every
+ * output of its pixel, a NaN (sign and payload unspecified); as written above
+ * its status is then max_iter when max_iter is 1 and XRT_DECOMPOSE_FAILED
+ * otherwise (the second iteration's sums are NaN, every channel is left out
+ * and the pivot is 0).  With a guess the NaN count starts at the floor, far
+ * from the other channels' line integrals, and the pixel may fail in its first
+ * iteration instead, its outputs the finite start.  With a guess,
+ * a channel whose response row is all zeros has y0 = 0: its p is finite for a
+ * count of 0 and infinite otherwise, and 0 * inf starts the pixel at NaN --
+ * leave such rows out, or pass guess = NULL.
+ *
+ * xrt_decompose_guess is a host function and never touches the device:
+ *   mbar[c][b] = 0.1 * ((sum_e (r[c][e] * w[e]) * mu[b][e]) / (sum_e r[c][e] * w[e])), in f64 and bin order
+ *   guess = (mbar^T mbar)^-1 mbar^T over the channels whose denominator is > 0 (the columns of the others
+ *   are 0): N[b][b'] summed over c ascending, each column solved by the LDL^T order above
+ * so that guess times the channels' -ln(y / y0) is the least-squares line
+ * integral under each channel's mean coefficient.  From A = 0 the iteration
+ * advances about one attenuation length a step; from the guess a few steps
+ * suffice.  XRT_ERR_ARGUMENT for a NULL guess, what xrt_decompose refuses in the
+ * tables, and a pivot that is not > 0 ("basis materials are not separable under
+ * this response").
+ *
+ * xrt_decompose[_device]: XRT_ERR_ARGUMENT, with xrt_last_error naming the
+ * argument, for a NULL channels, weight, mu, response or out; what
+ * xrt_spectral_detector refuses in its tables, gain or modes; num_basis outside
+ * 1..XRT_MAX_BASIS; num_channels below num_basis or outside
+ * 1..XRT_MAX_CHANNELS; max_iter outside 1..200; a tol or damping that is
+ * negative or not finite; a guess entry that is not finite; num_pixels of 0 or
+ * more than one launch's 2^31 - 1 workgroups of 256 pixels hold; an out or
+ * iters that overlaps channels or open anywhere.  All of that is checked before
+ * the context is looked at.  xrt_decompose: host buffers, synchronous.
+ * _device: device buffers, asynchronous on `stream`; the tables and the guess
+ * travel with the launch, so the next call may bring others at once.  Neither
+ * touches the context's model, scene, state generation or frames in flight.
+ * There is no xrt_multi_ form.
+ */
+#define XRT_MAX_BASIS 3
+#define XRT_DECOMPOSE_MASKED 254
+#define XRT_DECOMPOSE_FAILED 255
+int xrt_decompose(xrt_context* ctx, uint64_t num_pixels, const float* channels, const uint16_t* open, const float* weight,
+                  const float* mu, uint32_t num_basis, uint32_t num_bins, const float* response, uint32_t num_channels,
+                  float gain, int in_mode, const double* guess, uint32_t max_iter, double tol, double damping, float* out,
+                  uint8_t* iters);
+int xrt_decompose_device(xrt_context* ctx, uint64_t num_pixels, const float* d_channels, const uint16_t* d_open,
+                         const float* weight, const float* mu, uint32_t num_basis, uint32_t num_bins, const float* response,
+                         uint32_t num_channels, float gain, int in_mode, const double* guess, uint32_t max_iter, double tol,
+                         double damping, float* d_out, uint8_t* d_iters, void* stream);
+int xrt_decompose_guess(const float* weight, const float* mu, uint32_t num_basis, uint32_t num_bins, const float* response,
+                        uint32_t num_channels, double* guess);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

@@ -411,6 +411,17 @@ int xrt_host_sirt_tv(uint32_t width, uint32_t height, uint32_t num_planes, const
                      float lo, float hi, const xrt_tv_params* tv, float* volume);
 
 /*
+ * Test hook of material decomposition.  Host code, no device: xrt_decompose's
+ * pixel function -- decompose_pixel, the one k_decompose calls, compiled for
+ * the host -- over whole buffers, arguments and checks as xrt_decompose's, host
+ * buffers.
+ */
+int xrt_host_decompose(uint64_t num_pixels, const float* channels, const uint16_t* open, const float* weight, const float* mu,
+                       uint32_t num_basis, uint32_t num_bins, const float* response, uint32_t num_channels, float gain,
+                       int in_mode, const double* guess, uint32_t max_iter, double tol, double damping, float* out,
+                       uint8_t* iters);
+
+/*
  * Diagnostics of a multi context's transit (xrt_multi_set_transit): [0]
  * frames whose strips travelled in the hit layout, [1] frames that travelled
  * packed, [2] bytes the last frame sent into device 0, [3] 1 when a received

@@ -21,7 +21,8 @@ from . import _abi
 from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F401
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
                    XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_MAX_SOURCES, XRT_MAX_BIN, XRT_MAX_RAMP_WIDTH, XRT_RAMP_RAMLAK, XRT_RAMP_HANN, XRT_FP_PROJECT, XRT_FP_RESIDUAL, XRT_MAX_SUBSETS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
-                   XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED)
+                   XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED, XRT_MAX_BASIS, XRT_DECOMPOSE_MASKED,
+                   XRT_DECOMPOSE_FAILED)
 
 __all__ = [
     "Camera", "Stats", "Context", "MultiContext", "XrtError", "load_ply", "mesh_bbox", "camera_from_bbox",
@@ -40,6 +41,7 @@ __all__ = [
     "fdk_scale", "backprojection_matrix", "save_volume", "host_fdk_filter", "host_backproject",
     "XRT_FP_PROJECT", "XRT_FP_RESIDUAL", "XRT_MAX_SUBSETS", "ray_matrix", "host_forward_project", "host_volume_update",
     "host_sirt", "host_tv_gradient", "host_volume_sumsq", "host_tv_descend",
+    "XRT_MAX_BASIS", "XRT_DECOMPOSE_MASKED", "XRT_DECOMPOSE_FAILED", "decompose_guess", "host_decompose", "decompose",
 ]
 
 
@@ -478,6 +480,80 @@ def spectral_detector(paths, open, weights, mu, response, gain=1.0, seed=0, nois
     with Context(device) as ctx:
         return ctx.spectral_detector(paths, open, weights, mu, response, gain, seed, noisy, counts, read_noise,
                                      first_index)
+
+
+def _decompose_tables(weights, mu, response):
+    """Material decomposition's tables: (weights (K,), mu (B, K), response (C, K))."""
+    w, mu = _spectrum_arrays(weights, mu)
+    return w, mu, _detector_response_rows(response, w.size)
+
+
+def decompose_guess(weights, mu, response) -> np.ndarray:
+    """xrt_decompose_guess: the (B, C) f64 matrix that turns the channels' -ln(y / y0) into the iteration's
+    starting line integrals, for the basis table (weights[K], mu[B, K]) under the response (C, K).  Host
+    arithmetic; no device."""
+    w, mu, r = _decompose_tables(weights, mu, response)
+    out = np.zeros((mu.shape[0], r.shape[0]), np.float64)
+    lib = _abi.load()
+    rc = lib.xrt_decompose_guess(_fptr(w), _fptr(mu), mu.shape[0], w.size, _fptr(r), r.shape[0],
+                                 out.ctypes.data_as(_abi._dp))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, (lib.xrt_last_error(None) or b"").decode() or "xrt_decompose_guess")
+    return out
+
+
+def _decompose_guess_arg(guess, w, mu, r):
+    """guess="auto": decompose_guess of the tables; None: none; an array: (B, C) f64."""
+    if guess is None:
+        return None
+    if isinstance(guess, str):
+        if guess != "auto":
+            raise ValueError(f"guess must be 'auto', None or a ({mu.shape[0]}, {r.shape[0]}) array, got {guess!r}")
+        return decompose_guess(w, mu, r)
+    g = np.ascontiguousarray(guess, dtype=np.float64)
+    if g.shape != (mu.shape[0], r.shape[0]):
+        raise ValueError(f"guess must have shape {(mu.shape[0], r.shape[0])}, got {g.shape}")
+    return g
+
+
+def _decompose_arrays(channels, open, weights, mu, response, guess):
+    """xrt_decompose's host arguments: (channels (C, ...) f32, open uint16 of a plane's shape or None, weights
+    (K,), mu (B, K), response (C, K), guess (B, C) f64 or None)."""
+    w, mu, r = _decompose_tables(weights, mu, response)
+    ch = np.ascontiguousarray(channels, dtype=np.float32)
+    if ch.ndim < 1 or ch.shape[0] != r.shape[0]:
+        raise ValueError(f"channels must hold {r.shape[0]} planes, got shape {ch.shape}")
+    o = None if open is None else np.ascontiguousarray(open, dtype=np.uint16)
+    if o is not None and o.shape != ch.shape[1:]:
+        raise ValueError(f"open must have a plane's shape {ch.shape[1:]}, got {o.shape}")
+    return ch, o, w, mu, r, _decompose_guess_arg(guess, w, mu, r)
+
+
+def _dptr(a):
+    return None if a is None else a.ctypes.data_as(_abi._dp)
+
+
+def host_decompose(channels, open, weights, mu, response, gain=1.0, counts=True, guess="auto", max_iter=32, tol=1e-6,
+                   damping=0.0, return_iters=False):
+    """Context.decompose in the device's arithmetic on the host (xrt_host_decompose, a test hook)."""
+    ch, o, w, mu, r, g = _decompose_arrays(channels, open, weights, mu, response, guess)
+    out = np.empty((mu.shape[0],) + ch.shape[1:], np.float32)
+    iters = np.empty(ch.shape[1:], np.uint8)
+    rc = _abi.load().xrt_host_decompose(
+        out[0].size, _fptr(ch), _u16ptr(o) if o is not None else None, _fptr(w), _fptr(mu), mu.shape[0], w.size, _fptr(r),
+        r.shape[0], float(gain), _detector_modes(False, counts)[1], _dptr(g), int(max_iter), float(tol), float(damping),
+        _fptr(out), _u8ptr(iters))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_decompose")
+    return (out, iters) if return_iters else out
+
+
+def decompose(channels, open, weights, mu, response, gain=1.0, counts=True, guess="auto", max_iter=32, tol=1e-6,
+              damping=0.0, return_iters=False, device: int = 0):
+    """The basis planes of Context.decompose, on a context of its own on `device`."""
+    with Context(device) as ctx:
+        return ctx.decompose(channels, open, weights, mu, response, gain, counts, guess, max_iter, tol, damping,
+                             return_iters)
 
 
 def _volume_arrays(labels, spacing, origin, density, num_labels):
@@ -1023,6 +1099,39 @@ class Context:
             _fptr(r), r.shape[0], float(gain), float(read_noise), int(seed), int(first_index), draw, mode,
             d_out or None, stream or None)
         self._check(rc, "xrt_spectral_detector_device")
+
+    def decompose(self, channels, open, weights, mu, response, gain=1.0, counts=True, guess="auto", max_iter=32,
+                  tol=1e-6, damping=0.0, return_iters=False):
+        """Projection-domain material decomposition, the inverse of spectral_detector(noisy=False): from the
+        channel planes ((C, ...) f32, as counts or -- counts=False -- as intensities) and the masks (or None)
+        the line integrals of the B basis materials of the table (weights[K], mu[B, K]) under the response
+        (C, K) and gain: (B, ...) f32 path planes, +0 where the mask is set.  Per pixel at most max_iter steps
+        of Fisher scoring, until no line integral moves by more than tol; damping scales the normal matrix's
+        diagonal by 1 + damping.  guess="auto" starts from decompose_guess' matrix, None from zero, an array is
+        the (B, C) matrix itself.  return_iters=True: also the uint8 plane of each pixel's iterations,
+        XRT_DECOMPOSE_MASKED or XRT_DECOMPOSE_FAILED."""
+        ch, o, w, mu, r, g = _decompose_arrays(channels, open, weights, mu, response, guess)
+        out = np.empty((mu.shape[0],) + ch.shape[1:], np.float32)
+        iters = np.empty(ch.shape[1:], np.uint8) if return_iters else None
+        self._check(self._lib.xrt_decompose(
+            self._ctx, out[0].size, _fptr(ch), _u16ptr(o) if o is not None else None, _fptr(w), _fptr(mu), mu.shape[0],
+            w.size, _fptr(r), r.shape[0], float(gain), _detector_modes(False, counts)[1], _dptr(g), int(max_iter),
+            float(tol), float(damping), _fptr(out), _u8ptr(iters) if iters is not None else None), "xrt_decompose")
+        return (out, iters) if return_iters else out
+
+    def decompose_device(self, num_pixels: int, d_channels: int, d_open: int, weights, mu, response, d_out: int,
+                         d_iters: int = 0, gain: float = 1.0, counts: bool = True, guess="auto", max_iter: int = 32,
+                         tol: float = 1e-6, damping: float = 0.0, stream: int = 0):
+        """decompose over device buffers (raw pointers; d_channels holds C planes of num_pixels, d_out B planes,
+        d_iters a uint8 plane or 0; the tables and the guess are host data and travel with the launch);
+        asynchronous on `stream`."""
+        w, mu, r = _decompose_tables(weights, mu, response)
+        g = _decompose_guess_arg(guess, w, mu, r)
+        rc = self._lib.xrt_decompose_device(
+            self._ctx, int(num_pixels), d_channels or None, d_open or None, _fptr(w), _fptr(mu), mu.shape[0], w.size,
+            _fptr(r), r.shape[0], float(gain), _detector_modes(False, counts)[1], _dptr(g), int(max_iter), float(tol),
+            float(damping), d_out or None, d_iters or None, stream or None)
+        self._check(rc, "xrt_decompose_device")
 
     def upload_volume(self, labels, spacing, origin=(0.0, 0.0, 0.0), density=None, num_labels=None):
         """A voxel volume: labels (nz, ny, nx) uint8 (0: empty, L into plane L - 1), voxels of `spacing` (one

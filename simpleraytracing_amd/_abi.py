@@ -60,6 +60,9 @@ XRT_RAMP_HANN = 1
 XRT_FP_PROJECT = 0
 XRT_FP_RESIDUAL = 1
 XRT_MAX_SUBSETS = 64
+XRT_MAX_BASIS = 3
+XRT_DECOMPOSE_MASKED = 254
+XRT_DECOMPOSE_FAILED = 255
 
 XRT_GATHER_AUTO = 0
 XRT_GATHER_COPY = 1
@@ -276,6 +279,13 @@ XRT_SYMBOLS = {
     "xrt_host_tv_descend": (ctypes.c_int, [_fp, _u32p, ctypes.c_double, _u32, ctypes.c_double, _f, _f]),
     "xrt_host_sirt_tv": (ctypes.c_int, [_u32, _u32, _u32, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f, _TvP,
                                         _fp]),
+    "xrt_decompose": (ctypes.c_int, [_CtxP, _u64, _fp, _u16p, _fp, _fp, _u32, _u32, _fp, _u32, ctypes.c_float, ctypes.c_int, _dp,
+                                     _u32, ctypes.c_double, ctypes.c_double, _fp, _u8p]),
+    "xrt_decompose_device": (ctypes.c_int, [_CtxP, _u64, _vp, _vp, _fp, _fp, _u32, _u32, _fp, _u32, ctypes.c_float,
+                                            ctypes.c_int, _dp, _u32, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]),
+    "xrt_decompose_guess": (ctypes.c_int, [_fp, _fp, _u32, _u32, _fp, _u32, _dp]),
+    "xrt_host_decompose": (ctypes.c_int, [_u64, _fp, _u16p, _fp, _fp, _u32, _u32, _fp, _u32, ctypes.c_float, ctypes.c_int, _dp,
+                                          _u32, ctypes.c_double, ctypes.c_double, _fp, _u8p]),
     "xrt_host_philox4x32": (None, [_u32p, _u32p, _u32p]),
     "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
     "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),

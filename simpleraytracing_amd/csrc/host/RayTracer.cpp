@@ -482,6 +482,47 @@ void applySpectralDetector(std::vector<Image>& channels, const std::vector<std::
         check(ctx, xrt_hole_fill(ctx, width, height, out.data() + c * n, channels[c].getData(), nullptr), "xrt_hole_fill");
 }
 
+unsigned long long decomposeMaterials(std::vector<Image>& basis, const std::vector<Image>& channels,
+                                      const std::vector<float>& weight, const std::vector<float>& mu,
+                                      const std::vector<float>& response, float gain, unsigned max_iter, double tol,
+                                      double damping, bool counts, bool from_guess)
+{
+    if (channels.empty() || basis.empty()) throw std::invalid_argument("decomposeMaterials: no channel or no basis images");
+    const unsigned width = channels[0].getWidth(), height = channels[0].getHeight();
+    const size_t n = (size_t)width * height;
+    for (const Image& image : channels)
+        if (image.getWidth() != width || image.getHeight() != height)
+            throw std::invalid_argument("decomposeMaterials: the channel images differ in size");
+    for (const Image& image : basis)
+        if (image.getWidth() != width || image.getHeight() != height)
+            throw std::invalid_argument("decomposeMaterials: a basis image is not of the channels' size");
+    if (weight.empty() || mu.size() != basis.size() * weight.size())
+        throw std::invalid_argument("decomposeMaterials: one coefficient per basis material and bin");
+    if (response.size() != channels.size() * weight.size())
+        throw std::invalid_argument("decomposeMaterials: one response per channel and bin");
+    const uint32_t B = (uint32_t)basis.size(), C = (uint32_t)channels.size(), K = (uint32_t)weight.size();
+    std::vector<float> planes;
+    planes.reserve(n * C);
+    for (const Image& image : channels) planes.insert(planes.end(), image.getData(), image.getData() + n);
+    std::vector<double> guess(from_guess ? (size_t)B * C : 0);
+    if (from_guess &&
+        xrt_decompose_guess(weight.data(), mu.data(), B, K, response.data(), C, guess.data()) != XRT_OK)
+        throw std::runtime_error(std::string("xrt_decompose_guess: ") + xrt_last_error(nullptr));
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    std::vector<float> out(n * B);
+    std::vector<uint8_t> iters(n);
+    check(ctx, xrt_decompose(ctx, n, planes.data(), nullptr, weight.data(), mu.data(), B, K, response.data(), C, gain,
+                             counts ? XRT_DETECT_COUNTS : XRT_DETECT_INTENSITY, from_guess ? guess.data() : nullptr,
+                             max_iter, tol, damping, out.data(), iters.data()),
+          "xrt_decompose");
+    for (uint32_t b = 0; b < B; ++b) std::copy(out.begin() + b * n, out.begin() + (b + 1) * n, basis[b].getData());
+    unsigned long long unconverged = 0;
+    for (uint8_t it : iters) unconverged += it == XRT_DECOMPOSE_FAILED || it == max_iter;
+    return unconverged;
+}
+
 void applyDetectorResponse(Image& image, const std::vector<float>& lsf_x, const std::vector<float>& lsf_y)
 {
     const size_t n = (size_t)image.getWidth() * image.getHeight();

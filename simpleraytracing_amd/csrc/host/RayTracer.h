@@ -155,6 +155,22 @@ void applySpectralDetector(std::vector<Image>& channels, const std::vector<std::
                            float read_noise = 0.0f, unsigned long long seed = 0, unsigned long long first_index = 0,
                            bool noisy = false);
 
+// Material decomposition (xrt_decompose), the inverse of
+// applySpectralDetector without noise: from the channel images (as
+// intensities, the detector's output, unless `counts`) the line integrals of
+// basis.size() basis materials under the table (`weight`, and `mu`: one row of
+// weight.size() coefficients per basis material, one after another), `response`
+// and `gain`, all as the detector took them.  Per pixel at most max_iter
+// iterations, until no line integral moves by more than tol, from
+// xrt_decompose_guess' start (from_guess) or from zero; damping scales the
+// normal matrix's diagonal by 1 + damping.  Every basis image must come with
+// the channels' width and height.  Returns the number of pixels that failed
+// (XRT_DECOMPOSE_FAILED) or ran max_iter iterations.  One device.
+unsigned long long decomposeMaterials(std::vector<Image>& basis, const std::vector<Image>& channels,
+                                      const std::vector<float>& weight, const std::vector<float>& mu,
+                                      const std::vector<float>& response, float gain = 1.0f, unsigned max_iter = 32,
+                                      double tol = 1e-6, double damping = 0.0, bool counts = false, bool from_guess = true);
+
 // Voxel volumes (xrt_upload_volume).  getVolumeBBox: the
 // volume's box (xrt_volume_bbox), to pass to initialiseRayTracing alone or in
 // union with getBBox's.  uploadVolume: the volume onto the render device,

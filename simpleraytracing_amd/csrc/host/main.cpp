@@ -127,6 +127,18 @@
 //                              --sinogram, --supersample, --focal-spot, -g, --rows, --batch
 //       --read-noise SIGMA     with --detector and --noise: additive Gaussian (electronic)
 //                              noise of SIGMA counts (finite, >= 0) on every channel
+//       --decompose BASIS[:ITER[:TOL]]  with --detector: material decomposition of the
+//                              channels as written (the text files' six significant
+//                              digits, after the hole fill, as intensities under the
+//                              detector's gain), so that the files on disk reproduce it.
+//                              BASIS is text: one line of K coefficients (finite, >= 0)
+//                              per basis material, 1 to 3 lines ('#' starts a comment), K
+//                              the spectrum's bins; at most ITER iterations a pixel
+//                              (1 to 200, default 32) until no line integral moves by
+//                              more than TOL (default 1e-6), from xrt_decompose_guess'
+//                              start.  Writes NAME.b<b>.EXT per basis material, after the
+//                              channels, and prints the number of pixels that failed or
+//                              ran ITER iterations.  Not with -g N
 //       --volume FILE.mhd      with --paths: a voxel phantom beside the meshes (or alone:
 //                              -i may then be omitted).  FILE.mhd is a MetaImage header
 //                              of MET_UCHAR labels (0: empty) with its raw file beside
@@ -198,6 +210,7 @@ void showUsage(const std::string& prog)
               << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
               << "\t--detector FILE\t\t\tSpectral detector, with --paths --spectrum: FILE holds one line of K responses per energy channel (at most 8); writes NAME.c<c>.EXT per channel; with --noise GAIN[:SEED] a Poisson count per bin, divided by GAIN, otherwise the expected values at gain 1\n"
               << "\t--read-noise SIGMA\t\tWith --detector and --noise: additive Gaussian noise of SIGMA counts on every channel\n"
+              << "\t--decompose BASIS[:ITER[:TOL]]\tWith --detector: material decomposition of the written channels; BASIS holds one line of K coefficients per basis material (1 to 3); at most ITER iterations a pixel (1 to 200, default 32), until no line integral moves by more than TOL (default 1e-6); writes NAME.b<b>.EXT per basis material and prints the unconverged count\n"
               << "\t--volume FILE.mhd\t\tWith --paths: a voxel phantom (MetaImage header, MET_UCHAR labels, raw file beside it) beside the meshes or alone (no -i); one plane per label behind the meshes' (NAME.m<k>.EXT), one --spectrum row per mesh, then per label; not with -g, --rows, --batch, --supersample, --focal-spot, --turntable, --pose\n"
               << "\t--volume-density FILE.mhd\tWith --volume: a MET_FLOAT density per voxel, of the volume's dims\n"
               << "\t--lbuffer FILE\t\t\tWrite the L-buffer as raw float32\n"
@@ -252,6 +265,10 @@ struct Options {
     bool read_noise_set = false;               // --read-noise SIGMA
     float read_noise = 0.0f;
     std::string volume, volume_density;        // --volume FILE.mhd, --volume-density FILE.mhd
+    bool decompose = false;                    // --decompose BASIS[:ITER[:TOL]]: one row of K coefficients per basis material
+    std::vector<std::vector<float>> basis_rows;
+    unsigned decompose_iter = 32;
+    double decompose_tol = 1e-6;
 };
 
 // A whole, non-negative decimal number.
@@ -387,18 +404,21 @@ void read_spectrum(const std::string& path, std::vector<float>& weight, std::vec
     if (mu.empty()) throw std::runtime_error("--spectrum: " + path + " holds no mesh's coefficients");
 }
 
-// --detector FILE: every data line is one channel's responses ('#' starts a
-// comment, blank lines are skipped).  The lines' length is checked against the
-// spectrum's bins once every option is read.
-void read_detector(const std::string& path, std::vector<std::vector<float>>& rows)
+// A table of rows (--detector FILE, --decompose BASIS): every data line is one
+// row of finite values >= 0 ('#' starts a comment, blank lines are skipped), at
+// most max_rows of them.  `value` names a value, `row` a row and `many` several
+// in the errors.  The lines' length is checked against the spectrum's bins
+// once every option is read.
+void read_rows(const std::string& option, const std::string& path, const char* value, const char* row, const char* many,
+               size_t max_rows, std::vector<std::vector<float>>& rows)
 {
     std::ifstream in(path);
-    if (!in) throw std::runtime_error("--detector: cannot read " + path);
+    if (!in) throw std::runtime_error(option + ": cannot read " + path);
     std::string line;
     for (unsigned n = 1; std::getline(in, line); ++n) {
         line = line.substr(0, line.find('#'));
         std::istringstream fields(line);
-        std::vector<float> row;
+        std::vector<float> values;
         for (std::string f; fields >> f;) {
             size_t used = 0;
             float v = 0.0f;
@@ -408,17 +428,57 @@ void read_detector(const std::string& path, std::vector<std::vector<float>>& row
                 used = 0;
             }
             if (used != f.size() || !std::isfinite(v) || v < 0.0f)
-                throw std::runtime_error("--detector: " + path + ":" + std::to_string(n) + ": '" + f +
-                                         "' is not a response (a finite number, >= 0)");
-            row.push_back(v);
+                throw std::runtime_error(option + ": " + path + ":" + std::to_string(n) + ": '" + f + "' is not a " + value +
+                                         " (a finite number, >= 0)");
+            values.push_back(v);
         }
-        if (row.empty()) continue;
-        if (rows.size() == XRT_MAX_CHANNELS)
-            throw std::runtime_error("--detector: " + path + ":" + std::to_string(n) + ": more than " +
-                                     std::to_string(XRT_MAX_CHANNELS) + " channels");
-        rows.push_back(row);
+        if (values.empty()) continue;
+        if (rows.size() == max_rows)
+            throw std::runtime_error(option + ": " + path + ":" + std::to_string(n) + ": more than " +
+                                     std::to_string(max_rows) + " " + many);
+        rows.push_back(values);
     }
-    if (rows.empty()) throw std::runtime_error("--detector: " + path + " holds no channel");
+    if (rows.empty()) throw std::runtime_error(option + ": " + path + " holds no " + row);
+}
+
+// --detector FILE: one line of K responses per channel.
+void read_detector(const std::string& path, std::vector<std::vector<float>>& rows)
+{
+    read_rows("--detector", path, "response", "channel", "channels", XRT_MAX_CHANNELS, rows);
+}
+
+// --decompose BASIS[:ITER[:TOL]]: BASIS holds one line of K coefficients per
+// basis material.
+void parse_decompose(const std::string& arg, Options& o)
+{
+    const std::vector<std::string> parts = split(arg, ':');
+    bool ok = parts.size() >= 1 && parts.size() <= 3 && !parts[0].empty();
+    if (ok && parts.size() >= 2) ok = parse_index(parts[1], o.decompose_iter) && o.decompose_iter >= 1 && o.decompose_iter <= 200;
+    if (ok && parts.size() == 3) {
+        size_t used = 0;
+        try {
+            o.decompose_tol = std::stod(parts[2], &used);
+        } catch (const std::exception&) {
+            used = 0;
+        }
+        ok = !parts[2].empty() && used == parts[2].size() && std::isfinite(o.decompose_tol) && o.decompose_tol >= 0.0;
+    }
+    if (!ok)
+        throw std::runtime_error("--decompose BASIS[:ITER[:TOL]]: BASIS a file, ITER iterations (1 to 200), TOL a finite number, >= 0");
+    o.basis_rows.clear();
+    read_rows("--decompose", parts[0], "coefficient", "basis material", "basis materials", XRT_MAX_BASIS, o.basis_rows);
+}
+
+// A channel image as its text file holds it: every value through the writer's
+// "%.6g" and back, so that --decompose sees what a reader of the file sees.
+void round_as_written(Image& image)
+{
+    float* v = image.getData();
+    char buf[32];
+    for (size_t i = 0, n = (size_t)image.getWidth() * image.getHeight(); i < n; ++i) {
+        std::snprintf(buf, sizeof buf, "%.6g", (double)v[i]);
+        v[i] = (float)std::strtod(buf, nullptr);
+    }
 }
 
 // --read-noise SIGMA
@@ -682,6 +742,9 @@ Options processCmd(int argc, char** argv)
             o.detector = true;
             o.detector_rows.clear();
             read_detector(parse_str(argv[0], argc, argv, i), o.detector_rows);
+        } else if (a == "--decompose") {
+            o.decompose = true;
+            parse_decompose(parse_str(argv[0], argc, argv, i), o);
         } else if (a == "--read-noise") {
             o.read_noise = parse_read_noise(parse_str(argv[0], argc, argv, i));
             o.read_noise_set = true;
@@ -721,6 +784,17 @@ Options processCmd(int argc, char** argv)
                            : o.focal_spot ? "--focal-spot" : o.turntable ? "--turntable" : !o.poses.empty() ? "--pose" : nullptr;
         if (with)
             throw std::runtime_error(std::string("--volume traces whole frames on one GPU and has no pose: not with ") + with);
+    }
+    if (o.decompose) {
+        if (!o.detector) throw std::runtime_error("--decompose needs --detector FILE: it inverts that detector's channels");
+        if (o.gpus > 1) throw std::runtime_error("--decompose runs on one GPU: not with -g N");
+        for (const std::vector<float>& row : o.basis_rows)
+            if (row.size() != o.spectrum_weight.size())
+                throw std::runtime_error("--decompose: " + std::to_string(row.size()) + " coefficients in a line, " +
+                                         std::to_string(o.spectrum_weight.size()) + " bins in --spectrum's table");
+        if (o.basis_rows.size() > o.detector_rows.size())
+            throw std::runtime_error("--decompose: " + std::to_string(o.basis_rows.size()) + " basis materials need at least as many channels, --detector's file holds " +
+                                     std::to_string(o.detector_rows.size()));
     }
     if (o.rows && (o.row_begin >= o.row_end || o.row_end > o.height))
         throw std::out_of_range("--rows A:B must satisfy 0 <= A < B <= image height");
@@ -981,6 +1055,19 @@ int main(int argc, char** argv)
                                           opt.noise_seed, (unsigned long long)projection * opt.width * opt.height, opt.noise);
                     for (size_t c = 0; c < channels.size(); ++c)
                         channels[c].saveTextFile(stem + ".c" + std::to_string(c) + suffix);
+                    if (opt.decompose) {              // the channels as the files hold them, into one plane per basis material
+                        for (Image& channel : channels) round_as_written(channel);
+                        std::vector<float> basis_mu;
+                        for (const std::vector<float>& row : opt.basis_rows) basis_mu.insert(basis_mu.end(), row.begin(), row.end());
+                        std::vector<Image> basis(opt.basis_rows.size(), Image(opt.width, opt.height, 0.0f));
+                        const unsigned long long unconverged =
+                            decomposeMaterials(basis, channels, opt.spectrum_weight, basis_mu, response,
+                                               opt.noise ? opt.noise_gain : 1.0f, opt.decompose_iter, opt.decompose_tol);
+                        for (size_t b = 0; b < basis.size(); ++b)
+                            basis[b].saveTextFile(stem + ".b" + std::to_string(b) + suffix);
+                        std::cout << "Decomposition: " << unconverged << " of " << (size_t)opt.width * opt.height
+                                  << " pixels failed or ran " << opt.decompose_iter << " iterations" << std::endl;
+                    }
                 }
             } else if (area) {                        // every sub-source at the finer size, then one integration
                 std::vector<RayTracerInfo> sources(1, info);

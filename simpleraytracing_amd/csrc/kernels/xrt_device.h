@@ -1482,6 +1482,191 @@ __host__ __device__ __forceinline__ float xrt_detector_output(double acc, float 
 }
 
 // ---------------------------------------------------------------------------
+// Material decomposition (the contract is include/xrt.h's): the
+// inverse of the spectral detector under XRT_DETECT_EXPECTED.  Per pixel the
+// line integrals A[0 .. kB) of kB basis materials whose expected channels
+// match the measured ones, by Fisher scoring on the channels' Poisson
+// likelihood: per iteration the detector's bin chain with the Jacobian beside
+// it, a kB x kB normal matrix, an LDL^T solve.  All of it f64, every operation
+// rounded on its own, exp and division only.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMaxBasis = 3;
+constexpr uint32_t kDecomposeThreads = 256;
+constexpr uint32_t kDecomposeMaxIter = 200;
+constexpr uint32_t kDecomposeMasked = 254;
+constexpr uint32_t kDecomposeFailed = 255;
+
+// What k_decompose takes by value (a launch owns its tables).  mu quad by quad
+// as DetectorSpectrum's, with kMaxBasis rows a quad: the coefficients of basis
+// b for the four bins of quad q are one 16-byte scalar load.  weight, mu and
+// response are +0.0f past num_bins, num_basis and num_channels.  guess[b *
+// kMaxChannels + c] and y0[c] (the expected channels at A = 0) are the host's;
+// without a guess has_guess is 0 and neither is read.
+struct DecomposeTable {
+    float weight[kMaxBins];
+    float mu[kMaxBins * kMaxBasis];            // [decompose_mu_index(b, e)]
+    float response[kMaxChannels * kMaxBins];   // [c * kMaxBins + e]
+    double guess[kMaxBasis * kMaxChannels];
+    double y0[kMaxChannels];
+    double tol;
+    double damping;
+    float gain;
+    uint32_t num_bins;
+    uint32_t num_channels;
+    uint32_t max_iter;
+    uint32_t intensity;                        // XRT_DETECT_INTENSITY: 1
+    uint32_t has_guess;
+    const float* channels;
+    const uint16_t* open;
+    float* out;
+    uint8_t* iters;
+    uint64_t plane;
+};
+__host__ __device__ constexpr uint32_t decompose_mu_index(uint32_t b, uint32_t e)
+{
+    return ((e >> 2) * kMaxBasis + b) * 4u + (e & 3u);
+}
+static_assert(sizeof(DecomposeTable) + 64u <= 4096u, "k_decompose's argument segment");
+
+// H d = g for the upper triangle H of a symmetric kB x kB matrix by LDL^T
+// without pivoting, in the contract's order (kB = 1, 2 are its leading
+// blocks); false, with x untouched, when a pivot is not > 0.
+template <uint32_t kB>
+__host__ __device__ __forceinline__ bool decompose_solve(const double (&H)[kMaxBasis][kMaxBasis], const double (&g)[kMaxBasis],
+                                                         double (&x)[kMaxBasis])
+{
+    static_assert(kB >= 1 && kB <= kMaxBasis, "1 to 3 basis materials");
+    const double d0 = H[0][0];
+    if (kB == 1) {
+        if (!(d0 > 0.0)) return false;
+        x[0] = g[0] / d0;
+        return true;
+    }
+    const double l10 = H[0][1] / d0;
+    const double d1 = H[1][1] - l10 * H[0][1];
+    const double z0 = g[0];
+    const double z1 = g[1] - l10 * z0;
+    if (kB == 2) {
+        if (!(d0 > 0.0) || !(d1 > 0.0)) return false;
+        x[1] = z1 / d1;
+        x[0] = z0 / d0 - l10 * x[1];
+        return true;
+    }
+    const double l20 = H[0][2] / d0;
+    const double l21 = (H[1][2] - l20 * H[0][1]) / d1;
+    const double d2 = (H[2][2] - l20 * H[0][2]) - l21 * (l21 * d1);
+    const double z2 = (g[2] - l20 * z0) - l21 * z1;
+    if (!(d0 > 0.0) || !(d1 > 0.0) || !(d2 > 0.0)) return false;
+    x[2] = z2 / d2;
+    x[1] = z1 / d1 - l21 * x[2];
+    x[0] = (z0 / d0 - l10 * x[1]) - l20 * x[2];
+    return true;
+}
+
+// One unmasked pixel: A[0 .. kB) from its counts y[0 .. kC) (intensities
+// already times gain), and the status its iters entry gets -- the iterations
+// run, or kDecomposeFailed.  kC >= num_channels is a compile-time bound, so
+// that every sum keeps a static index: resp(c, e) is +0.0f for a row past
+// num_channels, whose ybar is then +0.0 or a NaN and which the contract's
+// !(ybar > 0) leaves out as it leaves out a zero row; the start reads only the
+// rows below num_channels.  mu(b, e), weight(e) and resp(c, e) are +0.0f for
+// a bin past num_bins in the last quad: its x is dropped, its lam is +0.0 and
+// adds +0.0 to sums that are never -0.0.  guess(b, c) and y0(c) are asked only
+// when has_guess.
+template <uint32_t kB, uint32_t kC, typename Mu, typename Weight, typename Resp, typename Guess, typename Y0>
+__host__ __device__ __forceinline__ uint32_t decompose_pixel(uint32_t num_bins, uint32_t num_channels, Mu mu, Weight weight,
+                                                             Resp resp, float gain, const double (&y)[kC], bool has_guess,
+                                                             Guess guess, Y0 y0, uint32_t max_iter, double tol, double damping,
+                                                             double (&A)[kB])
+{
+    const double gd = (double)gain;
+#pragma unroll
+    for (uint32_t b = 0; b < kB; ++b) A[b] = 0.0;
+    if (has_guess) {
+        double p[kC];
+#pragma unroll
+        for (uint32_t c = 0; c < kC; ++c) {
+            p[c] = 0.0;
+            if (c < num_channels) {
+                float t = (float)(y[c] / y0(c));
+                if (!(t >= 1e-30f)) t = 1e-30f;                 // zero, negative and NaN counts start at the floor
+                p[c] = -(double)xrt_logf(t);
+            }
+        }
+#pragma unroll
+        for (uint32_t b = 0; b < kB; ++b) {
+#pragma unroll
+            for (uint32_t c = 0; c < kC; ++c)
+                if (c < num_channels) A[b] = A[b] + guess(b, c) * p[c];
+        }
+    }
+    uint32_t it = 0;
+    while (it < max_iter) {
+        double ybar[kC], J[kC][kB];
+#pragma unroll
+        for (uint32_t c = 0; c < kC; ++c) {
+            ybar[c] = 0.0;
+#pragma unroll
+            for (uint32_t b = 0; b < kB; ++b) J[c][b] = 0.0;
+        }
+        double a01[kB];
+#pragma unroll
+        for (uint32_t b = 0; b < kB; ++b) a01[b] = A[b] * 0.1;
+        for (uint32_t q = 0; 4u * q < num_bins; ++q) {
+            double x[4] = {0.0, 0.0, 0.0, 0.0}, nx[4], ex[4];
+#pragma unroll
+            for (uint32_t b = 0; b < kB; ++b) {
+#pragma unroll
+                for (uint32_t r = 0; r < 4; ++r) x[r] = x[r] + (double)mu(b, 4u * q + r) * a01[b];
+            }
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) nx[r] = 4u * q + r < num_bins ? -x[r] : -0.0;
+            xrt_exp_quad(nx, ex);
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) {
+                const double lam = ((double)weight(4u * q + r) * ex[r]) * gd;
+#pragma unroll
+                for (uint32_t c = 0; c < kC; ++c) {
+                    const double t = (double)resp(c, 4u * q + r) * lam;
+                    ybar[c] = ybar[c] + t;
+#pragma unroll
+                    for (uint32_t b = 0; b < kB; ++b) J[c][b] = J[c][b] + (double)mu(b, 4u * q + r) * t;
+                }
+            }
+        }
+        double g[kMaxBasis] = {0.0, 0.0, 0.0}, H[kMaxBasis][kMaxBasis] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+        for (uint32_t c = 0; c < kC; ++c) {
+            if (!(ybar[c] > 0.0)) continue;                     // a zero response row, or underflow
+            const double qc = y[c] / ybar[c];
+            const double rc = 1.0 - qc;
+            const double v = 1.0 / ybar[c];
+#pragma unroll
+            for (uint32_t b = 0; b < kB; ++b) g[b] = g[b] + J[c][b] * rc;
+#pragma unroll
+            for (uint32_t b = 0; b < kB; ++b) {
+#pragma unroll
+                for (uint32_t b2 = b; b2 < kB; ++b2) H[b][b2] = H[b][b2] + (J[c][b] * J[c][b2]) * v;
+            }
+        }
+#pragma unroll
+        for (uint32_t b = 0; b < kB; ++b) H[b][b] = H[b][b] + H[b][b] * damping;
+        double d[kMaxBasis] = {0.0, 0.0, 0.0};
+        if (!decompose_solve<kB>(H, g, d)) return kDecomposeFailed;
+        bool done = true;
+#pragma unroll
+        for (uint32_t b = 0; b < kB; ++b) {
+            const double s = d[b] / 0.1;
+            A[b] = A[b] + s;
+            done = done && s <= tol && -s <= tol;
+        }
+        ++it;
+        if (done) break;
+    }
+    return it;
+}
+
+// ---------------------------------------------------------------------------
 // Voxel phantoms: a labelled, axis-aligned volume traced into
 // paths planes.  volume_ray is the contract: k_volume_paths calls it on the
 // device and xrt_host_volume_paths compiled for the host, and

@@ -4850,4 +4850,48 @@ __global__ __launch_bounds__(kUpdateThreads) void k_tv_step(uint64_t n, float* _
         x[i] = tv_step_voxel(x[i], g[i], c, lo, hi);
 }
 
+// ---------------------------------------------------------------------------
+// k_decompose: material decomposition over channel planes, in
+// k_spectral_detector's shape: one lane a pixel, 256-thread blocks, 64-bit
+// indices, the tables by value in the argument segment (a launch owns them).
+// A lane past the plane or with its mask set leaves at once; the others run
+// decompose_pixel, each its own number of iterations: the wave goes on, with
+// the converged lanes switched off, until its last lane is through.  kB is the
+// number of basis materials (1, 2, 3), kC bounds the channels (2, 4, 8: the
+// host picks the smallest that holds num_channels; rows past it are zero,
+// never read from the planes and left out by the pixel function itself).  The
+// channel sums and the Jacobian, kC (1 + kB) f64, stay in registers with
+// static indices across the bin loop; a quad's coefficients, weights and
+// responses are scalar loads from the argument segment.  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+template <uint32_t kB, uint32_t kC>
+__global__ __launch_bounds__(kDecomposeThreads) void k_decompose(size_t n, const DecomposeTable tab)
+{
+    static_assert(kC == 2 || kC == 4 || kC == 8, "the three channel bounds");
+    const size_t i = (size_t)blockIdx.x * kDecomposeThreads + threadIdx.x;
+    if (i >= n) return;
+    if (tab.open && tab.open[i] != 0) {
+#pragma unroll
+        for (uint32_t b = 0; b < kB; ++b) tab.out[b * tab.plane + i] = 0.0f;
+        if (tab.iters) tab.iters[i] = (uint8_t)kDecomposeMasked;
+        return;
+    }
+    const uint32_t C = tab.num_channels;
+    double y[kC];
+#pragma unroll
+    for (uint32_t c = 0; c < kC; ++c) {
+        y[c] = c < C ? (double)tab.channels[c * tab.plane + i] : 0.0;
+        if (tab.intensity) y[c] = y[c] * (double)tab.gain;
+    }
+    double A[kB];
+    const uint32_t status = decompose_pixel<kB, kC>(
+        tab.num_bins, C, [&](uint32_t b, uint32_t e) { return tab.mu[decompose_mu_index(b, e)]; },
+        [&](uint32_t e) { return tab.weight[e]; }, [&](uint32_t c, uint32_t e) { return tab.response[c * kMaxBins + e]; },
+        tab.gain, y, tab.has_guess != 0u, [&](uint32_t b, uint32_t c) { return tab.guess[b * kMaxChannels + c]; },
+        [&](uint32_t c) { return tab.y0[c]; }, tab.max_iter, tab.tol, tab.damping, A);
+#pragma unroll
+    for (uint32_t b = 0; b < kB; ++b) tab.out[b * tab.plane + i] = (float)A[b];
+    if (tab.iters) tab.iters[i] = (uint8_t)status;
+}
+
 }  // namespace XRT_KERNEL_NS

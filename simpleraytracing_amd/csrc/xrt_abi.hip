@@ -3423,6 +3423,91 @@ int xrt_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_pla
                        nullptr, volume);
 }
 
+// --- material decomposition ----------------------------------
+
+#include "xrt_decompose_host.inc"
+
+int xrt_decompose_guess(const float* weight, const float* mu, uint32_t num_basis, uint32_t num_bins, const float* response,
+                        uint32_t num_channels, double* guess)
+{
+    if (!guess) return fail(nullptr, XRT_ERR_ARGUMENT, "guess is NULL");
+    const char* why = decompose_table_arguments(weight, mu, num_basis, num_bins, response, num_channels, 1.0f);
+    if (!why) why = decompose_guess_matrix(weight, mu, num_basis, num_bins, response, num_channels, guess);
+    return why ? fail(nullptr, XRT_ERR_ARGUMENT, why) : XRT_OK;
+}
+
+// The launch of k_decompose (validated arguments, device pointers): the instantiation of num_basis and of
+// the smallest channel bound that holds num_channels.
+static int launch_decompose(xrt_context* ctx, uint64_t n, const float* d_channels, const uint16_t* d_open, const float* weight,
+                            const float* mu, uint32_t num_basis, uint32_t num_bins, const float* response,
+                            uint32_t num_channels, float gain, int in_mode, const double* guess, uint32_t max_iter, double tol,
+                            double damping, float* d_out, uint8_t* d_iters, hipStream_t stream)
+{
+    DecomposeTable tab;                 // by value: the launch owns its copy (no context state, no wait)
+    decompose_table(weight, mu, num_basis, num_bins, response, num_channels, gain, in_mode, guess, max_iter, tol, damping,
+                    &tab);
+    tab.channels = d_channels;
+    tab.open = d_open;
+    tab.out = d_out;
+    tab.iters = d_iters;
+    tab.plane = n;
+    const dim3 grid((unsigned)((n + kDecomposeThreads - 1u) / kDecomposeThreads)), block(kDecomposeThreads);
+#define XRT_DECOMPOSE_LAUNCH(B)                                                                                  \
+    do {                                                                                                         \
+        if (num_channels <= 2u)                                                                                  \
+            hipLaunchKernelGGL((k_decompose<B, 2>), grid, block, 0, stream, (size_t)n, tab);                     \
+        else if (num_channels <= 4u)                                                                             \
+            hipLaunchKernelGGL((k_decompose<B, 4>), grid, block, 0, stream, (size_t)n, tab);                     \
+        else                                                                                                     \
+            hipLaunchKernelGGL((k_decompose<B, 8>), grid, block, 0, stream, (size_t)n, tab);                     \
+    } while (0)
+    if (num_basis == 1u) XRT_DECOMPOSE_LAUNCH(1);
+    else if (num_basis == 2u) XRT_DECOMPOSE_LAUNCH(2);
+    else XRT_DECOMPOSE_LAUNCH(3);
+#undef XRT_DECOMPOSE_LAUNCH
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_decompose_device(xrt_context* ctx, uint64_t num_pixels, const float* d_channels, const uint16_t* d_open,
+                         const float* weight, const float* mu, uint32_t num_basis, uint32_t num_bins, const float* response,
+                         uint32_t num_channels, float gain, int in_mode, const double* guess, uint32_t max_iter, double tol,
+                         double damping, float* d_out, uint8_t* d_iters, void* stream)
+{
+    if (const char* why = decompose_arguments(num_pixels, d_channels, d_open, weight, mu, num_basis, num_bins, response,
+                                              num_channels, gain, in_mode, guess, max_iter, tol, damping, d_out, d_iters))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_decompose(ctx, num_pixels, d_channels, d_open, weight, mu, num_basis, num_bins, response, num_channels, gain,
+                            in_mode, guess, max_iter, tol, damping, d_out, d_iters, (hipStream_t)stream);
+}
+
+int xrt_decompose(xrt_context* ctx, uint64_t num_pixels, const float* channels, const uint16_t* open, const float* weight,
+                  const float* mu, uint32_t num_basis, uint32_t num_bins, const float* response, uint32_t num_channels,
+                  float gain, int in_mode, const double* guess, uint32_t max_iter, double tol, double damping, float* out,
+                  uint8_t* iters)
+{
+    if (const char* why = decompose_arguments(num_pixels, channels, open, weight, mu, num_basis, num_bins, response,
+                                              num_channels, gain, in_mode, guess, max_iter, tol, damping, out, iters))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)num_pixels;
+    DeviceScratch s(ctx, ctx->host_stream, "decomposition");
+    const float* dc = s.upload(channels, n * num_channels);
+    const uint16_t* dopen = s.upload(open, n);
+    float* dout = s.alloc<float>(n * num_basis);
+    uint8_t* diters = s.alloc<uint8_t>(n, iters != nullptr);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_decompose(ctx, n, dc, dopen, weight, mu, num_basis, num_bins, response, num_channels, gain, in_mode,
+                                  guess, max_iter, tol, damping, dout, diters, ctx->host_stream))
+        return rc;
+    s.download(out, dout, n * num_basis);
+    s.download(iters, static_cast<const uint8_t*>(diters), n);
+    return s.finish();
+}
+
 int xrt_hole_fill_device(xrt_context* ctx, uint32_t width, uint32_t height, const float* d_lbuffer,
                          float* d_image, uint8_t* d_u8, void* stream)
 {

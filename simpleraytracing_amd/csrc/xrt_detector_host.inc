@@ -25,6 +25,17 @@ static const char* spectrum_arguments(const float* weight, const float* mu, uint
 static_assert(XRT_MAX_CHANNELS == XRT_KERNEL_NS::kMaxChannels && XRT_MAX_BINS == XRT_KERNEL_NS::kMaxBins,
               "the contract's bounds are the tables'");
 
+// The argument checks of a response matrix (not NULL, under a checked num_bins) and its gain, which
+// xrt_decompose shares; null when they pass.
+static const char* response_arguments(const float* response, uint32_t num_channels, uint32_t num_bins, float gain)
+{
+    if (num_channels < 1 || num_channels > XRT_MAX_CHANNELS) return "num_channels is not 1 to XRT_MAX_CHANNELS";
+    for (uint32_t k = 0; k < num_channels * num_bins; ++k)
+        if (!std::isfinite(response[k]) || response[k] < 0.0f) return "a response must be finite and >= 0";
+    if (!std::isfinite(gain) || !(gain > 0.0f)) return "gain is not finite and > 0";
+    return nullptr;
+}
+
 // Every check of xrt_spectral_detector[_device], none of which needs a context:
 // what is wrong, or NULL.
 static const char* detector_arguments(uint64_t num_pixels, uint32_t num_meshes, const float* paths, const uint16_t* open,
@@ -36,10 +47,7 @@ static const char* detector_arguments(uint64_t num_pixels, uint32_t num_meshes, 
     if (!response) return "response is NULL";
     if (!out) return "out is NULL";
     if (const char* why = spectrum_arguments(weight, mu, num_meshes, num_bins)) return why;
-    if (num_channels < 1 || num_channels > XRT_MAX_CHANNELS) return "num_channels is not 1 to XRT_MAX_CHANNELS";
-    for (uint32_t k = 0; k < num_channels * num_bins; ++k)
-        if (!std::isfinite(response[k]) || response[k] < 0.0f) return "a response must be finite and >= 0";
-    if (!std::isfinite(gain) || !(gain > 0.0f)) return "gain is not finite and > 0";
+    if (const char* why = response_arguments(response, num_channels, num_bins, gain)) return why;
     if (draw_mode != XRT_DETECT_EXPECTED && draw_mode != XRT_DETECT_NOISY)
         return "draw_mode is neither XRT_DETECT_EXPECTED nor XRT_DETECT_NOISY";
     if (out_mode != XRT_DETECT_COUNTS && out_mode != XRT_DETECT_INTENSITY)
