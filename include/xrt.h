@@ -1247,6 +1247,74 @@ int xrt_decompose_device(xrt_context* ctx, uint64_t num_pixels, const float* d_c
 int xrt_decompose_guess(const float* weight, const float* mu, uint32_t num_basis, uint32_t num_bins, const float* response,
                         uint32_t num_channels, double* guess);
 
+/* --- voxelise the scene: occupancy, labels and truth volumes --------------- */
+
+/*
+ * The uploaded scene under its poses -- the soup the next render would read,
+ * what xrt_debug_posed_triangles gives -- as a volume on a grid (DESIGN
+ * 10.15): which voxel centres lie inside which mesh.  Mesh m is bit m.
+ *
+ * Grid.  dims = {nx, ny, nz}, origin and spacing as xrt_upload_volume's, with
+ * the same checks.  All arithmetic is f64, every operation rounded on its own,
+ * nothing fused; the f32 inputs are widened.  Centres:
+ *   c_a(i) = (double)origin[a] + ((double)i + 0.5) * (double)spacing[a]
+ *
+ * Crossing of triangle (p0, p1, p2) with column (i, j); px = c_x(i), py = c_y(j):
+ *   e1 = p1 - p0;  e2 = p2 - p0
+ *   n.x = e1.y * e2.z - e1.z * e2.y;  n.y = e1.z * e2.x - e1.x * e2.z;  n.z = e1.x * e2.y - e1.y * e2.x
+ *   n.z == 0: no crossing
+ *   each edge (p0 p1, p1 p2, p2 p0) with its ends named so that a.y < b.y (a.y == b.y: the edge does not count):
+ *     straddle = (a.y <= py) != (b.y <= py)
+ *     w = (b.x - a.x) * (py - a.y) - (b.y - a.y) * (px - a.x)
+ *     the edge counts when straddle && w > 0
+ *   the column is crossed when an odd number of the three edges count, and then
+ *   z = p0.z - (n.x * (px - p0.x) + n.y * (py - p0.y)) / n.z
+ *   the crossing's slice k = the least k in [0, nz] with c_z(k) >= z, nz when none is
+ * for every column of the grid: the footprint box the kernels walk leaves no
+ * crossing out.  Two triangles that share an edge evaluate the same w on the
+ * same operands, so a closed mesh closes over every column.
+ *
+ * Occupancy.  Voxel (i, j, k) is inside mesh m when the number of mesh-m
+ * crossings of column (i, j) with slice <= k is odd.  Crossings with slice nz
+ * only enter the column's total; a column whose total for mesh m is odd counts
+ * in odd_columns[m] -- the mesh is open or inconsistent there -- and is
+ * otherwise left as computed.
+ *
+ * Outputs, each [nz][ny][nx] (x fastest) and each optional (NULL), at least
+ * one of the four given:
+ *   mask    u16, bit m set for inside mesh m
+ *   labels  u8, 0 for an empty mask, else 1 + the highest set bit (the later
+ *           mesh wins: list an insert after its body) -- an xrt_upload_volume
+ *           labels array with num_labels = the scene's mesh count
+ *   volume  f32, (float) of the f64 sum, from 0 and in mesh order, of
+ *           (double)value[m] over the set bits; +0.0f where the mask is empty.
+ *           value: one f32 per mesh of the scene, a host array in both forms
+ *   odd_columns  XRT_MAX_MESHES u64 counts, 0 past the scene's meshes
+ *
+ * XRT_ERR_ARGUMENT, with xrt_last_error naming the fault and before the
+ * context is looked at, for what xrt_upload_volume refuses in dims, origin and
+ * spacing, for no output at all and for volume without value; then
+ * XRT_ERR_NO_MESH without a scene; XRT_ERR_MEMORY, with the byte count in
+ * xrt_last_error, when the working set -- the flip volume, u16 [nz + 1][ny][nx]
+ * -- cannot be allocated.  xrt_voxelize: host buffers, synchronous.
+ * xrt_voxelize_device: device buffers, asynchronous on `stream`.  The working
+ * flip volume, which the kernels update through 32-bit words, is the context's
+ * own (xrt_sirt's working set: a call first waits for that set's previous
+ * user, unless that was a voxelisation on the same stream that left the set
+ * large enough): d_mask needs no alignment beyond its type's and no padding.  A pose
+ * set since the soup was last written makes k_pose due: the call enqueues it
+ * on the context's preparation stream, where a render would, and `stream`
+ * waits for it through an event, the host does not; the next upload or pose
+ * change waits for the call's reads of the soup.  Neither form touches the
+ * model, the uploaded volume, the state generation or the frames prepared
+ * ahead.  There is no xrt_multi_ form.
+ */
+int xrt_voxelize(xrt_context* ctx, const uint32_t dims[3], const float origin[3], const float spacing[3], const float* value,
+                 uint16_t* mask, uint8_t* labels, float* volume, uint64_t* odd_columns);
+int xrt_voxelize_device(xrt_context* ctx, const uint32_t dims[3], const float origin[3], const float spacing[3],
+                        const float* value, uint16_t* d_mask, uint8_t* d_labels, float* d_volume, uint64_t* d_odd_columns,
+                        void* stream);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

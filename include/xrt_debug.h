@@ -411,6 +411,44 @@ int xrt_host_sirt_tv(uint32_t width, uint32_t height, uint32_t num_planes, const
                      float lo, float hi, const xrt_tv_params* tv, float* volume);
 
 /*
+ * Test hook of the voxeliser.  Host code, no device: xrt_voxelize's crossing
+ * and voxel functions -- voxel_footprint, voxel_crossing, voxel_label and
+ * voxel_value, the ones the kernels call, compiled for the host -- over whole
+ * host buffers.  The soup (the num_meshes meshes' triangles one after
+ * another, 9 f32 each, already posed) and mesh_triangles are taken directly;
+ * the grid, value and outputs and their checks are xrt_voxelize's.
+ */
+int xrt_host_voxelize(const float* soup, const uint64_t* mesh_triangles, uint32_t num_meshes, const uint32_t dims[3],
+                      const float origin[3], const float spacing[3], const float* value, uint16_t* mask, uint8_t* labels,
+                      float* volume, uint64_t* odd_columns);
+
+/*
+ * The scatter's schedule, for the A/B its threshold rests on
+ * (tools/voxelize_timing.py): a triangle whose footprint box holds at least
+ * `columns` grid columns is queued for the tile waves, a smaller one is
+ * covered by its own lane; 0 restores the default, 0xFFFFFFFF queues none.
+ * The outputs are the same bit for bit.
+ */
+int xrt_debug_voxelize_threshold(xrt_context* ctx, uint32_t columns);
+
+/*
+ * Diagnostics, timing only: the steps the next voxelisations enqueue, a sum of
+ * 1 (the scatter and the tile waves), 2 (the scan) and 4 (clearing the flip
+ * volume); 7 is the default.  With a step left out the outputs mean nothing.
+ * Adding 8 keeps the scan from splitting a small grid's slices into runs: the
+ * outputs are the same bit for bit.
+ */
+int xrt_debug_voxelize_stages(xrt_context* ctx, uint32_t stages);
+
+/*
+ * Diagnostics: the last voxelisation's triangles, [0] covered by their own
+ * lane, [1] queued for the tile waves, [2] the queue entries they reserved,
+ * [3] of [0] those that found the queue full.  Waits for that call;
+ * XRT_ERR_ARGUMENT once another user of the working set has run.
+ */
+int xrt_debug_voxelize_counters(xrt_context* ctx, uint64_t counters[4]);
+
+/*
  * Test hook of material decomposition.  Host code, no device: xrt_decompose's
  * pixel function -- decompose_pixel, the one k_decompose calls, compiled for
  * the host -- over whole buffers, arguments and checks as xrt_decompose's, host

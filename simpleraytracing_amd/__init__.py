@@ -42,6 +42,7 @@ __all__ = [
     "XRT_FP_PROJECT", "XRT_FP_RESIDUAL", "XRT_MAX_SUBSETS", "ray_matrix", "host_forward_project", "host_volume_update",
     "host_sirt", "host_tv_gradient", "host_volume_sumsq", "host_tv_descend",
     "XRT_MAX_BASIS", "XRT_DECOMPOSE_MASKED", "XRT_DECOMPOSE_FAILED", "decompose_guess", "host_decompose", "decompose",
+    "host_voxelize",
 ]
 
 
@@ -638,6 +639,59 @@ def host_volume_paths(cam: Camera, labels, spacing, origin=(0.0, 0.0, 0.0), dens
     return out
 
 
+def _voxel_grid_arrays(dims, spacing, origin):
+    """A voxeliser's grid as xrt_voxelize takes it: (dims (nx, ny, nz) uint32, origin f32[3], spacing f32[3])."""
+    d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(-1)
+    org = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1)
+    spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+    if d.size != 3 or org.size != 3:
+        raise ValueError("dims and origin must hold 3 values (x, y, z)")
+    return d, org, spc
+
+
+def _voxel_outputs(dims, num_meshes, value, mask, labels, volume, odd_columns):
+    """The host buffers of the outputs asked for (None: not asked for), and value as f32 per mesh."""
+    shape = (int(dims[2]), int(dims[1]), int(dims[0])) if dims.size == 3 else (0, 0, 0)
+    val = None
+    if value is not None:
+        val = np.ascontiguousarray(value, dtype=np.float32).reshape(-1)
+        if val.size != num_meshes:
+            raise ValueError(f"value must hold one entry per mesh ({num_meshes}), got {val.size}")
+    return (val, np.empty(shape, np.uint16) if mask else None, np.empty(shape, np.uint8) if labels else None,
+            np.empty(shape, np.float32) if volume else None, np.zeros(_abi.XRT_MAX_MESHES, np.uint64) if odd_columns else None)
+
+
+def _voxel_result(mask, labels, volume, odd, num_meshes):
+    out = {}
+    if mask is not None:
+        out["mask"] = mask
+    if labels is not None:
+        out["labels"] = labels
+    if volume is not None:
+        out["volume"] = volume
+    if odd is not None:
+        out["odd_columns"] = odd[:num_meshes].copy()
+    return out
+
+
+def host_voxelize(meshes, dims, spacing, origin=(0.0, 0.0, 0.0), value=None, mask=True, labels=True, volume=None,
+                  odd_columns=True) -> dict:
+    """Context.voxelize in the device's arithmetic on the host (xrt_host_voxelize, a test hook): `meshes` is the
+    list of (T, 9) soups as posed."""
+    tris, counts = _scene_arrays(meshes)
+    d, org, spc = _voxel_grid_arrays(dims, spacing, origin)
+    volume = value is not None if volume is None else volume
+    val, m, lab, vol, odd = _voxel_outputs(d, len(counts), value, mask, labels, volume, odd_columns)
+    rc = _abi.load().xrt_host_voxelize(_fptr(tris), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(counts),
+                                       _u32ptr(d), _fptr(org), _fptr(spc), _fptr(val) if val is not None else None,
+                                       _u16ptr(m) if m is not None else None, _u8ptr(lab) if lab is not None else None,
+                                       _fptr(vol) if vol is not None else None,
+                                       odd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if odd is not None else None)
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_voxelize")
+    return _voxel_result(m, lab, vol, odd, len(counts))
+
+
 def ramp_filter(num_taps: int, window: int = _abi.XRT_RAMP_RAMLAK) -> np.ndarray:
     """`num_taps` (odd) samples of the band-limited ramp at unit sample distance, plain (XRT_RAMP_RAMLAK) or
     under a Hann window (XRT_RAMP_HANN), as f32 (xrt_ramp_filter)."""
@@ -1172,6 +1226,56 @@ class Context:
         """k_volume_paths' waves as 64 x 1 row segments (rows=True) or 8 x 8 tiles (the default): a timing A/B,
         the planes are the same (xrt_debug_volume_wave_shape)."""
         self._check(self._lib.xrt_debug_volume_wave_shape(self._ctx, int(bool(rows))), "xrt_debug_volume_wave_shape")
+
+    def voxelize(self, dims, spacing, origin=(0.0, 0.0, 0.0), value=None, mask=True, labels=True, volume=None,
+                 odd_columns=True, upload=False) -> dict:
+        """The uploaded scene under its poses on a grid of dims (nx, ny, nz) voxels of `spacing` (one value or
+        (x, y, z)) whose minimum corner is `origin` (xrt_voxelize): a dict of the outputs asked for -- mask
+        (nz, ny, nx) uint16 (bit m: inside mesh m), labels uint8 (0, else 1 + the highest mesh), volume f32 (the
+        sum of value[m] over the meshes a voxel lies in; asked for by default when `value`, one entry per mesh,
+        is given) and odd_columns (one count per mesh: the columns over which it does not close).
+        upload=True hands the labels to upload_volume on the same grid, one label per mesh."""
+        d, org, spc = _voxel_grid_arrays(dims, spacing, origin)
+        volume = value is not None if volume is None else volume
+        val, m, lab, vol, odd = _voxel_outputs(d, self._num_meshes, value, mask, labels or upload, volume, odd_columns)
+        rc = self._lib.xrt_voxelize(self._ctx, _u32ptr(d), _fptr(org), _fptr(spc), _fptr(val) if val is not None else None,
+                                    _u16ptr(m) if m is not None else None, _u8ptr(lab) if lab is not None else None,
+                                    _fptr(vol) if vol is not None else None,
+                                    odd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if odd is not None else None)
+        self._check(rc, "xrt_voxelize")
+        if upload:
+            self.upload_volume(lab, spc, org, num_labels=self._num_meshes)
+        return _voxel_result(m, lab if labels else None, vol, odd, self._num_meshes)
+
+    def voxelize_device(self, dims, spacing, origin=(0.0, 0.0, 0.0), value=None, d_mask: int = 0, d_labels: int = 0,
+                        d_volume: int = 0, d_odd_columns: int = 0, stream: int = 0):
+        """Device-buffer voxelisation (raw device pointers, 0: not asked for: d_mask u16, d_labels u8 and d_volume
+        f32 of nz * ny * nx entries, d_odd_columns XRT_MAX_MESHES u64); asynchronous on `stream`."""
+        d, org, spc = _voxel_grid_arrays(dims, spacing, origin)
+        val = None if value is None else np.ascontiguousarray(value, dtype=np.float32).reshape(-1)
+        if val is not None and val.size != self._num_meshes:
+            raise ValueError(f"value must hold one entry per mesh ({self._num_meshes}), got {val.size}")
+        rc = self._lib.xrt_voxelize_device(self._ctx, _u32ptr(d), _fptr(org), _fptr(spc),
+                                           _fptr(val) if val is not None else None, d_mask or None, d_labels or None,
+                                           d_volume or None, d_odd_columns or None, stream or None)
+        self._check(rc, "xrt_voxelize_device")
+
+    def voxelize_threshold(self, columns: int = 0):
+        """The footprint, in grid columns, from which the scatter queues a triangle for the tile waves (0: the
+        default; 0xFFFFFFFF: a lane per triangle only): a timing A/B, the outputs are the same
+        (xrt_debug_voxelize_threshold)."""
+        self._check(self._lib.xrt_debug_voxelize_threshold(self._ctx, int(columns)), "xrt_debug_voxelize_threshold")
+
+    def voxelize_stages(self, stages: int = 7):
+        """The steps the next voxelisations enqueue, for timing them apart: 1 scatter + 2 scan + 4 clear
+        (xrt_debug_voxelize_stages)."""
+        self._check(self._lib.xrt_debug_voxelize_stages(self._ctx, int(stages)), "xrt_debug_voxelize_stages")
+
+    def voxelize_counters(self) -> dict:
+        """The last voxelisation's triangles by path (xrt_debug_voxelize_counters)."""
+        c = (ctypes.c_uint64 * 4)()
+        self._check(self._lib.xrt_debug_voxelize_counters(self._ctx, c), "xrt_debug_voxelize_counters")
+        return {"direct": int(c[0]), "queued": int(c[1]), "entries": int(c[2]), "overflowed": int(c[3])}
 
     def fdk_filter(self, image, taps, weight=None) -> np.ndarray:
         """The row filter of FDK over an (H, W) image or a (P, H, W) stack: every row of image * weight (one

@@ -286,6 +286,12 @@ XRT_SYMBOLS = {
     "xrt_decompose_guess": (ctypes.c_int, [_fp, _fp, _u32, _u32, _fp, _u32, _dp]),
     "xrt_host_decompose": (ctypes.c_int, [_u64, _fp, _u16p, _fp, _fp, _u32, _u32, _fp, _u32, ctypes.c_float, ctypes.c_int, _dp,
                                           _u32, ctypes.c_double, ctypes.c_double, _fp, _u8p]),
+    "xrt_voxelize": (ctypes.c_int, [_CtxP, _u32p, _fp, _fp, _fp, _u16p, _u8p, _fp, _u64p]),
+    "xrt_voxelize_device": (ctypes.c_int, [_CtxP, _u32p, _fp, _fp, _fp, _vp, _vp, _vp, _vp, _vp]),
+    "xrt_host_voxelize": (ctypes.c_int, [_fp, _u64p, _u32, _u32p, _fp, _fp, _fp, _u16p, _u8p, _fp, _u64p]),
+    "xrt_debug_voxelize_threshold": (ctypes.c_int, [_CtxP, _u32]),
+    "xrt_debug_voxelize_stages": (ctypes.c_int, [_CtxP, _u32]),
+    "xrt_debug_voxelize_counters": (ctypes.c_int, [_CtxP, _u64p]),
     "xrt_host_philox4x32": (None, [_u32p, _u32p, _u32p]),
     "xrt_host_poisson_batch": (None, [_dp, _u32p, _u64, _dp]),
     "xrt_host_photon_noise": (ctypes.c_int, [_u32, _u32, _u32, _fp, ctypes.c_float, _u64, _u64, ctypes.c_int, _fp]),

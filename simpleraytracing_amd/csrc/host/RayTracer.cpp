@@ -410,6 +410,34 @@ void uploadVolume(const Volume& volume)
           "xrt_upload_volume");
 }
 
+unsigned long long voxelizeScene(Volume& volume, const std::vector<TriangleMesh>& meshes, const unsigned dims[3],
+                                 const float origin[3], const float spacing[3], const std::vector<float>& value,
+                                 std::vector<float>* truth)
+{
+    if (!dims || !origin || !spacing) throw std::invalid_argument("voxelizeScene: NULL argument");
+    if (truth && value.size() != meshes.size()) throw std::invalid_argument("voxelizeScene: one value per mesh");
+    const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+    volume = Volume();
+    volume.labels.resize(n);
+    if (truth) truth->resize(n);
+    uint64_t odd[XRT_MAX_MESHES] = {};
+    {
+        SceneRender r(meshes, kEveryMesh, kAttenuation);
+        check(r.ctx, xrt_voxelize(r.ctx, dims, origin, spacing, truth ? value.data() : nullptr, nullptr, volume.labels.data(),
+                                  truth ? truth->data() : nullptr, odd),
+              "xrt_voxelize");
+    }
+    for (int a = 0; a < 3; ++a) {
+        volume.dims[a] = dims[a];
+        volume.origin[a] = origin[a];
+        volume.spacing[a] = spacing[a];
+    }
+    volume.num_labels = (unsigned)meshes.size();
+    unsigned long long total = 0;
+    for (uint64_t c : odd) total += c;
+    return total;
+}
+
 void renderLoopVolumePaths(std::vector<std::vector<float>>& planes, const Image& frame, const RayTracerInfo& info)
 {
     const xrt_camera cam = camera_for(frame, std::vector<TriangleMesh>(), info, &info.range);

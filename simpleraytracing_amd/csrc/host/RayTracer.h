@@ -186,6 +186,18 @@ void getVolumeBBox(const Volume& volume, Vec3& upper, Vec3& lower);
 void uploadVolume(const Volume& volume);
 void renderLoopVolumePaths(std::vector<std::vector<float>>& planes, const Image& frame, const RayTracerInfo& info);
 
+// The scene under setMeshPoses' poses voxelised on a grid (xrt_voxelize,
+// DESIGN 10.15): volume.labels receives 0 outside every mesh, else 1 + the
+// last mesh the voxel's centre lies in, on dims voxels of `spacing` whose
+// minimum corner is `origin`, num_labels the scene's mesh count, no density --
+// what uploadVolume takes.  With `value` (one entry per mesh) `truth` receives
+// the sum of the values of the meshes each voxel lies in, e.g. the scene's
+// attenuation volume from --materials' coefficients.  Returns the columns over
+// which some mesh does not close (0 for closed meshes).  One device.
+unsigned long long voxelizeScene(Volume& volume, const std::vector<TriangleMesh>& meshes, const unsigned dims[3],
+                                 const float origin[3], const float spacing[3],
+                                 const std::vector<float>& value = std::vector<float>(), std::vector<float>* truth = nullptr);
+
 // The detector response (xrt_detector_response): the image under a separable
 // line-spread function, lsf_x along the rows and lsf_y down the columns (odd
 // counts, at most XRT_MAX_LSF_TAPS; applied as written -- a correlation --,

@@ -158,8 +158,11 @@ void loadVolumeDensity(const std::string& path, Volume& volume)
     volume.density = std::move(img.f32);
 }
 
-void saveVolume(const std::string& path, const unsigned dims[3], const float origin[3], const float spacing[3],
-                const float* data)
+namespace {
+
+// A MetaImage header and its raw file: `data` holds dims' voxels of `bytes` bytes each, of ElementType `type`.
+void saveMetaImage(const std::string& path, const unsigned dims[3], const float origin[3], const float spacing[3],
+                   const void* data, size_t bytes, const char* type)
 {
     if (path.size() < 5 || path.compare(path.size() - 4, 4, ".mhd") != 0)
         throw VolumeError(XRT_ERR_ARGUMENT, path + ": a volume is written as NAME.mhd");
@@ -173,7 +176,7 @@ void saveVolume(const std::string& path, const unsigned dims[3], const float ori
     const size_t slash = raw.find_last_of('/');
     {
         std::ofstream out(raw, std::ios::binary);
-        out.write(reinterpret_cast<const char*>(data), (std::streamsize)((size_t)dims[0] * dims[1] * dims[2] * sizeof(float)));
+        out.write(static_cast<const char*>(data), (std::streamsize)((size_t)dims[0] * dims[1] * dims[2] * bytes));
         if (!out) throw VolumeError(XRT_ERR_IO, "Cannot write the file " + raw);
     }
     std::ofstream head(path);
@@ -183,8 +186,22 @@ void saveVolume(const std::string& path, const unsigned dims[3], const float ori
          << "Offset = " << origin[0] << ' ' << origin[1] << ' ' << origin[2] << "\n"
          << "ElementSpacing = " << spacing[0] << ' ' << spacing[1] << ' ' << spacing[2] << "\n"
          << "DimSize = " << dims[0] << ' ' << dims[1] << ' ' << dims[2] << "\n"
-         << "ElementType = MET_FLOAT\n"
+         << "ElementType = " << type << "\n"
          << "ElementDataFile = " << (slash == std::string::npos ? raw : raw.substr(slash + 1)) << "\n";
     head.close();
     if (!head) throw VolumeError(XRT_ERR_IO, "Cannot write the file " + path);
+}
+
+}  // namespace
+
+void saveVolume(const std::string& path, const unsigned dims[3], const float origin[3], const float spacing[3],
+                const float* data)
+{
+    saveMetaImage(path, dims, origin, spacing, data, sizeof(float), "MET_FLOAT");
+}
+
+void saveVolume(const std::string& path, const unsigned dims[3], const float origin[3], const float spacing[3],
+                const unsigned char* labels)
+{
+    saveMetaImage(path, dims, origin, spacing, labels, 1u, "MET_UCHAR");
 }

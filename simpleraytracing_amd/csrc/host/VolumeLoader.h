@@ -64,3 +64,6 @@ void loadVolumeDensity(const std::string& path, Volume& volume);
 // cannot be written.
 void saveVolume(const std::string& path, const unsigned dims[3], const float origin[3], const float spacing[3],
                 const float* data);
+// The same for u8 labels, ElementType = MET_UCHAR: what loadVolume reads back, a voxelised scene's way out.
+void saveVolume(const std::string& path, const unsigned dims[3], const float origin[3], const float spacing[3],
+                const unsigned char* labels);

@@ -63,6 +63,17 @@
 //                              every mesh about an axis parallel to the detector's up (--turntable N:z):
 //                              another axis is refused once the meshes are loaded and the
 //                              camera is known, before a projection is rendered.
+//       --voxelize FILE.mhd[:N]  the scene voxelised on the device on exactly the
+//                              grid --reconstruct FILE.mhd[:N] uses: FILE.mhd (MetaImage,
+//                              MET_UCHAR) and FILE.raw hold 0 outside every mesh, else 1 + the
+//                              last mesh the voxel's centre lies in -- a --volume phantom, and
+//                              the truth a reconstruction of the same N is compared with voxel
+//                              by voxel.  With --materials also FILE.mu.mhd (MET_FLOAT): the
+//                              sum of the coefficients of the meshes each voxel lies in.  The
+//                              meshes stand under --pose's poses, those --turntable turns at
+//                              rest (its projection 0).  Valid without --turntable: the cube's
+//                              centre is the loaded scene's box centre either way, which is the
+//                              turntable's.
 //       --sirt K[:S[:RELAX]]   with --reconstruct: reconstruct by K iterations of SIRT (S = 1,
 //                              the default) or OS-SART over S subsets (1 to 64, at most the
 //                              projections; subset s holds the projections p with p mod S
@@ -203,6 +214,7 @@ void showUsage(const std::string& prog)
               << "\t--log-projection I0\t\tLine integrals: write -ln(I / I0) (I0 finite and > 0; after --lsf) instead of the intensity I; --u8 and --lbuffer stay as rendered\n"
               << "\t--sinogram FILE\t\t\tWith --turntable N and --log-projection: also write the line integrals as raw float32 sinograms, (height, N, width)\n"
               << "\t--reconstruct FILE.mhd[:N]\tWith --turntable N:z (every mesh, about the detector's up) and --log-projection: reconstruct the scan by FDK into an N^3 grid (default 128) about the turntable's centre, its side the scene box's diagonal; writes FILE.mhd (MET_FLOAT) and FILE.raw\n"
+              << "\t--voxelize FILE.mhd[:N]\t\tVoxelise the scene (under --pose's poses) on the grid of --reconstruct FILE.mhd[:N]: writes FILE.mhd (MET_UCHAR, 0 or 1 + the last mesh a voxel's centre lies in) and FILE.raw, with --materials also FILE.mu.mhd (MET_FLOAT, the coefficients summed); valid without --turntable\n"
               << "\t--sirt K[:S[:RELAX]]\t\tWith --reconstruct: K iterations of SIRT (S = 1) or OS-SART over S subsets (1 to 64) instead of FDK, from zeros, relaxed by RELAX (default 1), kept >= 0\n"
               << "\t--tv STEPS[:ALPHA[:REDUCTION[:EPS]]]\tWith --sirt: STEPS total-variation descent steps after every iteration, each ALPHA (default 0.2) of the iteration's move, ALPHA times REDUCTION (default 1, in (0, 1]) after every iteration, EPS (default 1e-8) under the norm; ALPHA above about 0.5 flattens the object's level\n"
               << "\t--noise GAIN[:SEED]\t\tPhoton noise on the written image: each pixel a Poisson count of mean I * GAIN, divided by GAIN (after --lsf, before --log-projection; SEED defaults to 0); --u8 and --lbuffer stay as rendered\n"
@@ -248,6 +260,8 @@ struct Options {
     std::string sinogram;                      // --sinogram FILE
     std::string reconstruct;                   // --reconstruct FILE.mhd[:N]
     unsigned reconstruct_n = 128;              // N: the grid is N x N x N
+    std::string voxelize;                      // --voxelize FILE.mhd[:N]
+    unsigned voxelize_n = 128;                 // N: --reconstruct's grid of that N
     unsigned sirt_iterations = 0;              // --sirt K[:S[:RELAX]] (0: FDK)
     unsigned sirt_subsets = 1;
     double sirt_relax = 1.0;
@@ -697,6 +711,12 @@ Options processCmd(int argc, char** argv)
                 (parts.size() == 2 && (!parse_index(parts[1], o.reconstruct_n) || o.reconstruct_n < 1 || o.reconstruct_n > 2048)))
                 throw std::runtime_error("--reconstruct FILE.mhd[:N]: a MetaImage header's name and a grid size of 1 to 2048");
             o.reconstruct = parts[0];
+        } else if (a == "--voxelize") {
+            const std::vector<std::string> parts = split(parse_str(argv[0], argc, argv, i), ':');
+            if (parts.empty() || parts.size() > 2 || parts[0].size() < 5 || parts[0].substr(parts[0].size() - 4) != ".mhd" ||
+                (parts.size() == 2 && (!parse_index(parts[1], o.voxelize_n) || o.voxelize_n < 1 || o.voxelize_n > 2048)))
+                throw std::runtime_error("--voxelize FILE.mhd[:N]: a MetaImage header's name and a grid size of 1 to 2048");
+            o.voxelize = parts[0];
         } else if (a == "--sirt") {
             const std::vector<std::string> parts = split(parse_str(argv[0], argc, argv, i), ':');
             bool ok = parts.size() >= 1 && parts.size() <= 3 && parse_index(parts[0], o.sirt_iterations) && o.sirt_iterations >= 1;
@@ -863,6 +883,23 @@ Options processCmd(int argc, char** argv)
     return o;
 }
 
+// The grid of --reconstruct and --voxelize, so that truth and reconstruction share voxels: n^3 voxels, a cube
+// about the box centre of the scene as loaded -- the turntable's centre -- whose side is the box's diagonal, so
+// that it holds the scene under every turn.
+void scan_grid(const Vec3& lower, const Vec3& upper, unsigned n, unsigned dims[3], float centre[3], float origin[3],
+               float spacing[3])
+{
+    double diagonal = 0.0;
+    for (unsigned k = 0; k < 3; ++k) diagonal += (double)(upper[k] - lower[k]) * (double)(upper[k] - lower[k]);
+    diagonal = std::sqrt(diagonal);
+    for (unsigned k = 0; k < 3; ++k) {
+        dims[k] = n;
+        centre[k] = lower[k] + (float)((double)(upper[k] - lower[k]) / 2.0);
+        spacing[k] = (float)(diagonal / n);
+        origin[k] = (float)((double)centre[k] - diagonal / 2.0);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -944,6 +981,28 @@ int main(int argc, char** argv)
         std::vector<std::array<float, 12>> poses;
         if (!opt.poses.empty() || opt.turntable) poses.assign(meshes.size(), rest);
         for (const auto& q : opt.poses) poses[q.first] = q.second;
+        if (!opt.voxelize.empty()) {                  // the scene as --pose leaves it, the turntable's meshes at rest
+            if (meshes.empty()) throw std::runtime_error("--voxelize needs a scene: give -i");
+            if (!opt.materials.empty() && opt.materials.size() != meshes.size())
+                throw std::runtime_error("--materials takes one coefficient per mesh: " + std::to_string(meshes.size()) +
+                                         " meshes loaded, " + std::to_string(opt.materials.size()) + " coefficients given");
+            float centre[3], origin[3], spacing[3];
+            unsigned dims[3];
+            scan_grid(lower, upper, opt.voxelize_n, dims, centre, origin, spacing);
+            setMeshPoses(opt.poses.empty() ? std::vector<std::array<float, 12>>() : poses);
+            Volume truth;
+            std::vector<float> mu;
+            const unsigned long long odd =
+                voxelizeScene(truth, meshes, dims, origin, spacing, opt.materials, opt.materials.empty() ? nullptr : &mu);
+            if (odd) std::cout << "--voxelize: " << odd << " grid columns cross an open mesh" << std::endl;
+            try {
+                saveVolume(opt.voxelize, dims, origin, spacing, truth.labels.data());
+                if (!opt.materials.empty())
+                    saveVolume(opt.voxelize.substr(0, opt.voxelize.size() - 4) + ".mu.mhd", dims, origin, spacing, mu.data());
+            } catch (const VolumeError& e) {
+                throw std::runtime_error(std::string("--voxelize: ") + e.what());
+            }
+        }
         const std::string name = opt.output, lbuffer_name = opt.lbuffer, u8_name = opt.u8;
         std::vector<float> scan;                      // --sinogram: the projections' intensity images
         std::vector<float> integrals;                 // --reconstruct: the projections' line integrals
@@ -1141,18 +1200,9 @@ int main(int argc, char** argv)
             std::fclose(f);
         }
         if (!opt.reconstruct.empty()) {
-            // an N^3 cube about the turntable's centre whose side is the scene box's diagonal: it holds the
-            // scene under every turn
             float centre[3], origin[3], spacing[3];
-            double diagonal = 0.0;
-            for (unsigned k = 0; k < 3; ++k) diagonal += (double)(upper[k] - lower[k]) * (double)(upper[k] - lower[k]);
-            diagonal = std::sqrt(diagonal);
-            const unsigned dims[3] = {opt.reconstruct_n, opt.reconstruct_n, opt.reconstruct_n};
-            for (unsigned k = 0; k < 3; ++k) {
-                centre[k] = lower[k] + (float)((double)(upper[k] - lower[k]) / 2.0);
-                spacing[k] = (float)(diagonal / opt.reconstruct_n);
-                origin[k] = (float)((double)centre[k] - diagonal / 2.0);
-            }
+            unsigned dims[3];
+            scan_grid(lower, upper, opt.reconstruct_n, dims, centre, origin, spacing);
             std::vector<float> reconstruction;
             if (opt.sirt_iterations)
                 reconstructSIRT(reconstruction, integrals, opt.turntable, image, meshes, info, turns, dims, origin, spacing,

@@ -2005,4 +2005,144 @@ __host__ __device__ __forceinline__ float tv_step_voxel(float x, float g, double
     return v;
 }
 
+// ---------------------------------------------------------------------------
+// Voxelisation (include/xrt.h "voxelise the scene"): the
+// crossing of one triangle with one grid column and the outputs of one voxel,
+// shared by k_voxel_scatter, k_voxel_tiles, k_voxel_scan and
+// xrt_host_voxelize.  All f64, every operation rounded on its own (the build
+// contracts nothing).
+// ---------------------------------------------------------------------------
+struct VoxelGrid {
+    uint32_t nx, ny, nz;
+    float ox, oy, oz;                  // the minimum corner
+    float sx, sy, sz;                  // the voxel spacing
+};
+
+// The centre of voxel i along an axis of origin o and spacing s (f32 widened).
+__host__ __device__ __forceinline__ double voxel_centre(float o, float s, uint32_t i)
+{
+    return (double)o + ((double)i + 0.5) * (double)s;
+}
+
+// The least i in [0, n] with voxel_centre(i) >= v (kStrict: > v), n when none
+// is: an estimate by division, then settled by the comparisons themselves
+// (the centres never decrease with i, every operation being monotone).
+template <bool kStrict>
+__host__ __device__ inline uint32_t voxel_first_index(float o, float s, uint32_t n, double v)
+{
+    const double e = (v - (double)o) / (double)s;          // about i + 0.5
+    uint32_t i = e > 0.0 ? (e < (double)n ? (uint32_t)e : n) : 0u;   // (a NaN starts at 0)
+    auto before = [&](uint32_t q) {
+        const double c = voxel_centre(o, s, q);
+        return kStrict ? c <= v : c < v;
+    };
+    while (i > 0u && !before(i - 1u)) --i;
+    while (i < n && before(i)) ++i;
+    return i;
+}
+
+// A triangle's vertices widened and its normal n = e1 x e2, each component two
+// products and a difference.
+struct VoxelTriangle {
+    double x0, y0, z0, x1, y1, z1, x2, y2, z2;
+    double nx, ny, nz;
+};
+
+__host__ __device__ inline VoxelTriangle voxel_triangle(const float* __restrict__ t)
+{
+    VoxelTriangle v;
+    v.x0 = (double)t[0]; v.y0 = (double)t[1]; v.z0 = (double)t[2];
+    v.x1 = (double)t[3]; v.y1 = (double)t[4]; v.z1 = (double)t[5];
+    v.x2 = (double)t[6]; v.y2 = (double)t[7]; v.z2 = (double)t[8];
+    const double ax = v.x1 - v.x0, ay = v.y1 - v.y0, az = v.z1 - v.z0;
+    const double bx = v.x2 - v.x0, by = v.y2 - v.y0, bz = v.z2 - v.z0;
+    v.nx = ay * bz - az * by;
+    v.ny = az * bx - ax * bz;
+    v.nz = ax * by - ay * bx;
+    return v;
+}
+
+// Whether the edge between two vertices counts for the column at (px, py): the
+// endpoints ordered by y first, so that the two triangles of a shared edge
+// evaluate one expression on the same operands.
+__host__ __device__ __forceinline__ bool voxel_edge_counts(double ax, double ay, double bx, double by, double px, double py)
+{
+    if (ay == by) return false;
+    if (by < ay) {
+        const double tx = ax, ty = ay;
+        ax = bx; ay = by;
+        bx = tx; by = ty;
+    }
+    const bool straddle = (ay <= py) != (by <= py);
+    const double w = (bx - ax) * (py - ay) - (by - ay) * (px - ax);
+    return straddle && w > 0.0;
+}
+
+// Whether the triangle crosses the column at (px, py), and then the crossing's
+// slice: the least k in [0, nz] with centre_z(k) >= z.
+__host__ __device__ inline bool voxel_crossing(const VoxelTriangle& t, const VoxelGrid& g, double px, double py, uint32_t& k)
+{
+    if (t.nz == 0.0) return false;
+    const bool e01 = voxel_edge_counts(t.x0, t.y0, t.x1, t.y1, px, py);
+    const bool e12 = voxel_edge_counts(t.x1, t.y1, t.x2, t.y2, px, py);
+    const bool e20 = voxel_edge_counts(t.x2, t.y2, t.x0, t.y0, px, py);
+    if (!(e01 ^ e12 ^ e20)) return false;
+    const double z = t.z0 - (t.nx * (px - t.x0) + t.ny * (py - t.y0)) / t.nz;
+    k = voxel_first_index<false>(g.oz, g.sz, g.nz, z);
+    return true;
+}
+
+// The columns [i0, i1) x [j0, j1) outside which the triangle crosses nothing:
+// an optimisation that leaves no crossing out.  An edge can count only with
+// a.y <= py < b.y -- exact comparisons --, so py lies in [ymin, ymax).  To the
+// right of xmax every straddled edge has w <= 0 whatever the rounding (the
+// products round monotonically).  To the left of xmin the exact w is positive
+// for every straddled edge, and the rounded one can only fail to be within
+// 2^-51 (xmax - xmin) of xmin: the box keeps 2^-40 (xmax - xmin) there.
+struct VoxelBox {
+    uint32_t i0, i1, j0, j1;
+};
+
+__host__ __device__ inline VoxelBox voxel_footprint(const VoxelTriangle& t, const VoxelGrid& g)
+{
+    VoxelBox b = {0u, 0u, 0u, 0u};
+    if (t.nz == 0.0) return b;
+    const double xmin = ::fmin(t.x0, ::fmin(t.x1, t.x2)), xmax = ::fmax(t.x0, ::fmax(t.x1, t.x2));
+    const double ymin = ::fmin(t.y0, ::fmin(t.y1, t.y2)), ymax = ::fmax(t.y0, ::fmax(t.y1, t.y2));
+    b.i0 = voxel_first_index<false>(g.ox, g.sx, g.nx, xmin - (xmax - xmin) * 0x1p-40);
+    b.i1 = voxel_first_index<true>(g.ox, g.sx, g.nx, xmax);
+    b.j0 = voxel_first_index<false>(g.oy, g.sy, g.ny, ymin);
+    b.j1 = voxel_first_index<false>(g.oy, g.sy, g.ny, ymax);
+    if (b.i1 < b.i0) b.i1 = b.i0;
+    return b;
+}
+
+// A voxel's label: 0 for an empty mask, else 1 + its highest set bit.
+__host__ __device__ __forceinline__ uint8_t voxel_label(uint32_t mask)
+{
+    uint32_t l = 0u;
+    while (mask) {
+        ++l;
+        mask >>= 1;
+    }
+    return (uint8_t)l;
+}
+
+// A voxel's value: the f64 sum, from 0 and in mesh order, of the values of the
+// meshes it lies in, as f32.
+template <typename Value>
+__host__ __device__ __forceinline__ float voxel_value(uint32_t mask, uint32_t num_meshes, Value value)
+{
+    double sum = 0.0;
+    for (uint32_t m = 0; m < num_meshes; ++m)
+        if (mask >> m & 1u) sum = sum + (double)value(m);
+    return (float)sum;
+}
+
+// The entry of voxel (i, j, k) in a [nz (+ 1)][ny][nx] array.
+__host__ __device__ __forceinline__ uint64_t voxel_index(const VoxelGrid& g, uint32_t i, uint32_t j, uint32_t k)
+{
+    return ((uint64_t)k * g.ny + j) * g.nx + i;
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -4894,4 +4894,175 @@ __global__ __launch_bounds__(kDecomposeThreads) void k_decompose(size_t n, const
     if (tab.iters) tab.iters[i] = (uint8_t)status;
 }
 
+// ---------------------------------------------------------------------------
+// Voxelisation: a triangle-driven scatter of crossings into a
+// zeroed flip volume -- u16 [nz + 1][ny][nx], bit m of slice k of a column
+// flipped once per crossing of mesh m there, plane nz taking the crossings
+// above the grid --, then a scan along z.  The flips are no-return 32-bit XOR
+// atomics on the word that holds the u16 (the flip volume is the context's, 4-
+// byte aligned and padded to whole words): an XOR does not depend on the
+// order of arrival, so neither does any output.
+//
+// k_voxel_scatter: a lane a triangle.  A triangle whose footprint box holds
+// fewer than `threshold` columns is covered by its lane, column by column; a
+// larger one is queued as entries (triangle, first row) of kVoxelQueueRows
+// rows of its box each, for k_voxel_tiles.  A triangle that finds the queue
+// full is covered by its lane all the same (the slots are preset to
+// kVoxelNoEntry, so a reservation that ran past the end leaves only skipped
+// slots).  k_voxel_tiles: a wave an entry, 64 columns of a row at a time, x
+// fastest (16 columns of each of its four rows where the box is no wider); a
+// fixed grid whose waves stride over the entries, so the host need not know
+// their number.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kVoxelThreads = 256;
+constexpr uint32_t kVoxelQueueColumns = 16;      // footprint columns from which a triangle is queued (xrt_debug_voxelize_threshold;
+                                                 // measured: DESIGN 10.15, profiles/voxelize/timing.json)
+constexpr uint32_t kVoxelQueueRows = 4;          // rows of a footprint box per queue entry
+constexpr uint32_t kVoxelQueueCap = 1u << 16;    // queue entries
+constexpr uint32_t kVoxelTileBlocks = 1024;      // k_voxel_tiles' grid: 4096 waves
+constexpr uint32_t kVoxelNoEntry = 0xFFFFFFFFu;
+constexpr uint32_t kVoxelScanWaves = 16384;      // k_voxel_scan splits the slices until it has this many waves,
+constexpr uint32_t kVoxelScanRuns = 8;           // into at most this many runs
+constexpr uint32_t kVoxelScanRun = 16;           // of at least this many slices
+
+struct VoxelMeshes {
+    uint32_t end[kMaxMeshes];          // one past mesh m's last triangle; 0xFFFFFFFF past the scene's meshes
+    float value[kMaxMeshes];
+    uint32_t num;
+};
+
+struct VoxelControl {
+    uint32_t entries;                  // queue entries reserved (may pass kVoxelQueueCap)
+    uint32_t queued, direct, overflowed;   // triangles: queued, covered by their lane, of these for want of room
+};
+
+__device__ __forceinline__ void voxel_flip(uint32_t* __restrict__ flip, uint64_t e, uint32_t bit)
+{
+    atomicXor(flip + (e >> 1), bit << (((uint32_t)e & 1u) * 16u));   // (the result is unused: a no-return atomic)
+}
+
+__device__ __forceinline__ uint32_t voxel_mesh_bit(const VoxelMeshes& meshes, uint32_t t)
+{
+    uint32_t m = 0u;
+    while (m + 1u < kMaxMeshes && t >= meshes.end[m]) ++m;
+    return 1u << m;
+}
+
+__device__ __forceinline__ void voxel_count(uint32_t* counter, bool mine)
+{
+    const uint32_t n = (uint32_t)__popcll(__ballot(mine));
+    if (n && (threadIdx.x & 63u) == 0u) atomicAdd(counter, n);
+}
+
+__global__ __launch_bounds__(kVoxelThreads) void k_voxel_scatter(const float* __restrict__ soup, uint32_t num_tris,
+                                                                 const VoxelMeshes meshes, const VoxelGrid g,
+                                                                 uint32_t threshold, uint32_t* __restrict__ flip,
+                                                                 VoxelControl* __restrict__ ctl, uint2* __restrict__ queue)
+{
+    const uint32_t t = blockIdx.x * kVoxelThreads + threadIdx.x;
+    bool direct = false, queued = false, overflowed = false;
+    VoxelTriangle tri = {};
+    VoxelBox b = {0u, 0u, 0u, 0u};
+    if (t < num_tris) {
+        tri = voxel_triangle(soup + 9ull * t);
+        b = voxel_footprint(tri, g);
+        const uint64_t columns = (uint64_t)(b.i1 - b.i0) * (b.j1 - b.j0);
+        if (columns >= threshold && columns) {
+            const uint32_t entries = (b.j1 - b.j0 + kVoxelQueueRows - 1u) / kVoxelQueueRows;
+            // (the look first bounds how far the counter can pass the capacity: it never wraps)
+            if (__hip_atomic_load(&ctl->entries, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < kVoxelQueueCap) {
+                const uint32_t base = atomicAdd(&ctl->entries, entries);
+                if (base + entries <= kVoxelQueueCap) {
+                    for (uint32_t r = 0; r < entries; ++r) queue[base + r] = make_uint2(t, b.j0 + r * kVoxelQueueRows);
+                    queued = true;
+                }
+            }
+            overflowed = !queued;
+        }
+        direct = columns && !queued;
+    }
+    if (direct) {
+        const uint32_t bit = voxel_mesh_bit(meshes, t);
+        for (uint32_t j = b.j0; j < b.j1; ++j) {
+            const double py = voxel_centre(g.oy, g.sy, j);
+            for (uint32_t i = b.i0; i < b.i1; ++i) {
+                uint32_t k;
+                if (voxel_crossing(tri, g, voxel_centre(g.ox, g.sx, i), py, k)) voxel_flip(flip, voxel_index(g, i, j, k), bit);
+            }
+        }
+    }
+    voxel_count(&ctl->queued, queued);
+    voxel_count(&ctl->direct, direct);
+    voxel_count(&ctl->overflowed, overflowed);
+}
+
+__global__ __launch_bounds__(kVoxelThreads) void k_voxel_tiles(const float* __restrict__ soup, const VoxelMeshes meshes,
+                                                               const VoxelGrid g, uint32_t* __restrict__ flip,
+                                                               const VoxelControl* __restrict__ ctl,
+                                                               const uint2* __restrict__ queue)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * kVoxelThreads + threadIdx.x) >> 6, waves = gridDim.x * (kVoxelThreads >> 6);
+    const uint32_t reserved = ctl->entries, n = reserved < kVoxelQueueCap ? reserved : kVoxelQueueCap;
+    for (uint32_t e = wave; e < n; e += waves) {
+        const uint2 q = queue[e];
+        if (q.x == kVoxelNoEntry) continue;
+        const VoxelTriangle tri = voxel_triangle(soup + 9ull * q.x);
+        const VoxelBox b = voxel_footprint(tri, g);
+        const uint32_t bit = voxel_mesh_bit(meshes, q.x);
+        const uint32_t j1 = b.j1 - q.y < kVoxelQueueRows ? b.j1 : q.y + kVoxelQueueRows;
+        // the wave's 64 lanes as 64 x 1 columns of a row, or 16 x 4 over the entry's rows where the box is narrow
+        const uint32_t shift = b.i1 - b.i0 <= 16u ? 4u : 6u, width = 1u << shift;
+        for (uint32_t j = q.y + (lane >> shift); j < j1; j += 64u >> shift) {
+            const double py = voxel_centre(g.oy, g.sy, j);
+            for (uint32_t i = b.i0 + (lane & (width - 1u)); i < b.i1; i += width) {
+                uint32_t k;
+                if (voxel_crossing(tri, g, voxel_centre(g.ox, g.sx, i), py, k)) voxel_flip(flip, voxel_index(g, i, j, k), bit);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_voxel_scan: a lane a column, x fastest, so a wave reads 128 contiguous
+// bytes of each slice row of the flip volume and writes whole lines of each
+// output.  One pass along z: the running XOR of the flips is the voxel's mask,
+// and its label and value go out beside it.  The column's total -- the mask
+// after plane nz -- is odd for the meshes that do not close over the column:
+// integer counts per mesh, a ballot and one atomic add per wave and mesh.
+// A small grid has too few columns to fill the device: blockIdx.y then splits
+// the slices into runs of `chunk`, and a block first XORs the slices below its
+// run (reads only) to start from the right mask; the last run takes the total.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kVoxelThreads) void k_voxel_scan(const VoxelGrid g, const VoxelMeshes meshes,
+                                                              const uint16_t* __restrict__ flip, uint16_t* __restrict__ mask,
+                                                              uint8_t* __restrict__ labels, float* __restrict__ volume,
+                                                              unsigned long long* __restrict__ odd, uint32_t chunk)
+{
+    const uint64_t plane = (uint64_t)g.nx * g.ny;
+    const uint64_t c = (uint64_t)blockIdx.x * kVoxelThreads + threadIdx.x;
+    uint32_t total = 0u;
+    if (c < plane) {
+        const uint32_t k0 = blockIdx.y * chunk, k1 = g.nz - k0 < chunk ? g.nz : k0 + chunk;
+        uint32_t acc = 0u;
+#pragma unroll 8
+        for (uint32_t k = 0; k < k0; ++k) acc ^= flip[(uint64_t)k * plane + c];
+#pragma unroll 4
+        for (uint32_t k = k0; k < k1; ++k) {
+            const uint64_t e = (uint64_t)k * plane + c;
+            acc ^= flip[e];
+            if (mask) mask[e] = (uint16_t)acc;
+            if (labels) labels[e] = voxel_label(acc);
+            if (volume) volume[e] = acc ? voxel_value(acc, meshes.num, [&](uint32_t m) { return meshes.value[m]; }) : 0.0f;
+        }
+        if (k1 == g.nz) total = acc ^ flip[(uint64_t)g.nz * plane + c];
+    }
+    if (odd && __any(total != 0u)) {
+        for (uint32_t m = 0; m < meshes.num; ++m) {
+            const uint32_t n = (uint32_t)__popcll(__ballot((total >> m & 1u) != 0u));
+            if (n && (threadIdx.x & 63u) == 0u) atomicAdd(odd + m, (unsigned long long)n);
+        }
+    }
+}
+
 }  // namespace XRT_KERNEL_NS

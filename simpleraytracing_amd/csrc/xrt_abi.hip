@@ -561,6 +561,20 @@ struct xrt_context {
     hipEvent_t sirt_ev = nullptr;
     bool sirt_busy = false;
 
+    // The voxeliser (xrt_voxelize[_device]) lays its control
+    // words, queue and flip volume in that working set.  vox_ev marks the
+    // last scatter enqueued on the caller's stream, the soup's only reader
+    // there: sync_context waits for it, so an upload or a pose change does not
+    // replace the soup under it.  vox_counters: the set still holds the last
+    // call's control words (xrt_debug_voxelize_counters), laid there by
+    // work on vox_stream: a next voxelisation on that stream is ordered
+    // behind it by the stream and need not wait for the set on the host.
+    hipEvent_t vox_ev = nullptr, vox_pose_ev = nullptr;
+    hipStream_t vox_stream = nullptr;
+    bool vox_busy = false, vox_counters = false;
+    uint32_t vox_threshold = kVoxelQueueColumns;       // xrt_debug_voxelize_threshold
+    uint32_t vox_stages = 7u;                          // xrt_debug_voxelize_stages: 1 scatter, 2 scan, 4 clear, 8 the scan in one run
+
     // Ray table (DESIGN.md "Ray table"): the ray directions of one camera and
     // strip, filled by k_ray_table on the prep stream when an attenuation
     // BINNED frame repeats the previous one's RayKey, and read by
@@ -745,6 +759,10 @@ int sync_context(xrt_context* ctx)
         if (fs.done_valid) XRT_HIP(ctx, hipEventSynchronize(fs.done_ev));
     lap(6);
     if (ctx->pending) XRT_HIP(ctx, hipStreamSynchronize(ctx->last_stream));
+    if (ctx->vox_busy) {                              // a scatter of xrt_voxelize_device reads the soup
+        XRT_HIP(ctx, hipEventSynchronize(ctx->vox_ev));
+        ctx->vox_busy = false;
+    }
     lap(7);
     return XRT_OK;
 }
@@ -2235,6 +2253,8 @@ void xrt_destroy(xrt_context* ctx)
     if (ctx->sirt_busy) (void)hipEventSynchronize(ctx->sirt_ev);
     (void)hipFree(ctx->d_sirt);
     if (ctx->sirt_ev) (void)hipEventDestroy(ctx->sirt_ev);
+    for (hipEvent_t e : {ctx->vox_ev, ctx->vox_pose_ev})
+        if (e) (void)hipEventDestroy(e);
     for (auto& c : ctx->tchunks) (void)hipFree(c.p);
     lap(1);
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
@@ -3139,6 +3159,7 @@ static int sirt_working_set(xrt_context* ctx, size_t bytes)
         XRT_HIP(ctx, hipEventSynchronize(ctx->sirt_ev));
         ctx->sirt_busy = false;
     }
+    ctx->vox_counters = false;                        // (the caller lays its own data over them)
     if (bytes > ctx->sirt_cap || !ctx->d_sirt) {
         (void)hipFree(ctx->d_sirt);
         ctx->d_sirt = nullptr;
@@ -3421,6 +3442,150 @@ int xrt_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_pla
 {
     return xrt_sirt_tv(ctx, width, height, num_planes, proj, matrices, dims, spacing, iterations, subsets, relax, lo, hi,
                        nullptr, volume);
+}
+
+// --- voxelisation ---------------------------------------------
+
+#include "xrt_voxel_host.inc"
+
+// The bytes of the voxeliser's working set ahead of the flip volume: the control words, then the queue.
+constexpr size_t kVoxelQueueAt = 64, kVoxelFlipAt = kVoxelQueueAt + (size_t)kVoxelQueueCap * sizeof(uint2);
+static_assert(sizeof(VoxelControl) <= kVoxelQueueAt, "the control words lie ahead of the queue");
+
+// The checks both forms share, the arguments' first (no context needed).
+static int voxelize_checks(xrt_context* ctx, const uint32_t* dims, const float* origin, const float* spacing,
+                           const float* value, const void* mask, const void* labels, const void* volume, const void* odd)
+{
+    const std::string why = voxelize_arguments(dims, origin, spacing, value, mask, labels, volume, odd);
+    if (!why.empty()) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    if (ctx->mesh_tris.empty()) return fail(ctx, XRT_ERR_NO_MESH, "no scene uploaded (xrt_upload_mesh, xrt_upload_scene)");
+    return XRT_OK;
+}
+
+// The voxeliser over device buffers on `stream` (validated arguments): a k_pose that is due goes to the preparation
+// stream as before a render and `stream` waits for it by an event; then the working set is cleared, the scatter and
+// the tile waves flip it and the scan writes the outputs.
+static int run_voxelize(xrt_context* ctx, const uint32_t* dims, const float* origin, const float* spacing, const float* value,
+                        uint16_t* d_mask, uint8_t* d_labels, float* d_volume, uint64_t* d_odd, hipStream_t stream)
+{
+    const VoxelGrid g = voxel_grid(dims, origin, spacing);
+    const uint64_t plane = (uint64_t)g.nx * g.ny;
+    const size_t flip_bytes = ((size_t)(plane * (g.nz + 1u)) * sizeof(uint16_t) + 3u) & ~(size_t)3u;
+    VoxelMeshes meshes = {};
+    const size_t M = ctx->mesh_tris.size();
+    uint64_t end = 0;
+    for (size_t m = 0; m < kMaxMeshes; ++m) {
+        if (m < M) end += ctx->mesh_tris[m];
+        meshes.end[m] = m < M ? (uint32_t)end : 0xFFFFFFFFu;
+        meshes.value[m] = m < M && value ? value[m] : 0.0f;
+    }
+    meshes.num = (uint32_t)M;
+    if (ctx->num_tris > 0xFFFFFF00ull) return fail(ctx, XRT_ERR_ARGUMENT, "too many triangles to voxelise");
+    const float* soup = nullptr;
+    if (int rc = render_soup(ctx, soup)) return rc;
+    if (soup != ctx->d_tris) {                        // the posed soup: behind its k_pose on the preparation stream
+        if (!ctx->vox_pose_ev) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->vox_pose_ev, hipEventDisableTiming));
+        XRT_HIP(ctx, hipEventRecord(ctx->vox_pose_ev, ctx->prep_stream));
+        XRT_HIP(ctx, hipStreamWaitEvent(stream, ctx->vox_pose_ev, 0));
+    }
+    // (the set's last user ran on `stream` and the set is large enough: the stream orders this call behind it)
+    if (ctx->vox_counters && ctx->vox_stream == stream && kVoxelFlipAt + flip_bytes <= ctx->sirt_cap) ctx->sirt_busy = false;
+    if (int rc = sirt_working_set(ctx, kVoxelFlipAt + flip_bytes)) return rc;
+    ctx->sirt_busy = true;
+    ctx->vox_stream = stream;
+    VoxelControl* ctl = reinterpret_cast<VoxelControl*>(ctx->d_sirt);
+    uint2* queue = reinterpret_cast<uint2*>(ctx->d_sirt + kVoxelQueueAt);
+    uint32_t* flip = reinterpret_cast<uint32_t*>(ctx->d_sirt + kVoxelFlipAt);
+    const bool clear = ctx->vox_stages & 4u, scatter = ctx->vox_stages & 1u, scan = ctx->vox_stages & 2u;
+    hipError_t e = hipMemsetAsync(ctl, 0, kVoxelQueueAt, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(queue, 0xFF, kVoxelFlipAt - kVoxelQueueAt, stream);
+    if (e == hipSuccess && clear) e = hipMemsetAsync(flip, 0, flip_bytes, stream);
+    if (e == hipSuccess && d_odd) e = hipMemsetAsync(d_odd, 0, XRT_MAX_MESHES * sizeof(uint64_t), stream);
+    if (e == hipSuccess && ctx->num_tris && scatter) {
+        const uint32_t T = (uint32_t)ctx->num_tris;
+        hipLaunchKernelGGL(k_voxel_scatter, dim3((T + kVoxelThreads - 1u) / kVoxelThreads), dim3(kVoxelThreads), 0, stream,
+                           soup, T, meshes, g, ctx->vox_threshold, flip, ctl, queue);
+        hipLaunchKernelGGL(k_voxel_tiles, dim3(kVoxelTileBlocks), dim3(kVoxelThreads), 0, stream, soup, meshes, g, flip,
+                           (const VoxelControl*)ctl, (const uint2*)queue);
+        e = hipGetLastError();
+        if (!ctx->vox_ev && e == hipSuccess) e = hipEventCreateWithFlags(&ctx->vox_ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ctx->vox_ev, stream);
+        if (e == hipSuccess) ctx->vox_busy = true;
+    }
+    if (e == hipSuccess && scan) {
+        // runs of slices, so that a grid of few columns still fills the device (vox_stages & 8: one run, for the A/B)
+        const uint64_t waves = (plane + 63u) / 64u;
+        uint32_t runs = (uint32_t)std::min<uint64_t>(kVoxelScanRuns, std::max<uint64_t>(1u, kVoxelScanWaves / waves));
+        if (ctx->vox_stages & 8u) runs = 1u;
+        const uint32_t chunk = std::max(kVoxelScanRun, (g.nz + runs - 1u) / runs);
+        hipLaunchKernelGGL(k_voxel_scan, dim3((unsigned)((plane + kVoxelThreads - 1u) / kVoxelThreads), (g.nz + chunk - 1u) / chunk),
+                           dim3(kVoxelThreads), 0, stream, g, meshes, reinterpret_cast<const uint16_t*>(flip), d_mask, d_labels,
+                           d_volume, reinterpret_cast<unsigned long long*>(d_odd), chunk);
+        e = hipGetLastError();
+    }
+    (void)hipEventRecord(ctx->sirt_ev, stream);
+    ctx->vox_counters = e == hipSuccess;
+    if (e != hipSuccess) return fail(ctx, XRT_ERR_DEVICE, std::string("xrt_voxelize: ") + hipGetErrorString(e));
+    return XRT_OK;
+}
+
+int xrt_voxelize_device(xrt_context* ctx, const uint32_t dims[3], const float origin[3], const float spacing[3],
+                        const float* value, uint16_t* d_mask, uint8_t* d_labels, float* d_volume, uint64_t* d_odd_columns,
+                        void* stream)
+{
+    if (int rc = voxelize_checks(ctx, dims, origin, spacing, value, d_mask, d_labels, d_volume, d_odd_columns)) return rc;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return run_voxelize(ctx, dims, origin, spacing, value, d_mask, d_labels, d_volume, d_odd_columns, (hipStream_t)stream);
+}
+
+int xrt_voxelize(xrt_context* ctx, const uint32_t dims[3], const float origin[3], const float spacing[3], const float* value,
+                 uint16_t* mask, uint8_t* labels, float* volume, uint64_t* odd_columns)
+{
+    if (int rc = voxelize_checks(ctx, dims, origin, spacing, value, mask, labels, volume, odd_columns)) return rc;
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
+    DeviceScratch s(ctx, ctx->host_stream, "voxelisation");
+    uint16_t* dmask = s.alloc<uint16_t>(voxels, mask != nullptr);
+    uint8_t* dlabels = s.alloc<uint8_t>(voxels, labels != nullptr);
+    float* dvolume = s.alloc<float>(voxels, volume != nullptr);
+    uint64_t* dodd = s.alloc<uint64_t>(XRT_MAX_MESHES, odd_columns != nullptr);
+    if (s.rc()) return s.rc();
+    if (int rc = run_voxelize(ctx, dims, origin, spacing, value, dmask, dlabels, dvolume, dodd, ctx->host_stream)) return rc;
+    s.download(mask, (const uint16_t*)dmask, voxels);
+    s.download(labels, (const uint8_t*)dlabels, voxels);
+    s.download(volume, (const float*)dvolume, voxels);
+    s.download(odd_columns, (const uint64_t*)dodd, XRT_MAX_MESHES);
+    return s.finish();
+}
+
+int xrt_debug_voxelize_threshold(xrt_context* ctx, uint32_t columns)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    ctx->vox_threshold = columns ? columns : kVoxelQueueColumns;
+    return XRT_OK;
+}
+
+int xrt_debug_voxelize_stages(xrt_context* ctx, uint32_t stages)
+{
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    ctx->vox_stages = stages & 15u;
+    return XRT_OK;
+}
+
+int xrt_debug_voxelize_counters(xrt_context* ctx, uint64_t counters[4])
+{
+    if (!ctx || !counters) return XRT_ERR_ARGUMENT;
+    if (!ctx->vox_counters) return fail(ctx, XRT_ERR_ARGUMENT, "the working set no longer holds a voxelisation's counters");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->sirt_busy) XRT_HIP(ctx, hipEventSynchronize(ctx->sirt_ev));
+    VoxelControl c = {};
+    XRT_HIP(ctx, hipMemcpy(&c, ctx->d_sirt, sizeof c, hipMemcpyDeviceToHost));
+    counters[0] = c.direct;
+    counters[1] = c.queued;
+    counters[2] = c.entries;
+    counters[3] = c.overflowed;
+    return XRT_OK;
 }
 
 // --- material decomposition ----------------------------------
