@@ -79,20 +79,6 @@ constexpr size_t kLdsGranule = 512;
 constexpr size_t kRenderLdsPerCu = (size_t)XRT_RENDER_WAVES * 4 * kRenderLdsPerWave;
 static_assert(kRenderLdsPerCu < kLdsPerCu, "the render's stages fit a CU at full occupancy");
 constexpr size_t kPrepLds = (kLdsPerCu - kRenderLdsPerCu) / XRT_PREP_PER_CU / kLdsGranule * kLdsGranule;
-// Split tiles (DESIGN.md "Split tiles"): in a frame whose tile waves are at
-// most kSplitFillFactor x the GPU's wave slots (its span is its heaviest tiles'),
-// the regions with at least kSplitHeavyFrac of the heaviest region's candidates
-// (and at least kSplitFloor) render each tile with two waves.  Larger frames
-// split nothing (their heavy regions start first and others cover the tail).
-// XRT_SPLIT_MIN=n instead splits every region of at least n candidates in any
-// frame (0: never).
-constexpr double kSplitFillFactor = 2.0;
-constexpr double kSplitHeavyFrac = 0.6;
-constexpr uint32_t kSplitFloor = 64;
-constexpr uint32_t kSplitAuto = 0xFFFFFFFFu;
-// A camera that stays put this many frames over lists sized for another
-// camera is sized for itself.
-constexpr uint32_t kStillFrames = 2;
 // Frames prepared ahead of their call when a device-pointer render repeats
 // its geometry (xrt_context::ahead); with kFrameSets sets, two renders can be
 // in flight beside them.
@@ -298,6 +284,8 @@ struct PendingFrame {
     HostClock::time_point t_call;
 };
 
+#include "xrt_plan_host.inc"           // (here: the context carries its GeometryState)
+
 struct xrt_context {
     int device = 0;
     std::string error;
@@ -323,14 +311,12 @@ struct xrt_context {
     uint64_t motion_pool_forced = 0;   // test hook XRT_MOTION_POOL: that many entries, never grown
     bool device_fill = true;           // moving frames render over the device fill plan (XRT_DEVICE_FILL=0: off)
     bool device_first = true;          // a geometry's first frame sized on the device (XRT_DEVICE_FIRST=0: off)
-    bool dev_geometry = false;         // bin_key's only frame was sized on the device (no compact lists)
     // Box tile masks (BinBuffers::box_masks; XRT_BOX_MASKS): 0 (default)
     // never, 1 in the host-sized frames of meshes under kPrepBigMesh
     // triangles, 2 in every binned frame.  Exact either way; measured a wash
     // (DESIGN.md "Box tile masks"): the renders' dispatches shrink, k_prep's
     // grow by about as much, and the step does not move beyond box-to-box noise.
     int box_masks = 0;
-    bool compact = false;              // compact_layout is valid for bin_key
     size_t bin_force_cap = 0;          // test hook (xrt_set_bin_capacity)
     // Fill plan of the current geometry (bin_key): the compact layout's
     // slots [plan_tile_slots, regions) are the regions its sizing frame
@@ -430,35 +416,9 @@ struct xrt_context {
     bool pending = false;
     int kernel = XRT_KERNEL_AUTO;
     uint64_t mesh_gen = 0;             // bumped by every upload
-    // Binned list sizing: the region lists are sized by a synchronous count
-    // whenever the frame geometry changes (mesh, camera, strip); later frames
-    // of the same geometry reuse the size without a host round trip.
-    struct BinKey {
-        xrt_camera cam;
-        uint32_t row_begin, row_end;
-        uint64_t T, gen;
-        uint64_t pose_gen;             // the meshes' poses (xrt_set_pose)
-        // field by field (the struct has padding; the camera's floats by bits)
-        bool same(const BinKey& o) const
-        {
-            return std::memcmp(&cam, &o.cam, sizeof cam) == 0 && row_begin == o.row_begin &&
-                   row_end == o.row_end && T == o.T && gen == o.gen && pose_gen == o.pose_gen;
-        }
-        // the same region grid and mesh: only the camera's or the meshes' pose differs
-        bool same_layout(const BinKey& o) const
-        {
-            return cam.width == o.cam.width && cam.height == o.cam.height && row_begin == o.row_begin &&
-                   row_end == o.row_end && T == o.T && gen == o.gen;
-        }
-    } bin_key = {};
-    static_assert(sizeof(xrt_camera) == 15 * 4, "xrt_camera has no padding (compared bytewise)");
-    bool bin_key_valid = false;
-    // The last frame rendered over lists sized for another camera (DESIGN.md
-    // "Moving camera"): a sizing then plans for motion (roomier lists, no
-    // fill plan).
-    bool moving = false;
+    using BinKey = ::BinKey;
+    GeometryState geo;                 // the geometry the region lists were sized for (choose_list_mode)
     bool reuse_cameras = true;         // false for xrt_render_rows_multi's contexts
-    BinKey last_key = {};              // the last frame's geometry
     // Hit transit (xrt_set_transit_hits): the message buffer's capacity in
     // 32-bit words (0: off), and the hit plan of geometry hit_key
     // (xrt_plan_hit_layout): per tile of its fill plan the exclusive scan of
@@ -470,7 +430,6 @@ struct xrt_context {
     uint64_t hit_words = 0;
     uint32_t* d_hit_off = nullptr;
     size_t hit_off_cap = 0;
-    uint32_t still_frames = 0;         // frames in a row on one camera over reused lists
     // Prepare-ahead (DESIGN.md "Pipelining"): when a device-pointer render
     // repeats the previous call's frame geometry, the preparations of the next
     // kAheadFrames frames of that geometry are enqueued at once on the prep
@@ -897,11 +856,29 @@ int check_camera(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, ui
     return XRT_OK;
 }
 
+xrt_context::BinKey geometry_key(const xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin,
+                                 uint32_t row_end)
+{
+    xrt_context::BinKey key = {};
+    key.cam = *cam;
+    key.row_begin = row_begin;
+    key.row_end = row_end;
+    key.T = render_tris(ctx);
+    key.gen = ctx->mesh_gen;
+    key.pose_gen = ctx->pose_gen;
+    return key;
+}
+
+inline uint32_t frame_regions(const PendingFrame& pf) { return pf.rows ? pf.rx * pf.ry : 0u; }
+
 // k_prep: one thread per triangle, and at least one per image row and column
 // (the pixel-offset tables).
-int launch_prep(xrt_context* ctx, FrameSet& fs, const RenderParams& p, const CullParams& cp, bool culled,
-                const BinBuffers& bins, BinState* bin_ctl, hipStream_t stream, hipEvent_t done)
+int launch_prep(xrt_context* ctx, PendingFrame& pf)
 {
+    FrameSet& fs = *pf.fs;
+    const RenderParams& p = pf.p;
+    const BinBuffers& bins = pf.bins;
+    const bool culled = pf.kernel != XRT_KERNEL_BRUTE;
     const uint64_t T = render_tris(ctx);
     // p.prep_tris triangles per wave; every thread covers a pixel-offset entry / counter
     const uint64_t threads = std::max<uint64_t>((uint64_t)p.height + p.width, bins.clear ? bins.clear_regions : 0u);
@@ -915,12 +892,12 @@ int launch_prep(xrt_context* ctx, FrameSet& fs, const RenderParams& p, const Cul
         ptimes = ctx->d_prep_times;
         ctx->prep_times_n = (size_t)blocks * kPrepWaves;
     }
-    const float* soup = nullptr;                   // (k_pose first when a pose changed: `stream` is the prep stream)
+    const float* soup = nullptr;                   // (k_pose first when a pose changed, on the prep stream too)
     if (int rc = render_soup(ctx, soup)) return rc;
     const auto t_launch = HostClock::now();
     hipExtLaunchKernelGGL(k_prep, dim3((unsigned)blocks), dim3(kPrepThreads),
-                          ctx->prep_lds, stream, nullptr, done, 0u,
-                          soup, (uint32_t)T, p, cp, fs.recs, culled ? fs.cull : nullptr, bins, bin_ctl,
+                          ctx->prep_lds, ctx->prep_stream, nullptr, pf.prep_done, 0u,
+                          soup, (uint32_t)T, p, ctx->cull, fs.recs, culled ? fs.cull : nullptr, bins, pf.bin_ctl,
                           fs.frame, fs.offsets, ptimes);
     XRT_HIP(ctx, hipGetLastError());
     if (bins.counts) ctx->prep_reads_layout = true;
@@ -934,10 +911,11 @@ int launch_prep(xrt_context* ctx, FrameSet& fs, const RenderParams& p, const Cul
 // is cleared here, on the prep stream, only when it is not known clean for
 // this many regions (the first frames, a larger region grid, a re-run).  The
 // caller sets the launch layout (bins.desc / bins.rank).
-int bin_buffers(xrt_context* ctx, FrameSet& fs, uint32_t n_regions, uint64_t list_entries, BinBuffers& bins,
-                BinState*& ctl, hipStream_t stream, bool& cleared, bool rerun = false)
+int bin_buffers(xrt_context* ctx, PendingFrame& pf, uint64_t list_entries, bool rerun = false)
 {
-    cleared = false;
+    FrameSet& fs = *pf.fs;
+    BinBuffers& bins = pf.bins;
+    const uint32_t n_regions = frame_regions(pf);
     const uint64_t T = render_tris(ctx);
     static_assert(sizeof(BinState) <= kCounterStride * sizeof(uint32_t), "BinState fits its line");
     int rc;
@@ -953,10 +931,8 @@ int bin_buffers(xrt_context* ctx, FrameSet& fs, uint32_t n_regions, uint64_t lis
     const uint32_t q = rerun ? fs.half : fs.half ^ 1u;     // a re-run recounts into the same half
     uint32_t* mine = fs.bin_counts + (size_t)q * fs.bin_half_words;
     uint32_t* other = fs.bin_counts + (size_t)(q ^ 1u) * fs.bin_half_words;
-    if (rerun || fs.dirty[q] != 0u) {
-        XRT_HIP(ctx, hipMemsetAsync(mine, 0, half_words * sizeof(uint32_t), stream));
-        cleared = true;                                     // k_prep must not overtake it
-    }
+    if (rerun || fs.dirty[q] != 0u)                         // (on k_prep's stream: it must not overtake it)
+        XRT_HIP(ctx, hipMemsetAsync(mine, 0, half_words * sizeof(uint32_t), ctx->prep_stream));
     fs.half = q;
     fs.dirty[q] = n_regions;                                // this frame counts into it
     // k_prep clears the other half: its control block and its dirty counters
@@ -964,34 +940,12 @@ int bin_buffers(xrt_context* ctx, FrameSet& fs, uint32_t n_regions, uint64_t lis
     bins.clear = other + kCounterStride;
     bins.clear_regions = fs.dirty[q ^ 1u] == kDirtyAll ? alloc_regions : fs.dirty[q ^ 1u];
     fs.dirty[q ^ 1u] = 0u;
-    ctl = reinterpret_cast<BinState*>(mine);
-    fs.last_state = ctl;
+    pf.bin_ctl = reinterpret_cast<BinState*>(mine);
+    fs.last_state = pf.bin_ctl;
     bins.counts = mine + kCounterStride;
     bins.list = fs.bin_list;
     bins.global_list = fs.global_list;
     return XRT_OK;
-}
-
-// The base launch order of a region grid: centre first (regions by the
-// distance of their centre from the image centre), so the dense middle of a
-// centred object does not start last and set the tail.
-std::vector<uint32_t> centre_first_order(uint32_t rx, uint32_t ry)
-{
-    // by squared distance from the grid's centre, ties in region order: keys
-    // (4 x the squared distance, exact in integers) beside the indices, sorted
-    // once (a comparator recomputing the distances took 0.37 ms at 64 x 64)
-    const size_t n = (size_t)rx * ry;
-    std::vector<std::pair<uint64_t, uint32_t>> key(n);
-    for (uint32_t y = 0; y < ry; ++y)
-        for (uint32_t x = 0; x < rx; ++x) {
-            const int64_t dx = 2 * (int64_t)x - ((int64_t)rx - 1), dy = 2 * (int64_t)y - ((int64_t)ry - 1);
-            const size_t r = (size_t)y * rx + x;
-            key[r] = {(uint64_t)(dx * dx + dy * dy), (uint32_t)r};
-        }
-    std::sort(key.begin(), key.end());
-    std::vector<uint32_t> order(n);
-    for (size_t k = 0; k < n; ++k) order[k] = key[k].second;
-    return order;
 }
 
 // Uploads a launch layout: slot s renders region slot_region[s] from
@@ -1037,8 +991,14 @@ int upload_layout(xrt_context* ctx, SlotLayout& L, uint32_t rx, uint32_t ry, std
 
 // The fixed-capacity layout (centre-first order, `cap` entries per slot) of a
 // region grid: the first frame of a geometry bins into it.
-int fixed_layout(xrt_context* ctx, uint32_t rx, uint32_t ry, uint32_t cap, BinBuffers& bins)
+inline uint32_t fixed_region_cap(const xrt_context* ctx)
 {
+    return ctx->bin_force_cap ? (uint32_t)std::min<size_t>(kInitialRegionCap, ctx->bin_force_cap) : kInitialRegionCap;
+}
+
+int fixed_layout(xrt_context* ctx, PendingFrame& pf)
+{
+    const uint32_t rx = pf.rx, ry = pf.ry, cap = fixed_region_cap(ctx);
     SlotLayout& L = ctx->fixed;
     if (L.rx != rx || L.ry != ry || L.cap != cap || !L.d_desc) {
         const size_t n = (size_t)rx * ry;
@@ -1048,8 +1008,8 @@ int fixed_layout(xrt_context* ctx, uint32_t rx, uint32_t ry, uint32_t cap, BinBu
         if (rc) return rc;
         L.cap = cap;
     }
-    bins.desc = L.d_desc;
-    bins.rank = L.d_rank;
+    pf.bins.desc = L.d_desc;
+    pf.bins.rank = L.d_rank;
     return XRT_OK;
 }
 
@@ -1064,27 +1024,28 @@ void use_compact(xrt_context* ctx, uint32_t n_regions, BinBuffers& bins, bool fi
     bins.split_slots = fill && ctx->plan_valid && kCanSplit ? ctx->plan_split_slots : 0u;
 }
 
-// Arms the k_prep check of a frame whose region lists or fill plan k_prep's
-// binning has not yet been seen to match: the first frame over a new plan
-// (`validate`) and frames over lists sized for another camera (`reused`).
+// Arms the k_prep check of a frame whose fill plan k_prep's binning has not
+// yet been seen to match: the first frame over a new plan (`validate`).
 // The binning of a frame geometry (mesh, camera, strip) is deterministic --
 // the same footprints join the same regions, only the order of a list's
 // entries varies with the atomics -- so later frames of a validated geometry
 // cannot miss it and are launched without the host reading the check
 // (DESIGN.md "Pipelining").
-void arm_plan_check(FrameSet& fs, uint32_t n_regions, BinBuffers& bins, bool reused, bool validate)
+void arm_plan_check(FrameSet& fs, uint32_t n_regions, BinBuffers& bins, bool validate)
 {
     bins.plan_miss = nullptr;
-    if (fs.plan_flag && ((validate && bins.tile_slots < n_regions) || reused)) {
+    if (fs.plan_flag && validate && bins.tile_slots < n_regions) {
         fs.plan_flag[0] = 0u;
         fs.plan_flag[1] = 0u;
         bins.plan_miss = const_cast<uint32_t*>(fs.plan_flag);
     }
 }
 
-int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, uint32_t row_end,
-                  float* d_image, float* d_lbuffer, uint8_t* d_u8, hipStream_t stream, PendingFrame& pf,
-                  int set_index = -1)
+// prepare_frame's stages, in its order; each fills its part of the
+// PendingFrame.  First the arguments' checks and the kernel choice: pf's
+// kernel, binned, rows and region grid.
+int choose_kernel(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, uint32_t row_end,
+                  const float* d_image, const uint8_t* d_u8, PendingFrame& pf)
 {
     int rc = check_camera(ctx, cam, row_begin, row_end);
     if (rc) return rc;
@@ -1117,21 +1078,22 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     }
     // k_prep packs a footprint's region rectangle in 16-bit fields: grids past
     // 65535 regions a side render TILED (exact, slower) -- BRUTE for the signed model.
-    const bool binned = kernel == XRT_KERNEL_BINNED && rows > 0 && T > 0 && rx <= 0xFFFFu && ry <= 0xFFFFu;
-    if (signed_model && !binned) kernel = XRT_KERNEL_BRUTE;
-    const bool culled = kernel != XRT_KERNEL_BRUTE;
+    pf.binned = kernel == XRT_KERNEL_BINNED && rows > 0 && T > 0 && rx <= 0xFFFFu && ry <= 0xFFFFu;
+    if (signed_model && !pf.binned) kernel = XRT_KERNEL_BRUTE;
+    pf.kernel = kernel;
+    pf.rows = rows;
+    pf.rx = rx;
+    pf.ry = ry;
+    return XRT_OK;
+}
 
-    // This frame's buffer set.  The render that last used it (kFrameSets
-    // frames ago) must be complete before the set is prepared again.
-    FrameSet& fs = ctx->sets[set_index < 0 ? ctx->next_set : set_index];
-    // The preparation runs on the context's prep stream, beside the previous
-    // frame's render; the host waits for its completion before it launches
-    // the render (DESIGN.md "Pipelining": no cross-queue event on the render
-    // queue).  The fill plan needs the attenuation model (the signed render
-    // fills nothing).
-    hipStream_t ps = ctx->prep_stream;
-    const bool fill_ok = !signed_model;
-    const auto t_call = HostClock::now();
+// The frame's buffer set (pf.fs): the render that last used it (kFrameSets
+// frames ago) must be complete before the set is prepared again.
+int claim_set(xrt_context* ctx, const xrt_camera* cam, PendingFrame& pf)
+{
+    FrameSet& fs = *pf.fs;
+    const uint64_t T = render_tris(ctx);
+    int rc;
     if (fs.done_valid) {
         const auto t = HostClock::now();
         XRT_HIP(ctx, hipEventSynchronize(fs.done_ev));
@@ -1149,18 +1111,16 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
         }
     }
     if ((rc = ensure(ctx, fs.recs, fs.recs_cap, T))) return rc;
-    if (culled && (rc = ensure(ctx, fs.cull, fs.cull_cap, (size_t)T * kCullPlanes))) return rc;
-    if ((rc = ensure(ctx, fs.offsets, fs.offsets_cap, (size_t)cam->height + cam->width))) return rc;
+    if (pf.kernel != XRT_KERNEL_BRUTE && (rc = ensure(ctx, fs.cull, fs.cull_cap, (size_t)T * kCullPlanes))) return rc;
+    return ensure(ctx, fs.offsets, fs.offsets_cap, (size_t)cam->height + cam->width);
+}
 
-    RenderParams p = make_params(*cam, row_begin, row_end, T, ctx->hit_capacity);
-    p.model = ctx->model;
-    if (!ctx->cull_valid || std::memcmp(&ctx->cull_cam, cam, sizeof *cam) != 0) {
-        ctx->cull = make_cull_params(*cam);      // a scan over the rows / columns: once per camera
-        ctx->cull_cam = *cam;
-        ctx->cull_valid = true;
-    }
-    const CullParams cp = ctx->cull;
-    Outputs out;
+// The render's Outputs (launch_frame adds the timing records and the rays).
+int frame_outputs(xrt_context* ctx, const xrt_camera* cam, float* d_image, float* d_lbuffer, uint8_t* d_u8,
+                  PendingFrame& pf)
+{
+    const FrameSet& fs = *pf.fs;
+    Outputs& out = pf.out;
     out.image = d_image;
     out.lbuffer = d_lbuffer;
     out.image_u8 = d_u8;
@@ -1186,321 +1146,284 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     out.hit_off = nullptr;
     out.rays = nullptr;                // launch_frame
     if (ctx->packed_cap || ctx->hits_cap) {        // xrt_set_transit_layout / _hits
-        if (!binned || signed_model || d_image || d_u8)
+        if (!pf.binned || ctx->model != kModelAttenuation || d_image || d_u8)
             return fail(ctx, XRT_ERR_ARGUMENT,
                         "the transit layouts are for BINNED attenuation renders of the L-buffer only");
         out.packed = ctx->hits_cap ? kLayoutHits : kLayoutPacked;
         out.hit_tiles = ctx->hit_tiles;
         out.hit_off = ctx->d_hit_off;
     }
-    const uint32_t n_regions = rows ? rx * ry : 0u;
-    BinBuffers bins = {};
-    BinState* bin_ctl = nullptr;
-    xrt_context::BinKey key = {};                  // the frame geometry of the region lists
-    key.cam = *cam;
-    key.row_begin = row_begin;
-    key.row_end = row_end;
-    key.T = T;
-    key.gen = ctx->mesh_gen;
-    key.pose_gen = ctx->pose_gen;
-    // A new camera over the same region grid (a projection sweep) reuses the
-    // lists sized for an earlier camera instead of the synchronous sizing
-    // (DESIGN.md "Moving camera"), without a fill plan: k_prep flags a region
-    // count past its list's capacity, that region renders from the whole mesh
-    // (exact) and the next frame re-sizes.  A camera that then stays put for
-    // kStillFrames frames is sized for itself (tight lists and a fill plan).
-    // Contexts of xrt_render_rows_multi size every camera (reuse_cameras).
-    ctx->still_frames = key.same(ctx->last_key) ? ctx->still_frames + 1u : 0u;
-    ctx->last_key = key;
-    bool reuse = false;
-    if (binned && rows > 0 && fill_ok && ctx->bin_key_valid && (ctx->compact || ctx->dev_geometry) &&
-        !ctx->bin_force_cap && !ctx->packed_cap && !ctx->hits_cap) {
-        if (ctx->reuse_cameras && !key.same(ctx->bin_key) && key.same_layout(ctx->bin_key) &&
-            ctx->still_frames < kStillFrames) {
-            reuse = true;
-            ctx->moving = true;
-            ++ctx->hp_reused;
-        } else if (ctx->moving && ctx->still_frames >= kStillFrames) {
-            ctx->moving = false;           // the camera stopped: sized for it below
-            ctx->bin_key_valid = false;
-        }
-    }
-    if (!key.same_layout(ctx->bin_key)) ctx->moving = false;
-    // (a geometry whose only frame was sized on the device has no compact
-    // lists: the same camera again is sized on the host)
-    const bool new_geometry = binned && rows > 0 && !reuse &&
-                              (!ctx->bin_key_valid || !key.same(ctx->bin_key) || ctx->dev_geometry);
-    if (new_geometry) ctx->compact = false;
-    const uint32_t fixed_cap = ctx->bin_force_cap ? (uint32_t)std::min<size_t>(kInitialRegionCap, ctx->bin_force_cap)
-                                                  : kInitialRegionCap;
-    // A frame geometry seen for the first time -- a context's first frame, the
-    // reference's whole workload -- is sized on the device as a moving camera's
-    // frame is (below; one 32-byte read-back for the pool, no host plan and no
-    // second k_prep); the same geometry again is sized on the host (compact
-    // lists, fill plan, heaviest regions first) for the frames that follow.
-    // Host-buffer calls only (xrt_render_rows: the drop-in renderLoop's one
-    // frame into an Image): device-pointer callers -- pipelines, and strips
-    // whose transit plans (xrt_plan_region_map, xrt_plan_hit_layout) describe
-    // the host-sized layout of the frame before -- keep the host sizing.
-    const bool dev_first = new_geometry && !ctx->bin_force_cap && ctx->device_first && ctx->still_frames == 0u &&
-                           fill_ok && !ctx->packed_cap && !ctx->hits_cap && ctx->reuse_cameras &&
-                           stream == ctx->host_stream;
-    const bool device_sized = reuse || dev_first;
-    if (new_geometry) ctx->dev_geometry = false;
-    if (dev_first) {                               // later cameras over its region grid take the moving path
-        ctx->dev_geometry = true;
-        ctx->bin_key = key;
-        ctx->bin_key_valid = true;
-    }
-    // A new geometry's first k_prep only counts its pairs (no lists): the
-    // compact lists are sized from the counts and k_prep runs again into them.
-    const bool sizing = new_geometry && !ctx->bin_force_cap && !dev_first;
-    if ((sizing || dev_first) && ctx->sizing_profile) {
-        ctx->prof_t = t_call;
-        prof_mark(ctx, "set wait + buffers");
-    }
-    if (binned) {
-        bins.regions_x = rx;
-        bins.regions_y = ry;
-    }
-    if (binned && !device_sized) {
-        const bool compact = ctx->compact && !ctx->bin_force_cap;
-        bool cleared = false;
-        const uint64_t entries = compact ? ctx->slot_pool : sizing ? 0u : (uint64_t)n_regions * fixed_cap;
-        if ((rc = bin_buffers(ctx, fs, n_regions, entries, bins, bin_ctl, ps, cleared))) return rc;
-        if (sizing) prof_mark(ctx, "bin buffers (counter memset)");
-        if (sizing) bins.list = nullptr;
-        bins.tile_slots = n_regions;
-        if (compact) use_compact(ctx, n_regions, bins, fill_ok && !reuse);
-        else if ((rc = fixed_layout(ctx, rx, ry, fixed_cap, bins))) return rc;
-        bins.tile_plan = compact && fill_ok && !reuse && !sizing && ctx->plan_valid && ctx->tile_plan_enabled &&
-                         ctx->tile_plan_state == 1 ? 1u : 0u;
-        bins.box_masks = ctx->box_masks == 2 || (ctx->box_masks == 1 && T < kPrepBigMesh) ? 1u : 0u;
-        if (sizing) prof_mark(ctx, "fixed layout upload");
-        // the fill plan's test hook (every region planned empty) is checked every frame
-        arm_plan_check(fs, n_regions, bins, false, ctx->fill_plan == 2);
-    }
+    return XRT_OK;
+}
 
-    hipEvent_t prep_done = fs.ready;
-    if (device_sized) {
-        // A moving camera (DESIGN.md "Moving camera"): its lists sized on the
-        // device, no host round trip -- k_prep counts its pairs per slot of the
-        // region grid's base layout (centre first), k_size_lists carves each
-        // slot's list from the set's pool, k_prep bins into them.  Every region
-        // renders as tiles (no fill plan: the host never sees the counts).
-        // k_prep's flags are read when the set is next used (lazy_flags).
-        // (a geometry's first frame: room for ~6 pairs a triangle, checked below)
-        const uint64_t first_guess = dev_first ? 6u * (uint64_t)T + 2u * n_regions : 0u;
-        ctx->motion_pool = ctx->motion_pool_forced
-                               ? ctx->motion_pool_forced
-                               : std::max<uint64_t>(std::max<uint64_t>(ctx->motion_pool, first_guess),
-                                                    std::max<uint64_t>(2 * ctx->slot_pool, 65536u));
-        bool cleared = false;
-        if ((rc = bin_buffers(ctx, fs, n_regions, ctx->motion_pool, bins, bin_ctl, ps, cleared))) return rc;
-        if (dev_first) prof_mark(ctx, "device first: bin buffers");
-        if ((rc = fixed_layout(ctx, rx, ry, fixed_cap, bins))) return rc;
-        if (dev_first) prof_mark(ctx, "device first: fixed layout");
-        if ((rc = ensure(ctx, fs.dyn_desc, fs.dyn_desc_cap, n_regions))) return rc;
-        if ((rc = ensure(ctx, fs.pairs, fs.pairs_cap, ctx->motion_pool))) return rc;
-        // the device fill plan (not for the transit layouts, whose tiles follow a host plan)
-        const bool dev_plan = ctx->device_fill && ctx->fill_plan != 0 && out.packed == 0u;
-        if (dev_plan && ((rc = ensure(ctx, fs.plan_desc, fs.plan_desc_cap, n_regions)) ||
-                         (rc = ensure(ctx, fs.plan_counts, fs.plan_counts_cap, (size_t)n_regions * kCounterStride))))
-            return rc;
-        uint32_t pool = (uint32_t)std::min<uint64_t>(ctx->motion_pool, 0xFFFFFFFFull);
-        bins.tile_slots = n_regions;
-        bins.split_slots = 0u;
-        bins.tile_plan = 0u;
-        bins.plan_miss = nullptr;
-        bins.box_masks = ctx->box_masks == 2 ? 1u : 0u;
-        RegionEntry* list = bins.list;
-        bins.list = nullptr;                           // the count-only pass, appending its pairs
-        bins.pairs = fs.pairs;
-        bins.pairs_cap = pool;
-        if ((rc = launch_prep(ctx, fs, p, cp, culled, bins, bin_ctl, ps, prep_done))) return rc;
-        if (dev_first) prof_mark(ctx, "device first: count pass (buffers before it)");
-        if (dev_first) {
-            // A first frame has no earlier pose to size its pool from: the count
-            // pass's pair total (32 bytes read back) checks it, and a pool too
-            // small grows and counts again -- never the whole-mesh fallback.
-            ++ctx->hp_dev_first;
-            uint8_t* hs = nullptr;
-            if ((rc = sizing_scratch(ctx, sizeof(BinState), hs))) return rc;
-            XRT_HIP(ctx, hipMemcpyAsync(hs, bin_ctl, sizeof(BinState), hipMemcpyDeviceToHost, ps));
-            XRT_HIP(ctx, hipStreamSynchronize(ps));
-            BinState st;
-            std::memcpy(&st, hs, sizeof st);
-            prof_mark(ctx, "device first: pair total read back");
-            ctx->dev_first_pairs = st.pairs;
-            ctx->dev_first_pool = pool;
-            if (st.pairs > pool && !ctx->motion_pool_forced) {
-                ++ctx->hp_dev_first_recounts;
-                ctx->motion_pool = std::min<uint64_t>((uint64_t)st.pairs + st.pairs / 4u + 65536u, 0xFFFFFFFFull);
-                pool = (uint32_t)ctx->motion_pool;
-                if ((rc = bin_buffers(ctx, fs, n_regions, ctx->motion_pool, bins, bin_ctl, ps, cleared, true)))
-                    return rc;                     // (clears this frame's counters)
-                if ((rc = fixed_layout(ctx, rx, ry, fixed_cap, bins))) return rc;
-                if ((rc = ensure(ctx, fs.pairs, fs.pairs_cap, ctx->motion_pool))) return rc;
-                list = bins.list;
-                bins.list = nullptr;
-                bins.pairs = fs.pairs;
-                bins.pairs_cap = pool;
-                if ((rc = launch_prep(ctx, fs, p, cp, culled, bins, bin_ctl, ps, prep_done))) return rc;
-            }
-        }
-        uint32_t* const flag = fs.plan_flag ? const_cast<uint32_t*>(fs.plan_flag) : nullptr;
-        if (flag) {                                    // [1]: a list past the pool, read lazily
-            flag[0] = 0u;
-            flag[1] = 0u;
-            fs.lazy_flags = true;
-        }
-        // The lists of the frame: k_size_lists and k_scatter_pairs on the device's
-        // host stream (idle in a device-pointer pipeline, no extra queue) after
-        // the count pass's event, the preparation's event after them.  (Measured
-        // and dropped: on the render's stream they queue behind that stream's
-        // previous render, on the prep stream the next frame's k_prep queues
-        // behind them -- 2048^2 moving frames 47.0 / 57.5 us against 41.1,
-        // profiles/r06ac, r06ae.)
-        uint32_t* const pass_counts = bins.counts;     // the count pass's counter lines (the base layout's order)
-        const SlotDesc* const fixed = bins.desc;
-        SlotDesc* const plan_desc = dev_plan ? fs.plan_desc : nullptr;   // the device fill plan's layout (null: none)
-        uint32_t* const plan_counts = dev_plan ? fs.plan_counts : nullptr;
-        bins.list = list;
-        bins.desc = dev_plan ? fs.plan_desc : fs.dyn_desc;
-        if (dev_plan) {                                // the render reads the plan's order
-            bins.counts = fs.plan_counts;
-            bins.dev_plan = 1u;
-        }
-        bins.pairs = nullptr;
-        bins.clear = nullptr;
-        const hipStream_t ss = ctx->host_stream;
-        if (ss != ps) XRT_HIP(ctx, hipStreamWaitEvent(ss, prep_done, 0));
-        hipLaunchKernelGGL(k_size_lists, dim3((n_regions + 255) / 256), dim3(256), 0, ss, pass_counts, fixed,
-                           fs.dyn_desc, n_regions, pool, bin_ctl, plan_desc, plan_counts);
-        XRT_HIP(ctx, hipGetLastError());
-        const uint32_t scatter_blocks = (uint32_t)std::min<uint64_t>((pool + 255u) / 256u, 2048u);
-        hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, ss, (const uint4*)fs.pairs,
-                           (const BinState*)bin_ctl, pool, (const SlotDesc*)fs.dyn_desc, (const float4*)fs.cull,
-                           (uint32_t)T, bins.list, flag);
-        XRT_HIP(ctx, hipGetLastError());
-        XRT_HIP(ctx, hipEventRecord(prep_done, ss));
-    }
-    if (rows > 0 && !device_sized && (rc = launch_prep(ctx, fs, p, cp, culled, bins, bin_ctl, ps, prep_done)))
+// Lists already known (ListMode::Fixed, Compact) and a host-sized frame's
+// count pass (no lists yet): the buffers, the layout, the tile-plan and
+// box-mask bits and the plan check of the k_prep that follows.
+int known_lists(xrt_context* ctx, PendingFrame& pf, ListMode mode)
+{
+    BinBuffers& bins = pf.bins;
+    const uint32_t n_regions = frame_regions(pf);
+    const bool fill_ok = pf.p.model == kModelAttenuation;
+    const bool compact = mode == ListMode::Compact, counting = mode == ListMode::HostSized;
+    int rc;
+    const uint64_t entries = compact ? ctx->slot_pool : counting ? 0u : (uint64_t)n_regions * fixed_region_cap(ctx);
+    if ((rc = bin_buffers(ctx, pf, entries))) return rc;
+    if (counting) prof_mark(ctx, "bin buffers (counter memset)");
+    if (counting) bins.list = nullptr;
+    bins.tile_slots = n_regions;
+    if (compact) use_compact(ctx, n_regions, bins, fill_ok);
+    else if ((rc = fixed_layout(ctx, pf))) return rc;
+    bins.tile_plan = compact && fill_ok && ctx->plan_valid && ctx->tile_plan_enabled && ctx->tile_plan_state == 1 ? 1u
+                                                                                                                 : 0u;
+    bins.box_masks = ctx->box_masks == 2 || (ctx->box_masks == 1 && render_tris(ctx) < kPrepBigMesh) ? 1u : 0u;
+    if (counting) prof_mark(ctx, "fixed layout upload");
+    // the fill plan's test hook (every region planned empty) is checked every frame
+    arm_plan_check(*pf.fs, n_regions, bins, ctx->fill_plan == 2);
+    return XRT_OK;
+}
+
+// Device sizing's count pass: k_prep counts the frame's pairs per slot of the
+// region grid's base layout and appends them to the set's pairs, a pool of
+// ctx->motion_pool entries.  `rerun`: again, into a pool regrown.
+int count_pairs(xrt_context* ctx, PendingFrame& pf, bool dev_plan, bool mark, bool rerun)
+{
+    FrameSet& fs = *pf.fs;
+    BinBuffers& bins = pf.bins;
+    const uint32_t n_regions = frame_regions(pf);
+    int rc;
+    if ((rc = bin_buffers(ctx, pf, ctx->motion_pool, rerun))) return rc;   // (a re-run clears this frame's counters)
+    if (mark) prof_mark(ctx, "device first: bin buffers");
+    if ((rc = fixed_layout(ctx, pf))) return rc;
+    if (mark) prof_mark(ctx, "device first: fixed layout");
+    if ((rc = ensure(ctx, fs.dyn_desc, fs.dyn_desc_cap, n_regions))) return rc;
+    if ((rc = ensure(ctx, fs.pairs, fs.pairs_cap, ctx->motion_pool))) return rc;
+    if (dev_plan && ((rc = ensure(ctx, fs.plan_desc, fs.plan_desc_cap, n_regions)) ||
+                     (rc = ensure(ctx, fs.plan_counts, fs.plan_counts_cap, (size_t)n_regions * kCounterStride))))
         return rc;
-    if (sizing) {
-        // Size the compact region lists once per frame geometry (mesh, camera,
-        // strip): a synchronous read of every region's count (the count-only
-        // pass above), slot offsets from them, and a re-run of k_prep into the
-        // compact lists.
-        ++ctx->hp_sizings;
-        prof_mark(ctx, "k_prep count pass");
-        const auto t_sizing = HostClock::now();
-        // every region's count (line-padded) and the BinState, into the pinned scratch
-        const size_t cbytes = (size_t)n_regions * kCounterStride * sizeof(uint32_t);
+    bins.tile_slots = n_regions;
+    bins.split_slots = 0u;
+    bins.tile_plan = 0u;
+    bins.plan_miss = nullptr;
+    bins.box_masks = ctx->box_masks == 2 ? 1u : 0u;
+    bins.list = nullptr;                           // the count-only pass, appending its pairs
+    bins.pairs = fs.pairs;
+    bins.pairs_cap = (uint32_t)std::min<uint64_t>(ctx->motion_pool, 0xFFFFFFFFull);
+    if ((rc = launch_prep(ctx, pf))) return rc;
+    if (mark) prof_mark(ctx, "device first: count pass (buffers before it)");
+    return XRT_OK;
+}
+
+// ListMode::DeviceMoving and DeviceFirst (DESIGN.md "Moving camera"): the
+// lists sized on the device, no host round trip -- k_prep counts its pairs per
+// slot of the region grid's base layout (centre first), k_size_lists carves
+// each slot's list from the set's pool, k_scatter_pairs bins into them.  Every
+// region renders as tiles (no fill plan: the host never sees the counts).
+// k_prep's flags are read when the set is next used (lazy_flags).
+int device_sized_lists(xrt_context* ctx, PendingFrame& pf, ListMode mode)
+{
+    FrameSet& fs = *pf.fs;
+    BinBuffers& bins = pf.bins;
+    const hipStream_t ps = ctx->prep_stream;
+    const uint64_t T = render_tris(ctx);
+    const uint32_t n_regions = frame_regions(pf);
+    const bool first = mode == ListMode::DeviceFirst;
+    int rc;
+    // (a geometry's first frame: room for ~6 pairs a triangle, checked below)
+    const uint64_t first_guess = first ? 6u * (uint64_t)T + 2u * n_regions : 0u;
+    ctx->motion_pool = ctx->motion_pool_forced
+                           ? ctx->motion_pool_forced
+                           : std::max<uint64_t>(std::max<uint64_t>(ctx->motion_pool, first_guess),
+                                                std::max<uint64_t>(2 * ctx->slot_pool, 65536u));
+    // the device fill plan (not for the transit layouts, whose tiles follow a host plan)
+    const bool dev_plan = ctx->device_fill && ctx->fill_plan != 0 && pf.out.packed == 0u;
+    if ((rc = count_pairs(ctx, pf, dev_plan, first, false))) return rc;
+    if (first) {
+        // A first frame has no earlier pose to size its pool from: the count
+        // pass's pair total (32 bytes read back) checks it, and a pool too
+        // small grows and counts again -- never the whole-mesh fallback.
+        ++ctx->hp_dev_first;
         uint8_t* hs = nullptr;
-        if ((rc = sizing_scratch(ctx, cbytes + sizeof(BinState), hs))) return rc;
-        XRT_HIP(ctx, hipMemcpyAsync(hs, bins.counts, cbytes, hipMemcpyDeviceToHost, ps));
-        prof_mark(ctx, "count read-back: counts enqueued");
-        XRT_HIP(ctx, hipMemcpyAsync(hs + cbytes, bin_ctl, sizeof(BinState), hipMemcpyDeviceToHost, ps));
-        prof_mark(ctx, "count read-back: state enqueued");
+        if ((rc = sizing_scratch(ctx, sizeof(BinState), hs))) return rc;
+        XRT_HIP(ctx, hipMemcpyAsync(hs, pf.bin_ctl, sizeof(BinState), hipMemcpyDeviceToHost, ps));
         XRT_HIP(ctx, hipStreamSynchronize(ps));
-        prof_mark(ctx, "count read-back");
-        const uint32_t* counts = reinterpret_cast<const uint32_t*>(hs);
         BinState st;
-        std::memcpy(&st, hs + cbytes, sizeof st);
-        const std::vector<uint32_t>& fixed_region = ctx->fixed.slot_region;   // the counts' slots
-        std::vector<uint32_t> count_of(n_regions);     // by region
-        for (uint32_t s = 0; s < n_regions; ++s) count_of[fixed_region[s]] = counts[(size_t)s * kCounterStride];
-        // The fill plan (not for a moving camera, whose next pose would miss it):
-        // the regions this frame counted empty (with an empty global list) go to
-        // the end of the launch order, one workgroup each; the tile regions by
-        // candidate count, heaviest first (their long tiles start first instead
-        // of setting the tail: render 2048^2 -6 %, 1024^2 -10 %).
-        std::vector<uint32_t> slot_region = fixed_region;
-        uint32_t tile_slots = n_regions, split_slots = 0;
-        const int plan = ctx->fill_plan;
-        if (plan != 0 && st.global_count == 0u && !ctx->moving) {
-            std::vector<uint32_t> full, empty;
-            for (uint32_t r : fixed_region) (count_of[r] != 0u && plan != 2 ? full : empty).push_back(r);
-            std::stable_sort(full.begin(), full.end(), [&](uint32_t a, uint32_t b) { return count_of[a] > count_of[b]; });
-            tile_slots = (uint32_t)full.size();
-            // the heaviest regions (the first slots): two waves per tile
-            uint32_t split_min = ctx->split_min;
-            if (split_min == kSplitAuto) {
-                const bool small = (double)tile_slots * kWavesPerRegion <= kSplitFillFactor * ctx->wave_slots;
-                const uint32_t heaviest = tile_slots ? count_of[full[0]] : 0u;
-                split_min = small ? std::max<uint32_t>(kSplitFloor, (uint32_t)std::ceil(kSplitHeavyFrac * heaviest))
-                                  : 0u;
-            }
-            while (split_min && split_slots < tile_slots && count_of[full[split_slots]] >= split_min)
-                ++split_slots;
-            full.insert(full.end(), empty.begin(), empty.end());
-            slot_region.swap(full);
+        std::memcpy(&st, hs, sizeof st);
+        prof_mark(ctx, "device first: pair total read back");
+        ctx->dev_first_pairs = st.pairs;
+        ctx->dev_first_pool = bins.pairs_cap;
+        if (st.pairs > bins.pairs_cap && !ctx->motion_pool_forced) {
+            ++ctx->hp_dev_first_recounts;
+            ctx->motion_pool = std::min<uint64_t>((uint64_t)st.pairs + st.pairs / 4u + 65536u, 0xFFFFFFFFull);
+            if ((rc = count_pairs(ctx, pf, dev_plan, false, true))) return rc;
         }
-        std::vector<uint32_t> base(n_regions), cap(n_regions);
-        uint64_t run = 0;
-        for (uint32_t s = 0; s < n_regions; ++s) {
-            const uint64_t c = count_of[slot_region[s]];
-            // a moving camera: room for the counts of the next poses (2c + 64)
-            const uint64_t room = ctx->moving ? 2u * c + 64u : c + c / 8u + 4u;
-            base[s] = (uint32_t)run;
-            cap[s] = (uint32_t)std::min<uint64_t>(room, 0xFFFFFFFFull);
-            run += room;
-        }
-        if (run > 0xFFFFFFFFull) return fail(ctx, XRT_ERR_OVERFLOW, "region lists exceed 2^32 entries");
-        prof_mark(ctx, "plan (host)");
-        if ((rc = upload_layout(ctx, ctx->compact_layout, rx, ry, std::move(slot_region), base, cap))) return rc;
-        ctx->tile_plan_state = 0;                  // the new layout's tiles are all live
-        prof_mark(ctx, "compact layout upload");
-        ctx->acc_ms[1] += std::chrono::duration<double, std::milli>(HostClock::now() - t_sizing).count();
-        ctx->plan_tile_slots = tile_slots;
-        ctx->plan_split_slots = split_slots;
-        ctx->plan_valid = tile_slots < n_regions;
-        ctx->slot_pool = run;
-        ctx->compact = true;
-        ctx->bin_key = key;
-        ctx->bin_key_valid = true;
-        bool cleared = false;
-        if ((rc = bin_buffers(ctx, fs, n_regions, run, bins, bin_ctl, ps, cleared, true))) return rc;   // clears
-        bins.tile_slots = n_regions;
-        use_compact(ctx, n_regions, bins, fill_ok);
-        arm_plan_check(fs, n_regions, bins, false, true);
-        prof_mark(ctx, "counter memset (re-run)");
-        if ((rc = launch_prep(ctx, fs, p, cp, culled, bins, bin_ctl, ps, prep_done))) return rc;
-        prof_mark(ctx, "k_prep into the compact lists");
     }
+    const uint32_t pool = bins.pairs_cap;
+    uint32_t* const flag = fs.plan_flag ? const_cast<uint32_t*>(fs.plan_flag) : nullptr;
+    if (flag) {                                    // [1]: a list past the pool, read lazily
+        flag[0] = 0u;
+        flag[1] = 0u;
+        fs.lazy_flags = true;
+    }
+    // The lists of the frame: k_size_lists and k_scatter_pairs on the device's
+    // host stream (idle in a device-pointer pipeline, no extra queue) after
+    // the count pass's event, the preparation's event after them.  (Measured
+    // and dropped: on the render's stream they queue behind that stream's
+    // previous render, on the prep stream the next frame's k_prep queues
+    // behind them -- 2048^2 moving frames 47.0 / 57.5 us against 41.1,
+    // profiles/r06ac, r06ae.)
+    uint32_t* const pass_counts = bins.counts;     // the count pass's counter lines (the base layout's order)
+    const SlotDesc* const fixed = bins.desc;
+    SlotDesc* const plan_desc = dev_plan ? fs.plan_desc : nullptr;   // the device fill plan's layout (null: none)
+    uint32_t* const plan_counts = dev_plan ? fs.plan_counts : nullptr;
+    bins.list = fs.bin_list;
+    bins.desc = dev_plan ? fs.plan_desc : fs.dyn_desc;
+    if (dev_plan) {                                // the render reads the plan's order
+        bins.counts = fs.plan_counts;
+        bins.dev_plan = 1u;
+    }
+    bins.pairs = nullptr;
+    bins.clear = nullptr;
+    const hipStream_t ss = ctx->host_stream;
+    if (ss != ps) XRT_HIP(ctx, hipStreamWaitEvent(ss, pf.prep_done, 0));
+    hipLaunchKernelGGL(k_size_lists, dim3((n_regions + 255) / 256), dim3(256), 0, ss, pass_counts, fixed,
+                       fs.dyn_desc, n_regions, pool, pf.bin_ctl, plan_desc, plan_counts);
+    XRT_HIP(ctx, hipGetLastError());
+    const uint32_t scatter_blocks = (uint32_t)std::min<uint64_t>((pool + 255u) / 256u, 2048u);
+    hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, ss, (const uint4*)fs.pairs,
+                       (const BinState*)pf.bin_ctl, pool, (const SlotDesc*)fs.dyn_desc, (const float4*)fs.cull,
+                       (uint32_t)T, bins.list, flag);
+    XRT_HIP(ctx, hipGetLastError());
+    XRT_HIP(ctx, hipEventRecord(pf.prep_done, ss));
+    return XRT_OK;
+}
+
+// ListMode::HostSized, after its count pass: the compact region lists sized
+// once per frame geometry (mesh, camera, strip) -- a synchronous read of every
+// region's count, the plan from them (plan_lists), its layout's upload, and a
+// re-run of k_prep into the compact lists.
+int host_sized_lists(xrt_context* ctx, PendingFrame& pf)
+{
+    const hipStream_t ps = ctx->prep_stream;
+    const uint32_t n_regions = frame_regions(pf);
+    int rc;
+    ++ctx->hp_sizings;
+    prof_mark(ctx, "k_prep count pass");
+    const auto t_sizing = HostClock::now();
+    // every region's count (line-padded) and the BinState, into the pinned scratch
+    const size_t cbytes = (size_t)n_regions * kCounterStride * sizeof(uint32_t);
+    uint8_t* hs = nullptr;
+    if ((rc = sizing_scratch(ctx, cbytes + sizeof(BinState), hs))) return rc;
+    XRT_HIP(ctx, hipMemcpyAsync(hs, pf.bins.counts, cbytes, hipMemcpyDeviceToHost, ps));
+    prof_mark(ctx, "count read-back: counts enqueued");
+    XRT_HIP(ctx, hipMemcpyAsync(hs + cbytes, pf.bin_ctl, sizeof(BinState), hipMemcpyDeviceToHost, ps));
+    prof_mark(ctx, "count read-back: state enqueued");
+    XRT_HIP(ctx, hipStreamSynchronize(ps));
+    prof_mark(ctx, "count read-back");
+    BinState st;
+    std::memcpy(&st, hs + cbytes, sizeof st);
+    ListPlan plan;
+    if (!plan_lists(reinterpret_cast<const uint32_t*>(hs), kCounterStride, ctx->fixed.slot_region, st.global_count,
+                    ctx->fill_plan, ctx->geo.moving, ctx->split_min, ctx->wave_slots, kWavesPerRegion, plan))
+        return fail(ctx, XRT_ERR_OVERFLOW, "region lists exceed 2^32 entries");
+    prof_mark(ctx, "plan (host)");
+    if ((rc = upload_layout(ctx, ctx->compact_layout, pf.rx, pf.ry, std::move(plan.slot_region), plan.base, plan.cap)))
+        return rc;
+    ctx->tile_plan_state = 0;                  // the new layout's tiles are all live
+    prof_mark(ctx, "compact layout upload");
+    ctx->acc_ms[1] += std::chrono::duration<double, std::milli>(HostClock::now() - t_sizing).count();
+    ctx->plan_tile_slots = plan.tile_slots;
+    ctx->plan_split_slots = plan.split_slots;
+    ctx->plan_valid = plan.tile_slots < n_regions;
+    ctx->slot_pool = plan.pool;
+    ctx->geo.compact = true;
+    ctx->geo.bin_key = ctx->geo.last_key;      // this frame's
+    ctx->geo.bin_key_valid = true;
+    if ((rc = bin_buffers(ctx, pf, plan.pool, true))) return rc;   // clears
+    pf.bins.tile_slots = n_regions;
+    use_compact(ctx, n_regions, pf.bins, pf.p.model == kModelAttenuation);
+    arm_plan_check(*pf.fs, n_regions, pf.bins, true);
+    prof_mark(ctx, "counter memset (re-run)");
+    if ((rc = launch_prep(ctx, pf))) return rc;
+    prof_mark(ctx, "k_prep into the compact lists");
+    return XRT_OK;
+}
+
+// The render's grid, the set's statistics records, and what launch_frame needs
+// to know of the lists.
+int finish_frame(xrt_context* ctx, const BinKey& key, ListMode mode, PendingFrame& pf)
+{
+    FrameSet& fs = *pf.fs;
+    const BinBuffers& bins = pf.bins;
+    const uint32_t n_regions = frame_regions(pf);
+    int rc;
     // BINNED: one 8x8 tile per render wave, kTileWaves waves per workgroup, and
     // one workgroup per region of the fill plan
-    const dim3 grid = kernel == XRT_KERNEL_BRUTE ? dim3((cam->width + 15) / 16, (rows + 15) / 16)
-                    : binned ? dim3(kWavesPerRegion / kTileWaves * (bins.tile_slots + bins.split_slots) +
-                                    (n_regions - bins.tile_slots))
-                             : dim3(rx, ry);
+    pf.grid = pf.kernel == XRT_KERNEL_BRUTE ? dim3((pf.p.width + 15) / 16, (pf.rows + 15) / 16)
+              : pf.binned ? dim3(kWavesPerRegion / kTileWaves * (bins.tile_slots + bins.split_slots) +
+                                 (n_regions - bins.tile_slots))
+                          : dim3(pf.rx, pf.ry);
     // stats records: one per workgroup; BINNED one per tile wave, 16 per fill region
-    const uint32_t n_blocks = !rows ? 0u : binned ? kWavesPerRegion * n_regions : grid.x * grid.y;
+    const uint32_t n_blocks = !pf.rows ? 0u : pf.binned ? kWavesPerRegion * n_regions : pf.grid.x * pf.grid.y;
     if ((rc = ensure(ctx, fs.block_stats, fs.block_stats_cap, n_blocks))) return rc;
     if ((rc = ensure(ctx, fs.times, fs.times_cap, n_blocks))) return rc;
     fs.n_blocks = n_blocks;
-    fs.binned = binned;
-    out.block_stats = fs.block_stats;
-    pf.fs = &fs;
-    pf.plan_source = binned && fill_ok && !reuse && ctx->compact && ctx->plan_valid && !ctx->bin_force_cap &&
+    fs.binned = pf.binned;
+    pf.out.block_stats = fs.block_stats;
+    pf.plan_source = (mode == ListMode::Compact || mode == ListMode::HostSized) &&
+                     pf.p.model == kModelAttenuation && ctx->plan_valid &&
                      bins.desc == ctx->compact_layout.d_desc && bins.tile_slots == ctx->plan_tile_slots;
     pf.hit_plan_ok = ctx->hit_valid && key.same(ctx->hit_key);
-    pf.stream = stream;
-    pf.prep_done = rows > 0 ? prep_done : nullptr;
-    pf.host_wait = bins.plan_miss != nullptr && !device_sized;
-    pf.kernel = kernel;
-    pf.binned = binned;
-    pf.rows = rows;
-    pf.rx = rx;
-    pf.ry = ry;
-    pf.grid = grid;
-    pf.p = p;
-    pf.out = out;
-    pf.bins = bins;
-    pf.bin_ctl = bin_ctl;
-    pf.t_call = t_call;
+    if (!pf.rows) pf.prep_done = nullptr;
+    pf.host_wait = bins.plan_miss != nullptr;      // (never armed in a device-sized frame)
     return XRT_OK;
+}
+
+// A frame's preparation, enqueued on the context's prep stream beside the
+// previous frame's render; the host waits for its completion before it
+// launches the render (DESIGN.md "Pipelining": no cross-queue event on the
+// render queue).
+int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, uint32_t row_end,
+                  float* d_image, float* d_lbuffer, uint8_t* d_u8, hipStream_t stream, PendingFrame& pf,
+                  int set_index = -1)
+{
+    pf = PendingFrame{};
+    int rc = choose_kernel(ctx, cam, row_begin, row_end, d_image, d_u8, pf);
+    if (rc) return rc;
+    pf.fs = &ctx->sets[set_index < 0 ? ctx->next_set : set_index];
+    pf.stream = stream;
+    pf.prep_done = pf.fs->ready;
+    pf.t_call = HostClock::now();
+    if ((rc = claim_set(ctx, cam, pf))) return rc;
+    pf.p = make_params(*cam, row_begin, row_end, render_tris(ctx), ctx->hit_capacity);
+    pf.p.model = ctx->model;
+    if (!ctx->cull_valid || std::memcmp(&ctx->cull_cam, cam, sizeof *cam) != 0) {
+        ctx->cull = make_cull_params(*cam);      // a scan over the rows / columns: once per camera
+        ctx->cull_cam = *cam;
+        ctx->cull_valid = true;
+    }
+    if ((rc = frame_outputs(ctx, cam, d_image, d_lbuffer, d_u8, pf))) return rc;
+    const xrt_context::BinKey key = geometry_key(ctx, cam, row_begin, row_end);
+    const ListMode mode = choose_list_mode(
+        ctx->geo, FrameFacts{key, pf.binned, ctx->model == kModelAttenuation, ctx->bin_force_cap != 0,
+                             ctx->packed_cap || ctx->hits_cap, ctx->reuse_cameras, ctx->device_first,
+                             stream == ctx->host_stream});
+    if (mode == ListMode::DeviceMoving) ++ctx->hp_reused;
+    if ((mode == ListMode::HostSized || mode == ListMode::DeviceFirst) && ctx->sizing_profile) {
+        ctx->prof_t = pf.t_call;
+        prof_mark(ctx, "set wait + buffers");
+    }
+    if (pf.binned) {
+        pf.bins.regions_x = pf.rx;
+        pf.bins.regions_y = pf.ry;
+    }
+    if (mode == ListMode::DeviceMoving || mode == ListMode::DeviceFirst) {
+        if ((rc = device_sized_lists(ctx, pf, mode))) return rc;
+    } else {
+        if (mode != ListMode::None && (rc = known_lists(ctx, pf, mode))) return rc;
+        if (pf.rows > 0 && (rc = launch_prep(ctx, pf))) return rc;
+        if (mode == ListMode::HostSized && (rc = host_sized_lists(ctx, pf))) return rc;
+    }
+    return finish_frame(ctx, key, mode, pf);
 }
 
 // Room for n timing records of a sampled frame in the timed region's chunks
@@ -1668,7 +1591,7 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
         // tiles (split tiles only ever merge list-rendered halves)
         if (fs.plan_flag[1] != 0u) bins.split_slots = 0u;
         grid = dim3(kWavesPerRegion / kTileWaves * (bins.tile_slots + bins.split_slots));
-        ctx->bin_key_valid = false;
+        ctx->geo.resize_next_frame();
     }
     ctx->last_fill_regions = binned ? rx * ry - bins.tile_slots : 0u;
     if (pf.out.packed == kLayoutPacked && rows > 0 &&
@@ -1799,19 +1722,6 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
     ctx->pending = true;
     ctx->last_kernel = kernel;
     return XRT_OK;
-}
-
-xrt_context::BinKey geometry_key(const xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin,
-                                 uint32_t row_end)
-{
-    xrt_context::BinKey key = {};
-    key.cam = *cam;
-    key.row_begin = row_begin;
-    key.row_end = row_end;
-    key.T = render_tris(ctx);
-    key.gen = ctx->mesh_gen;
-    key.pose_gen = ctx->pose_gen;
-    return key;
 }
 
 // One frame: its preparation (or the one prepared ahead for it) and its
@@ -4036,8 +3946,8 @@ int xrt_plan_region_map(xrt_context* ctx, uint32_t width, uint32_t rows, uint32_
     const bool planned = ctx->last_fill_regions > 0 && ctx->plan_valid && layout;
     // no region of the geometry is empty: every region travels, in slot order
     // (the order of the hit layout's tiles)
-    const bool whole = !ctx->plan_valid && ctx->last_fill_regions == 0 && layout && ctx->compact &&
-                       ctx->bin_key_valid && ctx->last_key.same(ctx->bin_key);
+    const bool whole = !ctx->plan_valid && ctx->last_fill_regions == 0 && layout && ctx->geo.compact &&
+                       ctx->geo.bin_key_valid && ctx->geo.last_key.same(ctx->geo.bin_key);
     if (!planned && !whole) {                       // every region travels
         for (uint64_t r = 0; r < n_regions; ++r) map[r] = (uint32_t)r;
         *n_packed = (uint32_t)n_regions;
@@ -4126,8 +4036,8 @@ int xrt_plan_hit_layout(xrt_context* ctx, uint32_t* tile_hits, uint64_t capacity
     // (s < the plan's tile slots) are the plan's tiles
     const bool fill_frame = ctx->plan_valid && ctx->last_fill_regions > 0;
     const bool whole_frame = !ctx->plan_valid && ctx->last_fill_regions == 0;
-    if (!fs || !fs->binned || !ctx->bin_key_valid || !ctx->compact || !(fill_frame || whole_frame) ||
-        !ctx->last_key.same(ctx->bin_key) || (uint64_t)ctx->plan_tile_slots * kWavesPerRegion > fs->rendered_blocks)
+    if (!fs || !fs->binned || !ctx->geo.bin_key_valid || !ctx->geo.compact || !(fill_frame || whole_frame) ||
+        !ctx->geo.last_key.same(ctx->geo.bin_key) || (uint64_t)ctx->plan_tile_slots * kWavesPerRegion > fs->rendered_blocks)
         return fail(ctx, XRT_ERR_ARGUMENT, "the hit plan needs a BINNED frame rendered over its geometry's fill "
                                            "plan just before");
     const uint32_t tiles = ctx->plan_tile_slots * kWavesPerRegion;
@@ -4144,7 +4054,7 @@ int xrt_plan_hit_layout(xrt_context* ctx, uint32_t* tile_hits, uint64_t capacity
     off[tiles] = (uint32_t)run;
     if ((rc = ensure(ctx, ctx->d_hit_off, ctx->hit_off_cap, (size_t)tiles + 1u))) return rc;
     XRT_HIP(ctx, hipMemcpy(ctx->d_hit_off, off.data(), off.size() * 4u, hipMemcpyHostToDevice));
-    ctx->hit_key = ctx->bin_key;
+    ctx->hit_key = ctx->geo.bin_key;
     ctx->hit_tiles = tiles;
     ctx->hit_words = 2ull * tiles + run;
     ctx->hit_valid = true;
@@ -4319,7 +4229,7 @@ int xrt_set_fill_plan(xrt_context* ctx, int mode)
     if (!ctx) return XRT_ERR_ARGUMENT;
     if (mode < 0 || mode > 2) return fail(ctx, XRT_ERR_ARGUMENT, "fill plan mode must be 0, 1 or 2");
     ctx->fill_plan = mode;
-    ctx->bin_key_valid = false;         // the next frame re-sizes and re-plans
+    ctx->geo.resize_next_frame();       // the next frame re-sizes and re-plans
     ctx->plan_valid = false;
     ++ctx->state_gen;                   // frames prepared ahead are stale
     return XRT_OK;
@@ -4449,7 +4359,7 @@ int xrt_read_stats(xrt_context* ctx, xrt_stats* stats)
     stats->kernel_ms = fs->last_times && t.span_hi > t.span_lo ? (double)(t.span_hi - t.span_lo) / kTicksPerMs : 0.0;
     stats->global_triangles = fs->binned ? t.global_count : 0u;
     if (fs->binned && t.overflow && !ctx->bin_force_cap) {   // the next frame re-sizes its lists
-        ctx->bin_key_valid = false;
+        ctx->geo.resize_next_frame();
         ++ctx->state_gen;
     }
     return XRT_OK;

@@ -559,7 +559,7 @@ def test_box_masks_exact(dragon, monkeypatch, name, model):
                 assert getattr(got[3], f) == getattr(ref[3], f), (mode, k, f)
 
 
-@pytest.mark.parametrize("case", ["dragon-strip", "planes-recount", "soup"])
+@pytest.mark.parametrize("case", ["dragon-strip", "planes-recount", "soup", "soup-forced"])
 def test_first_frame_device_sized_exact(dragon, case):
     """A geometry's first host-buffer frame is sized on the device (the count
     pass, one read-back of its pair total, k_size_lists / k_scatter_pairs, the
@@ -567,7 +567,10 @@ def test_first_frame_device_sized_exact(dragon, case):
     a strip starting off the region grid; planes each covering every region, so
     the first pool (6 pairs a triangle, at least 65,536) is too small and the
     pass counts again; a random soup.  The same camera again is sized on the host, a new
-    one takes the moving path, every frame exact."""
+    one takes the moving path, every frame exact.  soup-forced, before the new camera: the
+    sized one over its compact lists, then under a forced capacity of 16 entries a region
+    (fixed lists, regions from the whole mesh), then without it -- exact, and the compact
+    lists stay the geometry's: no frame of the three is sized again."""
     from scene_kit import plane_stack
     if case == "dragon-strip":
         tris, W, H, r0, r1 = dragon, 1000, 777, 13, 700
@@ -601,6 +604,23 @@ def test_first_frame_device_sized_exact(dragon, case):
                 assert np.array_equal(bits(x), bits(y)), (case, k)
             for f in ("rays", "hits", "hit_rays", "odd_rays", "max_hits"):
                 assert getattr(got[3], f) == getattr(refs[k][3], f), (case, k, f)
+            if case == "soup-forced" and k == 1:               # (before the camera moves: a still camera's lists)
+                g0, f0 = g1, f1
+                more = [c.render_rows(cam, r0, r1)]
+                c.set_bin_capacity(16)
+                try:
+                    more.append(c.render_rows(cam, r0, r1))
+                finally:
+                    c.set_bin_capacity(0)
+                more.append(c.render_rows(cam, r0, r1))
+                g1, f1 = c.geometry_counters(), c.first_frames()
+                for j, got in enumerate(more):
+                    for x, y in zip(got[:3], refs[0][:3]):
+                        assert np.array_equal(bits(x), bits(y)), (case, "forced", j)
+                    for f in ("rays", "hits", "hit_rays", "odd_rays", "max_hits"):
+                        assert getattr(got[3], f) == getattr(refs[0][3], f), (case, "forced", j, f)
+                assert more[1][3].candidates > max(more[0][3].candidates, more[2][3].candidates), [m[3].candidates for m in more]
+                assert (g1, f1["device_sized"]) == (g0, f0["device_sized"]), (g0, g1)
     assert paths[0][0] == 1 and paths[0][2] == 0, paths       # device-sized, no host sizing
     assert paths[1][2] == 1 and paths[1][0] == 0, paths       # the same camera: sized on the host
     assert paths[2][3] == 1, paths                            # a new camera: the moving path
