@@ -122,18 +122,15 @@ constexpr int kD2HThreads = 8;
 // 10-22 ms in them (DESIGN.md "Measurement").
 constexpr size_t kSizingScratch = (size_t)1 << 20;
 
+#include "xrt_owned_host.inc"
+
 struct FrameSet {
-    TriRec* recs = nullptr;        // per-render records
-    size_t recs_cap = 0;
-    float4* cull = nullptr;        // per-render cull planes (4 x T float4)
-    size_t cull_cap = 0;
-    RenderParams* frame = nullptr;       // the frame's parameters (k_prep writes, make_ray reads)
-    float* offsets = nullptr;            // the frame's pixel offsets, rows then columns (k_prep)
-    size_t offsets_cap = 0;
-    BlockStats* block_stats = nullptr;   // the render's per-workgroup / per-wave records
-    size_t block_stats_cap = 0;
-    uint2* times = nullptr;              // their timing records (Outputs::wave_times), frames not sampled
-    size_t times_cap = 0;
+    Owned<TriRec> recs;            // per-render records
+    Owned<float4> cull;            // per-render cull planes (4 x T float4)
+    Owned<RenderParams> frame;           // the frame's parameters (k_prep writes, make_ray reads)
+    Owned<float> offsets;                // the frame's pixel offsets, rows then columns (k_prep)
+    Owned<BlockStats> block_stats;       // the render's per-workgroup / per-wave records
+    Owned<uint2> times;                  // their timing records (Outputs::wave_times), frames not sampled
     // where the set's last render stored its timing records: `times`, or a
     // timed region's chunk (copied back into `times` by xrt_timing_end)
     const uint2* last_times = nullptr;
@@ -146,39 +143,32 @@ struct FrameSet {
     // A frame counts into one half while its k_prep clears the other, which
     // the set's previous frame used (its render is complete: the host waited
     // for it before reusing the set) -- no memset on the per-frame path.
-    uint32_t* bin_counts = nullptr;
-    size_t bin_counts_cap = 0;         // words, both halves
+    Owned<uint32_t> bin_counts;        // words, both halves
     size_t bin_half_words = 0;         // words per half
     uint32_t half = 0;                 // half of the set's last frame
     // Per half: the counters past dirty[h] are zero, and so is its BinState
     // when dirty[h] == 0; kDirtyAll = unknown (fresh allocation).
     uint32_t dirty[2] = {kDirtyAll, kDirtyAll};
     BinState* last_state = nullptr;    // BinState of the set's last binned frame
-    RegionEntry* bin_list = nullptr;   // regions x capacity footprint entries
-    size_t bin_list_cap = 0;
-    RegionEntry* global_list = nullptr;
-    size_t global_list_cap = 0;
+    Owned<RegionEntry> bin_list;       // regions x capacity footprint entries
+    Owned<RegionEntry> global_list;
 
     // Completion events ride on the kernel dispatches themselves
     // (hipExtLaunchKernel stop events): no separate event packets.
-    SlotDesc* dyn_desc = nullptr;      // a device-sized frame's launch layout (k_size_lists)
-    size_t dyn_desc_cap = 0;
-    uint4* pairs = nullptr;            // its (slot, index, triangle) pairs (k_prep's count pass)
-    size_t pairs_cap = 0;
-    SlotDesc* plan_desc = nullptr;     // its render layout under the device fill plan (tiles first, then fills)
-    size_t plan_desc_cap = 0;
-    uint32_t* plan_counts = nullptr;   // and its counter lines in that order
-    size_t plan_counts_cap = 0;
+    Owned<SlotDesc> dyn_desc;          // a device-sized frame's launch layout (k_size_lists)
+    Owned<uint4> pairs;                // its (slot, index, triangle) pairs (k_prep's count pass)
+    Owned<SlotDesc> plan_desc;         // its render layout under the device fill plan (tiles first, then fills)
+    Owned<uint32_t> plan_counts;       // and its counter lines in that order
     bool lazy_flags = false;           // plan_flag armed for a frame launched without reading it
-    hipEvent_t ready = nullptr;        // k_prep complete (prep stream)
-    hipEvent_t done = nullptr;         // render end (a stop event on the render's dispatch)
-    hipEvent_t done_ev = nullptr;      // the event that marks the set's last render complete
+    TimedEvent ready;                  // k_prep complete (prep stream)
+    TimedEvent done;                   // render end (a stop event on the render's dispatch)
+    hipEvent_t done_ev = nullptr;      // the event that marks the set's last render complete: done, or a region's (tev)
     bool done_valid = false;
     bool ray_reader = false;           // the set's last render reads the context's ray table
     // k_prep's flags (BinBuffers::plan_miss): [0] the fill plan did not hold,
     // [1] a list overflowed.  Host-mapped, cleared by the host before k_prep,
     // read after the host has waited for k_prep's completion.
-    volatile uint32_t* plan_flag = nullptr;
+    Owned<volatile uint32_t, PinnedMem<hipHostMallocCoherent>> plan_flag;
 };
 
 using HostClock = std::chrono::steady_clock;
@@ -249,10 +239,8 @@ private:
 // (SlotDesc, device), region -> slot (k_prep's binning), and the host copy of
 // slot -> region (row-major over the strip).
 struct SlotLayout {
-    SlotDesc* d_desc = nullptr;
-    size_t desc_cap = 0;
-    uint32_t* d_rank = nullptr;
-    size_t rank_cap = 0;
+    Owned<SlotDesc> d_desc;
+    Owned<uint32_t> d_rank;
     std::vector<uint32_t> slot_region;
     uint32_t rx = 0, ry = 0, cap = 0;  // the fixed-capacity layout's key
 };
@@ -290,9 +278,8 @@ struct xrt_context {
     int device = 0;
     std::string error;
 
-    float* d_tris = nullptr;       // raw triangle soup, 9 f32 per triangle
+    Owned<float> d_tris;           // raw triangle soup, 9 f32 per triangle
     uint64_t num_tris = 0;
-    size_t tris_cap = 0;
     FrameSet sets[kFrameSets];
     int next_set = 0;
     FrameSet* last_set = nullptr;      // set of the last enqueued frame
@@ -340,30 +327,27 @@ struct xrt_context {
     bool tile_plan_enabled = false;
     // xrt_debug_prep_times: k_prep's per-wave timestamps of the last launch
     bool prep_times_on = false;
-    uint4* d_prep_times = nullptr;
-    size_t prep_times_cap = 0, prep_times_n = 0;
+    Owned<uint4> d_prep_times;
+    size_t prep_times_n = 0;
     int tile_plan_state = 0;
     uint64_t hp_tile_plan_frames = 0, hp_tile_plans = 0;
     uint32_t last_fill_regions = 0;    // regions the last enqueued frame filled (diagnostics)
     uint64_t packed_cap = 0;           // xrt_set_transit_layout: the packed L-buffer's floats (0: row-major)
 
     // staging for the host-pointer entry point
-    float* d_image = nullptr;
-    float* d_lbuffer = nullptr;
-    uint8_t* d_u8 = nullptr;
-    size_t stage_cap = 0;
+    Owned<float> d_image;
+    Owned<float> d_lbuffer;
+    Owned<uint8_t> d_u8;
     // The host-buffer entry points run on this context-owned non-blocking
     // stream (never the null stream, whose legacy semantics order it against
     // every blocking stream of the device), and copy back through the pinned
     // ring h_stage (kStageSlots x kStageChunk) with the copy threads of `pool`.
     hipStream_t host_stream = nullptr;
-    uint8_t* h_stage = nullptr;
-    hipEvent_t stage_ev[kStageSlots] = {};
-    uint8_t* h_sizing = nullptr;       // pinned scratch of the sizing path (kSizingScratch, grown on demand)
-    size_t h_sizing_cap = 0;
-    hipEvent_t sizing_ev = nullptr;    // the last upload from h_sizing (prep stream)
-    bool sizing_busy = false;
-    hipEvent_t host_render_done = nullptr;
+    Pinned<uint8_t> h_stage;
+    PlainEvent stage_ev[kStageSlots];
+    Pinned<uint8_t> h_sizing;          // pinned scratch of the sizing path (kSizingScratch, grown on demand)
+    Fence sizing_done;                 // the last upload from h_sizing (prep stream)
+    PlainEvent host_render_done;
     std::unique_ptr<CopyPool> pool;
     // the preparation stream holds work that reads a launch layout (k_prep)
     // since it was last synchronised (upload_layout needs it idle)
@@ -373,13 +357,13 @@ struct xrt_context {
     int sizing_profile = 0;
     HostClock::time_point prof_t{};
 
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    TimedEvent ev_begin, ev_end;
     // xrt_read_stats: the last render's records summed on the device
     // (k_reduce_stats) into one record, read through pinned memory
-    StatsSum* d_stats_partial = nullptr;   // [kReduceMaxBlocks]
-    unsigned int* d_stats_done = nullptr;  // the last-block counter (reset by that block)
-    StatsSum* d_stats_out = nullptr;
-    StatsSum* h_stats = nullptr;           // pinned
+    Owned<StatsSum> d_stats_partial;       // [kReduceMaxBlocks]
+    Owned<unsigned int> d_stats_done;      // the last-block counter (reset by that block)
+    Owned<StatsSum> d_stats_out;
+    Pinned<StatsSum> h_stats;
     // host time of the last host-buffer call (xrt_render_rows), ms:
     // [0] device planes, [1] enqueue (preparation, sizing, launch), [2] wait for
     // the render, [3] D2H of the planes (DMA into the pinned ring overlapped with
@@ -393,7 +377,7 @@ struct xrt_context {
     double acc_ms[kAccFields] = {};                  // running sums of [8..15]
     // region timing (xrt_timing_begin/end)
     bool timing = false;
-    std::vector<hipEvent_t> tev;      // pairs: [2i] start, [2i+1] stop of a sampled render dispatch
+    std::vector<TimedEvent> tev;      // pairs: [2i] start, [2i+1] stop of a sampled render dispatch
     size_t tev_used = 0;
     uint64_t timed_frames = 0;        // frames enqueued since xrt_timing_begin
     size_t timed_records = 0;         // their timing records kept
@@ -401,8 +385,8 @@ struct xrt_context {
     // the sampled frames' timing records: chunks of device memory (a chunk is
     // never moved while kernels may write it), and where each frame's are
     struct TimesChunk {
-        uint2* p;
-        size_t cap, used;
+        Owned<uint2> p;
+        size_t used = 0;
     };
     std::vector<TimesChunk> tchunks;
     struct TimesSample {              // a frame's records: where they are (chunks never move) and how many
@@ -428,8 +412,7 @@ struct xrt_context {
     BinKey hit_key = {};
     uint32_t hit_tiles = 0;
     uint64_t hit_words = 0;
-    uint32_t* d_hit_off = nullptr;
-    size_t hit_off_cap = 0;
+    Owned<uint32_t> d_hit_off;
     // Prepare-ahead (DESIGN.md "Pipelining"): when a device-pointer render
     // repeats the previous call's frame geometry, the preparations of the next
     // kAheadFrames frames of that geometry are enqueued at once on the prep
@@ -460,16 +443,16 @@ struct xrt_context {
     // kModelMaterials (xrt_set_materials): one coefficient per mesh, and the
     // device table of the scene's id ranges with them (upload_materials)
     std::vector<float> materials_mu;
-    MeshMaterial* d_materials = nullptr;
+    Owned<MeshMaterial> d_materials;
     // kModelSpectrum (xrt_set_spectrum): the bins' weights, the coefficients
     // (mesh-major, spectrum_meshes x weights.size()) and their device table
     // (upload_spectrum)
     std::vector<float> spectrum_weight, spectrum_mu;
     uint32_t spectrum_meshes = 0;
-    SpectrumTable* d_spectrum = nullptr;
+    Owned<SpectrumTable> d_spectrum;
     // kModelPaths (xrt_set_paths): the scene's id-range ends, kMaxMeshes words,
     // kept with every scene upload (upload_path_ends)
-    uint32_t* d_path_ends = nullptr;
+    Owned<uint32_t> d_path_ends;
     xrt_camera cull_cam = {};          // camera of the cached cull parameters
     CullParams cull = {};
     bool cull_valid = false;
@@ -490,8 +473,7 @@ struct xrt_context {
     // since the upload): the next render's k_pose rewrites the meshes that
     // differ, on the prep stream ahead of its k_prep.
     using Pose = std::array<float, kPoseFloats>;
-    float* d_tris_posed = nullptr;
-    size_t posed_cap = 0;
+    Owned<float> d_tris_posed;
     std::vector<Pose> poses;
     std::vector<Pose> posed_written;
     uint64_t pose_gen = 0;             // bumped by every pose change
@@ -499,11 +481,13 @@ struct xrt_context {
 
     // The voxel volume (xrt_upload_volume): apart from the
     // meshes, the model and the frames.  vol.labels is null while there is
-    // none.  vol_ev marks the last trace enqueued (on the caller's stream):
-    // the next upload waits for it before it frees the arrays.
+    // none; it and vol.density point into vol_labels and vol_density.
+    // vol_traced marks the last trace enqueued (on the caller's stream): the
+    // next upload waits for it before it frees the arrays.
     VolumeDesc vol = {};
-    hipEvent_t vol_ev = nullptr;
-    bool vol_busy = false;
+    Owned<uint8_t> vol_labels;
+    Owned<float> vol_density;
+    Fence vol_traced;
     uint32_t vol_tile_shift = kVolumeTileShift;        // xrt_debug_volume_wave_shape
 
     // The working set of xrt_sirt[_device]: one allocation
@@ -512,25 +496,24 @@ struct xrt_context {
     // TV also the sums' partials and x0; xrt_volume_sumsq and
     // xrt_tv_descend lay their partials and gradient volume in it --, kept
     // between calls.  sirt_mats is the upload's source (it must outlive the
-    // copy); sirt_ev marks the last call's end on its stream: the next call
+    // copy); sirt_done marks the last call's end on its stream: the next call
     // waits for it before it touches either.
-    uint8_t* d_sirt = nullptr;
-    size_t sirt_cap = 0;
+    Owned<uint8_t> d_sirt;
     std::vector<double> sirt_mats;
-    hipEvent_t sirt_ev = nullptr;
-    bool sirt_busy = false;
+    Fence sirt_done;
 
     // The voxeliser (xrt_voxelize[_device]) lays its control
-    // words, queue and flip volume in that working set.  vox_ev marks the
+    // words, queue and flip volume in that working set.  vox_scattered marks the
     // last scatter enqueued on the caller's stream, the soup's only reader
     // there: sync_context waits for it, so an upload or a pose change does not
     // replace the soup under it.  vox_counters: the set still holds the last
     // call's control words (xrt_debug_voxelize_counters), laid there by
     // work on vox_stream: a next voxelisation on that stream is ordered
     // behind it by the stream and need not wait for the set on the host.
-    hipEvent_t vox_ev = nullptr, vox_pose_ev = nullptr;
+    Fence vox_scattered;
+    PlainEvent vox_pose_ev;
     hipStream_t vox_stream = nullptr;
-    bool vox_busy = false, vox_counters = false;
+    bool vox_counters = false;
     uint32_t vox_threshold = kVoxelQueueColumns;       // xrt_debug_voxelize_threshold
     uint32_t vox_stages = 7u;                          // xrt_debug_voxelize_stages: 1 scatter, 2 scan, 4 clear, 8 the scan in one run
 
@@ -549,12 +532,10 @@ struct xrt_context {
                    row_begin == o.row_begin && row_end == o.row_end;
         }
     };
-    float* d_rays = nullptr;
-    size_t rays_cap = 0;               // bytes allocated
+    Owned<float> d_rays;
     RayKey ray_key = {};               // the table's, while ray_valid
     bool ray_valid = false;            // a fill for ray_key is enqueued (or complete)
-    hipEvent_t ray_filled = nullptr;   // that fill's end (prep stream)
-    bool ray_fill_done = false;        // ray_filled has passed: readers need no wait
+    Fence ray_filled;                  // that fill's end (prep stream); once it has passed, readers need no wait
     std::vector<hipStream_t> ray_waited;   // the streams already ordered after the fill
     RayKey ray_call_key = {};          // the previous eligible frame's key
     bool ray_call_valid = false;
@@ -661,20 +642,16 @@ int fail(xrt_context* ctx, int code, const std::string& msg)
                         std::string(#expr) + ": " + hipGetErrorString(_e));                   \
     } while (0)
 
-template <typename T>
-int ensure(xrt_context* ctx, T*& ptr, size_t& cap, size_t need_elems)
+// buf holds at least need_elems (Owned::reserve); a HIP error goes to ctx->error,
+// the allocation's time to acc_ms[0] (host_call_ms[8]).
+template <typename T, typename Mem>
+int ensure(xrt_context* ctx, Owned<T, Mem>& buf, size_t need_elems)
 {
-    if (need_elems <= cap && ptr) return XRT_OK;
-    if (ptr) {
-        (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-    }
-    size_t n = std::max<size_t>(need_elems, 1);
+    if (need_elems <= buf.cap() && buf) return XRT_OK;
+    buf.reset();                                   // (reserve's own test and free, here to keep the free out of the timed hipMalloc)
     const auto t = HostClock::now();
-    XRT_HIP(ctx, hipMalloc(&ptr, n * sizeof(T)));
+    XRT_HIP(ctx, buf.reserve(need_elems));
     if (ctx) ctx->acc_ms[0] += std::chrono::duration<double, std::milli>(HostClock::now() - t).count();
-    cap = n;
     return XRT_OK;
 }
 
@@ -682,18 +659,9 @@ int ensure(xrt_context* ctx, T*& ptr, size_t& cap, size_t need_elems)
 // in flight (its last upload's event, long complete as a rule).
 int sizing_scratch(xrt_context* ctx, size_t bytes, uint8_t*& out)
 {
-    if (ctx->sizing_busy) {
-        XRT_HIP(ctx, hipEventSynchronize(ctx->sizing_ev));
-        ctx->sizing_busy = false;
-    }
-    if (ctx->h_sizing_cap < bytes) {
-        if (ctx->h_sizing) (void)hipHostFree(ctx->h_sizing);
-        ctx->h_sizing = nullptr;
-        ctx->h_sizing_cap = 0;
-        XRT_HIP(ctx, hipHostMalloc((void**)&ctx->h_sizing, bytes, hipHostMallocDefault));
-        ctx->h_sizing_cap = bytes;
-    }
-    out = ctx->h_sizing;
+    XRT_HIP(ctx, ctx->sizing_done.wait());
+    XRT_HIP(ctx, ctx->h_sizing.reserve(bytes));
+    out = ctx->h_sizing.get();
     return XRT_OK;
 }
 
@@ -718,10 +686,7 @@ int sync_context(xrt_context* ctx)
         if (fs.done_valid) XRT_HIP(ctx, hipEventSynchronize(fs.done_ev));
     lap(6);
     if (ctx->pending) XRT_HIP(ctx, hipStreamSynchronize(ctx->last_stream));
-    if (ctx->vox_busy) {                              // a scatter of xrt_voxelize_device reads the soup
-        XRT_HIP(ctx, hipEventSynchronize(ctx->vox_ev));
-        ctx->vox_busy = false;
-    }
+    XRT_HIP(ctx, ctx->vox_scattered.wait());          // a scatter of xrt_voxelize_device reads the soup
     lap(7);
     return XRT_OK;
 }
@@ -794,13 +759,13 @@ inline uint64_t soup_gen(const xrt_context* ctx) { return ctx->mesh_gen + ctx->p
 // the prep stream.  The host does not wait.
 int render_soup(xrt_context* ctx, const float*& soup)
 {
-    soup = ctx->d_tris;
+    soup = ctx->d_tris.get();
     if (ctx->poses.empty()) return XRT_OK;
     const size_t M = ctx->mesh_tris.size();
-    if (!ctx->d_tris_posed || ctx->posed_cap < 9 * ctx->num_tris) ctx->posed_written.clear();
-    int rc = ensure(ctx, ctx->d_tris_posed, ctx->posed_cap, 9 * ctx->num_tris);
+    if (!ctx->d_tris_posed || ctx->d_tris_posed.cap() < 9 * ctx->num_tris) ctx->posed_written.clear();
+    int rc = ensure(ctx, ctx->d_tris_posed, 9 * ctx->num_tris);
     if (rc) return rc;
-    soup = ctx->d_tris_posed;
+    soup = ctx->d_tris_posed.get();
     const bool all = ctx->posed_written.size() != M;
     PoseTable tab;
     std::memset(&tab, 0, sizeof tab);
@@ -827,8 +792,8 @@ int render_soup(xrt_context* ctx, const float*& soup)
         for (uint64_t t = first; t < tab.end[last]; t += kPoseLaunchTris) {
             const uint64_t n = std::min<uint64_t>(kPoseLaunchTris, tab.end[last] - t);
             hipLaunchKernelGGL(k_pose, dim3((unsigned)((3 * n + kPoseThreads - 1) / kPoseThreads)),
-                               dim3(kPoseThreads), 0, ctx->prep_stream, ctx->d_tris + 9 * t,
-                               ctx->d_tris_posed + 9 * t, (uint32_t)t, (uint32_t)(3 * n), tab);
+                               dim3(kPoseThreads), 0, ctx->prep_stream, ctx->d_tris.get() + 9 * t,
+                               ctx->d_tris_posed.get() + 9 * t, (uint32_t)t, (uint32_t)(3 * n), tab);
             XRT_HIP(ctx, hipGetLastError());
             ++ctx->hp_pose_launches;
             ctx->hp_pose_tris += n;
@@ -887,9 +852,9 @@ int launch_prep(xrt_context* ctx, PendingFrame& pf)
                                                (threads + kPrepThreads - 1) / kPrepThreads);
     uint4* ptimes = nullptr;                       // xrt_debug_prep_times
     if (ctx->prep_times_on) {
-        int rc = ensure(ctx, ctx->d_prep_times, ctx->prep_times_cap, 2 * (size_t)blocks * kPrepWaves);
+        int rc = ensure(ctx, ctx->d_prep_times, 2 * (size_t)blocks * kPrepWaves);
         if (rc) return rc;
-        ptimes = ctx->d_prep_times;
+        ptimes = ctx->d_prep_times.get();
         ctx->prep_times_n = (size_t)blocks * kPrepWaves;
     }
     const float* soup = nullptr;                   // (k_pose first when a pose changed, on the prep stream too)
@@ -897,8 +862,8 @@ int launch_prep(xrt_context* ctx, PendingFrame& pf)
     const auto t_launch = HostClock::now();
     hipExtLaunchKernelGGL(k_prep, dim3((unsigned)blocks), dim3(kPrepThreads),
                           ctx->prep_lds, ctx->prep_stream, nullptr, pf.prep_done, 0u,
-                          soup, (uint32_t)T, p, ctx->cull, fs.recs, culled ? fs.cull : nullptr, bins, pf.bin_ctl,
-                          fs.frame, fs.offsets, ptimes);
+                          soup, (uint32_t)T, p, ctx->cull, fs.recs.get(), culled ? fs.cull.get() : nullptr, bins, pf.bin_ctl,
+                          fs.frame.get(), fs.offsets.get(), ptimes);
     XRT_HIP(ctx, hipGetLastError());
     if (bins.counts) ctx->prep_reads_layout = true;
     ctx->acc_ms[4] += std::chrono::duration<double, std::milli>(HostClock::now() - t_launch).count();
@@ -921,16 +886,16 @@ int bin_buffers(xrt_context* ctx, PendingFrame& pf, uint64_t list_entries, bool 
     int rc;
     // per half: control block padded to a line, then one line-padded counter per region
     const size_t half_words = kCounterStride + (size_t)kCounterStride * n_regions;
-    if (!fs.bin_counts || fs.bin_half_words < half_words) {
-        if ((rc = ensure(ctx, fs.bin_counts, fs.bin_counts_cap, 2 * half_words))) return rc;
+    if (!fs.bin_counts.get() || fs.bin_half_words < half_words) {
+        if ((rc = ensure(ctx, fs.bin_counts, 2 * half_words))) return rc;
         fs.bin_half_words = half_words;
         fs.dirty[0] = fs.dirty[1] = kDirtyAll;
     }
-    if ((rc = ensure(ctx, fs.bin_list, fs.bin_list_cap, (size_t)list_entries))) return rc;
-    if ((rc = ensure(ctx, fs.global_list, fs.global_list_cap, T))) return rc;
+    if ((rc = ensure(ctx, fs.bin_list, (size_t)list_entries))) return rc;
+    if ((rc = ensure(ctx, fs.global_list, T))) return rc;
     const uint32_t q = rerun ? fs.half : fs.half ^ 1u;     // a re-run recounts into the same half
-    uint32_t* mine = fs.bin_counts + (size_t)q * fs.bin_half_words;
-    uint32_t* other = fs.bin_counts + (size_t)(q ^ 1u) * fs.bin_half_words;
+    uint32_t* mine = fs.bin_counts.get() + (size_t)q * fs.bin_half_words;
+    uint32_t* other = fs.bin_counts.get() + (size_t)(q ^ 1u) * fs.bin_half_words;
     if (rerun || fs.dirty[q] != 0u)                         // (on k_prep's stream: it must not overtake it)
         XRT_HIP(ctx, hipMemsetAsync(mine, 0, half_words * sizeof(uint32_t), ctx->prep_stream));
     fs.half = q;
@@ -943,8 +908,8 @@ int bin_buffers(xrt_context* ctx, PendingFrame& pf, uint64_t list_entries, bool 
     pf.bin_ctl = reinterpret_cast<BinState*>(mine);
     fs.last_state = pf.bin_ctl;
     bins.counts = mine + kCounterStride;
-    bins.list = fs.bin_list;
-    bins.global_list = fs.global_list;
+    bins.list = fs.bin_list.get();
+    bins.global_list = fs.global_list.get();
     return XRT_OK;
 }
 
@@ -970,19 +935,18 @@ int upload_layout(xrt_context* ctx, SlotLayout& L, uint32_t rx, uint32_t ry, std
         if ((rc = sync_context(ctx))) return rc;
         ctx->acc_ms[2] += std::chrono::duration<double, std::milli>(HostClock::now() - t_sync).count();
     }
-    if ((rc = ensure(ctx, L.d_desc, L.desc_cap, n))) return rc;
-    if ((rc = ensure(ctx, L.d_rank, L.rank_cap, n))) return rc;
+    if ((rc = ensure(ctx, L.d_desc, n))) return rc;
+    if ((rc = ensure(ctx, L.d_rank, n))) return rc;
     // from the pinned scratch, on the prep stream, in order before the k_prep
     // that reads them
     uint8_t* h = nullptr;
     if ((rc = sizing_scratch(ctx, n * (sizeof(SlotDesc) + sizeof(uint32_t)), h))) return rc;
     std::memcpy(h, desc.data(), n * sizeof(SlotDesc));
     std::memcpy(h + n * sizeof(SlotDesc), rank.data(), n * sizeof(uint32_t));
-    XRT_HIP(ctx, hipMemcpyAsync(L.d_desc, h, n * sizeof(SlotDesc), hipMemcpyHostToDevice, ctx->prep_stream));
-    XRT_HIP(ctx, hipMemcpyAsync(L.d_rank, h + n * sizeof(SlotDesc), n * sizeof(uint32_t), hipMemcpyHostToDevice,
+    XRT_HIP(ctx, hipMemcpyAsync(L.d_desc.get(), h, n * sizeof(SlotDesc), hipMemcpyHostToDevice, ctx->prep_stream));
+    XRT_HIP(ctx, hipMemcpyAsync(L.d_rank.get(), h + n * sizeof(SlotDesc), n * sizeof(uint32_t), hipMemcpyHostToDevice,
                                 ctx->prep_stream));
-    XRT_HIP(ctx, hipEventRecord(ctx->sizing_ev, ctx->prep_stream));
-    ctx->sizing_busy = true;
+    XRT_HIP(ctx, ctx->sizing_done.record(ctx->prep_stream));
     L.slot_region = std::move(slot_region);
     L.rx = rx;
     L.ry = ry;
@@ -1000,7 +964,7 @@ int fixed_layout(xrt_context* ctx, PendingFrame& pf)
 {
     const uint32_t rx = pf.rx, ry = pf.ry, cap = fixed_region_cap(ctx);
     SlotLayout& L = ctx->fixed;
-    if (L.rx != rx || L.ry != ry || L.cap != cap || !L.d_desc) {
+    if (L.rx != rx || L.ry != ry || L.cap != cap || !L.d_desc.get()) {
         const size_t n = (size_t)rx * ry;
         std::vector<uint32_t> base(n), caps(n, cap);
         for (size_t s = 0; s < n; ++s) base[s] = (uint32_t)(s * cap);
@@ -1008,8 +972,8 @@ int fixed_layout(xrt_context* ctx, PendingFrame& pf)
         if (rc) return rc;
         L.cap = cap;
     }
-    pf.bins.desc = L.d_desc;
-    pf.bins.rank = L.d_rank;
+    pf.bins.desc = L.d_desc.get();
+    pf.bins.rank = L.d_rank.get();
     return XRT_OK;
 }
 
@@ -1018,8 +982,8 @@ int fixed_layout(xrt_context* ctx, PendingFrame& pf)
 // compact lists are sized by its slots) but renders every region as tiles.
 void use_compact(xrt_context* ctx, uint32_t n_regions, BinBuffers& bins, bool fill)
 {
-    bins.desc = ctx->compact_layout.d_desc;
-    bins.rank = ctx->compact_layout.d_rank;
+    bins.desc = ctx->compact_layout.d_desc.get();
+    bins.rank = ctx->compact_layout.d_rank.get();
     bins.tile_slots = fill && ctx->plan_valid ? ctx->plan_tile_slots : n_regions;
     bins.split_slots = fill && ctx->plan_valid && kCanSplit ? ctx->plan_split_slots : 0u;
 }
@@ -1034,10 +998,10 @@ void use_compact(xrt_context* ctx, uint32_t n_regions, BinBuffers& bins, bool fi
 void arm_plan_check(FrameSet& fs, uint32_t n_regions, BinBuffers& bins, bool validate)
 {
     bins.plan_miss = nullptr;
-    if (fs.plan_flag && validate && bins.tile_slots < n_regions) {
-        fs.plan_flag[0] = 0u;
-        fs.plan_flag[1] = 0u;
-        bins.plan_miss = const_cast<uint32_t*>(fs.plan_flag);
+    if (fs.plan_flag.get() && validate && bins.tile_slots < n_regions) {
+        fs.plan_flag.get()[0] = 0u;
+        fs.plan_flag.get()[1] = 0u;
+        bins.plan_miss = const_cast<uint32_t*>(fs.plan_flag.get());
     }
 }
 
@@ -1049,7 +1013,7 @@ int choose_kernel(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
 {
     int rc = check_camera(ctx, cam, row_begin, row_end);
     if (rc) return rc;
-    if (!ctx->d_tris && ctx->num_tris) return fail(ctx, XRT_ERR_NO_MESH, "no mesh uploaded");
+    if (!ctx->d_tris.get() && ctx->num_tris) return fail(ctx, XRT_ERR_NO_MESH, "no mesh uploaded");
     if (ctx->num_tris > 0xFFFFFFFFull) return fail(ctx, XRT_ERR_ARGUMENT, "too many triangles");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
 
@@ -1105,14 +1069,14 @@ int claim_set(xrt_context* ctx, const xrt_camera* cam, PendingFrame& pf)
         // k_prep's flags; its render is complete: a list past the pool there
         // (that region rendered from the whole mesh, exactly) grows the pool
         fs.lazy_flags = false;
-        if (fs.plan_flag && fs.plan_flag[1] != 0u) {
+        if (fs.plan_flag.get() && fs.plan_flag.get()[1] != 0u) {
             ++ctx->hp_overflow;
             ctx->motion_pool = std::min<uint64_t>(2 * ctx->motion_pool + 65536u, 0xFFFFFFFFull);
         }
     }
-    if ((rc = ensure(ctx, fs.recs, fs.recs_cap, T))) return rc;
-    if (pf.kernel != XRT_KERNEL_BRUTE && (rc = ensure(ctx, fs.cull, fs.cull_cap, (size_t)T * kCullPlanes))) return rc;
-    return ensure(ctx, fs.offsets, fs.offsets_cap, (size_t)cam->height + cam->width);
+    if ((rc = ensure(ctx, fs.recs, T))) return rc;
+    if (pf.kernel != XRT_KERNEL_BRUTE && (rc = ensure(ctx, fs.cull, (size_t)T * kCullPlanes))) return rc;
+    return ensure(ctx, fs.offsets, (size_t)cam->height + cam->width);
 }
 
 // The render's Outputs (launch_frame adds the timing records and the rays).
@@ -1124,20 +1088,20 @@ int frame_outputs(xrt_context* ctx, const xrt_camera* cam, float* d_image, float
     out.image = d_image;
     out.lbuffer = d_lbuffer;
     out.image_u8 = d_u8;
-    out.frame = (const __attribute__((address_space(4))) RenderParams*)fs.frame;
-    out.off.v = fs.offsets;
-    out.off.u = fs.offsets + cam->height;
+    out.frame = (const __attribute__((address_space(4))) RenderParams*)fs.frame.get();
+    out.off.v = fs.offsets.get();
+    out.off.u = fs.offsets.get() + cam->height;
     const uint32_t miss_bits = ctx->miss_code ? ctx->miss_code : 0x7F800000u;   // +inf
     std::memcpy(&out.miss_l, &miss_bits, sizeof miss_bits);
     out.mu = ctx->mu;
     if (ctx->model == kModelSpectrum) {
-        out.spectrum = (const __attribute__((address_space(4))) SpectrumTable*)ctx->d_spectrum;
+        out.spectrum = (const __attribute__((address_space(4))) SpectrumTable*)ctx->d_spectrum.get();
         out.num_meshes = ctx->spectrum_meshes;
     } else if (ctx->model == kModelPaths) {
-        out.path_ends = (const __attribute__((address_space(4))) uint32_t*)ctx->d_path_ends;
+        out.path_ends = (const __attribute__((address_space(4))) uint32_t*)ctx->d_path_ends.get();
         out.num_meshes = (uint32_t)ctx->mesh_tris.size();
     } else {
-        out.materials = (const __attribute__((address_space(4))) MeshMaterial*)ctx->d_materials;
+        out.materials = (const __attribute__((address_space(4))) MeshMaterial*)ctx->d_materials.get();
         out.num_meshes = (uint32_t)ctx->materials_mu.size();
     }
     out.packed = 0u;
@@ -1151,7 +1115,7 @@ int frame_outputs(xrt_context* ctx, const xrt_camera* cam, float* d_image, float
                         "the transit layouts are for BINNED attenuation renders of the L-buffer only");
         out.packed = ctx->hits_cap ? kLayoutHits : kLayoutPacked;
         out.hit_tiles = ctx->hit_tiles;
-        out.hit_off = ctx->d_hit_off;
+        out.hit_off = ctx->d_hit_off.get();
     }
     return XRT_OK;
 }
@@ -1195,10 +1159,10 @@ int count_pairs(xrt_context* ctx, PendingFrame& pf, bool dev_plan, bool mark, bo
     if (mark) prof_mark(ctx, "device first: bin buffers");
     if ((rc = fixed_layout(ctx, pf))) return rc;
     if (mark) prof_mark(ctx, "device first: fixed layout");
-    if ((rc = ensure(ctx, fs.dyn_desc, fs.dyn_desc_cap, n_regions))) return rc;
-    if ((rc = ensure(ctx, fs.pairs, fs.pairs_cap, ctx->motion_pool))) return rc;
-    if (dev_plan && ((rc = ensure(ctx, fs.plan_desc, fs.plan_desc_cap, n_regions)) ||
-                     (rc = ensure(ctx, fs.plan_counts, fs.plan_counts_cap, (size_t)n_regions * kCounterStride))))
+    if ((rc = ensure(ctx, fs.dyn_desc, n_regions))) return rc;
+    if ((rc = ensure(ctx, fs.pairs, ctx->motion_pool))) return rc;
+    if (dev_plan && ((rc = ensure(ctx, fs.plan_desc, n_regions)) ||
+                     (rc = ensure(ctx, fs.plan_counts, (size_t)n_regions * kCounterStride))))
         return rc;
     bins.tile_slots = n_regions;
     bins.split_slots = 0u;
@@ -1206,7 +1170,7 @@ int count_pairs(xrt_context* ctx, PendingFrame& pf, bool dev_plan, bool mark, bo
     bins.plan_miss = nullptr;
     bins.box_masks = ctx->box_masks == 2 ? 1u : 0u;
     bins.list = nullptr;                           // the count-only pass, appending its pairs
-    bins.pairs = fs.pairs;
+    bins.pairs = fs.pairs.get();
     bins.pairs_cap = (uint32_t)std::min<uint64_t>(ctx->motion_pool, 0xFFFFFFFFull);
     if ((rc = launch_prep(ctx, pf))) return rc;
     if (mark) prof_mark(ctx, "device first: count pass (buffers before it)");
@@ -1258,7 +1222,7 @@ int device_sized_lists(xrt_context* ctx, PendingFrame& pf, ListMode mode)
         }
     }
     const uint32_t pool = bins.pairs_cap;
-    uint32_t* const flag = fs.plan_flag ? const_cast<uint32_t*>(fs.plan_flag) : nullptr;
+    uint32_t* const flag = fs.plan_flag.get() ? const_cast<uint32_t*>(fs.plan_flag.get()) : nullptr;
     if (flag) {                                    // [1]: a list past the pool, read lazily
         flag[0] = 0u;
         flag[1] = 0u;
@@ -1273,12 +1237,12 @@ int device_sized_lists(xrt_context* ctx, PendingFrame& pf, ListMode mode)
     // profiles/r06ac, r06ae.)
     uint32_t* const pass_counts = bins.counts;     // the count pass's counter lines (the base layout's order)
     const SlotDesc* const fixed = bins.desc;
-    SlotDesc* const plan_desc = dev_plan ? fs.plan_desc : nullptr;   // the device fill plan's layout (null: none)
-    uint32_t* const plan_counts = dev_plan ? fs.plan_counts : nullptr;
-    bins.list = fs.bin_list;
-    bins.desc = dev_plan ? fs.plan_desc : fs.dyn_desc;
+    SlotDesc* const plan_desc = dev_plan ? fs.plan_desc.get() : nullptr;   // the device fill plan's layout (null: none)
+    uint32_t* const plan_counts = dev_plan ? fs.plan_counts.get() : nullptr;
+    bins.list = fs.bin_list.get();
+    bins.desc = dev_plan ? fs.plan_desc.get() : fs.dyn_desc.get();
     if (dev_plan) {                                // the render reads the plan's order
-        bins.counts = fs.plan_counts;
+        bins.counts = fs.plan_counts.get();
         bins.dev_plan = 1u;
     }
     bins.pairs = nullptr;
@@ -1286,11 +1250,11 @@ int device_sized_lists(xrt_context* ctx, PendingFrame& pf, ListMode mode)
     const hipStream_t ss = ctx->host_stream;
     if (ss != ps) XRT_HIP(ctx, hipStreamWaitEvent(ss, pf.prep_done, 0));
     hipLaunchKernelGGL(k_size_lists, dim3((n_regions + 255) / 256), dim3(256), 0, ss, pass_counts, fixed,
-                       fs.dyn_desc, n_regions, pool, pf.bin_ctl, plan_desc, plan_counts);
+                       fs.dyn_desc.get(), n_regions, pool, pf.bin_ctl, plan_desc, plan_counts);
     XRT_HIP(ctx, hipGetLastError());
     const uint32_t scatter_blocks = (uint32_t)std::min<uint64_t>((pool + 255u) / 256u, 2048u);
-    hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, ss, (const uint4*)fs.pairs,
-                       (const BinState*)pf.bin_ctl, pool, (const SlotDesc*)fs.dyn_desc, (const float4*)fs.cull,
+    hipLaunchKernelGGL(k_scatter_pairs, dim3(scatter_blocks), dim3(256), 0, ss, (const uint4*)fs.pairs.get(),
+                       (const BinState*)pf.bin_ctl, pool, (const SlotDesc*)fs.dyn_desc.get(), (const float4*)fs.cull.get(),
                        (uint32_t)T, bins.list, flag);
     XRT_HIP(ctx, hipGetLastError());
     XRT_HIP(ctx, hipEventRecord(pf.prep_done, ss));
@@ -1364,14 +1328,14 @@ int finish_frame(xrt_context* ctx, const BinKey& key, ListMode mode, PendingFram
                           : dim3(pf.rx, pf.ry);
     // stats records: one per workgroup; BINNED one per tile wave, 16 per fill region
     const uint32_t n_blocks = !pf.rows ? 0u : pf.binned ? kWavesPerRegion * n_regions : pf.grid.x * pf.grid.y;
-    if ((rc = ensure(ctx, fs.block_stats, fs.block_stats_cap, n_blocks))) return rc;
-    if ((rc = ensure(ctx, fs.times, fs.times_cap, n_blocks))) return rc;
+    if ((rc = ensure(ctx, fs.block_stats, n_blocks))) return rc;
+    if ((rc = ensure(ctx, fs.times, n_blocks))) return rc;
     fs.n_blocks = n_blocks;
     fs.binned = pf.binned;
-    pf.out.block_stats = fs.block_stats;
+    pf.out.block_stats = fs.block_stats.get();
     pf.plan_source = (mode == ListMode::Compact || mode == ListMode::HostSized) &&
                      pf.p.model == kModelAttenuation && ctx->plan_valid &&
-                     bins.desc == ctx->compact_layout.d_desc && bins.tile_slots == ctx->plan_tile_slots;
+                     bins.desc == ctx->compact_layout.d_desc.get() && bins.tile_slots == ctx->plan_tile_slots;
     pf.hit_plan_ok = ctx->hit_valid && key.same(ctx->hit_key);
     if (!pf.rows) pf.prep_done = nullptr;
     pf.host_wait = bins.plan_miss != nullptr;      // (never armed in a device-sized frame)
@@ -1391,7 +1355,7 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     if (rc) return rc;
     pf.fs = &ctx->sets[set_index < 0 ? ctx->next_set : set_index];
     pf.stream = stream;
-    pf.prep_done = pf.fs->ready;
+    pf.prep_done = pf.fs->ready.get();
     pf.t_call = HostClock::now();
     if ((rc = claim_set(ctx, cam, pf))) return rc;
     pf.p = make_params(*cam, row_begin, row_end, render_tris(ctx), ctx->hit_capacity);
@@ -1426,27 +1390,50 @@ int prepare_frame(xrt_context* ctx, const xrt_camera* cam, uint32_t row_begin, u
     return finish_frame(ctx, key, mode, pf);
 }
 
+// The timed region's record space: one chunk of `space` records in place of
+// every earlier one.
+int region_chunk(xrt_context* ctx, size_t space)
+{
+    ctx->tchunks.clear();
+    xrt_context::TimesChunk c;
+    XRT_HIP(ctx, c.p.reserve(space));
+    ctx->tchunks.push_back(std::move(c));
+    ctx->timing_space = space;
+    return XRT_OK;
+}
+
+// At least n timing-enabled events for the region's sampled dispatches.
+int region_events(xrt_context* ctx, size_t n)
+{
+    while (ctx->tev.size() < n) {
+        TimedEvent e;
+        XRT_HIP(ctx, e.create());
+        ctx->tev.push_back(std::move(e));
+    }
+    return XRT_OK;
+}
+
 // Room for n timing records of a sampled frame in the timed region's chunks
 // (a new chunk, never a moved one, when the last is full).
 int timing_slot(xrt_context* ctx, size_t n, uint2*& slot)
 {
-    if (ctx->tchunks.empty() || ctx->tchunks.back().cap - ctx->tchunks.back().used < n) {
+    if (ctx->tchunks.empty() || ctx->tchunks.back().p.cap() - ctx->tchunks.back().used < n) {
         size_t want = std::max<size_t>(n * 64, (size_t)1 << 16);
         // chunks of earlier regions are reused before new ones are allocated
         size_t k = 0;
-        while (k < ctx->tchunks.size() && !(ctx->tchunks[k].used == 0 && ctx->tchunks[k].cap >= n)) ++k;
+        while (k < ctx->tchunks.size() && !(ctx->tchunks[k].used == 0 && ctx->tchunks[k].p.cap() >= n)) ++k;
         if (k < ctx->tchunks.size() && k + 1 < ctx->tchunks.size()) {
             // an unused chunk to the end (the samples hold device pointers, not indices)
             std::swap(ctx->tchunks[k], ctx->tchunks.back());
         } else if (k == ctx->tchunks.size()) {
-            xrt_context::TimesChunk c = {nullptr, want, 0};
-            XRT_HIP(ctx, hipMalloc(&c.p, want * sizeof(uint2)));
-            ctx->tchunks.push_back(c);
+            xrt_context::TimesChunk c;
+            XRT_HIP(ctx, c.p.reserve(want));
+            ctx->tchunks.push_back(std::move(c));
         }
     }
     xrt_context::TimesChunk& c = ctx->tchunks.back();
-    ctx->tsamples.push_back({c.p + c.used, n});
-    slot = c.p + c.used;
+    slot = c.p.get() + c.used;
+    ctx->tsamples.push_back({slot, n});
     c.used += n;
     return XRT_OK;
 }
@@ -1488,8 +1475,8 @@ int frame_rays(xrt_context* ctx, const RenderParams& p, hipStream_t stream, cons
     ctx->ray_call_key = key;
     ctx->ray_call_valid = true;
     if (ctx->ray_valid && !key.same(ctx->ray_key)) ctx->ray_valid = false;
-    const uint64_t bytes = ray_table_floats(p.width, p.row_begin, p.row_end) * sizeof(float);
-    if (!ctx->ray_enabled || bytes > ctx->ray_budget) {
+    const uint64_t floats = ray_table_floats(p.width, p.row_begin, p.row_end);
+    if (!ctx->ray_enabled || floats * sizeof(float) > ctx->ray_budget) {
         ++ctx->hp_ray_computed;
         return XRT_OK;
     }
@@ -1503,26 +1490,15 @@ int frame_rays(xrt_context* ctx, const RenderParams& p, hipStream_t stream, cons
             if (!fs.done_valid || hipEventQuery(fs.done_ev) == hipSuccess) fs.ray_reader = false;
             else busy = true;
         }
-        if (!busy && bytes > ctx->rays_cap && ctx->d_rays && !ctx->ray_fill_done) {
-            if (hipEventQuery(ctx->ray_filled) == hipSuccess) ctx->ray_fill_done = true;
-            else busy = true;
-        }
+        if (!busy && floats > ctx->d_rays.cap() && ctx->d_rays && ctx->ray_filled.passed() != hipSuccess) busy = true;
         if (!busy) {
-            if (bytes > ctx->rays_cap) {
-                (void)hipFree(ctx->d_rays);
-                ctx->d_rays = nullptr;
-                ctx->rays_cap = 0;
-                XRT_HIP(ctx, hipMalloc(&ctx->d_rays, bytes));
-                ctx->rays_cap = bytes;
-            }
-            if (!ctx->ray_filled) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->ray_filled, hipEventDisableTiming));
+            XRT_HIP(ctx, ctx->d_rays.reserve(floats));
             const uint32_t tiles = ray_table_tiles_x(p.width) * ray_table_tiles_y(p.row_begin, p.row_end);
-            hipLaunchKernelGGL(k_ray_table, dim3((tiles + 3u) / 4u), dim3(256), 0, ctx->prep_stream, p, ctx->d_rays);
+            hipLaunchKernelGGL(k_ray_table, dim3((tiles + 3u) / 4u), dim3(256), 0, ctx->prep_stream, p, ctx->d_rays.get());
             XRT_HIP(ctx, hipGetLastError());
-            XRT_HIP(ctx, hipEventRecord(ctx->ray_filled, ctx->prep_stream));
+            XRT_HIP(ctx, ctx->ray_filled.record(ctx->prep_stream));
             ctx->ray_key = key;
             ctx->ray_valid = true;
-            ctx->ray_fill_done = false;
             ctx->ray_waited.clear();
             ++ctx->hp_ray_fills;
         }
@@ -1531,17 +1507,14 @@ int frame_rays(xrt_context* ctx, const RenderParams& p, hipStream_t stream, cons
         ++ctx->hp_ray_computed;
         return XRT_OK;
     }
-    if (!ctx->ray_fill_done) {
-        const hipError_t q = hipEventQuery(ctx->ray_filled);
-        if (q == hipSuccess) ctx->ray_fill_done = true;
-        else if (q != hipErrorNotReady) XRT_HIP(ctx, q);
-        else if (std::find(ctx->ray_waited.begin(), ctx->ray_waited.end(), stream) == ctx->ray_waited.end()) {
-            XRT_HIP(ctx, hipStreamWaitEvent(stream, ctx->ray_filled, 0));
-            ctx->ray_waited.push_back(stream);
-        }
+    const hipError_t q = ctx->ray_filled.passed();
+    if (q != hipErrorNotReady) XRT_HIP(ctx, q);
+    else if (std::find(ctx->ray_waited.begin(), ctx->ray_waited.end(), stream) == ctx->ray_waited.end()) {
+        XRT_HIP(ctx, ctx->ray_filled.order(stream));
+        ctx->ray_waited.push_back(stream);
     }
     ++ctx->hp_ray_frames;
-    rays = ctx->d_rays;
+    rays = ctx->d_rays.get();
     return XRT_OK;
 }
 
@@ -1577,19 +1550,19 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
     dim3 grid = pf.grid;
     BinBuffers bins = pf.bins;
     bool missed = false;
-    if (binned && bins.plan_miss && pf.host_wait && (fs.plan_flag[0] | fs.plan_flag[1]) != 0u) {
+    if (binned && bins.plan_miss && pf.host_wait && (fs.plan_flag.get()[0] | fs.plan_flag.get()[1]) != 0u) {
         missed = true;
         // k_prep binned a pair into a region the plan fills, into the global
         // list or past a list's capacity: this frame renders every region as
         // tiles (an overflowed region from the whole mesh -- exact, slower), and
         // the next frame re-sizes its lists.
-        ++(fs.plan_flag[1] != 0u ? ctx->hp_overflow : ctx->hp_plan_miss);
+        ++(fs.plan_flag.get()[1] != 0u ? ctx->hp_overflow : ctx->hp_plan_miss);
         bins.tile_slots = rx * ry;
         bins.tile_plan = 0u;
         pf.plan_source = false;
         // an overflowed list renders its region from the whole mesh: as ordinary
         // tiles (split tiles only ever merge list-rendered halves)
-        if (fs.plan_flag[1] != 0u) bins.split_slots = 0u;
+        if (fs.plan_flag.get()[1] != 0u) bins.split_slots = 0u;
         grid = dim3(kWavesPerRegion / kTileWaves * (bins.tile_slots + bins.split_slots));
         ctx->geo.resize_next_frame();
     }
@@ -1614,8 +1587,8 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
     // region's frames: xrt_timing_end) and every kEventStride-th
     // dispatch also carries a start event (xrt_timing_events).
     Outputs out = pf.out;
-    out.wave_times = fs.times;
-    hipEvent_t t0 = nullptr, t1 = fs.done;
+    out.wave_times = fs.times.get();
+    hipEvent_t t0 = nullptr, t1 = fs.done.get();
     const uint64_t frame_in_region = ctx->timing ? ctx->timed_frames++ : 0;
     if (ctx->timing && rows > 0 && frame_in_region == 0 &&
         ctx->timing_space < std::min(kTimingRecords, kTimingFrames * (size_t)fs.n_blocks)) {
@@ -1624,12 +1597,7 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
         // kTimingFrames of these, before any record of the region is kept
         const size_t space = std::min(kTimingRecords, kTimingFrames * (size_t)fs.n_blocks);
         XRT_HIP(ctx, hipStreamSynchronize(stream));
-        for (auto& c : ctx->tchunks) (void)hipFree(c.p);
-        ctx->tchunks.clear();
-        xrt_context::TimesChunk c = {nullptr, space, 0};
-        XRT_HIP(ctx, hipMalloc(&c.p, space * sizeof(uint2)));
-        ctx->tchunks.push_back(c);
-        ctx->timing_space = space;
+        if (int rc = region_chunk(ctx, space)) return rc;
     }
     if (ctx->timing && rows > 0 && ctx->timed_records + fs.n_blocks <= ctx->timing_space) {
         ctx->timed_records += fs.n_blocks;
@@ -1641,15 +1609,10 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
     fs.last_times = out.wave_times;
     fs.rendered_blocks = fs.n_blocks;
     if (ctx->timing && rows > 0 && frame_in_region % kEventStride == 0) {
-        if (ctx->tev_used + 2 > ctx->tev.size()) {
-            for (int k = 0; k < 64; ++k) {
-                hipEvent_t e;
-                XRT_HIP(ctx, hipEventCreate(&e));
-                ctx->tev.push_back(e);
-            }
-        }
-        t0 = ctx->tev[ctx->tev_used];
-        t1 = ctx->tev[ctx->tev_used + 1];
+        if (ctx->tev_used + 2 > ctx->tev.size())
+            if (int rc = region_events(ctx, ctx->tev.size() + 64)) return rc;
+        t0 = ctx->tev[ctx->tev_used].get();
+        t1 = ctx->tev[ctx->tev_used + 1].get();
         ctx->tev_used += 2;
     }
     if (rows > 0) {
@@ -1673,10 +1636,10 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
                                   : mat ? k_render_brute<kModelMaterials>
                                   : sgn ? k_render_brute<kModelSigned>
                                         : k_render_brute<kModelAttenuation>, grid, dim3(256), 0, stream,
-                                  t0, t1, 0, fs.recs, p, out);
+                                  t0, t1, 0, fs.recs.get(), p, out);
         else if (kernel == XRT_KERNEL_TILED || !binned)
             hipExtLaunchKernelGGL(k_render_tiled, dim3(rx, ry), dim3(256), 0, stream, t0, t1, 0,
-                                  fs.recs, fs.cull, p, out);
+                                  fs.recs.get(), fs.cull.get(), p, out);
         else
             hipExtLaunchKernelGGL(pth   ? k_render_binned<kModelPaths>
                                   : spc ? k_render_binned<kModelSpectrum>
@@ -1685,7 +1648,7 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
                                   : out.packed == kLayoutHits ? k_render_binned_hits
                                   : out.rays                  ? k_render_binned_rays
                                                               : k_render_binned<kModelAttenuation>, grid, dim3(64 * kTileWaves),
-                                  0, stream, t0, t1, 0, fs.recs, fs.cull, p, out, bins, (const BinState*)bin_ctl);
+                                  0, stream, t0, t1, 0, fs.recs.get(), fs.cull.get(), p, out, bins, (const BinState*)bin_ctl);
         XRT_HIP(ctx, hipGetLastError());
         ctx->acc_ms[4] += std::chrono::duration<double, std::milli>(HostClock::now() - t_launch).count();
         if (ctx->host_profile) ctx->hp_lrender += seconds_since(t_launch);
@@ -1698,14 +1661,14 @@ int launch_frame(xrt_context* ctx, PendingFrame& pf)
         if (binned && !sgn && pf.plan_source && ctx->tile_plan_enabled && ctx->tile_plan_state == 0 &&
             bins.tile_slots > bins.split_slots) {
             const uint32_t n = bins.tile_slots - bins.split_slots;
-            hipLaunchKernelGGL(k_tile_plan, dim3((n + 255) / 256), dim3(256), 0, stream, fs.block_stats,
-                               ctx->compact_layout.d_desc, bins.split_slots, bins.tile_slots);
+            hipLaunchKernelGGL(k_tile_plan, dim3((n + 255) / 256), dim3(256), 0, stream, fs.block_stats.get(),
+                               ctx->compact_layout.d_desc.get(), bins.split_slots, bins.tile_slots);
             XRT_HIP(ctx, hipGetLastError());
             // the set's completion event covers k_tile_plan too: the set's
             // statistics records and the layout's descriptions are not
             // rewritten while it reads / writes them
-            XRT_HIP(ctx, hipEventRecord(fs.done, stream));
-            fs.done_ev = fs.done;
+            XRT_HIP(ctx, hipEventRecord(fs.done.get(), stream));
+            fs.done_ev = fs.done.get();
             ctx->tile_plan_state = 1;
             ++ctx->hp_tile_plans;
         }
@@ -1833,19 +1796,19 @@ int d2h_copy(xrt_context* ctx, hipStream_t stream, const std::vector<D2HCopy>& c
             }
             std::this_thread::yield();
         }
-        if (hipEventSynchronize(ctx->stage_ev[i % kStageSlots]) != hipSuccess)
+        if (hipEventSynchronize(ctx->stage_ev[i % kStageSlots].get()) != hipSuccess)
             failed.store(1);
         else
-            std::memcpy(pieces[i].dst, ctx->h_stage + (i % kStageSlots) * kStageChunk, pieces[i].bytes);
+            std::memcpy(pieces[i].dst, ctx->h_stage.get() + (i % kStageSlots) * kStageChunk, pieces[i].bytes);
         moved[i].store(1, std::memory_order_release);
     });
     hipError_t err = hipSuccess;
     for (size_t i = 0; i < n; ++i) {
         if (i >= kStageSlots)                          // the slot's previous piece has been moved
             while (!moved[i - kStageSlots].load(std::memory_order_acquire)) std::this_thread::yield();
-        uint8_t* slot = ctx->h_stage + (i % kStageSlots) * kStageChunk;
+        uint8_t* slot = ctx->h_stage.get() + (i % kStageSlots) * kStageChunk;
         err = hipMemcpyAsync(slot, pieces[i].src, pieces[i].bytes, hipMemcpyDeviceToHost, stream);
-        if (err == hipSuccess) err = hipEventRecord(ctx->stage_ev[i % kStageSlots], stream);
+        if (err == hipSuccess) err = hipEventRecord(ctx->stage_ev[i % kStageSlots].get(), stream);
         if (err != hipSuccess) {
             failed.store(1);
             break;
@@ -1864,17 +1827,12 @@ int d2h_copy(xrt_context* ctx, hipStream_t stream, const std::vector<D2HCopy>& c
 // through buffers of their own call (DeviceScratch).
 
 // The context's staging planes (d_image, d_lbuffer, d_u8), each of at least
-// `need` elements: a plane that is too small is replaced by one of `need`,
-// and stage_cap is what all three hold.
+// `need` elements: a plane that is too small is replaced by one of `need`.
 int stage_planes(xrt_context* ctx, size_t need)
 {
-    int rc;
-    size_t cap_f = ctx->stage_cap, cap_l = ctx->stage_cap, cap_u = ctx->stage_cap;
-    if ((rc = ensure(ctx, ctx->d_image, cap_f, need))) return rc;
-    if ((rc = ensure(ctx, ctx->d_lbuffer, cap_l, need))) return rc;
-    if ((rc = ensure(ctx, ctx->d_u8, cap_u, need))) return rc;
-    ctx->stage_cap = std::min(cap_f, std::min(cap_l, cap_u));
-    return XRT_OK;
+    if (int rc = ensure(ctx, ctx->d_image, need)) return rc;
+    if (int rc = ensure(ctx, ctx->d_lbuffer, need)) return rc;
+    return ensure(ctx, ctx->d_u8, need);
 }
 
 // The copy-back list of a call's `n` pixels: the planes the caller asked for
@@ -2052,7 +2010,7 @@ int xrt_create(int device, xrt_context** out)
     ctx->wave_slots = (uint32_t)n_cu * 32u;
     // The prep stream at the default queue priority: frames are prepared ahead
     // of their renders (the highest and the lowest priority measured the same).
-    bool ok = hipEventCreate(&ctx->ev_begin) == hipSuccess && hipEventCreate(&ctx->ev_end) == hipSuccess;
+    bool ok = ctx->ev_begin.create() == hipSuccess && ctx->ev_end.create() == hipSuccess;
     ok = ok && acquire_streams(device, ctx->prep_stream, ctx->host_stream);
     ctx->owns_streams = ok;
     hipFuncAttributes prep_attr = {};
@@ -2060,27 +2018,20 @@ int xrt_create(int device, xrt_context** out)
     // k_prep's own LDS must fit the cap (else more than XRT_PREP_PER_CU would not fit beside the render)
     ok = ok && prep_attr.sharedSizeBytes <= kPrepLds;
     ctx->prep_lds = ok ? kPrepLds - prep_attr.sharedSizeBytes : 0;
-    ok = ok && hipMalloc(&ctx->d_stats_partial, kReduceMaxBlocks * sizeof(StatsSum)) == hipSuccess &&
-         hipMalloc(&ctx->d_stats_done, sizeof(unsigned int)) == hipSuccess &&
-         hipMemset(ctx->d_stats_done, 0, sizeof(unsigned int)) == hipSuccess &&
-         hipMalloc(&ctx->d_stats_out, sizeof(StatsSum)) == hipSuccess &&
-         hipHostMalloc((void**)&ctx->h_stats, sizeof(StatsSum), hipHostMallocDefault) == hipSuccess;
+    ok = ok && ctx->d_stats_partial.reserve(kReduceMaxBlocks) == hipSuccess &&
+         ctx->d_stats_done.reserve(1) == hipSuccess &&
+         hipMemset(ctx->d_stats_done.get(), 0, sizeof(unsigned int)) == hipSuccess &&
+         ctx->d_stats_out.reserve(1) == hipSuccess && ctx->h_stats.reserve(1) == hipSuccess;
     for (FrameSet& fs : ctx->sets)     // dispatch-attached events need timing enabled
-        ok = ok && hipMalloc(&fs.frame, sizeof(RenderParams)) == hipSuccess &&
-             hipEventCreate(&fs.ready) == hipSuccess &&
-             hipEventCreate(&fs.done) == hipSuccess &&
-             hipHostMalloc((void**)&fs.plan_flag, 2 * sizeof(uint32_t), hipHostMallocCoherent) == hipSuccess;
+        ok = ok && fs.frame.reserve(1) == hipSuccess && fs.ready.create() == hipSuccess &&
+             fs.done.create() == hipSuccess && fs.plan_flag.reserve(2) == hipSuccess;
     // the host-buffer entry points' stream, pinned D2H ring and copy threads
     int threads = kD2HThreads;
     if (const char* th = std::getenv("XRT_D2H_THREADS")) threads = std::max(0, std::atoi(th));
-    ok = ok && hipEventCreateWithFlags(&ctx->host_render_done, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&ctx->sizing_ev, hipEventDisableTiming) == hipSuccess &&
-         hipHostMalloc((void**)&ctx->h_sizing, kSizingScratch, hipHostMallocDefault) == hipSuccess;
-    if (ok) ctx->h_sizing_cap = kSizingScratch;
+    ok = ok && ctx->host_render_done.create() == hipSuccess && ctx->h_sizing.reserve(kSizingScratch) == hipSuccess;
     if (ok && threads > 0) {
-        ok = hipHostMalloc((void**)&ctx->h_stage, kStageSlots * kStageChunk, hipHostMallocDefault) == hipSuccess;
-        for (hipEvent_t& e : ctx->stage_ev)
-            ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        ok = ctx->h_stage.reserve(kStageSlots * kStageChunk) == hipSuccess;
+        for (auto& e : ctx->stage_ev) ok = ok && e.create() == hipSuccess;
         if (ok) ctx->pool.reset(new CopyPool(threads));
     }
     if (!ok) {
@@ -2115,72 +2066,34 @@ void xrt_destroy(xrt_context* ctx)
         g_destroy_ms[k] = std::chrono::duration<double, std::milli>(now - t).count();
         t = now;
     };
+    // [0] the context's work: its streams, its sets' renders, the last trace of
+    // the volume and the last user of the working set
     (void)sync_context(ctx);
     if (ctx->host_stream) (void)hipStreamSynchronize(ctx->host_stream);
+    (void)ctx->vol_traced.wait();
+    (void)ctx->sirt_done.wait();
     lap(0);
     ctx->pool.reset();
-    (void)hipFree(ctx->d_tris);
-    (void)hipFree(ctx->d_tris_posed);
-    for (FrameSet& fs : ctx->sets) {
-        (void)hipFree(fs.recs);
-        (void)hipFree(fs.cull);
-        (void)hipFree(fs.block_stats);
-        (void)hipFree(fs.frame);
-        if (fs.plan_flag) (void)hipHostFree((void*)fs.plan_flag);
-        (void)hipFree(fs.offsets);
-        (void)hipFree(fs.bin_counts);
-        (void)hipFree(fs.bin_list);
-        (void)hipFree(fs.global_list);
-        (void)hipFree(fs.times);
-        (void)hipFree(fs.dyn_desc);
-        (void)hipFree(fs.pairs);
-        (void)hipFree(fs.plan_desc);
-        (void)hipFree(fs.plan_counts);
-        for (hipEvent_t e : {fs.ready, fs.done})
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (SlotLayout* L : {&ctx->fixed, &ctx->compact_layout}) {
-        (void)hipFree(L->d_desc);
-        (void)hipFree(L->d_rank);
-    }
-    (void)hipFree(ctx->d_image);
-    (void)hipFree(ctx->d_lbuffer);
-    (void)hipFree(ctx->d_u8);
-    (void)hipFree(ctx->d_stats_partial);
-    (void)hipFree(ctx->d_stats_done);
-    (void)hipFree(ctx->d_stats_out);
-    (void)hipFree(ctx->d_hit_off);
-    (void)hipFree(ctx->d_materials);
-    (void)hipFree(ctx->d_spectrum);
-    (void)hipFree(ctx->d_path_ends);
-    (void)hipFree(ctx->d_prep_times);
-    (void)hipFree(ctx->d_rays);
-    if (ctx->ray_filled) (void)hipEventDestroy(ctx->ray_filled);
-    if (ctx->vol_busy) (void)hipEventSynchronize(ctx->vol_ev);
-    (void)hipFree(const_cast<uint8_t*>(ctx->vol.labels));
-    (void)hipFree(const_cast<float*>(ctx->vol.density));
-    if (ctx->vol_ev) (void)hipEventDestroy(ctx->vol_ev);
-    if (ctx->sirt_busy) (void)hipEventSynchronize(ctx->sirt_ev);
-    (void)hipFree(ctx->d_sirt);
-    if (ctx->sirt_ev) (void)hipEventDestroy(ctx->sirt_ev);
-    for (hipEvent_t e : {ctx->vox_ev, ctx->vox_pose_ev})
-        if (e) (void)hipEventDestroy(e);
-    for (auto& c : ctx->tchunks) (void)hipFree(c.p);
+    // [1] device memory (with the sets, their mapped flags and dispatch events)
+    for (FrameSet& fs : ctx->sets) fs = FrameSet();
+    ctx->fixed = SlotLayout();
+    ctx->compact_layout = SlotLayout();
+    ctx->tchunks.clear();
+    release(ctx->d_tris, ctx->d_tris_posed, ctx->d_image, ctx->d_lbuffer, ctx->d_u8, ctx->d_stats_partial,
+            ctx->d_stats_done, ctx->d_stats_out, ctx->d_hit_off, ctx->d_materials, ctx->d_spectrum, ctx->d_path_ends,
+            ctx->d_prep_times, ctx->d_rays, ctx->vol_labels, ctx->vol_density, ctx->d_sirt);
     lap(1);
-    if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->h_sizing) (void)hipHostFree(ctx->h_sizing);
+    // [2] pinned host memory
+    release(ctx->h_stats, ctx->h_stage, ctx->h_sizing);
     lap(2);
-    if (ctx->owns_streams) release_streams(ctx->device);     // the device's shared streams
-    for (hipEvent_t e : ctx->tev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->stage_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->host_render_done) (void)hipEventDestroy(ctx->host_render_done);
-    if (ctx->sizing_ev) (void)hipEventDestroy(ctx->sizing_ev);
-    if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
-    if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
+    // [3] the device's shared streams, and the events
+    if (ctx->owns_streams) release_streams(ctx->device);
+    ctx->tev.clear();
+    for (auto& e : ctx->stage_ev) e.reset();
+    release(ctx->host_render_done, ctx->sizing_done, ctx->ev_begin, ctx->ev_end, ctx->ray_filled, ctx->vol_traced,
+            ctx->sirt_done, ctx->vox_scattered, ctx->vox_pose_ev);
     lap(3);
-    delete ctx;
+    delete ctx;                        // (an owner not named above goes here, untimed)
 }
 
 const char* xrt_last_error(const xrt_context* ctx)
@@ -2202,9 +2115,9 @@ static int upload_materials(xrt_context* ctx)
         tab[m].end = (uint32_t)end;
         tab[m].mu = ctx->materials_mu[m];
     }
-    if (!ctx->d_materials && hipMalloc(&ctx->d_materials, sizeof tab) != hipSuccess)
+    if (ctx->d_materials.reserve(XRT_MAX_MESHES) != hipSuccess)
         return fail(ctx, XRT_ERR_DEVICE, "materials table allocation failed");
-    XRT_HIP(ctx, hipMemcpy(ctx->d_materials, tab, M * sizeof(MeshMaterial), hipMemcpyHostToDevice));
+    XRT_HIP(ctx, hipMemcpy(ctx->d_materials.get(), tab, M * sizeof(MeshMaterial), hipMemcpyHostToDevice));
     return XRT_OK;
 }
 
@@ -2224,9 +2137,9 @@ static int upload_spectrum(xrt_context* ctx)
     std::copy(ctx->spectrum_mu.begin(), ctx->spectrum_mu.end(), tab.mu);
     tab.num_bins = (uint32_t)K;
     tab.miss = spectrum_miss(tab.weight, tab.num_bins);
-    if (!ctx->d_spectrum && hipMalloc(&ctx->d_spectrum, sizeof tab) != hipSuccess)
+    if (ctx->d_spectrum.reserve(1) != hipSuccess)
         return fail(ctx, XRT_ERR_DEVICE, "spectrum table allocation failed");
-    XRT_HIP(ctx, hipMemcpy(ctx->d_spectrum, &tab, sizeof tab, hipMemcpyHostToDevice));
+    XRT_HIP(ctx, hipMemcpy(ctx->d_spectrum.get(), &tab, sizeof tab, hipMemcpyHostToDevice));
     return XRT_OK;
 }
 
@@ -2242,9 +2155,9 @@ static int upload_path_ends(xrt_context* ctx)
         end += ctx->mesh_tris[m];
         ends[m] = (uint32_t)end;
     }
-    if (!ctx->d_path_ends && hipMalloc(&ctx->d_path_ends, sizeof ends) != hipSuccess)
+    if (ctx->d_path_ends.reserve(kMaxMeshes) != hipSuccess)
         return fail(ctx, XRT_ERR_DEVICE, "paths table allocation failed");
-    XRT_HIP(ctx, hipMemcpy(ctx->d_path_ends, ends, sizeof ends, hipMemcpyHostToDevice));
+    XRT_HIP(ctx, hipMemcpy(ctx->d_path_ends.get(), ends, sizeof ends, hipMemcpyHostToDevice));
     return XRT_OK;
 }
 
@@ -2274,10 +2187,10 @@ int xrt_upload_scene(xrt_context* ctx, const float* triangles, const uint64_t* m
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     int rc = sync_context(ctx);                   // frames in flight read the mesh (prep stream)
     if (rc) return rc;
-    rc = ensure(ctx, ctx->d_tris, ctx->tris_cap, 9 * num_triangles);
+    rc = ensure(ctx, ctx->d_tris, 9 * num_triangles);
     if (rc) return rc;
     if (num_triangles)
-        XRT_HIP(ctx, hipMemcpy(ctx->d_tris, triangles, 9 * num_triangles * sizeof(float),
+        XRT_HIP(ctx, hipMemcpy(ctx->d_tris.get(), triangles, 9 * num_triangles * sizeof(float),
                                hipMemcpyHostToDevice));
     ctx->num_tris = num_triangles;
     ctx->mesh_tris.assign(mesh_triangles, mesh_triangles + num_meshes);
@@ -2296,10 +2209,10 @@ int xrt_upload_mesh(xrt_context* ctx, const float* triangles, uint64_t num_trian
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     int rc = sync_context(ctx);                   // frames in flight read the mesh (prep stream)
     if (rc) return rc;
-    rc = ensure(ctx, ctx->d_tris, ctx->tris_cap, 9 * num_triangles);
+    rc = ensure(ctx, ctx->d_tris, 9 * num_triangles);
     if (rc) return rc;
     if (num_triangles)
-        XRT_HIP(ctx, hipMemcpy(ctx->d_tris, triangles, 9 * num_triangles * sizeof(float),
+        XRT_HIP(ctx, hipMemcpy(ctx->d_tris.get(), triangles, 9 * num_triangles * sizeof(float),
                                hipMemcpyHostToDevice));
     ctx->num_tris = num_triangles;
     ctx->mesh_tris.assign(1, num_triangles);      // a one-mesh scene
@@ -2582,14 +2495,14 @@ int xrt_render_paths(xrt_context* ctx, const xrt_camera* camera, uint32_t row_be
     const size_t n = (size_t)(row_end - row_begin) * camera->width;
     // the planes in the context's L-buffer staging, the masks in its 8-bit one (2 bytes a pixel)
     if ((rc = stage_planes(ctx, n * std::max<size_t>(num_meshes, sizeof(uint16_t))))) return rc;
-    uint16_t* d_open = open ? reinterpret_cast<uint16_t*>(ctx->d_u8) : nullptr;
+    uint16_t* d_open = open ? reinterpret_cast<uint16_t*>(ctx->d_u8.get()) : nullptr;
     // (not prepared ahead: a host-buffer call, as xrt_render_rows)
-    if ((rc = enqueue_render(ctx, camera, row_begin, row_end, nullptr, ctx->d_lbuffer,
+    if ((rc = enqueue_render(ctx, camera, row_begin, row_end, nullptr, ctx->d_lbuffer.get(),
                              reinterpret_cast<uint8_t*>(d_open), ctx->host_stream, false, true)))
         return rc;
     std::vector<D2HCopy> copies;
     if (n) {
-        copies.push_back({paths, ctx->d_lbuffer, n * num_meshes * sizeof(float)});
+        copies.push_back({paths, ctx->d_lbuffer.get(), n * num_meshes * sizeof(float)});
         if (open) copies.push_back({open, d_open, n * sizeof(uint16_t)});
     }
     if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
@@ -2742,12 +2655,9 @@ int xrt_spectral_detector(xrt_context* ctx, uint64_t num_pixels, uint32_t num_me
 // Frees the context's volume once its last trace is through.
 static int free_volume(xrt_context* ctx)
 {
-    if (ctx->vol_busy) {
-        XRT_HIP(ctx, hipEventSynchronize(ctx->vol_ev));
-        ctx->vol_busy = false;
-    }
-    (void)hipFree(const_cast<uint8_t*>(ctx->vol.labels));
-    (void)hipFree(const_cast<float*>(ctx->vol.density));
+    XRT_HIP(ctx, ctx->vol_traced.wait());
+    ctx->vol_labels.reset();
+    ctx->vol_density.reset();
     ctx->vol = VolumeDesc{};
     return XRT_OK;
 }
@@ -2765,19 +2675,17 @@ int xrt_upload_volume(xrt_context* ctx, const uint8_t* labels, const float* dens
     if (int rc = free_volume(ctx)) return rc;
     if (release) return XRT_OK;
     const size_t n = (size_t)dims[0] * dims[1] * dims[2];
-    uint8_t* d_labels = nullptr;
-    float* d_density = nullptr;
-    hipError_t e = hipMalloc((void**)&d_labels, n);
-    if (e == hipSuccess && density) e = hipMalloc((void**)&d_density, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_labels, labels, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && density) e = hipMemcpy(d_density, density, n * sizeof(float), hipMemcpyHostToDevice);
+    hipError_t e = ctx->vol_labels.reserve(n);
+    if (e == hipSuccess && density) e = ctx->vol_density.reserve(n);
+    if (e == hipSuccess) e = hipMemcpy(ctx->vol_labels.get(), labels, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && density) e = hipMemcpy(ctx->vol_density.get(), density, n * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        (void)hipFree(d_labels);
-        (void)hipFree(d_density);
+        ctx->vol_labels.reset();
+        ctx->vol_density.reset();
         (void)hipGetLastError();
         return fail(ctx, XRT_ERR_DEVICE, std::string("xrt_upload_volume: ") + hipGetErrorString(e));
     }
-    ctx->vol = volume_desc(d_labels, d_density, dims, origin, spacing, num_labels);
+    ctx->vol = volume_desc(ctx->vol_labels.get(), ctx->vol_density.get(), dims, origin, spacing, num_labels);
     return XRT_OK;
 }
 
@@ -2816,9 +2724,7 @@ static int launch_volume_paths(xrt_context* ctx, const xrt_camera* camera, uint3
         hipLaunchKernelGGL((k_volume_paths<kMaxMeshes>), grid, block, 0, stream, p, ctx->vol, (uint32_t)tiles_x, shift,
                            d_paths);
     XRT_HIP(ctx, hipGetLastError());
-    if (!ctx->vol_ev) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->vol_ev, hipEventDisableTiming));
-    XRT_HIP(ctx, hipEventRecord(ctx->vol_ev, stream));
-    ctx->vol_busy = true;
+    XRT_HIP(ctx, ctx->vol_traced.record(stream));
     return XRT_OK;
 }
 
@@ -3061,27 +2967,16 @@ int xrt_volume_update(xrt_context* ctx, uint64_t n, float* x, const float* corr,
 #include "xrt_tv_host.inc"
 
 // The context's working set (d_sirt) for a call that needs `bytes` of it: the previous call's kernels and upload
-// are done with it, it is large enough, and sirt_ev exists.  The caller sets sirt_busy once it has enqueued work on
-// the set and records sirt_ev behind its last.
+// are done with it and it is large enough.  The caller marks sirt_done before it enqueues work on the set and
+// records it behind its last.
 static int sirt_working_set(xrt_context* ctx, size_t bytes)
 {
-    if (ctx->sirt_busy) {
-        XRT_HIP(ctx, hipEventSynchronize(ctx->sirt_ev));
-        ctx->sirt_busy = false;
-    }
+    XRT_HIP(ctx, ctx->sirt_done.wait());
     ctx->vox_counters = false;                        // (the caller lays its own data over them)
-    if (bytes > ctx->sirt_cap || !ctx->d_sirt) {
-        (void)hipFree(ctx->d_sirt);
-        ctx->d_sirt = nullptr;
-        ctx->sirt_cap = 0;
-        if (hipMalloc((void**)&ctx->d_sirt, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->d_sirt = nullptr;
-            return fail(ctx, XRT_ERR_MEMORY, "the working set of " + std::to_string(bytes) + " bytes cannot be allocated");
-        }
-        ctx->sirt_cap = bytes;
+    if (ctx->d_sirt.reserve(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, XRT_ERR_MEMORY, "the working set of " + std::to_string(bytes) + " bytes cannot be allocated");
     }
-    if (!ctx->sirt_ev) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->sirt_ev, hipEventDisableTiming));
     return XRT_OK;
 }
 
@@ -3170,9 +3065,9 @@ int xrt_tv_gradient(xrt_context* ctx, const float* volume, const uint32_t dims[3
 static int run_sumsq(xrt_context* ctx, uint64_t n, const float* d_a, const float* d_b, double* d_out, hipStream_t stream)
 {
     if (int rc = sirt_working_set(ctx, std::max<size_t>(sumsq_partials(n), 1u) * sizeof(double))) return rc;
-    ctx->sirt_busy = true;
-    const int rc = launch_sumsq(ctx, n, d_a, d_b, reinterpret_cast<double*>(ctx->d_sirt), d_out, stream);
-    (void)hipEventRecord(ctx->sirt_ev, stream);
+    XRT_HIP(ctx, ctx->sirt_done.mark());
+    const int rc = launch_sumsq(ctx, n, d_a, d_b, reinterpret_cast<double*>(ctx->d_sirt.get()), d_out, stream);
+    (void)ctx->sirt_done.record(stream);
     return rc;
 }
 
@@ -3206,11 +3101,11 @@ static int run_tv_descend(xrt_context* ctx, float* d_volume, const uint32_t dims
     const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
     const size_t sums = sumsq_partials(voxels) + 1u;
     if (int rc = sirt_working_set(ctx, sums * sizeof(double) + voxels * sizeof(float))) return rc;
-    ctx->sirt_busy = true;
-    double* d_sums = reinterpret_cast<double*>(ctx->d_sirt);
+    XRT_HIP(ctx, ctx->sirt_done.mark());
+    double* d_sums = reinterpret_cast<double*>(ctx->d_sirt.get());
     const int rc = launch_tv_descend(ctx, d_volume, dims, eps, steps, length, nullptr, lo, hi,
                                      reinterpret_cast<float*>(d_sums + sums), d_sums, stream);
-    (void)hipEventRecord(ctx->sirt_ev, stream);
+    (void)ctx->sirt_done.record(stream);
     return rc;
 }
 
@@ -3253,7 +3148,7 @@ static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t 
     const size_t bytes = mat_bytes + sums * sizeof(double) +
                          (plane * plan.widest + voxels * ((size_t)subsets + 1u + (with_tv ? 1u : 0u))) * sizeof(float);
     if (int rc = sirt_working_set(ctx, bytes)) return rc;
-    double* dA = reinterpret_cast<double*>(ctx->d_sirt);
+    double* dA = reinterpret_cast<double*>(ctx->d_sirt.get());
     double* dR = dA + (size_t)num_planes * 12u;
     double* d_sums = dR + (size_t)num_planes * 12u;
     double* d_moved = d_sums + (sums ? sums - 1u : 0u);      // D, behind the partials and G
@@ -3263,8 +3158,8 @@ static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t 
     float* d_x0 = d_norms + voxels * subsets;
     ctx->sirt_mats.assign(plan.A.begin(), plan.A.end());
     ctx->sirt_mats.insert(ctx->sirt_mats.end(), plan.R.begin(), plan.R.end());
+    XRT_HIP(ctx, ctx->sirt_done.mark());              // from here on the set is in use until sirt_done is recorded
     XRT_HIP(ctx, hipMemcpyAsync(dA, ctx->sirt_mats.data(), mat_bytes, hipMemcpyHostToDevice, stream));
-    ctx->sirt_busy = true;                            // from here on the set is in use until sirt_ev
     int rc = XRT_OK;
     // N_s: the backprojection of all-ones planes (1.0f's bits, word by word)
     if (hipMemsetD32Async((hipDeviceptr_t)d_res, 0x3F800000, plane * plan.widest, stream) != hipSuccess)
@@ -3293,7 +3188,7 @@ static int run_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t 
             a_k = a_k * tv->reduction;
         }
     }
-    (void)hipEventRecord(ctx->sirt_ev, stream);
+    (void)ctx->sirt_done.record(stream);
     return rc;
 }
 
@@ -3394,19 +3289,20 @@ static int run_voxelize(xrt_context* ctx, const uint32_t* dims, const float* ori
     if (ctx->num_tris > 0xFFFFFF00ull) return fail(ctx, XRT_ERR_ARGUMENT, "too many triangles to voxelise");
     const float* soup = nullptr;
     if (int rc = render_soup(ctx, soup)) return rc;
-    if (soup != ctx->d_tris) {                        // the posed soup: behind its k_pose on the preparation stream
-        if (!ctx->vox_pose_ev) XRT_HIP(ctx, hipEventCreateWithFlags(&ctx->vox_pose_ev, hipEventDisableTiming));
-        XRT_HIP(ctx, hipEventRecord(ctx->vox_pose_ev, ctx->prep_stream));
-        XRT_HIP(ctx, hipStreamWaitEvent(stream, ctx->vox_pose_ev, 0));
+    if (soup != ctx->d_tris.get()) {                        // the posed soup: behind its k_pose on the preparation stream
+        XRT_HIP(ctx, ctx->vox_pose_ev.create());
+        XRT_HIP(ctx, hipEventRecord(ctx->vox_pose_ev.get(), ctx->prep_stream));
+        XRT_HIP(ctx, hipStreamWaitEvent(stream, ctx->vox_pose_ev.get(), 0));
     }
     // (the set's last user ran on `stream` and the set is large enough: the stream orders this call behind it)
-    if (ctx->vox_counters && ctx->vox_stream == stream && kVoxelFlipAt + flip_bytes <= ctx->sirt_cap) ctx->sirt_busy = false;
+    if (ctx->vox_counters && ctx->vox_stream == stream && kVoxelFlipAt + flip_bytes <= ctx->d_sirt.cap())
+        ctx->sirt_done.forget();
     if (int rc = sirt_working_set(ctx, kVoxelFlipAt + flip_bytes)) return rc;
-    ctx->sirt_busy = true;
+    XRT_HIP(ctx, ctx->sirt_done.mark());
     ctx->vox_stream = stream;
-    VoxelControl* ctl = reinterpret_cast<VoxelControl*>(ctx->d_sirt);
-    uint2* queue = reinterpret_cast<uint2*>(ctx->d_sirt + kVoxelQueueAt);
-    uint32_t* flip = reinterpret_cast<uint32_t*>(ctx->d_sirt + kVoxelFlipAt);
+    VoxelControl* ctl = reinterpret_cast<VoxelControl*>(ctx->d_sirt.get());
+    uint2* queue = reinterpret_cast<uint2*>(ctx->d_sirt.get() + kVoxelQueueAt);
+    uint32_t* flip = reinterpret_cast<uint32_t*>(ctx->d_sirt.get() + kVoxelFlipAt);
     const bool clear = ctx->vox_stages & 4u, scatter = ctx->vox_stages & 1u, scan = ctx->vox_stages & 2u;
     hipError_t e = hipMemsetAsync(ctl, 0, kVoxelQueueAt, stream);
     if (e == hipSuccess) e = hipMemsetAsync(queue, 0xFF, kVoxelFlipAt - kVoxelQueueAt, stream);
@@ -3419,9 +3315,7 @@ static int run_voxelize(xrt_context* ctx, const uint32_t* dims, const float* ori
         hipLaunchKernelGGL(k_voxel_tiles, dim3(kVoxelTileBlocks), dim3(kVoxelThreads), 0, stream, soup, meshes, g, flip,
                            (const VoxelControl*)ctl, (const uint2*)queue);
         e = hipGetLastError();
-        if (!ctx->vox_ev && e == hipSuccess) e = hipEventCreateWithFlags(&ctx->vox_ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventRecord(ctx->vox_ev, stream);
-        if (e == hipSuccess) ctx->vox_busy = true;
+        if (e == hipSuccess) e = ctx->vox_scattered.record(stream);
     }
     if (e == hipSuccess && scan) {
         // runs of slices, so that a grid of few columns still fills the device (vox_stages & 8: one run, for the A/B)
@@ -3434,7 +3328,7 @@ static int run_voxelize(xrt_context* ctx, const uint32_t* dims, const float* ori
                            d_volume, reinterpret_cast<unsigned long long*>(d_odd), chunk);
         e = hipGetLastError();
     }
-    (void)hipEventRecord(ctx->sirt_ev, stream);
+    (void)ctx->sirt_done.record(stream);
     ctx->vox_counters = e == hipSuccess;
     if (e != hipSuccess) return fail(ctx, XRT_ERR_DEVICE, std::string("xrt_voxelize: ") + hipGetErrorString(e));
     return XRT_OK;
@@ -3488,9 +3382,9 @@ int xrt_debug_voxelize_counters(xrt_context* ctx, uint64_t counters[4])
     if (!ctx || !counters) return XRT_ERR_ARGUMENT;
     if (!ctx->vox_counters) return fail(ctx, XRT_ERR_ARGUMENT, "the working set no longer holds a voxelisation's counters");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->sirt_busy) XRT_HIP(ctx, hipEventSynchronize(ctx->sirt_ev));
+    XRT_HIP(ctx, ctx->sirt_done.wait());
     VoxelControl c = {};
-    XRT_HIP(ctx, hipMemcpy(&c, ctx->d_sirt, sizeof c, hipMemcpyDeviceToHost));
+    XRT_HIP(ctx, hipMemcpy(&c, ctx->d_sirt.get(), sizeof c, hipMemcpyDeviceToHost));
     counters[0] = c.direct;
     counters[1] = c.queued;
     counters[2] = c.entries;
@@ -3608,11 +3502,11 @@ int xrt_hole_fill(xrt_context* ctx, uint32_t width, uint32_t height, const float
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((rc = stage_planes(ctx, n))) return rc;
-    XRT_HIP(ctx, hipMemcpyAsync(ctx->d_lbuffer, lbuffer, n * sizeof(float), hipMemcpyHostToDevice, ctx->host_stream));
-    if ((rc = xrt_hole_fill_device(ctx, width, height, ctx->d_lbuffer, image ? ctx->d_image : nullptr,
-                                   image_u8 ? ctx->d_u8 : nullptr, ctx->host_stream)))
+    XRT_HIP(ctx, hipMemcpyAsync(ctx->d_lbuffer.get(), lbuffer, n * sizeof(float), hipMemcpyHostToDevice, ctx->host_stream));
+    if ((rc = xrt_hole_fill_device(ctx, width, height, ctx->d_lbuffer.get(), image ? ctx->d_image.get() : nullptr,
+                                   image_u8 ? ctx->d_u8.get() : nullptr, ctx->host_stream)))
         return rc;
-    return d2h_copy(ctx, ctx->host_stream, plane_copies(n, image, ctx->d_image, nullptr, nullptr, image_u8, ctx->d_u8));
+    return d2h_copy(ctx, ctx->host_stream, plane_copies(n, image, ctx->d_image.get(), nullptr, nullptr, image_u8, ctx->d_u8.get()));
 }
 
 // --- the detector response -------------------------------------
@@ -3854,14 +3748,14 @@ static int render_and_fill(xrt_context* ctx, const xrt_camera* camera, float* im
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)camera->width * camera->height;
     if ((rc = stage_planes(ctx, n))) return rc;
-    if ((rc = enqueue_render(ctx, camera, 0, camera->height, nullptr, ctx->d_lbuffer, nullptr, ctx->host_stream)))
+    if ((rc = enqueue_render(ctx, camera, 0, camera->height, nullptr, ctx->d_lbuffer.get(), nullptr, ctx->host_stream)))
         return rc;
-    if ((rc = xrt_hole_fill_device(ctx, camera->width, camera->height, ctx->d_lbuffer,
-                                   image ? ctx->d_image : nullptr, image_u8 ? ctx->d_u8 : nullptr,
+    if ((rc = xrt_hole_fill_device(ctx, camera->width, camera->height, ctx->d_lbuffer.get(),
+                                   image ? ctx->d_image.get() : nullptr, image_u8 ? ctx->d_u8.get() : nullptr,
                                    ctx->host_stream)))
         return rc;
     const std::vector<D2HCopy> copies =
-        plane_copies(n, image, ctx->d_image, lbuffer, ctx->d_lbuffer, image_u8, ctx->d_u8);
+        plane_copies(n, image, ctx->d_image.get(), lbuffer, ctx->d_lbuffer.get(), image_u8, ctx->d_u8.get());
     if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
     xrt_stats local;
     return xrt_read_stats(ctx, stats ? stats : &local);
@@ -4042,7 +3936,7 @@ int xrt_plan_hit_layout(xrt_context* ctx, uint32_t* tile_hits, uint64_t capacity
                                            "plan just before");
     const uint32_t tiles = ctx->plan_tile_slots * kWavesPerRegion;
     std::vector<BlockStats> rec(tiles);
-    if (tiles) XRT_HIP(ctx, hipMemcpy(rec.data(), fs->block_stats, tiles * sizeof(BlockStats), hipMemcpyDeviceToHost));
+    if (tiles) XRT_HIP(ctx, hipMemcpy(rec.data(), fs->block_stats.get(), tiles * sizeof(BlockStats), hipMemcpyDeviceToHost));
     std::vector<uint32_t> off(tiles + 1u);
     uint64_t run = 0;
     for (uint32_t i = 0; i < tiles; ++i) {
@@ -4052,8 +3946,8 @@ int xrt_plan_hit_layout(xrt_context* ctx, uint32_t* tile_hits, uint64_t capacity
     }
     if (run + 2ull * tiles > 0xFFFFFFFFull) return fail(ctx, XRT_ERR_OVERFLOW, "hit message exceeds 2^32 words");
     off[tiles] = (uint32_t)run;
-    if ((rc = ensure(ctx, ctx->d_hit_off, ctx->hit_off_cap, (size_t)tiles + 1u))) return rc;
-    XRT_HIP(ctx, hipMemcpy(ctx->d_hit_off, off.data(), off.size() * 4u, hipMemcpyHostToDevice));
+    if ((rc = ensure(ctx, ctx->d_hit_off, (size_t)tiles + 1u))) return rc;
+    XRT_HIP(ctx, hipMemcpy(ctx->d_hit_off.get(), off.data(), off.size() * 4u, hipMemcpyHostToDevice));
     ctx->hit_key = ctx->geo.bin_key;
     ctx->hit_tiles = tiles;
     ctx->hit_words = 2ull * tiles + run;
@@ -4122,12 +4016,12 @@ int xrt_debug_prep_times(xrt_context* ctx, int enable, uint32_t* dst, uint64_t c
     if (!ctx) return XRT_ERR_ARGUMENT;
     if (enable >= 0) ctx->prep_times_on = enable != 0;
     if (n_waves) *n_waves = ctx->prep_times_n;
-    if (!dst || !ctx->d_prep_times || !ctx->prep_times_n) return XRT_OK;
+    if (!dst || !ctx->d_prep_times.get() || !ctx->prep_times_n) return XRT_OK;
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     int rc = sync_context(ctx);
     if (rc) return rc;
     const size_t n = std::min<size_t>(capacity, ctx->prep_times_n);
-    XRT_HIP(ctx, hipMemcpy(dst, ctx->d_prep_times, n * 2 * sizeof(uint4), hipMemcpyDeviceToHost));
+    XRT_HIP(ctx, hipMemcpy(dst, ctx->d_prep_times.get(), n * 2 * sizeof(uint4), hipMemcpyDeviceToHost));
     return XRT_OK;
 }
 
@@ -4179,7 +4073,7 @@ int xrt_debug_ray_table_counters(xrt_context* ctx, uint64_t counters[4])
     counters[0] = ctx->hp_ray_fills;
     counters[1] = ctx->hp_ray_frames;
     counters[2] = ctx->hp_ray_computed;
-    counters[3] = ctx->rays_cap;
+    counters[3] = ctx->d_rays.cap() * sizeof(float);
     return XRT_OK;
 }
 
@@ -4191,9 +4085,8 @@ int xrt_debug_ray_table_read(xrt_context* ctx, float* dst, uint64_t floats, uint
     const uint64_t n = ray_table_floats(k.width, k.row_begin, k.row_end);
     if (!dst || floats < n) return fail(ctx, XRT_ERR_ARGUMENT, "dst is NULL or smaller than the table");
     XRT_HIP(ctx, hipSetDevice(ctx->device));
-    XRT_HIP(ctx, hipEventSynchronize(ctx->ray_filled));
-    ctx->ray_fill_done = true;
-    XRT_HIP(ctx, hipMemcpy(dst, ctx->d_rays, n * sizeof(float), hipMemcpyDeviceToHost));
+    XRT_HIP(ctx, ctx->ray_filled.wait());
+    XRT_HIP(ctx, hipMemcpy(dst, ctx->d_rays.get(), n * sizeof(float), hipMemcpyDeviceToHost));
     if (dims) {
         dims[0] = k.width;
         dims[1] = k.height;
@@ -4246,7 +4139,7 @@ int xrt_debug_block_records(xrt_context* ctx, void* dst, uint64_t capacity, uint
     const FrameSet* fs = ctx->last_set;
     *n_records = fs ? fs->rendered_blocks : 0u;
     const size_t bytes = std::min<size_t>((size_t)capacity, (size_t)*n_records * sizeof(BlockStats));
-    if (bytes && dst) XRT_HIP(ctx, hipMemcpy(dst, fs->block_stats, bytes, hipMemcpyDeviceToHost));
+    if (bytes && dst) XRT_HIP(ctx, hipMemcpy(dst, fs->block_stats.get(), bytes, hipMemcpyDeviceToHost));
     return XRT_OK;
 }
 
@@ -4305,9 +4198,9 @@ int xrt_render_frames(xrt_context* ctx, const xrt_camera* camera, uint32_t row_b
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)(row_end - row_begin) * camera->width;
     if ((rc = stage_planes(ctx, n))) return rc;
-    float* di = image ? ctx->d_image : nullptr;
-    float* dl = lbuffer ? ctx->d_lbuffer : nullptr;
-    uint8_t* du = image_u8 ? ctx->d_u8 : nullptr;
+    float* di = image ? ctx->d_image.get() : nullptr;
+    float* dl = lbuffer ? ctx->d_lbuffer.get() : nullptr;
+    uint8_t* du = image_u8 ? ctx->d_u8.get() : nullptr;
     void* st = ctx->host_stream;
     const auto t0 = HostClock::now();
     if ((rc = xrt_render_frames_device(ctx, camera, row_begin, row_end, n_frames, 1, &di, &dl, &du, &st))) return rc;
@@ -4315,7 +4208,7 @@ int xrt_render_frames(xrt_context* ctx, const xrt_camera* camera, uint32_t row_b
     if (ms_per_frame)
         *ms_per_frame = std::chrono::duration<double, std::milli>(HostClock::now() - t0).count() / n_frames;
     const std::vector<D2HCopy> copies =
-        plane_copies(n, image, ctx->d_image, lbuffer, ctx->d_lbuffer, image_u8, ctx->d_u8);
+        plane_copies(n, image, ctx->d_image.get(), lbuffer, ctx->d_lbuffer.get(), image_u8, ctx->d_u8.get());
     if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
     xrt_stats local;
     return xrt_read_stats(ctx, stats ? stats : &local);
@@ -4340,14 +4233,14 @@ int xrt_read_stats(xrt_context* ctx, xrt_stats* stats)
     const hipStream_t s = ctx->last_stream;
     const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(kReduceMaxBlocks, (n + 4 * kReduceThreads - 1) /
                                                                                           (4 * kReduceThreads)));
-    hipLaunchKernelGGL(k_reduce_stats, dim3(blocks), dim3(kReduceThreads), 0, s, fs->block_stats, fs->last_times, n,
-                       fs->binned ? (const BinState*)fs->last_state : nullptr, ctx->d_stats_partial, ctx->d_stats_done,
-                       ctx->d_stats_out);
+    hipLaunchKernelGGL(k_reduce_stats, dim3(blocks), dim3(kReduceThreads), 0, s, fs->block_stats.get(), fs->last_times, n,
+                       fs->binned ? (const BinState*)fs->last_state : nullptr, ctx->d_stats_partial.get(), ctx->d_stats_done.get(),
+                       ctx->d_stats_out.get());
     XRT_HIP(ctx, hipGetLastError());
-    XRT_HIP(ctx, hipMemcpyAsync(ctx->h_stats, ctx->d_stats_out, sizeof(StatsSum), hipMemcpyDeviceToHost, s));
+    XRT_HIP(ctx, hipMemcpyAsync(ctx->h_stats.get(), ctx->d_stats_out.get(), sizeof(StatsSum), hipMemcpyDeviceToHost, s));
     XRT_HIP(ctx, hipStreamSynchronize(s));
     ctx->pending = false;
-    const StatsSum& t = *ctx->h_stats;
+    const StatsSum& t = *ctx->h_stats.get();
     stats->rays = t.rays;
     stats->hit_rays = t.hit_rays;
     stats->odd_rays = t.odd_rays;
@@ -4384,20 +4277,11 @@ int xrt_timing_begin(xrt_context* ctx)
     const size_t last_blocks = ctx->last_set ? ctx->last_set->n_blocks : 0u;
     const size_t space = std::min(kTimingRecords, std::max<size_t>((size_t)1 << 20, kTimingFrames * last_blocks));
     bool have = false;
-    for (auto& c : ctx->tchunks) have = have || c.cap >= space;
-    if (!have) {
-        for (auto& c : ctx->tchunks) (void)hipFree(c.p);
-        ctx->tchunks.clear();
-        xrt_context::TimesChunk c = {nullptr, space, 0};
-        XRT_HIP(ctx, hipMalloc(&c.p, space * sizeof(uint2)));
-        ctx->tchunks.push_back(c);
-    }
+    for (auto& c : ctx->tchunks) have = have || c.p.cap() >= space;
+    if (!have)
+        if (int rc = region_chunk(ctx, space)) return rc;
     ctx->timing_space = space;
-    while (ctx->tev.size() < kTimingEvents) {
-        hipEvent_t e;
-        XRT_HIP(ctx, hipEventCreate(&e));
-        ctx->tev.push_back(e);
-    }
+    if (int rc = region_events(ctx, kTimingEvents)) return rc;
     ctx->timing = true;
     ctx->tev_used = 0;
     ctx->timed_frames = 0;
@@ -4413,9 +4297,9 @@ int xrt_timing_end(xrt_context* ctx, double* total_ms, uint64_t* launches)
     XRT_HIP(ctx, hipSetDevice(ctx->device));
     double ev = 0.0;
     for (size_t i = 0; i + 1 < ctx->tev_used; i += 2) {
-        XRT_HIP(ctx, hipEventSynchronize(ctx->tev[i + 1]));
+        XRT_HIP(ctx, hipEventSynchronize(ctx->tev[i + 1].get()));
         float ms = 0.0f;
-        XRT_HIP(ctx, hipEventElapsedTime(&ms, ctx->tev[i], ctx->tev[i + 1]));
+        XRT_HIP(ctx, hipEventElapsedTime(&ms, ctx->tev[i].get(), ctx->tev[i + 1].get()));
         ev += ms;
     }
     ctx->event_ms = ev;
@@ -4437,25 +4321,22 @@ int xrt_timing_end(xrt_context* ctx, double* total_ms, uint64_t* launches)
     // xrt_debug_wave_times read them there), then the chunks go: a context
     // keeps at most one small chunk (kKeptTimingBytes) for its next region.
     for (FrameSet& fs : ctx->sets) {
-        if (fs.last_times && fs.last_times != fs.times && fs.times && fs.rendered_blocks <= fs.times_cap)
-            XRT_HIP(ctx, hipMemcpy(fs.times, fs.last_times, fs.rendered_blocks * sizeof(uint2),
+        if (fs.last_times && fs.last_times != fs.times.get() && fs.times.get() && fs.rendered_blocks <= fs.times.cap())
+            XRT_HIP(ctx, hipMemcpy(fs.times.get(), fs.last_times, fs.rendered_blocks * sizeof(uint2),
                                    hipMemcpyDeviceToDevice));
-        if (fs.last_times) fs.last_times = fs.times;
+        if (fs.last_times) fs.last_times = fs.times.get();
     }
     size_t keep = ctx->tchunks.size();
     for (size_t k = 0; k < ctx->tchunks.size(); ++k)
-        if (ctx->tchunks[k].cap * sizeof(uint2) <= kKeptTimingBytes &&
-            (keep == ctx->tchunks.size() || ctx->tchunks[k].cap > ctx->tchunks[keep].cap))
+        if (ctx->tchunks[k].p.cap() * sizeof(uint2) <= kKeptTimingBytes &&
+            (keep == ctx->tchunks.size() || ctx->tchunks[k].p.cap() > ctx->tchunks[keep].p.cap()))
             keep = k;
-    for (size_t k = 0; k < ctx->tchunks.size(); ++k)
-        if (k != keep) (void)hipFree(ctx->tchunks[k].p);
+    std::vector<xrt_context::TimesChunk> kept;
     if (keep < ctx->tchunks.size()) {
-        xrt_context::TimesChunk c = ctx->tchunks[keep];
-        c.used = 0;
-        ctx->tchunks.assign(1, c);
-    } else {
-        ctx->tchunks.clear();
+        kept.push_back(std::move(ctx->tchunks[keep]));
+        kept.back().used = 0;
     }
+    ctx->tchunks = std::move(kept);                // the others are freed
     return XRT_OK;
 }
 
@@ -4490,15 +4371,15 @@ int xrt_render_rows(xrt_context* ctx, const xrt_camera* camera, uint32_t row_beg
     if ((rc = stage_planes(ctx, n))) return rc;
     lap(0, t);
     // the context's own non-blocking stream (not the null stream)
-    rc = enqueue_render(ctx, camera, row_begin, row_end, image ? ctx->d_image : nullptr,
-                        lbuffer ? ctx->d_lbuffer : nullptr, image_u8 ? ctx->d_u8 : nullptr, ctx->host_stream);
+    rc = enqueue_render(ctx, camera, row_begin, row_end, image ? ctx->d_image.get() : nullptr,
+                        lbuffer ? ctx->d_lbuffer.get() : nullptr, image_u8 ? ctx->d_u8.get() : nullptr, ctx->host_stream);
     if (rc) return rc;
-    XRT_HIP(ctx, hipEventRecord(ctx->host_render_done, ctx->host_stream));
+    XRT_HIP(ctx, hipEventRecord(ctx->host_render_done.get(), ctx->host_stream));
     lap(1, t);
-    XRT_HIP(ctx, hipEventSynchronize(ctx->host_render_done));
+    XRT_HIP(ctx, hipEventSynchronize(ctx->host_render_done.get()));
     lap(2, t);
     const std::vector<D2HCopy> copies =
-        plane_copies(n, image, ctx->d_image, lbuffer, ctx->d_lbuffer, image_u8, ctx->d_u8);
+        plane_copies(n, image, ctx->d_image.get(), lbuffer, ctx->d_lbuffer.get(), image_u8, ctx->d_u8.get());
     if ((rc = d2h_copy(ctx, ctx->host_stream, copies))) return rc;
     lap(3, t);
     double bytes = 0.0;
@@ -4606,8 +4487,8 @@ int xrt_probe_prep(xrt_context* ctx, const xrt_camera* camera, float* records, f
     if (!T) return XRT_OK;
     if ((rc = sync_context(ctx))) return rc;      // no frame in flight uses the set
     FrameSet& fs = ctx->sets[ctx->next_set];
-    if ((rc = ensure(ctx, fs.recs, fs.recs_cap, T))) return rc;
-    if ((rc = ensure(ctx, fs.cull, fs.cull_cap, (size_t)T * kCullPlanes))) return rc;
+    if ((rc = ensure(ctx, fs.recs, T))) return rc;
+    if ((rc = ensure(ctx, fs.cull, (size_t)T * kCullPlanes))) return rc;
     RenderParams p = make_params(*camera, 0, camera->height, T, ctx->hit_capacity);
     p.model = ctx->model;
     CullParams cp = make_cull_params(*camera);
@@ -4618,14 +4499,14 @@ int xrt_probe_prep(xrt_context* ctx, const xrt_camera* camera, float* records, f
     XRT_HIP(ctx, hipStreamSynchronize(ctx->prep_stream));
     hipLaunchKernelGGL(k_prep, dim3((unsigned)((T + kPrepWaves * p.prep_tris - 1) / (kPrepWaves * p.prep_tris))),
                        dim3(kPrepThreads), 0, 0, soup,
-                       (uint32_t)T, p, cp, fs.recs, fs.cull, nobins, nullptr, nullptr, nullptr, nullptr);
+                       (uint32_t)T, p, cp, fs.recs.get(), fs.cull.get(), nobins, nullptr, nullptr, nullptr, nullptr);
     XRT_HIP(ctx, hipGetLastError());
     if (records)
-        XRT_HIP(ctx, hipMemcpy(records, fs.recs, T * sizeof(TriRec), hipMemcpyDeviceToHost));
+        XRT_HIP(ctx, hipMemcpy(records, fs.recs.get(), T * sizeof(TriRec), hipMemcpyDeviceToHost));
     if (footprint) {
         // planes [bbox | e0 | e1 | e2] of T float4 -> per triangle 16 floats
         std::vector<float4> planes((size_t)T * kCullPlanes);
-        XRT_HIP(ctx, hipMemcpy(planes.data(), fs.cull, planes.size() * sizeof(float4),
+        XRT_HIP(ctx, hipMemcpy(planes.data(), fs.cull.get(), planes.size() * sizeof(float4),
                                hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < T; ++i)
             for (int k = 0; k < kCullPlanes; ++k)

@@ -39,26 +39,22 @@
 
 struct xrt_multi {
     struct Strip {
-        float* lbuffer = nullptr;       // the strip's L-buffer, misses as XRT_MISS_TRANSIT
-        size_t cap = 0;                 // pixels
-        float* packed = nullptr;        // its unfilled regions, 1024 floats each (packed transit)
-        size_t packed_cap = 0;          // floats
-        float* msg = nullptr;           // its hit-layout message (hit transit)
-        size_t msg_cap = 0;             // 32-bit words
-        hipEvent_t sent = nullptr;      // the gather that last read it
-        bool pending = false;
+        Owned<float> lbuffer;           // the strip's L-buffer, misses as XRT_MISS_TRANSIT
+        Owned<float> packed;            // its unfilled regions, 1024 floats each (packed transit)
+        Owned<float> msg;               // its hit-layout message (hit transit), 32-bit words
+        Fence sent;                     // the gather that last read it
     };
     // Packed transit (DESIGN.md "Multi-GPU"): per device g > 0 its strip's region
     // map (the fill plan of its last frame; identity without one) on device g, and
     // on device 0 the unpack descriptors of every strip and the receive buffer.
     std::vector<std::vector<uint32_t>> map_host;   // per device: the map behind d_map
-    std::vector<uint32_t*> d_map;
+    std::vector<Owned<uint32_t>> d_map;
     std::vector<uint32_t> n_packed, block_base;
-    uint32_t* d_desc = nullptr;         // device 0: 4 u32 per region of strips 1 .. n-1
+    Owned<uint32_t> d_desc;             // device 0: 4 u32 per region of strips 1 .. n-1
     size_t n_desc = 0;
-    float* rbuf = nullptr;              // device 0: every strip's packed regions
-    size_t rbuf_cap = 0;                // floats
+    Owned<float> rbuf;                  // device 0: every strip's packed regions
     uint32_t desc_w = 0, desc_h = 0;    // frame the descriptors were built for
+    std::vector<uint32_t> desc_b, desc_e;   // and its strips (the descriptors hold their rows)
     // Hit transit (XRT_TRANSIT_HITS): per sender the strip geometry of its last
     // frame and, once a geometry repeats, its hit plan (xrt_plan_hit_layout,
     // from that previous frame); on device 0 the hit descriptors of every
@@ -80,10 +76,10 @@ struct xrt_multi {
     std::vector<uint64_t> hit_words;    // per device: its message's words (>= 4)
     std::vector<uint32_t> hit_base;     // per device: its message's first word in rbuf
     std::vector<std::vector<uint32_t>> tile_hits;
-    uint32_t* d_hdesc = nullptr;        // device 0: 4 u32 per region of strips 1 .. n-1
-    uint32_t* d_tdesc = nullptr;        // device 0: 4 u32 per planned tile
+    Owned<uint32_t> d_hdesc;            // device 0: 4 u32 per region of strips 1 .. n-1
+    Owned<uint32_t> d_tdesc;            // device 0: 4 u32 per planned tile
     size_t n_hdesc = 0;
-    uint32_t* d_bad = nullptr;          // device 0: a mask disagreed with its plan
+    Owned<uint32_t> d_bad;              // device 0: a mask disagreed with its plan
     bool hits_failed = false;           // the last planning attempt failed (retried on a new geometry)
     bool maps_current = false;          // the last frame travelled packed: map_host is its geometry's
     uint64_t frames_hits = 0, frames_packed = 0, last_bytes = 0;
@@ -98,17 +94,15 @@ struct xrt_multi {
     std::vector<hipStream_t> compute;   // per device render stream (device 0: the caller's, else its own)
     std::vector<hipStream_t> comms;     // per device gather stream
     std::vector<std::array<Strip, 2>> strips;
-    std::vector<hipEvent_t> rendered;   // per device: its strip's render is complete
-    hipEvent_t gathered = nullptr;      // device 0: the frame is assembled
-    hipEvent_t caller_ready = nullptr;  // device 0: the caller's stream reached the call
+    std::vector<PlainEvent> rendered;   // per device: its strip's render is complete
+    PlainEvent gathered;                // device 0: the frame is assembled
+    PlainEvent caller_ready;            // device 0: the caller's stream reached the call
     hipStream_t own0 = nullptr;         // device 0 stream of the host-buffer entry point
     uint64_t frame = 0;
-    float* d_image = nullptr;           // device-0 frame of the host-buffer entry point
-    float* d_lbuffer = nullptr;
-    uint8_t* d_u8 = nullptr;
-    size_t frame_cap = 0;
-    float* scratch_l = nullptr;         // device-0 L-buffer when the caller wants none
-    size_t scratch_cap = 0;
+    Owned<float> d_image;               // device-0 frame of the host-buffer entry point
+    Owned<float> d_lbuffer;
+    Owned<uint8_t> d_u8;
+    Owned<float> scratch_l;             // device-0 L-buffer when the caller wants none
     // Strip split (xrt_multi_set_split): the mode, the caller's link rate
     // (bytes per microsecond one sender delivers into device 0; 0 = measured
     // once, link_measured), and the plan of the last frame geometry.
@@ -120,10 +114,9 @@ struct xrt_multi {
     // its render cost (us) and the bytes its strip would send.  No extra
     // render: the first frame of a multi context splits equally.
     struct StripModel {
-        BandModel* d = nullptr;         // ry + 1 entries: the bands, then the span (x = first start, y = last end)
-        BandModel* h = nullptr;         // pinned copy
-        size_t cap = 0;                 // entries
-        hipEvent_t ev = nullptr;        // the copy is complete
+        Owned<BandModel> d;             // ry + 1 entries: the bands, then the span (x = first start, y = last end)
+        Pinned<BandModel> h;            // pinned copy
+        Fence copied;                   // the copy is complete
         uint32_t b = 0, e = 0, ry = 0;  // the strip's rows and bands
     };
     std::vector<StripModel> smodel;
@@ -139,7 +132,7 @@ struct xrt_multi {
     // counters (xrt_multi_plan_stats): balanced plans made, frames split
     // equally for want of a model, link probes, strip models collected
     uint64_t n_plans = 0, n_equal_no_model = 0, n_link_probes = 0, n_models = 0;
-    uint32_t* h_bad = nullptr;          // pinned: device 0's d_bad after each hit gather
+    Pinned<uint32_t> h_bad;             // pinned: device 0's d_bad after each hit gather
     struct Plan {
         bool valid = false;
         xrt_camera cam = {};
@@ -314,12 +307,11 @@ bool balanced_split(const double* cost, const double* byts, uint32_t nb, uint32_
     return true;
 }
 
-template <typename T>
-int mensure(xrt_multi* m, T*& ptr, size_t n)
+// buf holds at least n (Owned::reserve); a HIP error goes to m->error.
+template <typename T, typename Mem>
+int mensure(xrt_multi* m, Owned<T, Mem>& buf, size_t n)
 {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    XRT_MHIP(m, hipMalloc(&ptr, std::max<size_t>(n, 1) * sizeof(T)));
+    XRT_MHIP(m, buf.reserve(n));
     return XRT_OK;
 }
 
@@ -342,12 +334,14 @@ void strip_map(xrt_multi* m, uint32_t g, uint32_t W, uint32_t rows, std::vector<
 
 // Packed transit state for this frame's maps: per-device maps on the devices,
 // device 0's descriptors and receive buffer.  Rebuilt (synchronously) only when
-// a map or the frame changes -- once per geometry.
+// a map, a strip or the frame changes -- once per geometry.  (A strip can move
+// under an equal map: a 64-row frame's two strips swap when the balanced split
+// follows the equal one, each one row of unfilled regions.)
 int refresh_transit(xrt_multi* m, uint32_t W, uint32_t H, const std::vector<uint32_t>& b,
                     const std::vector<uint32_t>& e, bool& changed)
 {
     const uint32_t n = (uint32_t)m->devices.size();
-    changed = m->desc_w != W || m->desc_h != H;
+    changed = m->desc_w != W || m->desc_h != H || m->desc_b != b || m->desc_e != e;
     std::vector<std::vector<uint32_t>> maps(n);
     std::vector<uint32_t> packed(n, 0);
     for (uint32_t g = 1; g < n; ++g) {
@@ -366,13 +360,10 @@ int refresh_transit(xrt_multi* m, uint32_t W, uint32_t H, const std::vector<uint
     for (uint32_t g = 1; g < n; ++g) {
         XRT_MHIP(m, hipSetDevice(m->devices[g]));
         if ((rc = mensure(m, m->d_map[g], maps[g].size()))) return rc;
-        XRT_MHIP(m, hipMemcpy(m->d_map[g], maps[g].data(), maps[g].size() * 4, hipMemcpyHostToDevice));
+        XRT_MHIP(m, hipMemcpy(m->d_map[g].get(), maps[g].data(), maps[g].size() * 4, hipMemcpyHostToDevice));
         for (auto& st : m->strips[g]) {
             const size_t need = (size_t)std::max<uint32_t>(packed[g], 1u) * kPackBlock;
-            if (st.packed_cap < need) {
-                if ((rc = mensure(m, st.packed, need))) return rc;
-                st.packed_cap = need;
-            }
+            if ((rc = mensure(m, st.packed, need))) return rc;
         }
         const uint32_t rows = e[g] - b[g];
         for (size_t r = 0; r < maps[g].size(); ++r) {
@@ -390,14 +381,13 @@ int refresh_transit(xrt_multi* m, uint32_t W, uint32_t H, const std::vector<uint
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
     if ((rc = mensure(m, m->d_desc, std::max<size_t>(desc.size(), 4)))) return rc;
     if (!desc.empty())
-        XRT_MHIP(m, hipMemcpy(m->d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice));
+        XRT_MHIP(m, hipMemcpy(m->d_desc.get(), desc.data(), desc.size() * 4, hipMemcpyHostToDevice));
     m->n_desc = desc.size() / 4;
-    if (m->rbuf_cap < (size_t)base * kPackBlock) {
-        if ((rc = mensure(m, m->rbuf, (size_t)base * kPackBlock))) return rc;
-        m->rbuf_cap = (size_t)base * kPackBlock;
-    }
+    if ((rc = mensure(m, m->rbuf, (size_t)base * kPackBlock))) return rc;
     m->desc_w = W;
     m->desc_h = H;
+    m->desc_b = b;
+    m->desc_e = e;
     return XRT_OK;
 }
 
@@ -442,14 +432,7 @@ bool plan_hits(xrt_multi* m, uint32_t W, const std::vector<uint32_t>& b, const s
             return false;                              // the map is not this plan's
         const uint64_t msg = std::max<uint64_t>(words, 4u);
         for (auto& st : m->strips[g]) {                // the message, and room for one tile's overrun
-            const size_t need = (size_t)msg + 64u;
-            if (st.msg_cap < need) {
-                (void)hipFree(st.msg);
-                st.msg = nullptr;
-                st.msg_cap = 0;
-                if (hipMalloc(&st.msg, need * 4) != hipSuccess) return false;
-                st.msg_cap = need;
-            }
+            if (st.msg.reserve((size_t)msg + 64u) != hipSuccess) return false;
         }
         std::vector<uint64_t> off(tiles + 1u, 0u);
         for (uint64_t i = 0; i < tiles; ++i) off[i + 1] = off[i] + th[i];
@@ -477,17 +460,14 @@ bool plan_hits(xrt_multi* m, uint32_t W, const std::vector<uint32_t>& b, const s
     if (mensure(m, m->d_hdesc, std::max<size_t>(desc.size(), 4)) || mensure(m, m->d_tdesc, tdesc.size()) ||
         mensure(m, m->d_bad, 4))
         return false;
-    if ((!desc.empty() && hipMemcpy(m->d_hdesc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(m->d_tdesc, tdesc.data(), tdesc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(m->d_bad, 0, 4) != hipSuccess)
+    if ((!desc.empty() && hipMemcpy(m->d_hdesc.get(), desc.data(), desc.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(m->d_tdesc.get(), tdesc.data(), tdesc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(m->d_bad.get(), 0, 4) != hipSuccess)
         return false;
     m->n_hdesc = desc.size() / 4;
-    if (m->rbuf_cap < base) {
-        if (mensure(m, m->rbuf, base)) return false;
-        m->rbuf_cap = base;
-    }
+    if (mensure(m, m->rbuf, base)) return false;
     for (uint32_t g = 1; g < n; ++g)
-        if (xrt_set_transit_hits(m->ctx[g], m->strips[g][0].msg_cap) != XRT_OK) return false;
+        if (xrt_set_transit_hits(m->ctx[g], m->strips[g][0].msg.cap()) != XRT_OK) return false;
     return true;
 }
 
@@ -566,7 +546,7 @@ void harvest_model(xrt_multi* m)
     const uint32_t n = (uint32_t)m->devices.size();
     for (uint32_t g = 0; g < n; ++g) {
         (void)hipSetDevice(m->devices[g]);
-        if (hipEventQuery(m->smodel[g].ev) != hipSuccess) return;
+        if (m->smodel[g].copied.passed() != hipSuccess) return;
     }
     m->model_pending = false;
     const uint32_t W = m->pending_cam.width, H = m->pending_cam.height;
@@ -575,16 +555,17 @@ void harvest_model(xrt_multi* m)
     double span_max = 0.0;
     for (uint32_t g = 0; g < n; ++g) {
         const xrt_multi::StripModel& sm = m->smodel[g];
-        const uint32_t s_lo = sm.h[sm.ry].ticks, s_hi = sm.h[sm.ry].hits;   // the span entry
+        const BandModel* const h = sm.h.get();
+        const uint32_t s_lo = h[sm.ry].ticks, s_hi = h[sm.ry].hits;         // the span entry
         const double span_us = s_hi > s_lo ? (double)(s_hi - s_lo) / (kTicksPerMs * 1e-3) : 0.0;
         uint64_t total = 0;
-        for (uint32_t j = 0; j < sm.ry; ++j) total += sm.h[j].ticks;
+        for (uint32_t j = 0; j < sm.ry; ++j) total += h[j].ticks;
         if (!(span_us > 0.0) || total == 0) return;            // not a usable record: keep the old model
         span_max = std::max(span_max, span_us);
         for (uint32_t j = 0; j < sm.ry; ++j) {
-            const double c = (double)sm.h[j].ticks / (double)total * span_us;
-            const double by = m->transit == XRT_TRANSIT_HITS ? 8.0 * kWavesPerRegion * sm.h[j].tiles + 4.0 * sm.h[j].hits
-                                                             : 4.0 * kPackBlock * sm.h[j].tiles;
+            const double c = (double)h[j].ticks / (double)total * span_us;
+            const double by = m->transit == XRT_TRANSIT_HITS ? 8.0 * kWavesPerRegion * h[j].tiles + 4.0 * h[j].hits
+                                                             : 4.0 * kPackBlock * h[j].tiles;
             const uint32_t r0 = sm.b + j * kRegion, r1 = std::min(sm.e, r0 + kRegion);
             for (uint32_t fb = r0 / kRegion; fb * kRegion < r1 && fb < nb; ++fb) {
                 const uint32_t o0 = std::max(r0, fb * kRegion), o1 = std::min(r1, (fb + 1) * kRegion);
@@ -621,7 +602,7 @@ int collect_model(xrt_multi* m, const xrt_camera* camera, const std::vector<uint
     if (m->model_pending) {                            // an older frame's records: wait for their copies
         for (uint32_t g = 0; g < n; ++g) {
             XRT_MHIP(m, hipSetDevice(m->devices[g]));
-            XRT_MHIP(m, hipEventSynchronize(m->smodel[g].ev));
+            XRT_MHIP(m, m->smodel[g].copied.wait());
         }
     }
     for (uint32_t g = 0; g < n; ++g) {
@@ -631,29 +612,23 @@ int collect_model(xrt_multi* m, const xrt_camera* camera, const std::vector<uint
         hipStream_t sg = g == 0 ? s0 : m->compute[g];
         XRT_MHIP(m, hipSetDevice(m->devices[g]));
         const uint32_t ry = pf[g].ry, n_slots = pf[g].rx * pf[g].ry;
-        if (sm.cap < (size_t)ry + 1u) {
+        if (std::min(sm.d.cap(), sm.h.cap()) < (size_t)ry + 1u) {
             XRT_MHIP(m, hipStreamSynchronize(sg));
-            (void)hipFree(sm.d);
-            (void)hipHostFree(sm.h);
-            sm.d = nullptr;
-            sm.h = nullptr;
-            sm.cap = 0;
-            XRT_MHIP(m, hipMalloc(&sm.d, ((size_t)ry + 1u) * sizeof(BandModel)));
-            XRT_MHIP(m, hipHostMalloc(&sm.h, ((size_t)ry + 1u) * sizeof(BandModel), 0));
-            sm.cap = (size_t)ry + 1u;
+            if (int rc = mensure(m, sm.d, (size_t)ry + 1u)) return rc;
+            if (int rc = mensure(m, sm.h, (size_t)ry + 1u)) return rc;
         }
-        XRT_MHIP(m, hipMemsetAsync(sm.d, 0, (size_t)ry * sizeof(BandModel), sg));
-        XRT_MHIP(m, hipMemsetAsync(sm.d + ry, 0xFF, sizeof(uint32_t), sg));          // span start: ~0
-        XRT_MHIP(m, hipMemsetAsync(reinterpret_cast<uint32_t*>(sm.d + ry) + 1, 0, 3 * sizeof(uint32_t), sg));
+        BandModel* const d = sm.d.get();
+        XRT_MHIP(m, hipMemsetAsync(d, 0, (size_t)ry * sizeof(BandModel), sg));
+        XRT_MHIP(m, hipMemsetAsync(d + ry, 0xFF, sizeof(uint32_t), sg));             // span start: ~0
+        XRT_MHIP(m, hipMemsetAsync(reinterpret_cast<uint32_t*>(d + ry) + 1, 0, 3 * sizeof(uint32_t), sg));
         const uint32_t tile_slots = n_slots - c->last_fill_regions;
-        hipLaunchKernelGGL(k_band_model, dim3((n_slots + 255) / 256), dim3(256), 0, sg, fs.block_stats,
-                           fs.last_times, pf[g].bins.desc, n_slots, tile_slots, sm.d,
-                           reinterpret_cast<uint32_t*>(sm.d + ry));
+        hipLaunchKernelGGL(k_band_model, dim3((n_slots + 255) / 256), dim3(256), 0, sg, fs.block_stats.get(),
+                           fs.last_times, pf[g].bins.desc, n_slots, tile_slots, d, reinterpret_cast<uint32_t*>(d + ry));
         XRT_MHIP(m, hipGetLastError());
-        XRT_MHIP(m, hipMemcpyAsync(sm.h, sm.d, ((size_t)ry + 1u) * sizeof(BandModel), hipMemcpyDeviceToHost, sg));
-        XRT_MHIP(m, hipEventRecord(sm.ev, sg));
-        XRT_MHIP(m, hipEventRecord(fs.done, sg));      // the set is reused after the model read it
-        fs.done_ev = fs.done;
+        XRT_MHIP(m, hipMemcpyAsync(sm.h.get(), d, ((size_t)ry + 1u) * sizeof(BandModel), hipMemcpyDeviceToHost, sg));
+        XRT_MHIP(m, sm.copied.record(sg));
+        XRT_MHIP(m, hipEventRecord(fs.done.get(), sg));      // the set is reused after the model read it
+        fs.done_ev = fs.done.get();
         sm.b = b[g];
         sm.e = e[g];
         sm.ry = ry;
@@ -740,14 +715,14 @@ int plan_strips(xrt_multi* m, const xrt_camera* camera, std::vector<uint32_t>& b
 // the flag reaches h_bad behind each hit gather): that frame's values were not
 // its plan's.  Every hit plan is dropped (the next frame of each geometry
 // travels packed, the one after plans again) and the error is reported.
-bool hit_mismatch(xrt_multi* m) { return m->h_bad && *(volatile uint32_t*)m->h_bad != 0u; }
+bool hit_mismatch(xrt_multi* m) { return m->h_bad.get() && *(volatile uint32_t*)m->h_bad.get() != 0u; }
 
 int report_hit_mismatch(xrt_multi* m)
 {
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
     XRT_MHIP(m, hipStreamSynchronize(m->comms[0]));
-    if (m->d_bad) XRT_MHIP(m, hipMemset(m->d_bad, 0, 4));
-    *m->h_bad = 0u;
+    if (m->d_bad.get()) XRT_MHIP(m, hipMemset(m->d_bad.get(), 0, 4));
+    *m->h_bad.get() = 0u;
     for (auto& k : m->planned) k = xrt_multi::HitKey();
     m->hits_failed = false;
     return mfail(m, XRT_ERR_DEVICE, "hit transit: a received hit mask disagreed with its sender's plan (that frame's "
@@ -815,9 +790,9 @@ int xrt_multi_create(const int* devices, int num_devices, xrt_multi** out)
     m->compute.assign(n, nullptr);
     m->comms.assign(n, nullptr);
     m->strips.resize(n);
-    m->rendered.assign(n, nullptr);
+    m->rendered.resize(n);
     m->map_host.resize(n);
-    m->d_map.assign(n, nullptr);
+    m->d_map.resize(n);
     m->n_packed.assign(n, 0);
     m->block_base.assign(n, 0);
     m->seen.assign(n, xrt_multi::HitKey());
@@ -838,14 +813,11 @@ int xrt_multi_create(const int* devices, int num_devices, xrt_multi** out)
         m->ctx[g]->reuse_cameras = false;
         (void)hipSetDevice(m->devices[g]);
         bool ok = hipStreamCreateWithFlags(&m->comms[g], hipStreamNonBlocking) == hipSuccess &&
-                  hipEventCreateWithFlags(&m->rendered[g], hipEventDisableTiming) == hipSuccess;
+                  m->rendered[g].create() == hipSuccess;
         if (g > 0) ok = ok && hipStreamCreateWithFlags(&m->compute[g], hipStreamNonBlocking) == hipSuccess;
-        for (auto& s : m->strips[g]) ok = ok && hipEventCreateWithFlags(&s.sent, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&m->smodel[g].ev, hipEventDisableTiming) == hipSuccess;
         if (g == 0)
-            ok = ok && hipHostMalloc(&m->h_bad, sizeof(uint32_t), 0) == hipSuccess && (*m->h_bad = 0u, true) &&
-                 hipEventCreateWithFlags(&m->gathered, hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&m->caller_ready, hipEventDisableTiming) == hipSuccess &&
+            ok = ok && m->h_bad.reserve(1) == hipSuccess && (*m->h_bad.get() = 0u, true) &&
+                 m->gathered.create() == hipSuccess && m->caller_ready.create() == hipSuccess &&
                  hipStreamCreateWithFlags(&m->own0, hipStreamNonBlocking) == hipSuccess;
         if (!ok) rc = mfail(m, XRT_ERR_DEVICE, "stream / event creation failed");
         else if (g > 0 && xrt_set_miss_code(m->ctx[g], XRT_MISS_TRANSIT) != XRT_OK)
@@ -873,36 +845,17 @@ void xrt_multi_destroy(xrt_multi* m)
         if (c) (void)ncclCommDestroy(c);
     for (size_t g = 0; g < m->devices.size(); ++g) {
         (void)hipSetDevice(m->devices[g]);
-        if (g < m->d_map.size()) (void)hipFree(m->d_map[g]);
-        for (auto& s : m->strips[g]) {
-            (void)hipFree(s.lbuffer);
-            (void)hipFree(s.packed);
-            (void)hipFree(s.msg);
-            if (s.sent) (void)hipEventDestroy(s.sent);
-        }
-        if (m->rendered[g]) (void)hipEventDestroy(m->rendered[g]);
-        if (g < m->smodel.size()) {
-            xrt_multi::StripModel& sm = m->smodel[g];
-            (void)hipFree(sm.d);
-            if (sm.h) (void)hipHostFree(sm.h);
-            if (sm.ev) (void)hipEventDestroy(sm.ev);
-        }
+        if (g < m->d_map.size()) m->d_map[g].reset();
+        m->strips[g] = {};                             // the strip buffers and their fences
+        m->rendered[g].reset();
+        if (g < m->smodel.size()) m->smodel[g] = xrt_multi::StripModel();
         if (m->comms[g]) (void)hipStreamDestroy(m->comms[g]);
         if (m->compute[g]) (void)hipStreamDestroy(m->compute[g]);
         if (g == 0) {
-            if (m->gathered) (void)hipEventDestroy(m->gathered);
-            if (m->caller_ready) (void)hipEventDestroy(m->caller_ready);
+            release(m->gathered, m->caller_ready);
             if (m->own0) (void)hipStreamDestroy(m->own0);
-            (void)hipFree(m->d_image);
-            (void)hipFree(m->d_lbuffer);
-            (void)hipFree(m->d_u8);
-            (void)hipFree(m->scratch_l);
-            (void)hipFree(m->d_desc);
-            (void)hipFree(m->d_hdesc);
-            (void)hipFree(m->d_tdesc);
-            (void)hipFree(m->d_bad);
-            if (m->h_bad) (void)hipHostFree(m->h_bad);
-            (void)hipFree(m->rbuf);
+            release(m->d_image, m->d_lbuffer, m->d_u8, m->scratch_l, m->d_desc, m->d_hdesc, m->d_tdesc, m->d_bad,
+                    m->h_bad, m->rbuf);
         }
         xrt_destroy(m->ctx[g]);
     }
@@ -1021,12 +974,11 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
     float* lroot = d_lbuffer;
     if (!lroot && planes && (n > 1 || sgn)) {
-        if (m->scratch_cap < (size_t)W * H) {
+        if (m->scratch_l.cap() < (size_t)W * H) {
             XRT_MHIP(m, hipDeviceSynchronize());
             if ((rc = mensure(m, m->scratch_l, (size_t)W * H))) return rc;
-            m->scratch_cap = (size_t)W * H;
         }
-        lroot = m->scratch_l;
+        lroot = m->scratch_l.get();
     }
     // Hit transit: every sender's strip geometry repeats one its plan was made
     // for (or its previous, packed frame can give that plan now)
@@ -1048,8 +1000,8 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
     for (uint32_t g = 1; g < n; ++g)                   // a packed frame renders its senders row-major
         if (!hits && m->ctx[g]->hits_cap && (rc = check_ctx(m, g, xrt_set_transit_hits(m->ctx[g], 0)))) return rc;
     // the gather into the caller's planes comes after the caller's earlier work on them
-    XRT_MHIP(m, hipEventRecord(m->caller_ready, s0));
-    XRT_MHIP(m, hipStreamWaitEvent(m->comms[0], m->caller_ready, 0));
+    XRT_MHIP(m, hipEventRecord(m->caller_ready.get(), s0));
+    XRT_MHIP(m, hipStreamWaitEvent(m->comms[0], m->caller_ready.get(), 0));
     // every device's preparation first, then the renders
     for (uint32_t g = 0; g < n; ++g) {
         const size_t px = (size_t)(e[g] - b[g]) * W;
@@ -1064,22 +1016,21 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
         } else if (planes) {
             XRT_MHIP(m, hipSetDevice(m->devices[g]));
             xrt_multi::Strip& st = m->strips[g][buf];
-            if (st.pending) {                          // the gather two frames ago still reads it
-                XRT_MHIP(m, hipStreamWaitEvent(sg, st.sent, 0));
-                st.pending = false;
+            if (st.sent.pending()) {                   // the gather two frames ago still reads it
+                XRT_MHIP(m, st.sent.order(sg));
+                st.sent.forget();
             }
             if (hits) {
                 if (!m->ctx[g]->hits_cap &&
-                    (rc = check_ctx(m, g, xrt_set_transit_hits(m->ctx[g], st.msg_cap))))
+                    (rc = check_ctx(m, g, xrt_set_transit_hits(m->ctx[g], st.msg.cap()))))
                     return rc;
-                lb = st.msg;
+                lb = st.msg.get();
             } else {
-                if (st.cap < px) {
+                if (st.lbuffer.cap() < px) {
                     XRT_MHIP(m, hipStreamSynchronize(sg));
                     if ((rc = mensure(m, st.lbuffer, px))) return rc;
-                    st.cap = px;
                 }
-                lb = st.lbuffer;
+                lb = st.lbuffer.get();
             }
         }
         if ((rc = check_ctx(m, g, prepare_frame(m->ctx[g], camera, b[g], e[g], img, lb, u8, sg, pf[g]))))
@@ -1089,13 +1040,13 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
         if ((rc = check_ctx(m, g, launch_frame(m->ctx[g], pf[g])))) return rc;
         if (g == 0 && sgn && planes) {                 // the hole fill reads device 0's rows too
             XRT_MHIP(m, hipSetDevice(m->devices[0]));
-            XRT_MHIP(m, hipEventRecord(m->rendered[0], s0));
-            XRT_MHIP(m, hipStreamWaitEvent(m->comms[0], m->rendered[0], 0));
+            XRT_MHIP(m, hipEventRecord(m->rendered[0].get(), s0));
+            XRT_MHIP(m, hipStreamWaitEvent(m->comms[0], m->rendered[0].get(), 0));
         }
         if (g > 0) {
             XRT_MHIP(m, hipSetDevice(m->devices[g]));
-            XRT_MHIP(m, hipEventRecord(m->rendered[g], m->compute[g]));
-            XRT_MHIP(m, hipStreamWaitEvent(m->comms[g], m->rendered[g], 0));
+            XRT_MHIP(m, hipEventRecord(m->rendered[g].get(), m->compute[g]));
+            XRT_MHIP(m, hipStreamWaitEvent(m->comms[g], m->rendered[g].get(), 0));
         }
     }
     // the balanced split's model from this frame's strips (a new camera)
@@ -1107,8 +1058,8 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
         if ((rc = refresh_transit(m, W, H, b, e, changed))) return rc;
         for (uint32_t g = 1; g < n; ++g) {             // pack on the strip's device, after its render
             XRT_MHIP(m, hipSetDevice(m->devices[g]));
-            if ((rc = check_ctx(m, g, xrt_pack_regions_device(m->ctx[g], W, e[g] - b[g], m->d_map[g],
-                                                              m->strips[g][buf].lbuffer, m->strips[g][buf].packed,
+            if ((rc = check_ctx(m, g, xrt_pack_regions_device(m->ctx[g], W, e[g] - b[g], m->d_map[g].get(),
+                                                              m->strips[g][buf].lbuffer.get(), m->strips[g][buf].packed.get(),
                                                               m->comms[g]))))
                 return rc;
         }
@@ -1129,11 +1080,11 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
         // the root gather: device g's strip (packed regions, or its L-buffer rows
         // [b_g, e_g)) to device 0
         auto src = [&](uint32_t g) -> const float* {
-            return hits ? m->strips[g][buf].msg : packed ? m->strips[g][buf].packed : m->strips[g][buf].lbuffer;
+            return hits ? m->strips[g][buf].msg.get() : packed ? m->strips[g][buf].packed.get() : m->strips[g][buf].lbuffer.get();
         };
         auto dst = [&](uint32_t g) -> float* {
-            return hits     ? m->rbuf + m->hit_base[g]
-                   : packed ? m->rbuf + (size_t)m->block_base[g] * kPackBlock
+            return hits     ? m->rbuf.get() + m->hit_base[g]
+                   : packed ? m->rbuf.get() + (size_t)m->block_base[g] * kPackBlock
                             : lroot + (size_t)b[g] * W;
         };
         auto count = [&](uint32_t g) -> size_t {
@@ -1147,10 +1098,10 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
         if (send_on_root) {                            // the root's gather stream follows each strip's pack
             for (uint32_t g = 1; g < n; ++g) {
                 XRT_MHIP(m, hipSetDevice(m->devices[g]));
-                XRT_MHIP(m, hipEventRecord(m->rendered[g], m->comms[g]));
+                XRT_MHIP(m, hipEventRecord(m->rendered[g].get(), m->comms[g]));
             }
             XRT_MHIP(m, hipSetDevice(m->devices[0]));
-            for (uint32_t g = 1; g < n; ++g) XRT_MHIP(m, hipStreamWaitEvent(m->comms[0], m->rendered[g], 0));
+            for (uint32_t g = 1; g < n; ++g) XRT_MHIP(m, hipStreamWaitEvent(m->comms[0], m->rendered[g].get(), 0));
         }
         if (!m->comm.empty()) {
             XRT_MNCCL(m, ncclGroupStart());
@@ -1168,18 +1119,17 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
         for (uint32_t g = 1; g < n; ++g) {
             XRT_MHIP(m, hipSetDevice(m->devices[g]));
             xrt_multi::Strip& st = m->strips[g][buf];
-            XRT_MHIP(m, hipEventRecord(st.sent, send_on_root ? m->comms[0] : m->comms[g]));
-            st.pending = true;
+            XRT_MHIP(m, st.sent.record(send_on_root ? m->comms[0] : m->comms[g]));
         }
         // the received rows into the image and 8-bit planes (and the miss codes back to +inf)
         if (hits) {
-            if ((rc = check_ctx(m, 0, xrt_unpack_hits_device(m->ctx[0], W, m->n_hdesc, m->d_hdesc, m->d_tdesc,
-                                                             reinterpret_cast<const uint32_t*>(m->rbuf), lroot,
-                                                             d_image, d_u8, m->d_bad, m->comms[0]))))
+            if ((rc = check_ctx(m, 0, xrt_unpack_hits_device(m->ctx[0], W, m->n_hdesc, m->d_hdesc.get(), m->d_tdesc.get(),
+                                                             reinterpret_cast<const uint32_t*>(m->rbuf.get()), lroot,
+                                                             d_image, d_u8, m->d_bad.get(), m->comms[0]))))
                 return rc;
-            XRT_MHIP(m, hipMemcpyAsync(m->h_bad, m->d_bad, 4, hipMemcpyDeviceToHost, m->comms[0]));
+            XRT_MHIP(m, hipMemcpyAsync(m->h_bad.get(), m->d_bad.get(), 4, hipMemcpyDeviceToHost, m->comms[0]));
         } else if (packed) {
-            if ((rc = check_ctx(m, 0, xrt_unpack_blocks_device(m->ctx[0], W, m->n_desc, m->d_desc, m->rbuf, lroot,
+            if ((rc = check_ctx(m, 0, xrt_unpack_blocks_device(m->ctx[0], W, m->n_desc, m->d_desc.get(), m->rbuf.get(), lroot,
                                                                d_image, d_u8, m->comms[0]))))
                 return rc;
         } else if (!sgn) {                             // the rows above and below the root's strip
@@ -1200,8 +1150,8 @@ int xrt_render_rows_multi_device(xrt_multi* m, const xrt_camera* camera, float* 
     }
     // the caller's stream sees the assembled frame
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
-    XRT_MHIP(m, hipEventRecord(m->gathered, m->comms[0]));
-    XRT_MHIP(m, hipStreamWaitEvent(s0, m->gathered, 0));
+    XRT_MHIP(m, hipEventRecord(m->gathered.get(), m->comms[0]));
+    XRT_MHIP(m, hipStreamWaitEvent(s0, m->gathered.get(), 0));
     ++m->frame;
     return XRT_OK;
 }
@@ -1223,10 +1173,10 @@ int xrt_multi_transit_stats(xrt_multi* m, uint64_t out[4])
     out[1] = m->frames_packed;
     out[2] = m->last_bytes;
     uint32_t bad = 0;
-    if (m->d_bad) {
+    if (m->d_bad.get()) {
         XRT_MHIP(m, hipSetDevice(m->devices[0]));
         XRT_MHIP(m, hipStreamSynchronize(m->comms[0]));
-        XRT_MHIP(m, hipMemcpy(&bad, m->d_bad, 4, hipMemcpyDeviceToHost));
+        XRT_MHIP(m, hipMemcpy(&bad, m->d_bad.get(), 4, hipMemcpyDeviceToHost));
     }
     out[3] = bad;
     return XRT_OK;
@@ -1245,13 +1195,13 @@ int xrt_multi_plan_stats(xrt_multi* m, uint64_t out[4])
 int xrt_multi_debug_corrupt_hit_plan(xrt_multi* m)
 {
     if (!m) return XRT_ERR_ARGUMENT;
-    if (!m->d_tdesc) return mfail(m, XRT_ERR_ARGUMENT, "no hit plan");
+    if (!m->d_tdesc.get()) return mfail(m, XRT_ERR_ARGUMENT, "no hit plan");
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
     XRT_MHIP(m, hipDeviceSynchronize());
     uint32_t td[4];
-    XRT_MHIP(m, hipMemcpy(td, m->d_tdesc, sizeof td, hipMemcpyDeviceToHost));
+    XRT_MHIP(m, hipMemcpy(td, m->d_tdesc.get(), sizeof td, hipMemcpyDeviceToHost));
     td[2] += 1u;                                      // tile 0 of the first sender expects one more hit
-    XRT_MHIP(m, hipMemcpy(m->d_tdesc, td, sizeof td, hipMemcpyHostToDevice));
+    XRT_MHIP(m, hipMemcpy(m->d_tdesc.get(), td, sizeof td, hipMemcpyHostToDevice));
     return XRT_OK;
 }
 
@@ -1337,18 +1287,17 @@ int xrt_render_rows_multi(xrt_multi* m, const xrt_camera* camera, float* image, 
     if (rc) return mfail(m, rc, m->ctx[0]->error);
     const size_t px = (size_t)camera->width * camera->height;
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
-    if (m->frame_cap < px) {
+    if (std::min({m->d_image.cap(), m->d_lbuffer.cap(), m->d_u8.cap()}) < px) {
         XRT_MHIP(m, hipDeviceSynchronize());
         if ((rc = mensure(m, m->d_image, px)) || (rc = mensure(m, m->d_lbuffer, px)) || (rc = mensure(m, m->d_u8, px)))
             return rc;
-        m->frame_cap = px;
     }
-    rc = xrt_render_rows_multi_device(m, camera, image ? m->d_image : nullptr, lbuffer ? m->d_lbuffer : nullptr,
-                                      image_u8 ? m->d_u8 : nullptr, m->own0);
+    rc = xrt_render_rows_multi_device(m, camera, image ? m->d_image.get() : nullptr, lbuffer ? m->d_lbuffer.get() : nullptr,
+                                      image_u8 ? m->d_u8.get() : nullptr, m->own0);
     if (rc) return rc;
     XRT_MHIP(m, hipSetDevice(m->devices[0]));
     // (through device 0's pinned ring and copy threads)
-    const std::vector<D2HCopy> copies = plane_copies(px, image, m->d_image, lbuffer, m->d_lbuffer, image_u8, m->d_u8);
+    const std::vector<D2HCopy> copies = plane_copies(px, image, m->d_image.get(), lbuffer, m->d_lbuffer.get(), image_u8, m->d_u8.get());
     if ((rc = check_ctx(m, 0, d2h_copy(m->ctx[0], m->own0, copies)))) return rc;
     XRT_MHIP(m, hipStreamSynchronize(m->own0));
     if (hit_mismatch(m)) return report_hit_mismatch(m);          // this frame's gather

@@ -15,7 +15,7 @@ from simpleraytracing_amd.scenes import orbit_camera, tiled_mesh
 from oracle import oracle
 from conftest import DRAGON, GOLDEN, ROOT, bits
 from kat import kat_vectors
-from scene_kit import corner_soup, plane_stack, synthetic_soup
+from scene_kit import corner_soup, plane_stack, striped_sheets, synthetic_soup
 
 pytestmark = pytest.mark.gpu
 KERNELS = [xrt.XRT_KERNEL_BRUTE, xrt.XRT_KERNEL_TILED, xrt.XRT_KERNEL_BINNED]
@@ -1506,6 +1506,79 @@ def test_fresh_context_after_two_stream_loop(dragon):
             assert np.array_equal(bits(x.cpu().numpy()), bits(y))
     for x, y in zip(again[:3], got[:3]):
         assert np.array_equal(bits(x), bits(y))
+
+
+def _regrow_frames(c, mesh, W, H, multi):
+    """The step's planes on context c: three frames (the strip buffers rotate, a repeated strip
+    geometry switches to hit transit) through the host entry point, and for a single context
+    also through xrt_render_rows_device on a stream of its own."""
+    import torch
+    cam = xrt.camera_for_mesh(mesh, W, H)
+    c.upload_mesh(mesh)
+    if multi:
+        return [plane for _ in range(3) for plane in c.render(cam)[:3]]
+    out = list(c.render_rows(cam)[:3])
+    dev = torch.device("cuda", c.device)
+    img, lb = torch.empty(W * H, device=dev), torch.empty(W * H, device=dev)
+    u8 = torch.empty(W * H, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+    c.render_rows_device(cam, 0, H, img.data_ptr(), lb.data_ptr(), u8.data_ptr(), stream.cuda_stream)
+    stream.synchronize()
+    return out + [t.cpu().numpy() for t in (img, lb, u8)]
+
+
+@pytest.mark.parametrize("multi", [False, True], ids=["context", "multi-0-0"])
+def test_regrown_buffers_equal_fresh_contexts(multi):
+    """A live context's buffers grow with its frames and are kept when a smaller frame follows:
+    a small mesh at 64 x 64, a mesh of 100 times the triangles at 192 x 160 (the soup, the
+    records, the lists, the staging planes, the strip / frame / receive buffers are replaced),
+    then the first mesh and size again (everything is larger than it needs).  Each step's
+    planes equal, bit for bit, those of a context created for that step alone.  (The multi
+    contexts split equally: the strips stay where they are, and the buffers are what changes;
+    test_multi_strips_swap_under_equal_maps moves them.)"""
+    small, large = striped_sheets(seed=5, n=10), synthetic_soup(seed=23, n=3000)
+    steps = [(small, 64, 64), (large, 192, 160), (small, 64, 64)]
+
+    def make():
+        c = xrt.MultiContext([0, 0]) if multi else xrt.Context(0)
+        c.set_kernel(xrt.XRT_KERNEL_BINNED)
+        if multi:
+            c.set_split(xrt.XRT_SPLIT_EQUAL)
+        return c
+
+    with make() as live:
+        got = [_regrow_frames(live, *s, multi) for s in steps]
+    for k, s in enumerate(steps):
+        with make() as fresh:
+            want = _regrow_frames(fresh, *s, multi)
+        assert len(got[k]) == len(want) == (9 if multi else 6)
+        for j, (x, y) in enumerate(zip(got[k], want)):
+            assert x.shape == y.shape and np.array_equal(bits(x), bits(y)), (k, j)
+    for k in range(3):                                  # (every step's mesh is in view: its L-buffer holds hits)
+        assert np.isfinite(got[k][1]).any(), k
+
+
+@pytest.mark.parametrize("transit", [xrt.XRT_TRANSIT_PACKED, xrt.XRT_TRANSIT_HITS], ids=["packed", "hits"])
+def test_multi_strips_swap_under_equal_maps(transit):
+    """A 64-row frame on two devices is two strips of one row of regions each.  The first frame
+    splits equally; the balanced split that follows may give the root the lower band, so the
+    sender's strip moves from rows 32-64 to rows 0-32 while its region map (no region filled)
+    stays what it was: the unpack descriptors hold the strip's rows and follow it.  Every frame
+    equals one device's, bit for bit, whichever way the plans fall."""
+    mesh = striped_sheets(seed=5, n=10)
+    cam = xrt.camera_for_mesh(mesh, 64, 64)
+    with xrt.Context(0) as one:
+        one.set_kernel(xrt.XRT_KERNEL_BINNED)
+        one.upload_mesh(mesh)
+        ref = one.render_rows(cam)
+    with xrt.MultiContext([0, 0]) as m:
+        m.set_kernel(xrt.XRT_KERNEL_BINNED)
+        m.set_transit(transit)
+        m.upload_mesh(mesh)
+        for k in range(5):
+            got = m.render(cam)
+            for j, (x, y) in enumerate(zip(got[:3], ref[:3])):
+                assert np.array_equal(bits(x), bits(np.asarray(y).reshape(-1))), (k, j)
 
 
 def test_host_buffer_d2h_pieces_exact(dragon):
