@@ -604,6 +604,9 @@ int collect_model(xrt_multi* m, const xrt_camera* camera, const std::vector<uint
             XRT_MHIP(m, hipSetDevice(m->devices[g]));
             XRT_MHIP(m, m->smodel[g].copied.wait());
         }
+        // ... and take them: a host that runs ahead of the caller's stream never finds them complete in
+        // plan_strips, and the records below would overwrite every model unread
+        harvest_model(m);
     }
     for (uint32_t g = 0; g < n; ++g) {
         xrt_context* c = m->ctx[g];

@@ -260,6 +260,22 @@ static void fence_checks()
         EXPECT(f.mark() == hipSuccess && f.pending() && f.wait() == hipSuccess && !f.pending());   // marked, never recorded
     }
     EXPECT(E::live == 0);
+    {
+        TestFence f;                               // the working set's fence through the voxeliser's shortcut (run_voxelize)
+        const int syncs = E::syncs;
+        EXPECT(f.mark() == hipSuccess && f.record(7) == hipSuccess && f.pending());   // a voxelisation on stream 7
+        f.forget();                                // the next one on stream 7: the stream orders it
+        EXPECT(!f.pending() && f.wait() == hipSuccess && E::syncs == syncs);           // the set's wait finds nothing
+        EXPECT(f.mark() == hipSuccess && f.pending());                                 // in use again ahead of its kernels
+        EXPECT(f.record(7) == hipSuccess && f.pending() && E::live == 1);              // the same event
+        EXPECT(f.wait() == hipSuccess && E::syncs == syncs + 1 && !f.pending());       // a user on another stream waits, once
+        f.forget();                                // nothing pending: nothing changes
+        EXPECT(!f.pending() && f.wait() == hipSuccess && E::syncs == syncs + 1);
+        EXPECT(f.mark() == hipSuccess && f.pending());
+        f.forget();                                // marked, never recorded, forgotten: no wait on an event never recorded
+        EXPECT(!f.pending() && f.wait() == hipSuccess && E::syncs == syncs + 1);
+    }
+    EXPECT(E::live == 0);
 }
 
 int main()
