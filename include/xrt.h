@@ -1315,6 +1315,107 @@ int xrt_voxelize_device(xrt_context* ctx, const uint32_t dims[3], const float or
                         const float* value, uint16_t* d_mask, uint8_t* d_labels, float* d_volume, uint64_t* d_odd_columns,
                         void* stream);
 
+/* --- the scatter model -------------------------------------- */
+
+/*
+ * A kernel-superposition estimate of scattered radiation from the paths
+ * model's planes, in three steps: xrt_scatter_source forms the scatter source
+ * per material and energy bin and bins it to a coarse grid; the caller blurs
+ * the coarse planes with xrt_detector_response, once per scatter kernel;
+ * xrt_scatter_add interpolates the blurred planes back onto the detector,
+ * weighs and sums them and adds them to the primary.
+ *
+ * For num_planes projections of width x height, N = num_planes * height *
+ * width: paths is num_meshes mesh-major f32 planes of N values and open the
+ * uint16 masks or NULL, as xrt_apply_spectrum takes them; weight[num_bins] and
+ * mu[num_meshes][num_bins] are the spectrum table; sigma, in mu's layout, is
+ * the part of each coefficient that scatters, every entry finite and >= 0; bin
+ * = D is a power of two in 1..XRT_MAX_SCATTER_BIN.  The coarse grid is Wc =
+ * (width + D - 1) / D by Hc = (height + D - 1) / D.
+ *
+ * xrt_scatter_source.  Per fine pixel i = (p * height + y) * width + x, in
+ * f64, every operation rounded on its own, exp as the spectrum model's:
+ *
+ *   E = 0; Q = 0
+ *   for e in bins:
+ *       xe = 0; se = 0
+ *       for m in meshes:
+ *           d  = (double)paths[m * N + i] * 0.1
+ *           xe = xe + (double)mu[m][e] * d
+ *           se = se + (double)sigma[m][e] * d
+ *       t = (double)weight[e] * exp(-xe)
+ *       E = E + t
+ *       Q = Q + t * se
+ *   flagged = open && open[i] != 0
+ *   lbuffer[i] = flagged ? -1.0f : (float)E     (lbuffer may be NULL)
+ *   q = flagged ? +0.0 : Q
+ *
+ * lbuffer is xrt_apply_spectrum's L-buffer bit for bit (a NaN E is stored as
+ * 0x7FC00000, as there).  Per coarse pixel (p, yc, xc), over the rows and
+ * columns of its D x D block that lie on the detector (rows x cols pixels,
+ * fewer at the right and bottom edges):
+ *
+ *   acc = -0.0
+ *   for y ascending: r = -0.0; for x ascending: r = r + q;  acc = acc + r
+ *   source[(p * Hc + yc) * Wc + xc] = (float)(acc / (double)(rows * cols))
+ *
+ * A row's sum first, then the rows, in that order.  With D = 1 source is
+ * (float)Q.  A NaN path length propagates as IEEE 754 has it, its sign and
+ * payload unspecified: it is the source of its whole block, and after the blur
+ * it reaches every fine pixel within the scatter kernel's width of the block.
+ *
+ * xrt_scatter_add.  blurred is num_kernels (G, 1..XRT_MAX_SCATTER_KERNELS)
+ * stacks [g][p][Hc][Wc] of blurred coarse planes, amp[G] their amplitudes
+ * (f32, finite, >= 0, host memory in both forms), primary N values or NULL.
+ * Per fine pixel, in f64 with nothing fused:
+ *
+ *   u  = ((double)x + 0.5) / (double)D - 0.5, clamped to [0, Wc - 1]
+ *   x0 = floor(u); fx = u - x0; x1 = min(x0 + 1, Wc - 1)
+ *   (v, y0, fy, y1 likewise from y, D, Hc)
+ *   S = 0.0
+ *   for g in kernels:                         c.. = (double)blurred[g][p][y.][x.]
+ *       a  = fx == 0 ? c00 : c00 + fx * (c01 - c00)
+ *       b  = fx == 0 ? c10 : c10 + fx * (c11 - c10)
+ *       vg = fy == 0 ? a : a + fy * (b - a)
+ *       S  = S + (double)amp[g] * vg
+ *   out_scatter[i] = (float)S
+ *   out[i]         = primary ? (float)((double)primary[i] + S) : (float)S
+ *   out_u8[i]      = the 8-bit LUT of out[i]
+ *
+ * Any of out, out_scatter and out_u8 may be NULL, not all.  A constant coarse
+ * plane comes back as that constant exactly; with D = 1 the sample is the
+ * coarse value itself.
+ *
+ * XRT_ERR_ARGUMENT, with xrt_last_error naming the argument and before the
+ * context is looked at: a NULL paths, sigma, source, blurred or amp, or no
+ * output; what xrt_set_spectrum refuses in the table; a sigma entry that is
+ * NaN, infinite or negative; a bin that is no power of two in
+ * 1..XRT_MAX_SCATTER_BIN; num_kernels outside 1..XRT_MAX_SCATTER_KERNELS or an
+ * amp that is NaN, infinite or negative; a width, height or num_planes of 0, a
+ * width or height above 2^31 - 1, more than 65535 planes or tile rows (a tile
+ * is max(D, 4) rows in the source, 64 in the sum) or a plane of more than 2^40
+ * pixels; an output that overlaps an input.  The host forms take host buffers
+ * and are synchronous; the _device forms take device buffers and are
+ * asynchronous on `stream`, the tables and amplitudes, host data, travelling
+ * with the launch.  Neither entry touches the model, the scene, the frames in
+ * flight or the context's working set.  There is no xrt_multi_ form.
+ */
+#define XRT_MAX_SCATTER_BIN 64
+#define XRT_MAX_SCATTER_KERNELS 4
+int xrt_scatter_source(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t num_meshes,
+                       const float* paths, const uint16_t* open, const float* weight, const float* mu, const float* sigma,
+                       uint32_t num_bins, uint32_t bin, float* lbuffer, float* source);
+int xrt_scatter_source_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t num_meshes,
+                              const float* d_paths, const uint16_t* d_open, const float* weight, const float* mu,
+                              const float* sigma, uint32_t num_bins, uint32_t bin, float* d_lbuffer, float* d_source,
+                              void* stream);
+int xrt_scatter_add(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t bin,
+                    const float* blurred, uint32_t num_kernels, const float* amp, const float* primary, float* out,
+                    float* out_scatter, uint8_t* out_u8);
+int xrt_scatter_add_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t bin,
+                           const float* d_blurred, uint32_t num_kernels, const float* amp, const float* d_primary,
+                           float* d_out, float* d_out_scatter, uint8_t* d_out_u8, void* stream);
+
 /* --- multi-GPU: row strips + RCCL root gather (one process) --------------- */
 
 /*

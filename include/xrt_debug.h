@@ -332,6 +332,20 @@ int xrt_host_photon_noise(uint32_t width, uint32_t height, uint32_t num_planes, 
 int xrt_debug_poisson_batch(xrt_context* ctx, const double* lam, const uint32_t* words, uint64_t n, double* out);
 
 /*
+ * Test hooks of the scatter model.  Host code, no device: the arithmetic of
+ * k_scatter_source and k_scatter_add -- the pixel functions the kernels call,
+ * the source's two-level sum in the contract's order -- over whole planes,
+ * arguments and checks as xrt_scatter_source's and xrt_scatter_add's, host
+ * buffers.
+ */
+int xrt_host_scatter_source(uint32_t width, uint32_t height, uint32_t num_planes, uint32_t num_meshes, const float* paths,
+                            const uint16_t* open, const float* weight, const float* mu, const float* sigma,
+                            uint32_t num_bins, uint32_t bin, float* lbuffer, float* source);
+int xrt_host_scatter_add(uint32_t width, uint32_t height, uint32_t num_planes, uint32_t bin, const float* blurred,
+                         uint32_t num_kernels, const float* amp, const float* primary, float* out, float* out_scatter,
+                         uint8_t* out_u8);
+
+/*
  * Test hook of the area sampling.  Host code, no device: xrt_area_integrate's
  * pixel function -- the one k_area_integrate calls -- over whole buffers,
  * arguments and checks as xrt_area_integrate's, host buffers.

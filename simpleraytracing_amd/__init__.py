@@ -22,7 +22,7 @@ from ._abi import (Camera, Stats, XRT_KERNEL_AUTO, XRT_KERNEL_BINNED,  # noqa: F
                    XRT_KERNEL_BRUTE, XRT_KERNEL_TILED, XRT_MISS_TRANSIT, XRT_MODEL_ATTENUATION,
                    XRT_MODEL_SIGNED, XRT_MODEL_MATERIALS, XRT_MAX_MESHES, XRT_MODEL_SPECTRUM, XRT_MAX_BINS, XRT_MODEL_PATHS, XRT_MAX_LSF_TAPS, XRT_ORDER_PROJECTIONS, XRT_ORDER_SINOGRAMS, XRT_NOISE_INTENSITY, XRT_NOISE_COUNTS, XRT_MAX_SOURCES, XRT_MAX_BIN, XRT_MAX_RAMP_WIDTH, XRT_RAMP_RAMLAK, XRT_RAMP_HANN, XRT_FP_PROJECT, XRT_FP_RESIDUAL, XRT_MAX_SUBSETS, XRT_GATHER_AUTO, XRT_GATHER_COPY, XRT_GATHER_RCCL, XRT_SPLIT_EQUAL,
                    XRT_SPLIT_BALANCED, XRT_TRANSIT_HITS, XRT_TRANSIT_PACKED, XRT_MAX_BASIS, XRT_DECOMPOSE_MASKED,
-                   XRT_DECOMPOSE_FAILED)
+                   XRT_DECOMPOSE_FAILED, XRT_MAX_SCATTER_BIN, XRT_MAX_SCATTER_KERNELS)
 
 __all__ = [
     "Camera", "Stats", "Context", "MultiContext", "XrtError", "load_ply", "mesh_bbox", "camera_from_bbox",
@@ -43,6 +43,8 @@ __all__ = [
     "host_sirt", "host_tv_gradient", "host_volume_sumsq", "host_tv_descend",
     "XRT_MAX_BASIS", "XRT_DECOMPOSE_MASKED", "XRT_DECOMPOSE_FAILED", "decompose_guess", "host_decompose", "decompose",
     "host_voxelize",
+    "XRT_MAX_SCATTER_BIN", "XRT_MAX_SCATTER_KERNELS", "host_scatter_source", "host_scatter_add", "scatter_gaussian",
+    "scatter",
 ]
 
 
@@ -249,6 +251,89 @@ def detector_response(image, lsf_x, lsf_y=None, device: int = 0) -> np.ndarray:
     """The blurred f32 image(s) of Context.detector_response, on a context of its own on `device`."""
     with Context(device) as ctx:
         return ctx.detector_response(image, lsf_x, lsf_y, u8=False)[0]
+
+
+def _scatter_planes(paths, open, num_meshes):
+    """xrt_scatter_source's planes from (M, H, W) or (M, P, H, W) paths and (H, W) or (P, H, W) masks (or None):
+    (paths, open, P, H, W, a plane stack's shape)."""
+    p = np.ascontiguousarray(paths, dtype=np.float32)
+    if p.ndim not in (3, 4) or p.shape[0] != num_meshes:
+        raise ValueError(f"paths must be ({num_meshes}, H, W) or ({num_meshes}, P, H, W), got shape {p.shape}")
+    o = None if open is None else np.ascontiguousarray(open, dtype=np.uint16)
+    if o is not None and o.shape != p.shape[1:]:
+        raise ValueError(f"open must have a plane stack's shape {p.shape[1:]}, got {o.shape}")
+    return p, o, (1 if p.ndim == 3 else p.shape[1]), p.shape[-2], p.shape[-1], p.shape[1:]
+
+
+def _scatter_tables(weights, mu, sigma):
+    w, mu = _spectrum_arrays(weights, mu)
+    sg = np.ascontiguousarray(sigma, dtype=np.float32)
+    if sg.shape != mu.shape:
+        raise ValueError(f"sigma must have mu's shape {mu.shape}, got {sg.shape}")
+    return w, mu, sg
+
+
+def _scatter_coarse(blurred, amp, shape, bin):
+    """xrt_scatter_add's coarse planes for a fine (H, W) or (P, H, W) `shape`: (blurred (G, ...), amp (G,))."""
+    a = np.ascontiguousarray(amp, dtype=np.float32).reshape(-1)
+    d = max(int(bin), 1)
+    want = (a.size,) + tuple(shape[:-2]) + ((shape[-2] + d - 1) // d, (shape[-1] + d - 1) // d)
+    b = np.ascontiguousarray(blurred, dtype=np.float32)
+    if b.shape != want:
+        raise ValueError(f"blurred must have shape {want}, got {b.shape}")
+    return b, a
+
+
+def host_scatter_source(paths, open, weights, mu, sigma, bin, lbuffer=True):
+    """Context.scatter_source in the device's arithmetic on the host (xrt_host_scatter_source, a test hook)."""
+    w, mu, sg = _scatter_tables(weights, mu, sigma)
+    p, o, planes, h, wd, shape = _scatter_planes(paths, open, mu.shape[0])
+    d = max(int(bin), 1)
+    src = np.empty(tuple(shape[:-2]) + ((h + d - 1) // d, (wd + d - 1) // d), np.float32)
+    lb = np.empty(shape, np.float32) if lbuffer else None
+    rc = _abi.load().xrt_host_scatter_source(wd, h, planes, mu.shape[0], _fptr(p), _u16ptr(o) if o is not None else None,
+                                             _fptr(w), _fptr(mu), _fptr(sg), w.size, int(bin),
+                                             _fptr(lb) if lb is not None else None, _fptr(src))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_scatter_source")
+    return src, lb
+
+
+def host_scatter_add(blurred, amp, bin, shape, primary=None, out=True, scatter=True, u8=True):
+    """Context.scatter_add in the device's arithmetic on the host (xrt_host_scatter_add, a test hook)."""
+    shape = tuple(int(v) for v in shape)
+    b, a = _scatter_coarse(blurred, amp, shape, bin)
+    pr = None if primary is None else np.ascontiguousarray(primary, dtype=np.float32).reshape(shape)
+    o = np.empty(shape, np.float32) if out else None
+    s = np.empty(shape, np.float32) if scatter else None
+    u = np.empty(shape, np.uint8) if u8 else None
+    planes = 1 if len(shape) == 2 else shape[0]
+    rc = _abi.load().xrt_host_scatter_add(shape[-1], shape[-2], planes, int(bin), _fptr(b), a.size, _fptr(a),
+                                          _fptr(pr) if pr is not None else None, _fptr(o) if o is not None else None,
+                                          _fptr(s) if s is not None else None, _u8ptr(u) if u is not None else None)
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_scatter_add")
+    return o, s, u
+
+
+def scatter_gaussian(sigma_pixels: float, bin: int, taps: int | None = None) -> np.ndarray:
+    """A Gaussian scatter kernel of `sigma_pixels` detector pixels as taps on the grid binned by `bin`:
+    lsf_gaussian(sigma / bin, taps), taps by default 2 * ceil(4 * sigma / bin) + 1, at most XRT_MAX_LSF_TAPS."""
+    s = float(sigma_pixels) / float(bin)
+    if taps is None:
+        if not (np.isfinite(s) and s > 0.0):
+            raise XrtError(_abi.XRT_ERR_ARGUMENT, "scatter_gaussian: sigma and bin must be finite and > 0")
+        taps = 2 * int(np.ceil(4.0 * s)) + 1
+    if int(taps) > XRT_MAX_LSF_TAPS:
+        raise XrtError(_abi.XRT_ERR_ARGUMENT, f"scatter_gaussian: {int(taps)} taps on the coarse grid, more than "
+                                              f"XRT_MAX_LSF_TAPS = {XRT_MAX_LSF_TAPS}: bin further")
+    return lsf_gaussian(s, int(taps))
+
+
+def scatter(paths, open, weights, mu, sigma, kernels, bin, width, height, device: int = 0):
+    """(total, scatter, primary) of Context.scatter, on a context of its own on `device`."""
+    with Context(device) as ctx:
+        return ctx.scatter(paths, open, weights, mu, sigma, kernels, bin, width, height)
 
 
 def _projection_arrays(image, flat, dark, flat_value, sinograms):
@@ -1493,6 +1578,75 @@ class Context:
                                                     d_image or None, _fptr(hx), hx.size, _fptr(hy), hy.size,
                                                     d_out or None, d_u8 or None, stream or None)
         self._check(rc, "xrt_detector_response_device")
+
+    def scatter_source(self, paths, open, weights, mu, sigma, bin, lbuffer=True):
+        """The scatter model's source (xrt_scatter_source) from render_paths' planes ((M, H, W) or (M, P, H, W) f32
+        and the masks, or None) under the table (weights[K], mu[M, K], sigma[M, K]), binned by `bin`: (source
+        (..., Hc, Wc), lbuffer of a plane stack's shape -- apply_spectrum's -- or None with lbuffer=False)."""
+        w, mu, sg = _scatter_tables(weights, mu, sigma)
+        p, o, planes, h, wd, shape = _scatter_planes(paths, open, mu.shape[0])
+        d = max(int(bin), 1)
+        src = np.empty(tuple(shape[:-2]) + ((h + d - 1) // d, (wd + d - 1) // d), np.float32)
+        lb = np.empty(shape, np.float32) if lbuffer else None
+        self._check(self._lib.xrt_scatter_source(
+            self._ctx, wd, h, planes, mu.shape[0], _fptr(p), _u16ptr(o) if o is not None else None, _fptr(w), _fptr(mu),
+            _fptr(sg), w.size, int(bin), _fptr(lb) if lb is not None else None, _fptr(src)), "xrt_scatter_source")
+        return src, lb
+
+    def scatter_source_device(self, width: int, height: int, num_planes: int, d_paths: int, d_open: int, weights, mu,
+                              sigma, bin: int, d_lbuffer: int, d_source: int, stream: int = 0):
+        """scatter_source over device buffers (raw pointers; the tables are host data and travel with the launch);
+        asynchronous on `stream`."""
+        w, mu, sg = _scatter_tables(weights, mu, sigma)
+        rc = self._lib.xrt_scatter_source_device(self._ctx, int(width), int(height), int(num_planes), mu.shape[0],
+                                                 d_paths or None, d_open or None, _fptr(w), _fptr(mu), _fptr(sg), w.size,
+                                                 int(bin), d_lbuffer or None, d_source or None, stream or None)
+        self._check(rc, "xrt_scatter_source_device")
+
+    def scatter_add(self, blurred, amp, bin, shape, primary=None, out=True, scatter=True, u8=True):
+        """The scatter model's last step (xrt_scatter_add): the G blurred coarse stacks (G, [P,] Hc, Wc) sampled on
+        the fine (H, W) or (P, H, W) `shape`, weighed by amp[G], summed and added to `primary` (or None):
+        (out, scatter, u8), any of them None when left out."""
+        shape = tuple(int(v) for v in shape)
+        b, a = _scatter_coarse(blurred, amp, shape, bin)
+        pr = None if primary is None else np.ascontiguousarray(primary, dtype=np.float32).reshape(shape)
+        o = np.empty(shape, np.float32) if out else None
+        s = np.empty(shape, np.float32) if scatter else None
+        u = np.empty(shape, np.uint8) if u8 else None
+        planes = 1 if len(shape) == 2 else shape[0]
+        self._check(self._lib.xrt_scatter_add(
+            self._ctx, shape[-1], shape[-2], planes, int(bin), _fptr(b), a.size, _fptr(a),
+            _fptr(pr) if pr is not None else None, _fptr(o) if o is not None else None,
+            _fptr(s) if s is not None else None, _u8ptr(u) if u is not None else None), "xrt_scatter_add")
+        return o, s, u
+
+    def scatter_add_device(self, width: int, height: int, num_planes: int, bin: int, d_blurred: int, amp, d_primary: int,
+                           d_out: int, d_out_scatter: int = 0, d_out_u8: int = 0, stream: int = 0):
+        """scatter_add over device buffers (raw pointers; the amplitudes are host data and travel with the launch);
+        asynchronous on `stream`."""
+        a = np.ascontiguousarray(amp, dtype=np.float32).reshape(-1)
+        rc = self._lib.xrt_scatter_add_device(self._ctx, int(width), int(height), int(num_planes), int(bin),
+                                              d_blurred or None, a.size, _fptr(a), d_primary or None, d_out or None,
+                                              d_out_scatter or None, d_out_u8 or None, stream or None)
+        self._check(rc, "xrt_scatter_add_device")
+
+    def scatter(self, paths, open, weights, mu, sigma, kernels, bin, width, height):
+        """The scatter estimate end to end over render_paths' planes of `width` x `height` projections: the source
+        and the L-buffer in one pass, the fork's hole fill of the L-buffer (the primary), one detector_response
+        per scatter kernel -- `kernels` a list of (amp, taps_x, taps_y) on the grid binned by `bin` -- and the
+        sum.  (total, scatter, primary), each of a plane stack's shape."""
+        kernels = list(kernels)
+        if not 1 <= len(kernels) <= _abi.XRT_MAX_SCATTER_KERNELS:
+            raise ValueError(f"1 to {_abi.XRT_MAX_SCATTER_KERNELS} scatter kernels, got {len(kernels)}")
+        src, lb = self.scatter_source(paths, open, weights, mu, sigma, bin)
+        if lb.shape[-2:] != (int(height), int(width)):
+            raise ValueError(f"the planes are {lb.shape[-2:]}, not ({height}, {width})")
+        frames = lb.reshape(-1, int(height), int(width))
+        primary = np.stack([self.hole_fill(f, int(width), int(height))[0].reshape(int(height), int(width))
+                            for f in frames]).reshape(lb.shape)
+        blurred = np.stack([self.detector_response(src, hx, hy, u8=False)[0] for _, hx, hy in kernels])
+        total, sc, _ = self.scatter_add(blurred, [k[0] for k in kernels], bin, lb.shape, primary, u8=False)
+        return total, sc, primary
 
     def log_projection(self, image, flat=None, dark=None, flat_value=None, t_min=0.0, sinograms=False):
         """Line integrals -ln((I - dark) / (flat - dark)) of an (H, W) image or a (P, H, W) stack of projections;

@@ -54,6 +54,8 @@ XRT_DETECT_COUNTS = 0
 XRT_DETECT_INTENSITY = 1
 XRT_MAX_SOURCES = 64
 XRT_MAX_BIN = 8
+XRT_MAX_SCATTER_BIN = 64
+XRT_MAX_SCATTER_KERNELS = 4
 XRT_MAX_RAMP_WIDTH = 4096
 XRT_RAMP_RAMLAK = 0
 XRT_RAMP_HANN = 1
@@ -301,6 +303,13 @@ XRT_SYMBOLS = {
     "xrt_area_integrate_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _u32, _u32, _u32, _fp, _vp, _vp, _vp, _vp]),
     "xrt_host_area_integrate": (ctypes.c_int, [_u32, _u32, _u32, _u32, _u32, _u32, _fp, _fp, _fp,
                                                ctypes.POINTER(ctypes.c_uint8)]),
+    "xrt_scatter_source": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _u32, _fp, _u16p, _fp, _fp, _fp, _u32, _u32, _fp, _fp]),
+    "xrt_scatter_source_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _u32, _vp, _vp, _fp, _fp, _fp, _u32, _u32, _vp,
+                                                 _vp, _vp]),
+    "xrt_scatter_add": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _u32, _fp, _u32, _fp, _fp, _fp, _fp, _u8p]),
+    "xrt_scatter_add_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _u32, _vp, _u32, _fp, _vp, _vp, _vp, _vp, _vp]),
+    "xrt_host_scatter_source": (ctypes.c_int, [_u32, _u32, _u32, _u32, _fp, _u16p, _fp, _fp, _fp, _u32, _u32, _fp, _fp]),
+    "xrt_host_scatter_add": (ctypes.c_int, [_u32, _u32, _u32, _u32, _fp, _u32, _fp, _fp, _fp, _fp, _u8p]),
     "xrt_camera_supersample": (ctypes.c_int, [ctypes.POINTER(Camera), _u32, ctypes.POINTER(Camera)]),
     "xrt_focal_spot": (ctypes.c_int, [ctypes.POINTER(Camera), ctypes.c_float, ctypes.c_float, _u32, _u32,
                                       ctypes.POINTER(Camera), _fp]),

@@ -510,6 +510,51 @@ void applySpectralDetector(std::vector<Image>& channels, const std::vector<std::
         check(ctx, xrt_hole_fill(ctx, width, height, out.data() + c * n, channels[c].getData(), nullptr), "xrt_hole_fill");
 }
 
+void applyScatter(Image& image, Image& scatter, const std::vector<std::vector<float>>& paths,
+                  const std::vector<unsigned short>& open, const std::vector<float>& weight, const std::vector<float>& mu,
+                  const ScatterModel& model, std::vector<float>* lbuffer)
+{
+    const unsigned width = image.getWidth(), height = image.getHeight();
+    const size_t n = (size_t)width * height;
+    if (scatter.getWidth() != width || scatter.getHeight() != height)
+        throw std::invalid_argument("applyScatter: the scatter image is not of the image's size");
+    if (weight.empty() || paths.empty() || mu.size() != paths.size() * weight.size())
+        throw std::invalid_argument("applyScatter: one coefficient per mesh and bin");
+    if (model.sigma.size() != mu.size()) throw std::invalid_argument("applyScatter: one sigma per mesh and bin");
+    if (model.kernels.empty() || model.kernels.size() > XRT_MAX_SCATTER_KERNELS)
+        throw std::invalid_argument("applyScatter: 1 to XRT_MAX_SCATTER_KERNELS kernels");
+    if (model.bin == 0) throw std::invalid_argument("applyScatter: bin is 0");
+    if (open.size() != n) throw std::invalid_argument("applyScatter: the mask is not of the image's size");
+    std::vector<float> planes;
+    planes.reserve(n * paths.size());
+    for (const std::vector<float>& plane : paths) {
+        if (plane.size() != n) throw std::invalid_argument("applyScatter: a plane is not of the image's size");
+        planes.insert(planes.end(), plane.begin(), plane.end());
+    }
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    const unsigned wc = (width + model.bin - 1u) / model.bin, hc = (height + model.bin - 1u) / model.bin;
+    const size_t nc = (size_t)wc * hc, G = model.kernels.size();
+    std::vector<float> local, source(nc), blurred(nc * G), primary(n), amp(G);
+    std::vector<float>& lb = lbuffer ? *lbuffer : local;
+    lb.resize(n);
+    check(ctx, xrt_scatter_source(ctx, width, height, 1, (uint32_t)paths.size(), planes.data(), open.data(), weight.data(),
+                                  mu.data(), model.sigma.data(), (uint32_t)weight.size(), model.bin, lb.data(), source.data()),
+          "xrt_scatter_source");
+    check(ctx, xrt_hole_fill(ctx, width, height, lb.data(), primary.data(), nullptr), "xrt_hole_fill");
+    for (size_t k = 0; k < G; ++k) {
+        const ScatterKernel& kernel = model.kernels[k];
+        amp[k] = kernel.amp;
+        check(ctx, xrt_detector_response(ctx, wc, hc, 1, source.data(), kernel.taps_x.data(), (uint32_t)kernel.taps_x.size(),
+                                         kernel.taps_y.data(), (uint32_t)kernel.taps_y.size(), blurred.data() + k * nc, nullptr),
+              "xrt_detector_response");
+    }
+    check(ctx, xrt_scatter_add(ctx, width, height, 1, model.bin, blurred.data(), (uint32_t)G, amp.data(), primary.data(),
+                               image.getData(), scatter.getData(), nullptr),
+          "xrt_scatter_add");
+}
+
 unsigned long long decomposeMaterials(std::vector<Image>& basis, const std::vector<Image>& channels,
                                       const std::vector<float>& weight, const std::vector<float>& mu,
                                       const std::vector<float>& response, float gain, unsigned max_iter, double tol,

@@ -155,6 +155,31 @@ void applySpectralDetector(std::vector<Image>& channels, const std::vector<std::
                            float read_noise = 0.0f, unsigned long long seed = 0, unsigned long long first_index = 0,
                            bool noisy = false);
 
+// The scatter model (xrt_scatter_source, xrt_detector_response, xrt_scatter_add;
+// DESIGN 10.16): `bin`, the power of two in 1..XRT_MAX_SCATTER_BIN the source is
+// binned by; `sigma`, the part of each coefficient that scatters, in mu's
+// layout (one row of weight.size() values per plane, one after another); and 1
+// to XRT_MAX_SCATTER_KERNELS kernels, each an amplitude and its taps along x
+// and y on the binned grid (odd counts, at most XRT_MAX_LSF_TAPS).
+// applyScatter is applySpectrum with the estimate added: from such planes the
+// source and the L-buffer in one pass, the hole fill of the L-buffer (the
+// primary), one blur of the coarse source per kernel, and their weighted sum,
+// interpolated back, added to the primary.  output_image receives the total,
+// scatter_image -- of the same size -- the scatter alone; lbuffer as
+// applySpectrum's.  One device.
+struct ScatterKernel {
+    float amp = 0.0f;
+    std::vector<float> taps_x, taps_y;
+};
+struct ScatterModel {
+    unsigned bin = 1;
+    std::vector<float> sigma;
+    std::vector<ScatterKernel> kernels;
+};
+void applyScatter(Image& output_image, Image& scatter_image, const std::vector<std::vector<float>>& paths,
+                  const std::vector<unsigned short>& open, const std::vector<float>& weight, const std::vector<float>& mu,
+                  const ScatterModel& model, std::vector<float>* lbuffer = nullptr);
+
 // Material decomposition (xrt_decompose), the inverse of
 // applySpectralDetector without noise: from the channel images (as
 // intensities, the detector's output, unless `counts`) the line integrals of

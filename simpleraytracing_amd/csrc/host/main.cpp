@@ -136,6 +136,20 @@
 //                              p of --turntable draws the noise of pixels p*W*H onwards.
 //                              Not with --lsf, --lsf-gaussian, --log-projection,
 //                              --sinogram, --supersample, --focal-spot, -g, --rows, --batch
+//       --scatter FILE         the scatter model, with --paths --spectrum FILE2: a kernel-
+//                              superposition estimate of scattered radiation added to
+//                              the image.  FILE is text ('#' starts a comment): a line
+//                              with the binning factor D (a power of two, 1 to 64), one
+//                              line of K coefficients (finite, >= 0) per mesh -- the part
+//                              of --spectrum's coefficient that scatters --, then one to
+//                              four lines AMP SIGMA_PIXELS[:TAPS], a Gaussian scatter
+//                              kernel each (TAPS on the binned grid, odd, default
+//                              2*ceil(4*SIGMA/D)+1, at most 129).  Runs after the hole
+//                              fill and before --lsf, --noise and --log-projection, per
+//                              projection of --turntable (and so under --reconstruct).
+//                              NAME.EXT and --u8 receive the total, NAME.scatter.EXT the
+//                              scatter alone.  Not with --detector, --supersample,
+//                              --focal-spot, --volume, -g, --rows, --batch
 //       --read-noise SIGMA     with --detector and --noise: additive Gaussian (electronic)
 //                              noise of SIGMA counts (finite, >= 0) on every channel
 //       --decompose BASIS[:ITER[:TOL]]  with --detector: material decomposition of the
@@ -221,6 +235,7 @@ void showUsage(const std::string& prog)
               << "\t--supersample B\t\t\tPixel-area integration: render W*B x H*B samples (B in 1..8) and write each pixel's mean over its B x B samples; -s stays the written size\n"
               << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
               << "\t--detector FILE\t\t\tSpectral detector, with --paths --spectrum: FILE holds one line of K responses per energy channel (at most 8); writes NAME.c<c>.EXT per channel; with --noise GAIN[:SEED] a Poisson count per bin, divided by GAIN, otherwise the expected values at gain 1\n"
+              << "\t--scatter FILE\t\t\tScatter estimate, with --paths --spectrum: FILE holds the binning factor D (a power of two, 1 to 64), one line of K scattering coefficients per mesh, then 1 to 4 lines AMP SIGMA_PIXELS[:TAPS] (Gaussian kernels); NAME.EXT receives primary + scatter, NAME.scatter.EXT the scatter; before --lsf, --noise and --log-projection, per --turntable projection\n"
               << "\t--read-noise SIGMA\t\tWith --detector and --noise: additive Gaussian noise of SIGMA counts on every channel\n"
               << "\t--decompose BASIS[:ITER[:TOL]]\tWith --detector: material decomposition of the written channels; BASIS holds one line of K coefficients per basis material (1 to 3); at most ITER iterations a pixel (1 to 200, default 32), until no line integral moves by more than TOL (default 1e-6); writes NAME.b<b>.EXT per basis material and prints the unconverged count\n"
               << "\t--volume FILE.mhd\t\tWith --paths: a voxel phantom (MetaImage header, MET_UCHAR labels, raw file beside it) beside the meshes or alone (no -i); one plane per label behind the meshes' (NAME.m<k>.EXT), one --spectrum row per mesh, then per label; not with -g, --rows, --batch, --supersample, --focal-spot, --turntable, --pose\n"
@@ -274,6 +289,10 @@ struct Options {
     bool focal_spot = false;                   // --focal-spot UxV[:NUxNV]
     float spot_u = 0.0f, spot_v = 0.0f;
     unsigned spot_nu = 3, spot_nv = 3;
+    bool scatter = false;                      // --scatter FILE: D, a row of K coefficients per mesh, the kernels
+    std::vector<std::vector<std::string>> scatter_lines;   // its data lines' fields, read once the table's size is known
+    std::string scatter_file;
+    ScatterModel scatter_model;
     bool detector = false;                     // --detector FILE: one row of K responses per channel
     std::vector<std::vector<float>> detector_rows;
     bool read_noise_set = false;               // --read-noise SIGMA
@@ -453,6 +472,83 @@ void read_rows(const std::string& option, const std::string& path, const char* v
         rows.push_back(values);
     }
     if (rows.empty()) throw std::runtime_error(option + ": " + path + " holds no " + row);
+}
+
+void check_taps(const std::string& option, const std::string& where, size_t n);
+
+// --scatter FILE: the data lines' fields ('#' starts a comment, blank lines are
+// skipped); scatter_model reads them once --spectrum's table is known.
+void read_scatter(const std::string& path, std::vector<std::vector<std::string>>& lines)
+{
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("--scatter: cannot read " + path);
+    lines.clear();
+    for (std::string line; std::getline(in, line);) {
+        std::istringstream fields(line.substr(0, line.find('#')));
+        std::vector<std::string> row;
+        for (std::string f; fields >> f;) row.push_back(f);
+        if (!row.empty()) lines.push_back(row);
+    }
+    if (lines.empty()) throw std::runtime_error("--scatter: " + path + " holds no binning factor");
+}
+
+// A finite number >= 0 of --scatter's file.
+float scatter_value(const std::string& path, const std::string& f, const char* what)
+{
+    size_t used = 0;
+    float v = 0.0f;
+    try {
+        v = std::stof(f, &used);
+    } catch (const std::exception&) {
+        used = 0;
+    }
+    if (f.empty() || used != f.size() || !std::isfinite(v) || v < 0.0f)
+        throw std::runtime_error("--scatter: " + path + ": '" + f + "' is not " + what + " (a finite number, >= 0)");
+    return v;
+}
+
+// --scatter's model from its file's lines under a table of K bins: D, then a
+// row of K coefficients per mesh (as many as --spectrum's file holds), then 1
+// to XRT_MAX_SCATTER_KERNELS lines AMP SIGMA_PIXELS[:TAPS].
+void scatter_model(const std::string& path, const std::vector<std::vector<std::string>>& lines, size_t num_meshes, size_t K,
+                   ScatterModel& model)
+{
+    unsigned D = 0;
+    if (lines[0].size() != 1 || !parse_index(lines[0][0], D) || D == 0 || D > XRT_MAX_SCATTER_BIN || (D & (D - 1u)) != 0)
+        throw std::runtime_error("--scatter: " + path + ": the first line is the binning factor, a power of two in 1.." +
+                                 std::to_string(XRT_MAX_SCATTER_BIN));
+    if (lines.size() < 1 + num_meshes + 1 || lines.size() > 1 + num_meshes + XRT_MAX_SCATTER_KERNELS)
+        throw std::runtime_error("--scatter: " + path + " holds " + std::to_string(lines.size() - 1) + " lines after the binning factor; " +
+                                 std::to_string(num_meshes) + " rows of coefficients (--spectrum's meshes) and 1 to " +
+                                 std::to_string(XRT_MAX_SCATTER_KERNELS) + " kernels are expected");
+    model = ScatterModel();
+    model.bin = D;
+    for (size_t m = 0; m < num_meshes; ++m) {
+        const std::vector<std::string>& row = lines[1 + m];
+        if (row.size() != K)
+            throw std::runtime_error("--scatter: " + path + ": " + std::to_string(row.size()) + " coefficients in a line, " +
+                                     std::to_string(K) + " bins in --spectrum's table");
+        for (const std::string& f : row) model.sigma.push_back(scatter_value(path, f, "a coefficient"));
+    }
+    for (size_t k = 1 + num_meshes; k < lines.size(); ++k) {
+        const std::vector<std::string>& row = lines[k];
+        if (row.size() != 2) throw std::runtime_error("--scatter: " + path + ": a kernel line is AMP SIGMA_PIXELS[:TAPS]");
+        ScatterKernel kernel;
+        kernel.amp = scatter_value(path, row[0], "an amplitude");
+        const std::vector<std::string> parts = split(row[1], ':');
+        if (parts.empty() || parts.size() > 2) throw std::runtime_error("--scatter: " + path + ": a kernel line is AMP SIGMA_PIXELS[:TAPS]");
+        const double sigma = (double)scatter_value(path, parts[0], "a kernel's sigma") / (double)D;
+        if (!(sigma > 0.0)) throw std::runtime_error("--scatter: " + path + ": a kernel's SIGMA_PIXELS is above 0");
+        unsigned taps = 2u * (unsigned)std::min(std::ceil(4.0 * sigma), 1e6) + 1u;
+        if (parts.size() == 2 && !parse_index(parts[1], taps))
+            throw std::runtime_error("--scatter: " + path + ": '" + parts[1] + "' is not a tap count");
+        check_taps("--scatter", path + ": sigma " + parts[0] + " at D = " + std::to_string(D) + " takes ", taps);
+        kernel.taps_x.resize(taps);
+        if (xrt_lsf_gaussian(sigma, taps, kernel.taps_x.data()) != XRT_OK)
+            throw std::runtime_error("--scatter: " + path + ": '" + row[1] + "' is not a kernel");
+        kernel.taps_y = kernel.taps_x;
+        model.kernels.push_back(kernel);
+    }
 }
 
 // --detector FILE: one line of K responses per channel.
@@ -758,6 +854,10 @@ Options processCmd(int argc, char** argv)
                 throw std::runtime_error("--supersample B: '" + b + "' is not a factor in 1.." + std::to_string(XRT_MAX_BIN));
         } else if (a == "--focal-spot") {
             parse_focal_spot(parse_str(argv[0], argc, argv, i), o);
+        } else if (a == "--scatter") {
+            o.scatter = true;
+            o.scatter_file = parse_str(argv[0], argc, argv, i);
+            read_scatter(o.scatter_file, o.scatter_lines);
         } else if (a == "--detector") {
             o.detector = true;
             o.detector_rows.clear();
@@ -796,6 +896,14 @@ Options processCmd(int argc, char** argv)
         }
     }
     if (o.inputs.empty() && o.volume.empty()) o.inputs.push_back("./dragon.ply");
+    if (o.scatter) {
+        if (!o.paths || !o.spectrum) throw std::runtime_error("--scatter needs --paths --spectrum FILE: it reads the planes under the table");
+        const char* with = o.detector ? "--detector" : o.supersample ? "--supersample" : o.focal_spot ? "--focal-spot"
+                           : !o.volume.empty() ? "--volume" : o.gpus > 1 ? "-g" : o.rows ? "--rows" : o.batch ? "--batch" : nullptr;
+        if (with) throw std::runtime_error(std::string("--scatter adds its estimate to whole frames of the meshes' planes on one GPU: not with ") + with);
+        scatter_model(o.scatter_file, o.scatter_lines, o.spectrum_mu.size() / o.spectrum_weight.size(), o.spectrum_weight.size(),
+                      o.scatter_model);
+    }
     if (!o.volume_density.empty() && o.volume.empty())
         throw std::runtime_error("--volume-density needs --volume FILE.mhd: it is the density of that volume's voxels");
     if (!o.volume.empty()) {
@@ -837,7 +945,7 @@ Options processCmd(int argc, char** argv)
     }
     if (o.read_noise_set && (!o.detector || !o.noise))
         throw std::runtime_error("--read-noise needs --detector FILE and --noise GAIN[:SEED]: it is added to the drawn channels");
-    if (o.turntable && ((o.paths && !o.detector) || o.batch || o.gpus > 1))
+    if (o.turntable && ((o.paths && !o.detector && !o.scatter) || o.batch || o.gpus > 1))
         throw std::runtime_error("--turntable renders on one GPU, without --paths, --batch and -g");
     if (o.lsf_file && o.lsf_gauss) throw std::runtime_error("--lsf and --lsf-gaussian are two detector responses: give one");
     if (!o.lsf_x.empty() && (o.gpus > 1 || o.rows))
@@ -1076,6 +1184,10 @@ int main(int argc, char** argv)
                 for (unsigned long long k = 0; k < st.odd_rays; ++k) std::cout << "Only one intersect on this ray" << std::endl;
             } else if (opt.paths) {
                 const bool with_volume = !opt.volume.empty();
+                if (opt.scatter && opt.scatter_model.sigma.size() / opt.spectrum_weight.size() != meshes.size())
+                    throw std::runtime_error("--scatter takes one row of coefficients per mesh, as --spectrum does: " +
+                                             std::to_string(meshes.size()) + " meshes loaded, " +
+                                             std::to_string(opt.scatter_model.sigma.size() / opt.spectrum_weight.size()) + " rows");
                 if (!with_volume && opt.spectrum && opt.spectrum_mu.size() / opt.spectrum_weight.size() != meshes.size())
                     throw std::runtime_error("--spectrum takes one row of coefficients per mesh: " + std::to_string(meshes.size()) +
                                              " meshes loaded, " +
@@ -1103,7 +1215,12 @@ int main(int argc, char** argv)
                 }
                 std::copy(open.begin(), open.end(), plane.getData());
                 plane.saveTextFile(stem + ".open" + suffix);
-                if (opt.spectrum)                     // (without a table the planes are the output)
+                if (opt.scatter) {                    // the primary and the estimate in one pass; the image is their sum
+                    Image scattered(opt.width, opt.height, 0.0f);
+                    applyScatter(image, scattered, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.scatter_model,
+                                 opt.lbuffer.empty() ? nullptr : &lb);
+                    scattered.saveTextFile(stem + ".scatter" + suffix);
+                } else if (opt.spectrum)              // (without a table the planes are the output)
                     applySpectrum(image, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.lbuffer.empty() ? nullptr : &lb);
                 if (opt.detector) {                   // the channels beside the image; a scan's projection draws its own
                     std::vector<float> response;

@@ -2145,4 +2145,116 @@ __host__ __device__ __forceinline__ uint64_t voxel_index(const VoxelGrid& g, uin
     return ((uint64_t)k * g.ny + j) * g.nx + i;
 }
 
+// ---------------------------------------------------------------------------
+// The scatter model: a kernel-superposition estimate from the
+// paths model's planes.  The tables travel by value in the kernels' arguments:
+// the spectrum's weights and coefficients as SpectrumTable holds them and,
+// in the same layout, the part of each coefficient that scatters.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMaxScatterBin = 64;
+constexpr uint32_t kMaxScatterKernels = 4;
+struct ScatterTable {
+    float weight[kMaxBins];
+    uint32_t num_bins;
+    float miss;                           // spectrum_miss of the weights: the L-buffer of a pixel that hits nothing
+    float mu[kMaxBins * kMaxMeshes];      // [e * kMaxMeshes + m], 0 past the meshes: a bin's row is one scalar load
+    float sigma[kMaxBins * kMaxMeshes];   // [e * kMaxMeshes + m]
+};
+struct ScatterAmps {
+    float amp[kMaxScatterKernels];
+    uint32_t num;
+};
+
+// One pixel's primary E and scatter source Q from its n per-mesh lengths
+// dist(j) = (double)path * 0.1, in f64, left to right, every operation rounded
+// on its own (no contraction):
+//   E = 0; Q = 0
+//   for each bin e: xe = 0; se = 0
+//       for each mesh j: xe = xe + mu(j, e) * dist(j); se = se + sigma(j, e) * dist(j)
+//       t = weight(e) * exp(-xe); E = E + t; Q = Q + t * se
+// E's chain is spectrum_lbuffer's, so scatter_lbuffer(E) is its L bit for bit.
+// A mesh with dist = +0.0 may be left out or listed under any finite row: it
+// adds +0.0 to sums that are never -0.0.
+template <typename Dist, typename Mu, typename Sigma, typename Weight>
+__host__ __device__ __forceinline__ void scatter_pixel(uint32_t n, uint32_t num_bins, Dist dist, Mu mu, Sigma sigma,
+                                                       Weight weight, double& E, double& Q)
+{
+    E = 0.0;
+    Q = 0.0;
+#pragma unroll 1
+    for (uint32_t e = 0; e < num_bins; ++e) {       // (one bin's coefficients in scalar registers at a time)
+        double xe = 0.0, se = 0.0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const double d = dist(j);
+            xe = xe + (double)mu(j, e) * d;
+            se = se + (double)sigma(j, e) * d;
+        }
+        const double t = (double)weight(e) * xrt_exp(-xe);
+        E = E + t;
+        Q = Q + t * se;
+    }
+}
+
+// The L-buffer value of scatter_pixel's E: spectrum_lbuffer's rounding and its
+// explicit NaN.
+__host__ __device__ __forceinline__ float scatter_lbuffer(double E)
+{
+    const float f = (float)E;
+    return f != f ? xrt_f32_from_bits(kX86SignedNaN) : f;
+}
+
+// Where fine pixel x of a detector binned by 2^bin_log2 falls on the coarse
+// axis of nc samples: u = (x + 0.5) / D - 0.5 clamped to [0, nc - 1], its two
+// neighbours and the weight of the second.  (x + 0.5) * (1 / D) is the
+// quotient exactly: D is a power of two.
+struct ScatterAxis {
+    uint32_t i0, i1;
+    double f;
+};
+__host__ __device__ __forceinline__ ScatterAxis scatter_axis(uint32_t x, uint32_t bin_log2, uint32_t nc)
+{
+    const double inv = 1.0 / (double)(1u << bin_log2);
+    double u = ((double)x + 0.5) * inv - 0.5;
+    const double hi = (double)(nc - 1u);
+    u = u < 0.0 ? 0.0 : u;
+    u = u > hi ? hi : u;
+    const double u0 = __builtin_floor(u);
+    ScatterAxis a;
+    a.i0 = (uint32_t)u0;
+    a.i1 = a.i0 + 1u < nc ? a.i0 + 1u : nc - 1u;
+    a.f = u - u0;
+    return a;
+}
+
+// One fine pixel's scatter S from the G blurred coarse planes, coarse(g, y, x)
+// their f32 values: per plane the bilinear sample in the c + f * (c' - c) form
+// (a constant plane comes back exactly; f == 0 selects c whatever c' holds),
+// times the plane's amplitude, summed from 0.0 in plane order.  f64, nothing
+// fused.
+template <typename Coarse, typename Amp>
+__host__ __device__ __forceinline__ double scatter_sample(const ScatterAxis& ax, const ScatterAxis& ay, uint32_t num_kernels,
+                                                          Amp amp, Coarse coarse)
+{
+    double S = 0.0;
+    for (uint32_t g = 0; g < num_kernels; ++g) {
+        const double c00 = (double)coarse(g, ay.i0, ax.i0), c01 = (double)coarse(g, ay.i0, ax.i1);
+        const double c10 = (double)coarse(g, ay.i1, ax.i0), c11 = (double)coarse(g, ay.i1, ax.i1);
+        const double a = ax.f == 0.0 ? c00 : c00 + ax.f * (c01 - c00);
+        const double b = ax.f == 0.0 ? c10 : c10 + ax.f * (c11 - c10);
+        const double v = ay.f == 0.0 ? a : a + ay.f * (b - a);
+        S = S + (double)amp(g) * v;
+    }
+    return S;
+}
+
+// The fine tile a workgroup of k_scatter_source owns: 64 columns by
+// max(D, 4) rows, whole blocks for every allowed D.
+constexpr uint32_t kScatterTile = 64;
+constexpr uint32_t kScatterThreads = 256;
+constexpr uint32_t kScatterBatchRows = kScatterThreads / kScatterTile;
+__host__ __device__ __forceinline__ uint32_t scatter_tile_rows(uint32_t bin_log2)
+{
+    return (1u << bin_log2) > kScatterBatchRows ? (1u << bin_log2) : kScatterBatchRows;
+}
+
 }  // namespace XRT_KERNEL_NS

@@ -5065,4 +5065,162 @@ __global__ __launch_bounds__(kVoxelThreads) void k_voxel_scan(const VoxelGrid g,
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_scatter_source: the scatter model's source.  A workgroup
+// owns a tile of 64 columns by max(D, 4) rows of plane blockIdx.z and walks it
+// in batches of 4 rows, a wave a row, a lane a pixel (coalesced loads of the
+// kN >= M planes, kN a compile-time bound: the lane's lengths sit in registers
+// with static indices; the tables arrive in the argument segment and their
+// coefficients are widened into LDS once, the weights stay scalar loads):
+//   1. scatter_pixel; the L-buffer value goes out, q to the wave's LDS row --
+//      at column x + x / D, so that stage 2's lanes, D columns apart, meet
+//      distinct banks;
+//   2. one lane per (row, block) adds the row's D values in column order;
+//   3. one lane of wave 0 per block column adds the batch's row sums in row
+//      order into its register, and stores the mean at the block's last row.
+// The order of both sums is the contract's.  Lanes and rows past the detector
+// compute nothing and are never summed.  LDS only; no scratch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kScatterPitch = 2u * kScatterTile + 8u;      // doubles a row: x + x / D <= 126, rows 8 banks apart
+
+template <uint32_t kN>
+__global__ __launch_bounds__(kScatterThreads) void k_scatter_source(const float* __restrict__ paths,
+                                                                   const uint16_t* __restrict__ open, uint32_t W, uint32_t H,
+                                                                   uint32_t M, uint32_t bin_log2, const ScatterTable tab,
+                                                                   float* __restrict__ lbuffer, float* __restrict__ source)
+{
+    __shared__ double s_q[kScatterBatchRows][kScatterPitch];
+    __shared__ double s_r[kScatterBatchRows][kScatterTile];
+    __shared__ double s_mu[kMaxBins * kMaxMeshes], s_sigma[kMaxBins * kMaxMeshes];
+    const uint32_t lane = threadIdx.x & 63u, wave = wave_in_block();
+    const uint32_t D = 1u << bin_log2, th = scatter_tile_rows(bin_log2);
+    const uint32_t x0 = blockIdx.x * kScatterTile, y0 = blockIdx.y * th;
+    const uint32_t y_end = min(y0 + th, H);
+    const size_t N = (size_t)gridDim.z * H * W;
+    const uint32_t K = tab.num_bins;
+    const uint32_t x = x0 + lane;
+    // (per-lane offsets, the plane's folded in: few scalars live across xrt_exp's bins)
+    const size_t lane_at = (size_t)blockIdx.z * H * W + x;
+    // stage 2's lane: row t2_r of the batch, block column t2_b of the tile
+    const uint32_t blocks = kScatterTile >> bin_log2;              // block columns a tile
+    const bool t2 = threadIdx.x < kScatterBatchRows * blocks;
+    const uint32_t t2_r = threadIdx.x >> (6u - bin_log2), t2_b = threadIdx.x & (blocks - 1u);
+    const uint32_t t2_x = x0 + (t2_b << bin_log2);
+    const uint32_t t2_cols = t2 && t2_x < W ? min(D, W - t2_x) : 0u;
+    // stage 3's lane: block column threadIdx.x of the tile
+    const uint32_t t3_x = x0 + (threadIdx.x << bin_log2);
+    const bool t3 = threadIdx.x < blocks && t3_x < W;
+    const uint32_t t3_cols = t3 ? min(D, W - t3_x) : 0u;
+    const uint32_t Wc = (W + D - 1u) >> bin_log2;
+    float* const t3_out = source + (size_t)blockIdx.z * ((H + D - 1u) >> bin_log2) * Wc + (t3_x >> bin_log2);
+    double acc = -0.0;
+    // the coefficients, widened once, where every lane reads them at one address (a broadcast): as scalars a bin's
+    // 2 x kN values and xrt_exp's constants do not fit the scalar registers
+    for (uint32_t k = threadIdx.x; k < K * kMaxMeshes; k += kScatterThreads) {
+        s_mu[k] = (double)tab.mu[k];
+        s_sigma[k] = (double)tab.sigma[k];
+    }
+    __syncthreads();
+
+    for (uint32_t yb = y0; yb < y_end; yb += kScatterBatchRows) {                  // workgroup-uniform
+        const uint32_t y = yb + wave;
+        const bool in = x < W && y < H;
+        double q = 0.0;
+        if (in) {
+            const size_t i = lane_at + (size_t)y * W;
+            const float* at = paths + i;                  // (a per-lane pointer stepped by N: no scalar base a plane)
+            double d[kN];
+            bool hit = false;
+            uint32_t m_here = M;                          // opaque: the kN comparisons are formed here, batch by
+            asm volatile("" : "+s"(m_here));              // batch, not kept in scalar registers across the loop
+#pragma unroll
+            for (uint32_t j = 0; j < kN; ++j) {
+                d[j] = 0.0;
+                if (j < m_here) {                         // wave-uniform
+                    const float v = *at;
+                    hit |= __float_as_uint(v) != 0u;
+                    d[j] = (double)v * 0.1;
+                }
+                at += N;
+            }
+            // a wave whose every pixel on the detector has +0.0 in every plane (k_apply_spectrum's miss): each
+            // exp(-0.0) is 1 and each se is +0.0, so E is the weights' chain -- tab.miss as f32 -- and Q is +0.0
+            float l = tab.miss;
+            double Q = 0.0;
+            if (__ballot(hit)) {
+                double E;
+                scatter_pixel(
+                    kN, K, [&](uint32_t j) { return d[j]; },
+                    [&](uint32_t j, uint32_t e) { return s_mu[e * kMaxMeshes + j]; },     // (0 past the meshes)
+                    [&](uint32_t j, uint32_t e) { return s_sigma[e * kMaxMeshes + j]; },
+                    [&](uint32_t e) { return tab.weight[e]; }, E, Q);
+                l = scatter_lbuffer(E);
+            }
+            const bool flagged = open && open[i] != 0;
+            if (lbuffer) lbuffer[i] = flagged ? -1.0f : l;
+            q = flagged ? 0.0 : Q;
+        }
+        s_q[wave][lane + (lane >> bin_log2)] = q;
+        __syncthreads();
+        if (t2) {
+            const uint32_t at = (t2_b << bin_log2) + t2_b;
+            double r = -0.0;
+            for (uint32_t j = 0; j < t2_cols; ++j) r = r + s_q[t2_r][at + j];
+            s_r[t2_r][t2_b] = r;
+        }
+        __syncthreads();
+        if (t3) {
+#pragma unroll
+            for (uint32_t r = 0; r < kScatterBatchRows; ++r) {
+                const uint32_t yr = yb + r;
+                if (yr < H) {
+                    const uint32_t in_block = yr & (D - 1u);
+                    if (in_block == 0u) acc = -0.0;
+                    acc = acc + s_r[r][threadIdx.x];
+                    if (in_block == D - 1u || yr == H - 1u) {
+                        t3_out[(size_t)(yr >> bin_log2) * Wc] = (float)(acc / (double)((in_block + 1u) * t3_cols));
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_scatter_add: the scatter model's last step.  A workgroup
+// owns a 64 x 64 fine tile of plane blockIdx.z, a lane a column: its place on
+// the coarse x axis is formed once, each row's on the y axis per wave, and
+// scatter_sample reads the G blurred planes' four neighbours (cache hits: D^2
+// fine pixels share them).  One read of the primary and up to three stores a
+// pixel: bandwidth-shaped.  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kScatterThreads) void k_scatter_add(const float* __restrict__ blurred,
+                                                                const float* __restrict__ primary, uint32_t W, uint32_t H,
+                                                                uint32_t bin_log2, const ScatterAmps amps,
+                                                                float* __restrict__ outp, float* __restrict__ out_scatter,
+                                                                uint8_t* __restrict__ out_u8)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = wave_in_block();
+    const uint32_t D = 1u << bin_log2;
+    const uint32_t Wc = (W + D - 1u) >> bin_log2, Hc = (H + D - 1u) >> bin_log2;
+    const uint32_t x = blockIdx.x * kScatterTile + lane, p = blockIdx.z, P = gridDim.z;
+    if (x >= W) return;
+    const ScatterAxis ax = scatter_axis(x, bin_log2, Wc);
+    const size_t coarse_plane = (size_t)Hc * Wc;
+    const uint32_t y_end = min(H, (blockIdx.y + 1u) * kScatterTile);
+    for (uint32_t y = blockIdx.y * kScatterTile + wave; y < y_end; y += kScatterBatchRows) {
+        const ScatterAxis ay = scatter_axis(y, bin_log2, Hc);
+        const double S = scatter_sample(
+            ax, ay, amps.num, [&](uint32_t g) { return amps.amp[g]; },
+            [&](uint32_t g, uint32_t yi, uint32_t xi) {
+                return blurred[((size_t)g * P + p) * coarse_plane + (size_t)yi * Wc + xi];
+            });
+        const size_t i = ((size_t)p * H + y) * W + x;
+        const float total = primary ? (float)((double)primary[i] + S) : (float)S;
+        if (out_scatter) out_scatter[i] = (float)S;
+        if (outp) outp[i] = total;
+        if (out_u8) out_u8[i] = lut_u8(total);
+    }
+}
+
 }  // namespace XRT_KERNEL_NS

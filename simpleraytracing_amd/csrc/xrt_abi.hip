@@ -3739,6 +3739,132 @@ int xrt_area_integrate(xrt_context* ctx, uint32_t width, uint32_t height, uint32
     return s.finish();
 }
 
+// --- the scatter model ------------------------------------------
+
+#include "xrt_scatter_host.inc"
+
+// The launch of k_scatter_source (validated arguments, device pointers): the instantiation of the smallest mesh
+// bound that holds num_meshes.
+static int launch_scatter_source(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t num_meshes,
+                                 const float* d_paths, const uint16_t* d_open, const float* weight, const float* mu,
+                                 const float* sigma, uint32_t num_bins, uint32_t bin, float* d_lbuffer, float* d_source,
+                                 hipStream_t stream)
+{
+    ScatterTable tab = {};              // by value: the launch owns its copy (no context state, no wait)
+    std::copy(weight, weight + num_bins, tab.weight);
+    for (uint32_t m = 0; m < num_meshes; ++m)
+        for (uint32_t e = 0; e < num_bins; ++e) {
+            tab.mu[e * kMaxMeshes + m] = mu[m * num_bins + e];
+            tab.sigma[e * kMaxMeshes + m] = sigma[m * num_bins + e];
+        }
+    tab.num_bins = num_bins;
+    tab.miss = spectrum_miss(tab.weight, num_bins);
+    const uint32_t lg = (uint32_t)scatter_bin_log2(bin), th = scatter_tile_rows(lg);
+    auto kernel = k_scatter_source<kMaxMeshes>;
+    if (num_meshes <= 2u) kernel = k_scatter_source<2>;
+    else if (num_meshes <= 4u) kernel = k_scatter_source<4>;
+    else if (num_meshes <= 8u) kernel = k_scatter_source<8>;
+    const dim3 grid((width + kScatterTile - 1u) / kScatterTile, (height + th - 1u) / th, num_planes);
+    hipLaunchKernelGGL(kernel, grid, dim3(kScatterThreads), 0, stream, d_paths, d_open, width, height, num_meshes, lg, tab,
+                       d_lbuffer, d_source);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_scatter_source_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t num_meshes,
+                              const float* d_paths, const uint16_t* d_open, const float* weight, const float* mu,
+                              const float* sigma, uint32_t num_bins, uint32_t bin, float* d_lbuffer, float* d_source,
+                              void* stream)
+{
+    if (const char* why = scatter_source_arguments(width, height, num_planes, num_meshes, d_paths, d_open, weight, mu, sigma,
+                                                   num_bins, bin, d_lbuffer, d_source))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_scatter_source(ctx, width, height, num_planes, num_meshes, d_paths, d_open, weight, mu, sigma, num_bins,
+                                 bin, d_lbuffer, d_source, (hipStream_t)stream);
+}
+
+int xrt_scatter_source(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t num_meshes,
+                       const float* paths, const uint16_t* open, const float* weight, const float* mu, const float* sigma,
+                       uint32_t num_bins, uint32_t bin, float* lbuffer, float* source)
+{
+    if (const char* why = scatter_source_arguments(width, height, num_planes, num_meshes, paths, open, weight, mu, sigma,
+                                                   num_bins, bin, lbuffer, source))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)width * height * num_planes;
+    const size_t nc = (size_t)((width + bin - 1u) / bin) * ((height + bin - 1u) / bin) * num_planes;
+    DeviceScratch s(ctx, ctx->host_stream, "scatter source");
+    const float* dp = s.upload(paths, n * num_meshes);
+    const uint16_t* dopen = s.upload(open, n);
+    float* dl = s.alloc<float>(n, lbuffer != nullptr);
+    float* ds = s.alloc<float>(nc);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_scatter_source(ctx, width, height, num_planes, num_meshes, dp, dopen, weight, mu, sigma, num_bins, bin,
+                                       dl, ds, ctx->host_stream))
+        return rc;
+    s.download(lbuffer, (const float*)dl, n);
+    s.download(source, (const float*)ds, nc);
+    return s.finish();
+}
+
+// The launch of k_scatter_add (validated arguments, device pointers).
+static int launch_scatter_add(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t bin,
+                              const float* d_blurred, uint32_t num_kernels, const float* amp, const float* d_primary,
+                              float* d_out, float* d_out_scatter, uint8_t* d_out_u8, hipStream_t stream)
+{
+    ScatterAmps amps = {};              // by value, as the tables
+    std::copy(amp, amp + num_kernels, amps.amp);
+    amps.num = num_kernels;
+    const dim3 grid((width + kScatterTile - 1u) / kScatterTile, (height + kScatterTile - 1u) / kScatterTile, num_planes);
+    hipLaunchKernelGGL(k_scatter_add, grid, dim3(kScatterThreads), 0, stream, d_blurred, d_primary, width, height,
+                       (uint32_t)scatter_bin_log2(bin), amps, d_out, d_out_scatter, d_out_u8);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_scatter_add_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t bin,
+                           const float* d_blurred, uint32_t num_kernels, const float* amp, const float* d_primary,
+                           float* d_out, float* d_out_scatter, uint8_t* d_out_u8, void* stream)
+{
+    if (const char* why = scatter_add_arguments(width, height, num_planes, bin, d_blurred, num_kernels, amp, d_primary, d_out,
+                                                d_out_scatter, d_out_u8))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_scatter_add(ctx, width, height, num_planes, bin, d_blurred, num_kernels, amp, d_primary, d_out,
+                              d_out_scatter, d_out_u8, (hipStream_t)stream);
+}
+
+int xrt_scatter_add(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, uint32_t bin,
+                    const float* blurred, uint32_t num_kernels, const float* amp, const float* primary, float* out,
+                    float* out_scatter, uint8_t* out_u8)
+{
+    if (const char* why = scatter_add_arguments(width, height, num_planes, bin, blurred, num_kernels, amp, primary, out,
+                                                out_scatter, out_u8))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)width * height * num_planes;
+    const size_t nc = (size_t)((width + bin - 1u) / bin) * ((height + bin - 1u) / bin) * num_planes * num_kernels;
+    DeviceScratch s(ctx, ctx->host_stream, "scatter add");
+    const float* db = s.upload(blurred, nc);
+    const float* dprim = s.upload(primary, n);
+    float* dout = s.alloc<float>(n, out != nullptr);
+    float* dsc = s.alloc<float>(n, out_scatter != nullptr);
+    uint8_t* du8 = s.alloc<uint8_t>(n, out_u8 != nullptr);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_scatter_add(ctx, width, height, num_planes, bin, db, num_kernels, amp, dprim, dout, dsc, du8,
+                                    ctx->host_stream))
+        return rc;
+    s.download(out, (const float*)dout, n);
+    s.download(out_scatter, (const float*)dsc, n);
+    s.download(out_u8, (const uint8_t*)du8, n);
+    return s.finish();
+}
+
 // Render of the L-buffer plane and the fork's hole fill over it, into host buffers.
 static int render_and_fill(xrt_context* ctx, const xrt_camera* camera, float* image, float* lbuffer,
                            uint8_t* image_u8, xrt_stats* stats)
