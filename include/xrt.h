@@ -1141,6 +1141,96 @@ int xrt_sirt_tv_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32
                        uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv, float* d_volume,
                        void* stream);
 
+/* --- OS-MLTR: Poisson-likelihood reconstruction from transmission counts --- */
+
+/*
+ * The statistical side of reconstruction: a
+ * maximum-likelihood solver for transmission counts in ordered subsets.  It
+ * takes the counts themselves -- no logarithm, so a pixel that counted zero
+ * is an ordinary measurement -- and an optional background, the expected
+ * counts that did not come through the object (scatter, dark current).  Like
+ * the SIRT entries, none of these looks at or changes the context's model,
+ * scene, poses, frames in flight or state generation, and there is no
+ * xrt_multi_ form.  All arithmetic is f64 where written, every operation
+ * rounded on its own (no FMA), every select the written one; xrt_exp is the
+ * library's exp (glibc's, bit for bit).
+ *
+ * xrt_poisson_project[_device].  volume, dims, spacing and rays as
+ * xrt_forward_project's; counts: num_planes planes of width x height, the
+ * measured y; flat: one plane, the expected counts without the object, shared
+ * by every plane; background: num_planes planes, or NULL; pairs:
+ * float[num_planes][height][width][2], (num, den) interleaved, aligned to 8
+ * bytes.  Per pixel, with the ray, acc, te, tx and ell of
+ * xrt_forward_project:
+ *   l   = acc * ell;  L = (tx - te) * ell
+ *   psi = (double)flat[row][col] * xrt_exp(-l)
+ *   r   = background ? (double)background[p][row][col] : +0.0
+ *   yh  = psi + r
+ *   a miss, or !(L > 0), or !(yh > 0):  num = den = +0.0f      (a NaN compares false)
+ *   else  q = psi / yh;  num = (float)(psi - (double)y * q);  den = (float)((L * psi) * q)
+ * With r = 0, q is exactly 1: a NULL background and a plane of zeros give the
+ * same bits.  XRT_ERR_ARGUMENT, before the context is looked at, for a NULL
+ * volume, dims, spacing, rays, counts, flat or pairs, pairs not aligned to 8
+ * bytes, sizes outside xrt_forward_project's limits, a spacing that is not
+ * finite and > 0, a ray matrix entry that is not finite (the host form only)
+ * and pairs overlapping an input.
+ *
+ * xrt_backproject_update[_device].  pairs as above, matrices and dims as
+ * xrt_backproject's, the whole volume f32 [nz][ny][nx], updated in place.  Per
+ * voxel and per plane in order, a, b, c, w, col, row, x0, y0, fx, fy and the
+ * acceptance tests are xrt_backproject's, formed once; vn and vd are its
+ * three f32 expressions (top, bot, v) over the pairs' first and second
+ * components, +0.0f outside the plane;
+ *   accn = accn + (double)vn * (w * w);  accd = accd + (double)vd * (w * w)
+ * and then x = xrt_volume_update's voxel with corr = (float)accn and norm =
+ * (float)accd: only where (float)accd > 0, elsewhere x keeps its bits.  The
+ * result equals, bit for bit, xrt_backproject of the num planes and of the den
+ * planes (scale 1, no accumulate) followed by xrt_volume_update.
+ * XRT_ERR_ARGUMENT, before the context is looked at, for a NULL pointer,
+ * pairs not aligned to 8 bytes, sizes outside xrt_backproject's limits, a
+ * relax that is not finite, a NaN bound, lo > hi, a matrix entry that is not
+ * finite (the host form only) and a volume that overlaps the pairs or the
+ * matrices.
+ *
+ * xrt_mltr[_device].  xrt_sirt_tv's arguments and checks, with counts, flat
+ * and background (may be NULL) in the place of proj -- NULL counts or flat and
+ * a volume that overlaps any of them are refused too.  Subsets as xrt_sirt's.
+ * For k = 0 .. iterations - 1 and s = 0 .. S - 1 in this order:
+ *   pairs  = xrt_poisson_project(volume, R_s, counts_s, flat, background_s)
+ *   volume = xrt_backproject_update(pairs, A_s, relax, lo, hi)
+ * and tv as in xrt_sirt_tv after every iteration (x0, D, xrt_tv_descend with
+ * length a_k * sqrt(D), a_(k+1) = a_k * reduction); tv NULL or tv->steps == 0:
+ * the plain solver, bit for bit.  One update is x + relax * sum(psi - y q) /
+ * sum(L psi q) under the backprojector's weights: the separable-surrogate
+ * step of the transmission likelihood with its curvature at the current
+ * estimate.  xrt_mltr: host buffers, synchronous.  _device: device counts,
+ * flat, background and volume, asynchronous on `stream`.  The working set --
+ * the largest subset's pairs and the gathered matrices, with tv x0, the
+ * gradient volume and the partials; no norm volumes -- is the context's
+ * xrt_sirt working set, ordered as xrt_sirt_device says (a call waits for the
+ * context's previous solver call); XRT_ERR_MEMORY, with the byte count in
+ * xrt_last_error, when it cannot be allocated.
+ */
+int xrt_poisson_project(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* volume,
+                        const uint32_t dims[3], const float spacing[3], const double* rays, const float* counts,
+                        const float* flat, const float* background, float* pairs);
+int xrt_poisson_project_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                               const float* d_volume, const uint32_t dims[3], const float spacing[3], const double* d_rays,
+                               const float* d_counts, const float* d_flat, const float* d_background, float* d_pairs,
+                               void* stream);
+int xrt_backproject_update(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* pairs,
+                           const double* matrices, const uint32_t dims[3], double relax, float lo, float hi, float* volume);
+int xrt_backproject_update_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                                  const float* d_pairs, const double* d_matrices, const uint32_t dims[3], double relax,
+                                  float lo, float hi, float* d_volume, void* stream);
+int xrt_mltr(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* counts, const float* flat,
+             const float* background, const double* matrices, const uint32_t dims[3], const float spacing[3],
+             uint32_t iterations, uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv, float* volume);
+int xrt_mltr_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_counts,
+                    const float* d_flat, const float* d_background, const double* matrices, const uint32_t dims[3],
+                    const float spacing[3], uint32_t iterations, uint32_t subsets, double relax, float lo, float hi,
+                    const xrt_tv_params* tv, float* d_volume, void* stream);
+
 /* --- material decomposition: a per-pixel Newton solver -------------------- */
 
 /*

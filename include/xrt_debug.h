@@ -425,6 +425,24 @@ int xrt_host_sirt_tv(uint32_t width, uint32_t height, uint32_t num_planes, const
                      float lo, float hi, const xrt_tv_params* tv, float* volume);
 
 /*
+ * Test hooks of OS-MLTR.  Host code, no device: poisson_pixel,
+ * backproject_pair_term and volume_update_voxel -- the functions
+ * k_poisson_project and k_backproject_update call, compiled for the host --
+ * over whole host buffers, and xrt_mltr's algorithm over them and
+ * xrt_host_sirt_tv's descent.  Arguments and checks as the host forms'.
+ */
+int xrt_host_poisson_project(uint32_t width, uint32_t height, uint32_t num_planes, const float* volume,
+                             const uint32_t dims[3], const float spacing[3], const double* rays, const float* counts,
+                             const float* flat, const float* background, float* pairs);
+int xrt_host_backproject_update(uint32_t width, uint32_t height, uint32_t num_planes, const float* pairs,
+                                const double* matrices, const uint32_t dims[3], double relax, float lo, float hi,
+                                float* volume);
+int xrt_host_mltr(uint32_t width, uint32_t height, uint32_t num_planes, const float* counts, const float* flat,
+                  const float* background, const double* matrices, const uint32_t dims[3], const float spacing[3],
+                  uint32_t iterations, uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv,
+                  float* volume);
+
+/*
  * Test hook of the voxeliser.  Host code, no device: xrt_voxelize's crossing
  * and voxel functions -- voxel_footprint, voxel_crossing, voxel_label and
  * voxel_value, the ones the kernels call, compiled for the host -- over whole

@@ -973,6 +973,81 @@ def host_sirt(proj, matrices, dims, spacing, iterations, subsets=1, relax=1.0, l
     return vol
 
 
+def _poisson_project_arrays(volume, spacing, rays, counts, flat, background):
+    """xrt_poisson_project's arguments: (volume, dims, spacing, rays, counts, flat, background or None, P, H, W)."""
+    v, d, spc, r, y, p, h, w = _forward_arrays(volume, spacing, rays, _abi.XRT_FP_RESIDUAL, counts, None)
+    f = np.ascontiguousarray(flat, dtype=np.float32)
+    if f.shape != (h, w):
+        raise ValueError(f"flat is one (H, W) = ({h}, {w}) plane, got shape {f.shape}")
+    if background is not None:
+        background = np.ascontiguousarray(background, dtype=np.float32)
+        if background.size != y.size:
+            raise ValueError(f"the background has the counts' shape {y.shape}, got {background.shape}")
+    return v, d, spc, r, y, f, background, p, h, w
+
+
+def _pairs_arrays(pairs, matrices, dims, volume):
+    """xrt_backproject_update's arguments: (pairs (P, H, W, 2) f32, matrices (P, 12) f64, dims u32[3], a copy of the
+    volume, P, H, W)."""
+    a = np.ascontiguousarray(pairs, dtype=np.float32)
+    if a.ndim == 3:
+        a = a[None]
+    if a.ndim != 4 or a.shape[-1] != 2:
+        raise ValueError(f"pairs are (P, H, W, 2), got shape {a.shape}")
+    p, h, w = a.shape[:3]
+    m = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 12)
+    if m.shape[0] != p:
+        raise ValueError(f"{p} planes of pairs need {p} matrices, got {m.shape[0]}")
+    d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+    shape = (int(d[2]), int(d[1]), int(d[0]))
+    vol = np.array(volume, dtype=np.float32, order="C")
+    if vol.shape != shape:
+        raise ValueError(f"the volume must have shape {shape}, got {vol.shape}")
+    return a, m, d, vol, p, h, w
+
+
+def _mltr_arrays(counts, flat, background, matrices, dims, spacing, start):
+    y, m, d, spc, vol, p, h, w = _sirt_arrays(counts, matrices, dims, spacing, start)
+    f = np.ascontiguousarray(np.broadcast_to(np.asarray(flat, np.float32), (h, w)))
+    if background is not None:
+        background = np.ascontiguousarray(np.broadcast_to(np.asarray(background, np.float32), y.shape))
+    return y, f, background, m, d, spc, vol, p, h, w
+
+
+def host_poisson_project(volume, spacing, rays, counts, flat, background=None) -> np.ndarray:
+    """Context.poisson_project in the device's arithmetic on the host (xrt_host_poisson_project, a test hook)."""
+    v, d, spc, r, y, f, b, p, h, w = _poisson_project_arrays(volume, spacing, rays, counts, flat, background)
+    out = np.empty((p, h, w, 2), np.float32)
+    rc = _abi.load().xrt_host_poisson_project(w, h, p, _fptr(v), _u32ptr(d), _fptr(spc), _dptr(r), _fptr(y), _fptr(f),
+                                              _fptr(b) if b is not None else None, _fptr(out))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_poisson_project")
+    return out
+
+
+def host_backproject_update(pairs, matrices, dims, volume, relax=1.0, lo=-np.inf, hi=np.inf) -> np.ndarray:
+    """Context.backproject_update on the host (xrt_host_backproject_update, a test hook): the updated copy."""
+    a, m, d, vol, p, h, w = _pairs_arrays(pairs, matrices, dims, volume)
+    rc = _abi.load().xrt_host_backproject_update(w, h, p, _fptr(a), _dptr(m), _u32ptr(d), float(relax), float(lo), float(hi),
+                                                 _fptr(vol))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_backproject_update")
+    return vol
+
+
+def host_mltr(counts, flat, matrices, dims, spacing, iterations, subsets=1, relax=1.0, lo=0.0, hi=np.inf, start=None,
+              tv=None, background=None) -> np.ndarray:
+    """Context.mltr_matrices in the device's arithmetic on the host (xrt_host_mltr, a test hook)."""
+    y, f, b, m, d, spc, vol, p, h, w = _mltr_arrays(counts, flat, background, matrices, dims, spacing, start)
+    params = _tv_params(tv)
+    rc = _abi.load().xrt_host_mltr(w, h, p, _fptr(y), _fptr(f), _fptr(b) if b is not None else None, _dptr(m), _u32ptr(d),
+                                   _fptr(spc), int(iterations), int(subsets), float(relax), float(lo), float(hi),
+                                   ctypes.byref(params) if params is not None else None, _fptr(vol))
+    if rc != _abi.XRT_OK:
+        raise XrtError(rc, "xrt_host_mltr")
+    return vol
+
+
 def _tv_volume(volume, copy=False):
     """(volume f32 (nz, ny, nx), dims u32[3]) of xrt_tv_gradient and xrt_tv_descend."""
     v = np.array(volume, dtype=np.float32, order="C") if copy else np.ascontiguousarray(volume, dtype=np.float32)
@@ -1555,6 +1630,90 @@ class Context:
                                        _u32ptr(d), _fptr(spc), int(iterations), int(subsets), float(relax), float(lo),
                                        float(hi), d_volume or None, stream or None)
         self._check(rc, "xrt_sirt_device")
+
+    def poisson_project(self, volume, spacing, rays, counts, flat, background=None) -> np.ndarray:
+        """The pixel stage of mltr: under P ray matrices, from the (P, H, W) measured `counts`, the (H, W) `flat`
+        field and the (P, H, W) `background` (None: none), the expected counts psi = flat * exp(-line integral) and
+        per pixel (psi - y psi / (psi + r), L psi psi / (psi + r)) with L the ray's length inside the grid:
+        (P, H, W, 2) f32, (num, den) interleaved."""
+        v, d, spc, r, y, f, b, p, h, w = _poisson_project_arrays(volume, spacing, rays, counts, flat, background)
+        out = np.empty((p, h, w, 2), np.float32)
+        self._check(self._lib.xrt_poisson_project(self._ctx, w, h, p, _fptr(v), _u32ptr(d), _fptr(spc), _dptr(r), _fptr(y),
+                                                  _fptr(f), _fptr(b) if b is not None else None, _fptr(out)),
+                    "xrt_poisson_project")
+        return out
+
+    def poisson_project_device(self, width: int, height: int, num_planes: int, d_volume: int, dims, spacing,
+                               d_rays: int, d_counts: int, d_flat: int, d_pairs: int, d_background: int = 0,
+                               stream: int = 0):
+        """poisson_project over device buffers (raw pointers: the f32 volume, f64 ray matrices, f32 planes and
+        pairs); asynchronous on `stream`."""
+        d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+        spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+        rc = self._lib.xrt_poisson_project_device(self._ctx, int(width), int(height), int(num_planes), d_volume or None,
+                                                  _u32ptr(d), _fptr(spc), d_rays or None, d_counts or None, d_flat or None,
+                                                  d_background or None, d_pairs or None, stream or None)
+        self._check(rc, "xrt_poisson_project_device")
+
+    def backproject_update(self, pairs, matrices, dims, volume, relax=1.0, lo=-np.inf, hi=np.inf) -> np.ndarray:
+        """The backprojections of both components of (P, H, W, 2) `pairs` under P (3, 4) f64 matrices and the update
+        x + relax * num / den where den > 0, clamped to [lo, hi], in one pass: the updated copy of `volume`."""
+        a, m, d, vol, p, h, w = _pairs_arrays(pairs, matrices, dims, volume)
+        self._check(self._lib.xrt_backproject_update(self._ctx, w, h, p, _fptr(a), _dptr(m), _u32ptr(d), float(relax),
+                                                     float(lo), float(hi), _fptr(vol)), "xrt_backproject_update")
+        return vol
+
+    def backproject_update_device(self, width: int, height: int, num_planes: int, d_pairs: int, d_matrices: int, dims,
+                                  d_volume: int, relax: float = 1.0, lo: float = -np.inf, hi: float = np.inf,
+                                  stream: int = 0):
+        """backproject_update over device buffers (raw pointers), in place in d_volume; asynchronous on `stream`."""
+        d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+        rc = self._lib.xrt_backproject_update_device(self._ctx, int(width), int(height), int(num_planes), d_pairs or None,
+                                                     d_matrices or None, _u32ptr(d), float(relax), float(lo), float(hi),
+                                                     d_volume or None, stream or None)
+        self._check(rc, "xrt_backproject_update_device")
+
+    def mltr_matrices(self, counts, flat, matrices, dims, spacing, iterations: int, subsets: int = 1, relax: float = 1.0,
+                      lo: float = 0.0, hi: float = np.inf, start=None, tv=None, background=None) -> np.ndarray:
+        """mltr under P given (3, 4) f64 backprojection matrices in place of cameras and poses."""
+        y, f, b, m, d, spc, vol, p, h, w = _mltr_arrays(counts, flat, background, matrices, dims, spacing, start)
+        params = _tv_params(tv)
+        self._check(self._lib.xrt_mltr(self._ctx, w, h, p, _fptr(y), _fptr(f), _fptr(b) if b is not None else None,
+                                       _dptr(m), _u32ptr(d), _fptr(spc), int(iterations), int(subsets), float(relax),
+                                       float(lo), float(hi), ctypes.byref(params) if params is not None else None,
+                                       _fptr(vol)), "xrt_mltr")
+        return vol
+
+    def mltr(self, counts, flat, camera: Camera, poses, dims, origin, spacing, iterations: int, subsets: int = 1,
+             relax: float = 1.0, lo: float = 0.0, hi: float = np.inf, start=None, tv=None, background=None) -> np.ndarray:
+        """OS-MLTR: the maximum-likelihood reconstruction of the (P, H, W) transmission `counts` -- the measurement
+        itself, no logarithm; zero counts are fine -- under the Poisson model counts ~ flat * exp(-line integral) +
+        background, with `flat` an (H, W) plane (or a scalar) of the expected counts without the object and
+        `background` (P, H, W) expected counts that did not come through it (scatter, dark current; None: none).
+        Cameras, poses, grid, subsets, relax, the clamp, start and tv as sirt's.  (nz, ny, nx) f32."""
+        a, p, h, w = _lsf_planes(counts)
+        cams = [camera] * p if isinstance(camera, Camera) else list(camera)
+        poses = [None] * p if poses is None else list(poses)
+        if len(cams) != p or len(poses) != p:
+            raise ValueError(f"{p} projections need one camera or {p}, and {p} poses or None")
+        mats = np.stack([backprojection_matrix(c, origin, spacing, q) for c, q in zip(cams, poses)])
+        return self.mltr_matrices(a, flat, mats, dims, spacing, iterations, subsets, relax, lo, hi, start, tv, background)
+
+    def mltr_device(self, width: int, height: int, num_planes: int, d_counts: int, d_flat: int, matrices, dims, spacing,
+                    iterations: int, d_volume: int, subsets: int = 1, relax: float = 1.0, lo: float = 0.0,
+                    hi: float = np.inf, stream: int = 0, tv=None, d_background: int = 0):
+        """mltr over device buffers (raw pointers: the f32 counts, flat plane, background or 0, and the f32 volume,
+        start and result); `matrices` is a host (P, 12) f64 array.  Asynchronous on `stream`."""
+        m = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 12)
+        d = np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+        spc = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+        params = _tv_params(tv)
+        rc = self._lib.xrt_mltr_device(self._ctx, int(width), int(height), int(num_planes), d_counts or None,
+                                       d_flat or None, d_background or None, _dptr(m), _u32ptr(d), _fptr(spc),
+                                       int(iterations), int(subsets), float(relax), float(lo), float(hi),
+                                       ctypes.byref(params) if params is not None else None, d_volume or None,
+                                       stream or None)
+        self._check(rc, "xrt_mltr_device")
 
     def detector_response(self, image, lsf_x, lsf_y=None, out=True, u8=True):
         """The detector's line-spread function over an (H, W) image or a (P, H, W) stack of them (taps as

@@ -281,6 +281,19 @@ XRT_SYMBOLS = {
     "xrt_host_tv_descend": (ctypes.c_int, [_fp, _u32p, ctypes.c_double, _u32, ctypes.c_double, _f, _f]),
     "xrt_host_sirt_tv": (ctypes.c_int, [_u32, _u32, _u32, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f, _TvP,
                                         _fp]),
+    "xrt_poisson_project": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _u32p, _fp, _dp, _fp, _fp, _fp, _fp]),
+    "xrt_poisson_project_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _u32p, _fp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xrt_backproject_update": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _dp, _u32p, ctypes.c_double, _f, _f, _fp]),
+    "xrt_backproject_update_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _vp, _u32p, ctypes.c_double, _f, _f, _vp,
+                                                     _vp]),
+    "xrt_mltr": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _fp, _fp, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f,
+                                _TvP, _fp]),
+    "xrt_mltr_device": (ctypes.c_int, [_CtxP, _u32, _u32, _u32, _vp, _vp, _vp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double,
+                                       _f, _f, _TvP, _vp, _vp]),
+    "xrt_host_poisson_project": (ctypes.c_int, [_u32, _u32, _u32, _fp, _u32p, _fp, _dp, _fp, _fp, _fp, _fp]),
+    "xrt_host_backproject_update": (ctypes.c_int, [_u32, _u32, _u32, _fp, _dp, _u32p, ctypes.c_double, _f, _f, _fp]),
+    "xrt_host_mltr": (ctypes.c_int, [_u32, _u32, _u32, _fp, _fp, _fp, _dp, _u32p, _fp, _u32, _u32, ctypes.c_double, _f, _f,
+                                     _TvP, _fp]),
     "xrt_decompose": (ctypes.c_int, [_CtxP, _u64, _fp, _u16p, _fp, _fp, _u32, _u32, _fp, _u32, ctypes.c_float, ctypes.c_int, _dp,
                                      _u32, ctypes.c_double, ctypes.c_double, _fp, _u8p]),
     "xrt_decompose_device": (ctypes.c_int, [_CtxP, _u64, _vp, _vp, _fp, _fp, _u32, _u32, _fp, _u32, ctypes.c_float,

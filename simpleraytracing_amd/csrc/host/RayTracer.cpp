@@ -766,6 +766,35 @@ void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& proje
           "xrt_sirt_tv");
 }
 
+void reconstructMLTR(std::vector<float>& volume, const std::vector<float>& counts, const std::vector<float>& flat,
+                     const std::vector<float>& background, unsigned num_projections, const Image& frame,
+                     const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                     const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                     const float spacing[3], unsigned iterations, unsigned subsets, double relax, float lo, float hi,
+                     const TVParams& tv)
+{
+    const unsigned W = frame.getWidth(), H = frame.getHeight();
+    if (num_projections == 0 || counts.size() != (size_t)W * H * num_projections)
+        throw std::runtime_error("reconstructMLTR: the stack does not hold num_projections images");
+    if (flat.size() != (size_t)W * H) throw std::runtime_error("reconstructMLTR: the flat field is not one image");
+    if (!background.empty() && background.size() != counts.size())
+        throw std::runtime_error("reconstructMLTR: one background image per projection, or none");
+    if (!poses.empty() && poses.size() != num_projections)
+        throw std::runtime_error("reconstructMLTR: one pose per projection, or none");
+    const xrt_camera cam = camera_for(frame, meshes, info);
+    const std::vector<double> matrices = scan_matrices("reconstructMLTR", cam, poses, num_projections, origin, spacing);
+    const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
+    if (volume.size() != voxels) volume.assign(voxels, 0.0f);
+    DeviceSlot& slot = device_slot(device_choice());
+    std::lock_guard<std::mutex> g(slot.lock);
+    xrt_context* ctx = slot.ctx;
+    const xrt_tv_params params = {tv.steps, tv.alpha, tv.reduction, tv.eps};
+    check(ctx, xrt_mltr(ctx, W, H, num_projections, counts.data(), flat.data(), background.empty() ? nullptr : background.data(),
+                        matrices.data(), dims, spacing, iterations, subsets, relax, lo, hi, tv.steps ? &params : nullptr,
+                        volume.data()),
+          "xrt_mltr");
+}
+
 void denoiseTV(std::vector<float>& volume, const unsigned dims[3], unsigned steps, double length, double eps, float lo,
                float hi)
 {

@@ -292,6 +292,19 @@ void reconstructSIRT(std::vector<float>& volume, const std::vector<float>& proje
                      const float spacing[3], unsigned iterations, unsigned subsets, double relax, float lo, float hi,
                      const TVParams& tv);
 
+// OS-MLTR (xrt_mltr): the maximum-likelihood reconstruction of
+// the same scan from its transmission counts -- `counts` as reconstructSIRT's
+// projections, the intensities themselves, no logarithm --, `flat` one image of
+// the expected counts without the object and `background` the expected counts
+// that did not come through it, one image per projection (empty: none).  The
+// rest as reconstructSIRT's.  One device.
+void reconstructMLTR(std::vector<float>& volume, const std::vector<float>& counts, const std::vector<float>& flat,
+                     const std::vector<float>& background, unsigned num_projections, const Image& frame,
+                     const std::vector<TriangleMesh>& meshes, const RayTracerInfo& info,
+                     const std::vector<std::array<float, 12>>& poses, const unsigned dims[3], const float origin[3],
+                     const float spacing[3], unsigned iterations, unsigned subsets = 1, double relax = 1.0, float lo = 0.0f,
+                     float hi = std::numeric_limits<float>::infinity(), const TVParams& tv = TVParams());
+
 // `steps` descent steps of `length` each on the total variation of a f32
 // volume of dims[0] * dims[1] * dims[2] values (x fastest), in place, clamped
 // to [lo, hi] (xrt_tv_descend).  One device.

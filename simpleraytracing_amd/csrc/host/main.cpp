@@ -80,8 +80,16 @@
 //                              == s) instead of FDK, from zeros, every update relaxed by
 //                              RELAX (default 1) and kept >= 0.  The same cube and the same
 //                              refusals as FDK's.
+//       --mltr K[:S[:RELAX]]   with --reconstruct, in the place of --sirt: K iterations of
+//                              OS-MLTR, the maximum-likelihood solver for
+//                              transmission counts.  It is given each projection's intensity as
+//                              it stands just before the logarithm -- after --scatter, --lsf
+//                              and --noise; zero counts are fine --, a flat field of I0 and,
+//                              with --scatter, each projection's scatter estimate as the
+//                              background; FILE.counts.mhd (and FILE.background.mhd) keep
+//                              those planes.  NAME.EXT receives what --log-projection writes.
 //       --tv STEPS[:ALPHA[:REDUCTION[:EPS]]]
-//                              with --sirt: after every iteration STEPS descent steps on the
+//                              with --sirt or --mltr: after every iteration STEPS descent steps on the
 //                              volume's total variation, each ALPHA (default
 //                              0.2) times as long as the distance the iteration moved the
 //                              volume; ALPHA is multiplied by REDUCTION (default 1, in
@@ -230,7 +238,8 @@ void showUsage(const std::string& prog)
               << "\t--reconstruct FILE.mhd[:N]\tWith --turntable N:z (every mesh, about the detector's up) and --log-projection: reconstruct the scan by FDK into an N^3 grid (default 128) about the turntable's centre, its side the scene box's diagonal; writes FILE.mhd (MET_FLOAT) and FILE.raw\n"
               << "\t--voxelize FILE.mhd[:N]\t\tVoxelise the scene (under --pose's poses) on the grid of --reconstruct FILE.mhd[:N]: writes FILE.mhd (MET_UCHAR, 0 or 1 + the last mesh a voxel's centre lies in) and FILE.raw, with --materials also FILE.mu.mhd (MET_FLOAT, the coefficients summed); valid without --turntable\n"
               << "\t--sirt K[:S[:RELAX]]\t\tWith --reconstruct: K iterations of SIRT (S = 1) or OS-SART over S subsets (1 to 64) instead of FDK, from zeros, relaxed by RELAX (default 1), kept >= 0\n"
-              << "\t--tv STEPS[:ALPHA[:REDUCTION[:EPS]]]\tWith --sirt: STEPS total-variation descent steps after every iteration, each ALPHA (default 0.2) of the iteration's move, ALPHA times REDUCTION (default 1, in (0, 1]) after every iteration, EPS (default 1e-8) under the norm; ALPHA above about 0.5 flattens the object's level\n"
+              << "\t--mltr K[:S[:RELAX]]\t\tWith --reconstruct, in the place of --sirt: K iterations of OS-MLTR over S subsets, the maximum-likelihood solver for transmission counts, on each projection's intensity before the logarithm (after --scatter, --lsf, --noise), a flat field of I0 and --scatter's estimate as the background; FILE.counts.mhd keeps the planes\n"
+              << "\t--tv STEPS[:ALPHA[:REDUCTION[:EPS]]]\tWith --sirt or --mltr: STEPS total-variation descent steps after every iteration, each ALPHA (default 0.2) of the iteration's move, ALPHA times REDUCTION (default 1, in (0, 1]) after every iteration, EPS (default 1e-8) under the norm; ALPHA above about 0.5 flattens the object's level\n"
               << "\t--noise GAIN[:SEED]\t\tPhoton noise on the written image: each pixel a Poisson count of mean I * GAIN, divided by GAIN (after --lsf, before --log-projection; SEED defaults to 0); --u8 and --lbuffer stay as rendered\n"
               << "\t--supersample B\t\t\tPixel-area integration: render W*B x H*B samples (B in 1..8) and write each pixel's mean over its B x B samples; -s stays the written size\n"
               << "\t--focal-spot UxV[:NUxNV]\tA finite focal spot of U x V scene units (along right and up), NU x NV sub-sources (default 3x3, at most 64), averaged on the device; not with -g, --rows, --batch, --paths, --lbuffer\n"
@@ -280,6 +289,9 @@ struct Options {
     unsigned sirt_iterations = 0;              // --sirt K[:S[:RELAX]] (0: FDK)
     unsigned sirt_subsets = 1;
     double sirt_relax = 1.0;
+    unsigned mltr_iterations = 0;              // --mltr K[:S[:RELAX]] (0: not chosen)
+    unsigned mltr_subsets = 1;
+    double mltr_relax = 1.0;
     bool tv = false;                           // --tv STEPS[:ALPHA[:REDUCTION[:EPS]]]
     TVParams tv_params;
     bool noise = false;                        // --noise GAIN[:SEED]
@@ -829,6 +841,22 @@ Options processCmd(int argc, char** argv)
             }
             if (!ok)
                 throw std::runtime_error("--sirt K[:S[:RELAX]]: K iterations (>= 1), S subsets (1 to 64), RELAX a finite number");
+        } else if (a == "--mltr") {
+            const std::vector<std::string> parts = split(parse_str(argv[0], argc, argv, i), ':');
+            bool ok = parts.size() >= 1 && parts.size() <= 3 && parse_index(parts[0], o.mltr_iterations) && o.mltr_iterations >= 1;
+            if (ok && parts.size() >= 2)
+                ok = parse_index(parts[1], o.mltr_subsets) && o.mltr_subsets >= 1 && o.mltr_subsets <= XRT_MAX_SUBSETS;
+            if (ok && parts.size() == 3) {
+                size_t used = 0;
+                try {
+                    o.mltr_relax = std::stod(parts[2], &used);
+                } catch (const std::exception&) {
+                    used = 0;
+                }
+                ok = !parts[2].empty() && used == parts[2].size() && std::isfinite(o.mltr_relax);
+            }
+            if (!ok)
+                throw std::runtime_error("--mltr K[:S[:RELAX]]: K iterations (>= 1), S subsets (1 to 64), RELAX a finite number");
         } else if (a == "--tv") {
             const std::vector<std::string> parts = split(parse_str(argv[0], argc, argv, i), ':');
             bool ok = parts.size() >= 1 && parts.size() <= 4 && parse_index(parts[0], o.tv_params.steps) && o.tv_params.steps >= 1;
@@ -962,8 +990,14 @@ Options processCmd(int argc, char** argv)
         throw std::runtime_error("--reconstruct needs a --turntable that turns every mesh: the scene is reconstructed as one object");
     if (o.sirt_iterations && o.reconstruct.empty())
         throw std::runtime_error("--sirt needs --reconstruct FILE.mhd: it chooses how the scan is reconstructed");
-    if (o.tv && !o.sirt_iterations)
-        throw std::runtime_error("--tv needs --sirt K: it regularises the iterative reconstruction");
+    if (o.mltr_iterations && o.sirt_iterations)
+        throw std::runtime_error("--mltr and --sirt are two solvers: give one");
+    if (o.mltr_iterations && o.reconstruct.empty())
+        throw std::runtime_error("--mltr needs --reconstruct FILE.mhd: it chooses how the scan is reconstructed");
+    if (o.tv && !o.sirt_iterations && !o.mltr_iterations)
+        throw std::runtime_error("--tv needs --sirt K or --mltr K: it regularises the iterative reconstruction");
+    if (o.mltr_iterations && o.mltr_subsets > o.turntable)
+        throw std::runtime_error("--mltr K[:S[:RELAX]]: more subsets than projections");
     if (o.sirt_iterations && o.sirt_subsets > o.turntable)
         throw std::runtime_error("--sirt K[:S[:RELAX]]: more subsets than projections");
     if (o.log_projection && (o.gpus > 1 || o.rows))
@@ -1114,6 +1148,7 @@ int main(int argc, char** argv)
         const std::string name = opt.output, lbuffer_name = opt.lbuffer, u8_name = opt.u8;
         std::vector<float> scan;                      // --sinogram: the projections' intensity images
         std::vector<float> integrals;                 // --reconstruct: the projections' line integrals
+        std::vector<float> counts, backgrounds;       // --mltr: their intensities before the logarithm, --scatter's estimates
         std::vector<std::array<float, 12>> turns;     //                and the turntable's pose under each
         for (unsigned projection = 0; projection < std::max(opt.turntable, 1u); ++projection) {
             if (opt.turntable) {
@@ -1220,6 +1255,9 @@ int main(int argc, char** argv)
                     applyScatter(image, scattered, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.scatter_model,
                                  opt.lbuffer.empty() ? nullptr : &lb);
                     scattered.saveTextFile(stem + ".scatter" + suffix);
+                    if (opt.mltr_iterations)          // the estimate is the solver's background
+                        backgrounds.insert(backgrounds.end(), scattered.getData(),
+                                           scattered.getData() + (size_t)opt.width * opt.height);
                 } else if (opt.spectrum)              // (without a table the planes are the output)
                     applySpectrum(image, planes, open, opt.spectrum_weight, opt.spectrum_mu, opt.lbuffer.empty() ? nullptr : &lb);
                 if (opt.detector) {                   // the channels beside the image; a scan's projection draws its own
@@ -1288,6 +1326,8 @@ int main(int argc, char** argv)
                     applyPhotonNoise(written, opt.noise_gain, opt.noise_seed,
                                      (unsigned long long)projection * opt.width * opt.height);
                 if (!opt.sinogram.empty()) scan.insert(scan.end(), written.getData(), written.getData() + (size_t)opt.width * opt.height);
+                if (opt.mltr_iterations)              // the intensity as it stands just before the logarithm
+                    counts.insert(counts.end(), written.getData(), written.getData() + (size_t)opt.width * opt.height);
                 if (opt.log_projection) applyLogProjection(written, opt.flat_value);
                 if (!opt.reconstruct.empty())
                     integrals.insert(integrals.end(), written.getData(), written.getData() + (size_t)opt.width * opt.height);
@@ -1321,7 +1361,22 @@ int main(int argc, char** argv)
             unsigned dims[3];
             scan_grid(lower, upper, opt.reconstruct_n, dims, centre, origin, spacing);
             std::vector<float> reconstruction;
-            if (opt.sirt_iterations)
+            if (opt.mltr_iterations) {
+                // the planes the solver receives, kept beside the volume: FILE.counts.mhd (and FILE.background.mhd)
+                const std::string stem = opt.reconstruct.substr(0, opt.reconstruct.size() - 4);
+                const unsigned stack[3] = {opt.width, opt.height, opt.turntable};
+                const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
+                try {
+                    saveVolume(stem + ".counts.mhd", stack, zero, one, counts.data());
+                    if (!backgrounds.empty()) saveVolume(stem + ".background.mhd", stack, zero, one, backgrounds.data());
+                } catch (const VolumeError& e) {
+                    throw std::runtime_error(std::string("--mltr: ") + e.what());
+                }
+                reconstructMLTR(reconstruction, counts, std::vector<float>((size_t)opt.width * opt.height, opt.flat_value),
+                                backgrounds, opt.turntable, image, meshes, info, turns, dims, origin, spacing,
+                                opt.mltr_iterations, opt.mltr_subsets, opt.mltr_relax, 0.0f,
+                                std::numeric_limits<float>::infinity(), opt.tv ? opt.tv_params : TVParams());
+            } else if (opt.sirt_iterations)
                 reconstructSIRT(reconstruction, integrals, opt.turntable, image, meshes, info, turns, dims, origin, spacing,
                                 opt.sirt_iterations, opt.sirt_subsets, opt.sirt_relax, 0.0f,
                                 std::numeric_limits<float>::infinity(), opt.tv ? opt.tv_params : TVParams());

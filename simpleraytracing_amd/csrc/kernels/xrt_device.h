@@ -1934,6 +1934,88 @@ __host__ __device__ __forceinline__ float volume_update_voxel(float x, float cor
 }
 
 // ---------------------------------------------------------------------------
+// OS-MLTR: the Poisson likelihood's pixel stage over
+// forward_ray, and the backprojector's term over a plane of (num, den) pairs.
+// poisson_pixel and backproject_pair_term are the contract: k_poisson_project
+// and k_backproject_update call them on the device,
+// xrt_host_poisson_project and xrt_host_backproject_update compiled for the
+// host, and tests/mltr_ref.py restates them.
+// ---------------------------------------------------------------------------
+
+// A pixel of xrt_poisson_project: y the measured counts, flat the expected
+// counts without the object, bg the expected counts that did not come through
+// it (with_bg false: +0.0).  (num, den) = (+0.0f, +0.0f) for a miss, a ray
+// without length and an expectation that is not above zero.
+__host__ __device__ __forceinline__ void poisson_pixel(const float* __restrict__ vol, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                       double sx, double sy, double sz, const double* R, uint32_t row,
+                                                       uint32_t col, float y, float flat, bool with_bg, float bg, float& num,
+                                                       float& den)
+{
+    num = den = 0.0f;
+    const double dr = (double)row, dc = (double)col;
+    const double dx = forward_direction(R, dr, dc), dy = forward_direction(R + 4, dr, dc),
+                 dz = forward_direction(R + 8, dr, dc);
+    double acc, span;
+    if (!forward_ray(vol, nx, ny, nz, R[3], R[7], R[11], dx, dy, dz, acc, span)) return;
+    const double ell = forward_ell(sx, sy, sz, dx, dy, dz);
+    const double l = acc * ell, L = span * ell;
+    const double psi = (double)flat * xrt_exp(-l);
+    const double r = with_bg ? (double)bg : 0.0;
+    const double yh = psi + r;
+    if (!(L > 0.0) || !(yh > 0.0)) return;           // (a NaN compares false)
+    const double q = psi / yh;
+    num = (float)(psi - (double)y * q);
+    den = (float)((L * psi) * q);
+}
+
+// A sample of a plane of pairs: the pixel's (num, den) inside, (+0.0f, +0.0f)
+// outside.  A pair is one 8-byte load or store (the entries check the
+// planes' alignment).
+struct alignas(8) FloatPair {
+    float n, d;
+};
+
+__host__ __device__ __forceinline__ void backproject_pair_sample(const FloatPair* plane, uint32_t W, uint32_t H, int32_t y,
+                                                                 int32_t x, float& n, float& d)
+{
+    n = 0.0f;
+    d = 0.0f;
+    if (x >= 0 && y >= 0 && (uint32_t)x < W && (uint32_t)y < H) {
+        const FloatPair s = plane[(size_t)y * W + (size_t)x];
+        n = s.n;
+        d = s.d;
+    }
+}
+
+// backproject_term over a plane of pairs: its coordinates, acceptance tests
+// and weights once, its three f32 expressions per component.
+__host__ __device__ __forceinline__ void backproject_pair_term(const FloatPair* plane, uint32_t W, uint32_t H, double a,
+                                                               double b, double c, double& accn, double& accd)
+{
+    if (!(c > 0.0)) return;                          // (a NaN compares false)
+    const double w = 1.0 / c;
+    const double col = a * w, row = b * w;
+    if (!(col > -1.0 && col < (double)W && row > -1.0 && row < (double)H)) return;
+    const double fc = floor(col), fr = floor(row);
+    const float fx = (float)(col - fc), fy = (float)(row - fr);
+    const int32_t x0 = (int32_t)fc, y0 = (int32_t)fr;          // -1 .. W - 1 and -1 .. H - 1
+    float n00, n01, n10, n11, d00, d01, d10, d11;
+    backproject_pair_sample(plane, W, H, y0, x0, n00, d00);
+    backproject_pair_sample(plane, W, H, y0, x0 + 1, n01, d01);
+    backproject_pair_sample(plane, W, H, y0 + 1, x0, n10, d10);
+    backproject_pair_sample(plane, W, H, y0 + 1, x0 + 1, n11, d11);
+    const float topn = n00 + fx * (n01 - n00);
+    const float botn = n10 + fx * (n11 - n10);
+    const float vn = topn + fy * (botn - topn);
+    const float topd = d00 + fx * (d01 - d00);
+    const float botd = d10 + fx * (d11 - d10);
+    const float vd = topd + fy * (botd - topd);
+    const double ww = w * w;
+    accn = accn + (double)vn * ww;
+    accd = accd + (double)vd * ww;
+}
+
+// ---------------------------------------------------------------------------
 // TV-regularised SIRT: the gradient of the smoothed isotropic
 // total variation, the sum of squares' chunk order and the descent step.
 // tv_quotients and tv_voxel are the gradient's contract: k_tv_gradient calls

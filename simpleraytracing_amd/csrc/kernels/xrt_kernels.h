@@ -4717,6 +4717,92 @@ __global__ __launch_bounds__(kUpdateThreads) void k_volume_update(uint64_t n, fl
 }
 
 // ---------------------------------------------------------------------------
+// k_poisson_project: the pixel stage of OS-MLTR, in
+// k_forward_project's launch shape: one lane a pixel, one single-wave
+// workgroup an 8x8 tile of one plane (blockIdx.y), R through a wave-uniform
+// address.  Plane p's counts lie at counts + p * stride and its background,
+// when there is one, at background + p * stride: the solver's subsets read
+// the scan where it is; flat is one plane for all.  A lane writes its (num,
+// den) in one 8-byte store.  Offsets are 64-bit.  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_poisson_project(const float* __restrict__ vol, const double* __restrict__ rays,
+                                                        const float* __restrict__ counts, const float* __restrict__ flat,
+                                                        const float* __restrict__ background, uint64_t stride,
+                                                        FloatPair* __restrict__ pairs, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                        double sx, double sy, double sz, uint32_t width, uint32_t height,
+                                                        uint32_t tiles_x)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const uint32_t col = tile_x * kForwardTile + (lane & (kForwardTile - 1u));
+    const uint32_t row = tile_y * kForwardTile + lane / kForwardTile;
+    if (col >= width || row >= height) return;
+    const uint64_t p = blockIdx.y;
+    const double* R = rays + p * 12u;
+    const uint64_t pix = (uint64_t)row * width + col;
+    const bool with_bg = background != nullptr;       // (wave-uniform)
+    const float bg = with_bg ? background[p * stride + pix] : 0.0f;
+    FloatPair out;
+    poisson_pixel(vol, nx, ny, nz, sx, sy, sz, R, row, col, counts[p * stride + pix], flat[pix], with_bg, bg, out.n, out.d);
+    pairs[p * ((uint64_t)width * height) + pix] = out;
+}
+
+// ---------------------------------------------------------------------------
+// k_backproject_update: OS-MLTR's hot path, k_backproject's
+// shape over planes of (num, den) pairs: a wave owns kPairChunks * 64 voxels
+// of one row (j, k), lanes along x, a plane's matrix by scalar loads and its
+// three brackets once for all of them.  A voxel's coordinates, acceptance
+// tests, floor and division serve both components; each corner is one 8-byte
+// gather.  The two sums never reach memory: the voxel is updated in place
+// (volume_update_voxel).  64-bit offsets, no LDS, no scratch.
+// ---------------------------------------------------------------------------
+// Three chunks, not k_backproject's four: the second set of sums takes 62 VGPRs at three and 68 at four, and 64
+// is what eight waves a SIMD -- k_backproject's occupancy -- allow.
+constexpr uint32_t kPairChunks = 3;
+constexpr uint32_t kPairSpan = 64u * kPairChunks;
+
+__global__ __launch_bounds__(kBackprojectThreads) void k_backproject_update(const FloatPair* __restrict__ pairs,
+                                                                            const double* __restrict__ matrices,
+                                                                            uint32_t width, uint32_t height,
+                                                                            uint32_t num_planes, uint32_t nx, uint32_t ny,
+                                                                            uint64_t rows, uint32_t spans, double relax,
+                                                                            float lo, float hi, float* volume)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t g = (uint64_t)blockIdx.x * (kBackprojectThreads / 64u) + wave_in_block();
+    const uint64_t row = g / spans;                   // k * ny + j
+    if (row >= rows) return;                          // (no barrier below)
+    const uint32_t x0 = (uint32_t)(g - row * spans) * kPairSpan + lane;
+    const double dj = (double)(uint32_t)(row % ny), dk = (double)(uint32_t)(row / ny);
+    double accn[kPairChunks], accd[kPairChunks], di[kPairChunks];
+#pragma unroll
+    for (uint32_t c = 0; c < kPairChunks; ++c) {
+        accn[c] = 0.0;
+        accd[c] = 0.0;
+        di[c] = (double)(x0 + 64u * c);
+    }
+    const size_t plane = (size_t)width * height;
+    for (uint32_t p = 0; p < num_planes; ++p) {
+        const double* A = matrices + (size_t)p * 12u;
+        const double ba = backproject_bracket(A, dj, dk), bb = backproject_bracket(A + 4, dj, dk),
+                     bc = backproject_bracket(A + 8, dj, dk);
+        const double a0 = A[0], a4 = A[4], a8 = A[8];
+        const FloatPair* img = pairs + (size_t)p * plane;
+#pragma unroll
+        for (uint32_t c = 0; c < kPairChunks; ++c)
+            if (x0 + 64u * c < nx)
+                backproject_pair_term(img, width, height, a0 * di[c] + ba, a4 * di[c] + bb, a8 * di[c] + bc, accn[c],
+                                      accd[c]);
+    }
+    float* dst = volume + row * nx;
+#pragma unroll
+    for (uint32_t c = 0; c < kPairChunks; ++c) {
+        const uint32_t x = x0 + 64u * c;
+        if (x < nx) dst[x] = volume_update_voxel(dst[x], (float)accn[c], (float)accd[c], relax, lo, hi);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // k_tv_gradient: the gradient of the smoothed isotropic TV of a f32 volume
 // (DESIGN 10.13).  A workgroup of kTvLanesX x kTvLanesY lanes owns the
 // kTvOwnX x kTvOwnY columns of an (x, y) tile -- its lanes of column 0 and

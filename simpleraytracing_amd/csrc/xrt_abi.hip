@@ -3249,6 +3249,207 @@ int xrt_sirt(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_pla
                        nullptr, volume);
 }
 
+// --- OS-MLTR ------------------------------------------------------
+
+#include "xrt_mltr_host.inc"
+
+// The launch of k_poisson_project (validated arguments, device pointers); plane p's counts lie at
+// d_counts + p * stride and its background, when there is one, at d_background + p * stride.
+static int launch_poisson_project(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                                  const float* d_volume, const uint32_t dims[3], const float spacing[3],
+                                  const double* d_rays, const float* d_counts, const float* d_flat,
+                                  const float* d_background, uint64_t stride, float* d_pairs, hipStream_t stream)
+{
+    const uint32_t tiles_x = (width + kForwardTile - 1u) / kForwardTile, tiles_y = (height + kForwardTile - 1u) / kForwardTile;
+    hipLaunchKernelGGL(k_poisson_project, dim3(tiles_x * tiles_y, num_planes), dim3(64), 0, stream, d_volume, d_rays, d_counts,
+                       d_flat, d_background, stride, reinterpret_cast<FloatPair*>(d_pairs), dims[0], dims[1], dims[2],
+                       (double)spacing[0], (double)spacing[1], (double)spacing[2], width, height, tiles_x);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_poisson_project_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                               const float* d_volume, const uint32_t dims[3], const float spacing[3], const double* d_rays,
+                               const float* d_counts, const float* d_flat, const float* d_background, float* d_pairs,
+                               void* stream)
+{
+    if (const char* why = poisson_project_arguments(width, height, num_planes, d_volume, dims, spacing, d_rays, d_counts,
+                                                    d_flat, d_background, d_pairs, false))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_poisson_project(ctx, width, height, num_planes, d_volume, dims, spacing, d_rays, d_counts, d_flat,
+                                  d_background, (uint64_t)width * height, d_pairs, (hipStream_t)stream);
+}
+
+int xrt_poisson_project(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* volume,
+                        const uint32_t dims[3], const float spacing[3], const double* rays, const float* counts,
+                        const float* flat, const float* background, float* pairs)
+{
+    if (const char* why = poisson_project_arguments(width, height, num_planes, volume, dims, spacing, rays, counts, flat,
+                                                    background, pairs, true))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t plane = (size_t)width * height, all = plane * num_planes;
+    DeviceScratch s(ctx, ctx->host_stream, "Poisson projection");
+    const float* dvol = s.upload(volume, (size_t)dims[0] * dims[1] * dims[2]);
+    const double* drays = s.upload(rays, (size_t)num_planes * 12u);
+    const float* dcounts = s.upload(counts, all);
+    const float* dflat = s.upload(flat, plane);
+    const float* dbg = s.upload(background, all);
+    float* dpairs = s.alloc<float>(2u * all);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_poisson_project(ctx, width, height, num_planes, dvol, dims, spacing, drays, dcounts, dflat, dbg,
+                                        (uint64_t)plane, dpairs, ctx->host_stream))
+        return rc;
+    s.download(pairs, (const float*)dpairs, 2u * all);
+    return s.finish();
+}
+
+// The launch of k_backproject_update (validated arguments, device pointers).
+static int launch_backproject_update(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                                     const float* d_pairs, const double* d_matrices, const uint32_t dims[3], double relax,
+                                     float lo, float hi, float* d_volume, hipStream_t stream)
+{
+    const uint32_t spans = (dims[0] + kPairSpan - 1u) / kPairSpan;
+    const uint64_t rows = (uint64_t)dims[2] * dims[1];
+    const uint64_t waves = rows * spans, per_block = kBackprojectThreads / 64u;
+    hipLaunchKernelGGL(k_backproject_update, dim3((unsigned)((waves + per_block - 1u) / per_block)), dim3(kBackprojectThreads),
+                       0, stream, reinterpret_cast<const FloatPair*>(d_pairs), d_matrices, width, height, num_planes, dims[0],
+                       dims[1], rows, spans, relax, lo, hi, d_volume);
+    XRT_HIP(ctx, hipGetLastError());
+    return XRT_OK;
+}
+
+int xrt_backproject_update_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes,
+                                  const float* d_pairs, const double* d_matrices, const uint32_t dims[3], double relax,
+                                  float lo, float hi, float* d_volume, void* stream)
+{
+    if (const char* why = backproject_update_arguments(width, height, num_planes, d_pairs, d_matrices, dims, relax, lo, hi,
+                                                       d_volume, false))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_backproject_update(ctx, width, height, num_planes, d_pairs, d_matrices, dims, relax, lo, hi, d_volume,
+                                     (hipStream_t)stream);
+}
+
+int xrt_backproject_update(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* pairs,
+                           const double* matrices, const uint32_t dims[3], double relax, float lo, float hi, float* volume)
+{
+    if (const char* why = backproject_update_arguments(width, height, num_planes, pairs, matrices, dims, relax, lo, hi, volume,
+                                                       true))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t voxels = (size_t)dims[0] * dims[1] * dims[2];
+    DeviceScratch s(ctx, ctx->host_stream, "backprojection update");
+    const float* dpairs = s.upload(pairs, (size_t)width * height * num_planes * 2u);
+    const double* dmat = s.upload(matrices, (size_t)num_planes * 12u);
+    float* dvol = s.upload(volume, voxels);
+    if (s.rc()) return s.rc();
+    if (int rc = launch_backproject_update(ctx, width, height, num_planes, dpairs, dmat, dims, relax, lo, hi, dvol,
+                                           ctx->host_stream))
+        return rc;
+    s.download(volume, (const float*)dvol, voxels);
+    return s.finish();
+}
+
+// xrt_mltr's loop over device buffers on `stream` (validated arguments, a plan whose every matrix has its ray
+// matrix).  The working set lies in the context's d_sirt: the matrices, with TV the sums (the partials, G, D), the
+// largest subset's pairs, and with TV the gradient volume and x0.
+static int run_mltr(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_counts,
+                    const float* d_flat, const float* d_background, SirtPlan& plan, const uint32_t dims[3],
+                    const float spacing[3], uint32_t iterations, uint32_t subsets, double relax, float lo, float hi,
+                    const xrt_tv_params* tv, float* d_volume, hipStream_t stream)
+{
+    const bool with_tv = tv && tv->steps > 0u;
+    const size_t plane = (size_t)width * height, voxels = (size_t)dims[0] * dims[1] * dims[2];
+    const size_t mat_bytes = (size_t)num_planes * 24u * sizeof(double);
+    const size_t sums = with_tv ? sumsq_partials(voxels) + 2u : 0u;
+    const size_t bytes = mat_bytes + sums * sizeof(double) +
+                         (2u * plane * plan.widest + (with_tv ? 2u * voxels : 0u)) * sizeof(float);
+    if (int rc = sirt_working_set(ctx, bytes)) return rc;
+    double* dA = reinterpret_cast<double*>(ctx->d_sirt.get());
+    double* dR = dA + (size_t)num_planes * 12u;
+    double* d_sums = dR + (size_t)num_planes * 12u;
+    double* d_moved = d_sums + (sums ? sums - 1u : 0u);      // D, behind the partials and G
+    float* d_pairs = reinterpret_cast<float*>(d_sums + sums);  // (behind doubles: aligned to 8 bytes)
+    float* d_grad = d_pairs + 2u * plane * plan.widest;
+    float* d_x0 = d_grad + voxels;
+    ctx->sirt_mats.assign(plan.A.begin(), plan.A.end());
+    ctx->sirt_mats.insert(ctx->sirt_mats.end(), plan.R.begin(), plan.R.end());
+    XRT_HIP(ctx, ctx->sirt_done.mark());              // from here on the set is in use until sirt_done is recorded
+    XRT_HIP(ctx, hipMemcpyAsync(dA, ctx->sirt_mats.data(), mat_bytes, hipMemcpyHostToDevice, stream));
+    int rc = XRT_OK;
+    double a_k = with_tv ? tv->alpha : 0.0;
+    for (uint32_t k = 0; k < iterations && !rc; ++k) {
+        if (with_tv && hipMemcpyAsync(d_x0, d_volume, voxels * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+            rc = fail(ctx, XRT_ERR_DEVICE, "MLTR: keeping the iteration's start failed");
+        for (uint32_t s = 0; s < subsets && !rc; ++s) {
+            // subset s's planes lie `subsets` planes apart in the scan, from plane s
+            rc = launch_poisson_project(ctx, width, height, plan.count[s], d_volume, dims, spacing,
+                                        dR + (size_t)plan.first[s] * 12u, d_counts + plane * s, d_flat,
+                                        d_background ? d_background + plane * s : nullptr, (uint64_t)plane * subsets, d_pairs,
+                                        stream);
+            if (!rc)
+                rc = launch_backproject_update(ctx, width, height, plan.count[s], d_pairs, dA + (size_t)plan.first[s] * 12u,
+                                               dims, relax, lo, hi, d_volume, stream);
+        }
+        if (with_tv && !rc) {
+            rc = launch_sumsq(ctx, voxels, d_volume, d_x0, d_sums, d_moved, stream);
+            if (!rc) rc = launch_tv_descend(ctx, d_volume, dims, tv->eps, tv->steps, a_k, d_moved, lo, hi, d_grad, d_sums, stream);
+            a_k = a_k * tv->reduction;
+        }
+    }
+    (void)ctx->sirt_done.record(stream);
+    return rc;
+}
+
+int xrt_mltr_device(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* d_counts,
+                    const float* d_flat, const float* d_background, const double* matrices, const uint32_t dims[3],
+                    const float spacing[3], uint32_t iterations, uint32_t subsets, double relax, float lo, float hi,
+                    const xrt_tv_params* tv, float* d_volume, void* stream)
+{
+    if (const char* why = mltr_arguments(width, height, num_planes, d_counts, d_flat, d_background, matrices, dims, spacing,
+                                         iterations, subsets, relax, lo, hi, d_volume, false))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (const char* why = tv_params_arguments(tv)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    SirtPlan plan;
+    if (!sirt_plan(num_planes, subsets, matrices, plan)) return fail(ctx, XRT_ERR_ARGUMENT, "a matrix has no ray matrix (xrt_ray_matrix)");
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    return run_mltr(ctx, width, height, num_planes, d_counts, d_flat, d_background, plan, dims, spacing, iterations, subsets,
+                    relax, lo, hi, tv, d_volume, (hipStream_t)stream);
+}
+
+int xrt_mltr(xrt_context* ctx, uint32_t width, uint32_t height, uint32_t num_planes, const float* counts, const float* flat,
+             const float* background, const double* matrices, const uint32_t dims[3], const float spacing[3],
+             uint32_t iterations, uint32_t subsets, double relax, float lo, float hi, const xrt_tv_params* tv, float* volume)
+{
+    if (const char* why = mltr_arguments(width, height, num_planes, counts, flat, background, matrices, dims, spacing,
+                                         iterations, subsets, relax, lo, hi, volume, true))
+        return fail(ctx, XRT_ERR_ARGUMENT, why);
+    if (const char* why = tv_params_arguments(tv)) return fail(ctx, XRT_ERR_ARGUMENT, why);
+    SirtPlan plan;
+    if (!sirt_plan(num_planes, subsets, matrices, plan)) return fail(ctx, XRT_ERR_ARGUMENT, "a matrix has no ray matrix (xrt_ray_matrix)");
+    if (!ctx) return fail(nullptr, XRT_ERR_ARGUMENT, "context is NULL");
+    XRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t plane = (size_t)width * height, voxels = (size_t)dims[0] * dims[1] * dims[2];
+    DeviceScratch s(ctx, ctx->host_stream, "MLTR");
+    const float* dcounts = s.upload(counts, plane * num_planes);
+    const float* dflat = s.upload(flat, plane);
+    const float* dbg = s.upload(background, plane * num_planes);
+    float* dvol = s.upload(volume, voxels);
+    if (s.rc()) return s.rc();
+    if (int rc = run_mltr(ctx, width, height, num_planes, dcounts, dflat, dbg, plan, dims, spacing, iterations, subsets, relax,
+                          lo, hi, tv, dvol, ctx->host_stream))
+        return rc;
+    s.download(volume, (const float*)dvol, voxels);
+    return s.finish();
+}
+
 // --- voxelisation ---------------------------------------------
 
 #include "xrt_voxel_host.inc"
